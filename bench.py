@@ -5,7 +5,14 @@ A step = one frame of the workload rendered by the HIP path into HBM-resident bu
 (+ for N > 1 the RCCL gather of the per-rank stripe buffers to rank 0 and the
 de-interleave into the frame).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--stack-mode literal|per_pixel]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--stack-mode literal|per_pixel] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps), times exactly K steps once and prints the headline line (`value`, `ms_per_step`,
+the workload's `config`).  `--full` adds everything else: the timed loop repeated, the frames-in-flight and gather checks,
+single-frame latencies (`frame`), the per-pixel-stack counterpart, `roofline` and `cpu_baseline`.  `--dump-outputs DIR`
+writes the frame of the last timed step (float RGB, hit IDs, u8 image) as .npy files: the inputs are fixed, so two builds
+can be compared output for output.
 
 Workloads
     N = 1 (default `cfg2`): BASELINE.json configs[1] = balls_low.p3f 1024x1024, Whitted MAX_DEPTH 4, BVH.
@@ -27,7 +34,7 @@ streams (i % 2) and everything behind it on one of two "tail" streams (p3d_scene
 hardware queues; per-pixel frames (and `--tail-streams 0`): four scenes, whole frames on four streams.
 `frame.kernel_ms` is ONE frame on its own (HIP events inside the library).
 
-Prints ONE JSON line on rank 0.  `roofline` and `cpu_baseline` follow DESIGN.md "Measurement".
+Prints ONE JSON line on rank 0.  `roofline` and `cpu_baseline` (--full) follow DESIGN.md "Measurement".
 """
 import argparse
 import hashlib
@@ -46,7 +53,8 @@ VALU_CYCLES = 2        # a wave64 VALU instruction issues over 2 cycles on a SIM
 #                        4 cycles is what ONE wave alone sustains, and what round 1 mistook for the SIMD's rate)
 HBM_PEAK_GBPS = 8000.0
 LDS_PEAK_GBPS = 256 * 128 * CLOCK_HZ / 1e9  # 128 B per clock and CU
-TIMED_REPEATS = 5      # the timed loop (exactly --steps steps, barrier + synchronize on both sides) is run this often: median counted, all reported
+TIMED_REPEATS = 5      # --full: the timed loop (exactly --steps steps, barrier + synchronize on both sides) is run this often: median counted, all reported
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -70,7 +78,7 @@ def parse():
                          "this many streams of their own (p3d_scene_set_tail_stream) and pass 1 of all frames to --bulk-streams "
                          "streams, instead of whole frames on --frames-in-flight streams (then 6 frames in flight by default); 0 = off")
     ap.add_argument("--bulk-streams", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--tile-order", default="cost", choices=["cost", "frame"],
                     help="p3d_config.tile_order: cost = tiles most-expensive-class first (schedule recorded by the first "
                          "launch, i.e. during warmup); frame = image order.  Scheduling only, same bits either way.")
@@ -85,7 +93,39 @@ def parse():
                          "with a single rank: exercises the RCCL gather on a one-GPU box")
     ap.add_argument("--gather", default=None, choices=["u8", "f32"],
                     help="N>1: what rank 0 collects per frame: float RGB + hit IDs (16 B/px, default) or the u8 image (3 B/px, cfg2w default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the timed loop repeated (median of up to %d), "
+                         "the frames-in-flight and gather checks, single-frame latencies, the per-pixel-stack counterpart, the "
+                         "roofline block and the CPU baseline.  Without it a run sets up, warms up, times --steps steps once "
+                         "and prints the headline line" % TIMED_REPEATS)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step rendered (the frame as its caller receives "
+                         "it: float RGB, hit IDs, u8 image) as DIR/<name>.npy in float32 / float64, at most %d MB in all "
+                         "(a fixed, seeded sample of pixels beyond that, with DIR/pixel_index.npy)" % (DUMP_LIMIT_BYTES // 10**6))
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write `arrays` (name -> numpy array of shape (h, w) or (h, w, c), all of one frame) as out_dir/<name>.npy: integers
+    of 4 bytes or more as float64 (exact for the int32 hit IDs), everything else as float32.  If they come to more than `limit`
+    bytes in all, every array keeps the same fixed, seeded sample of pixels (rows of its (h*w, ...) view, ascending) and
+    the flat pixel indices y*w + x go to out_dir/pixel_index.npy.  -> {name: shape written}"""
+    import numpy as np
+    conv = {k: a.astype(np.float64 if a.dtype.kind in "iu" and a.dtype.itemsize >= 4 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > limit:
+        n_px = {a.shape[0] * a.shape[1] for a in conv.values()}
+        assert len(n_px) == 1, "dump_outputs: the arrays of one frame must have one (h, w)"
+        n_px = n_px.pop()
+        per_px = total // n_px + 8  # + the float64 pixel index
+        m = max(1, (limit - 4096 * (len(conv) + 1)) // per_px)  # (an .npy header per file)
+        idx = np.sort(np.random.default_rng(20261016).choice(n_px, size=m, replace=False))
+        conv = {k: a.reshape((n_px,) + a.shape[2:])[idx] for k, a in conv.items()}
+        conv["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: a.shape for k, a in conv.items()}
 
 
 def workload_setup(name, p3d):
@@ -363,16 +403,36 @@ def main():
     for sc_, st_ in flight[1:]:  # the other slots record their tile schedules outside the timed region too
         render_into(bufs[0], tile, cfg, stats=p3d.Stats(), scene=sc_, on=st_)
     def timed_repeats(cfg_):
-        """the timed loop up to TIMED_REPEATS times (fewer when one loop takes seconds: the heavy workloads), sorted"""
+        """--full: the timed loop up to TIMED_REPEATS times (fewer when one loop takes seconds: the heavy workloads), sorted;
+        otherwise once"""
         first = timed_loop(cfg_)
+        if not args.full:
+            return [first]
         n = TIMED_REPEATS if first < 0.5 else (3 if first < 3.0 else 1)
         return sorted([first] + [timed_loop(cfg_) for _ in range(n - 1)])
     dts = timed_repeats(cfg)
     dt = dts[len(dts) // 2]
 
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed step, as the caller of the timed path holds it (nothing has rendered since)
+        last = args.steps - 1
+        if dist_on:
+            slot_, k_ = last_frame[0]
+            if gather == "u8":
+                outs = {"rgb8": frame8[slot_][k_]}
+            else:
+                outs = {"rgb": frame_rgb[slot_][k_], "hit": frame_hit[slot_][k_]}
+        else:
+            packed, u8 = flight_bufs[last % nfl] if nfl > 1 else bufs[last & 1]
+            n_px = tile.w * tile.h
+            outs = {"rgb": packed[: n_px * 12].view(torch.float32).view(tile.h, tile.w, 3),
+                    "hit": packed[n_px * 12: n_px * 16].view(torch.int32).view(tile.h, tile.w),
+                    "rgb8": u8[: n_px * 3].view(tile.h, tile.w, 3)}
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outs.items()})
+
     # what the timed frames left in their slots must be, bit for bit, the frame one scene renders on its own
     flight_check = None
-    if nfl > 1 and not dist_on:
+    if args.full and nfl > 1 and not dist_on:
         frames = [(b[0].clone(), b[1].clone()) for b in flight_bufs[:min(nfl, args.steps)]]
         render_into(bufs[1], tile, cfg)
         torch.cuda.synchronize()
@@ -381,16 +441,17 @@ def main():
         flight_check = "ok" if ok else "MISMATCH"
 
     # Launch durations inside the frame, live: HIP events of the library on the launch stream (p3d_stats.kernel_ms /
-    # pass1_ms / handoff_ms), 16 frames after the timed region, smallest and mean.
-    probes = []
+    # pass1_ms / handoff_ms), 16 frames after the timed region, smallest and mean.  (--full)
     n_probes = 16 if dt / args.steps < 0.05 else 3  # (frames of seconds: three)
-    for _ in range(n_probes):
-        st_ = p3d.Stats()
-        render_into(bufs[0], tile, cfg, stats=st_)
-        probes.append((st_.kernel_ms, st_.pass1_ms, st_.handoff_ms))
-    kernel_ms = sum(p[0] for p in probes) / len(probes)
-    pass1_ms = sum(p[1] for p in probes) / len(probes) if literal else kernel_ms
-    handoff_ms = sum(p[2] for p in probes) / len(probes) if literal else 0.0
+    if args.full:
+        probes = []
+        for _ in range(n_probes):
+            st_ = p3d.Stats()
+            render_into(bufs[0], tile, cfg, stats=st_)
+            probes.append((st_.kernel_ms, st_.pass1_ms, st_.handoff_ms))
+        kernel_ms = sum(p[0] for p in probes) / len(probes)
+        pass1_ms = sum(p[1] for p in probes) / len(probes) if literal else kernel_ms
+        handoff_ms = sum(p[2] for p in probes) / len(probes) if literal else 0.0
 
     # Rays of the frame as the reference counts them = the queries of the final frame.  The per-pixel-stack launch
     # traces exactly those (the literal launches trace some of them twice: that is overhead, not throughput).
@@ -405,7 +466,7 @@ def main():
     rays_total, _ = counts.tolist()
     rays_total_rank0 = st.rays
     handoff = None
-    if literal:
+    if args.full and literal:
         cfg_counted.stack_mode = p3d.STACK_LITERAL
         hst = p3d.Stats()
         render_into(bufs[0], tile, cfg_counted, stats=hst)
@@ -413,7 +474,7 @@ def main():
 
     # the same frames with the stack emptied at every primary sample (one launch per frame): N = 1 only
     per_pixel = None
-    if literal and not dist_on:
+    if args.full and literal and not dist_on:
         cfg_pp = p3d.Config.from_buffer_copy(bytes(cfg))
         cfg_pp.stack_mode = p3d.STACK_PER_PIXEL
         pp_cold = p3d.Stats()
@@ -436,7 +497,7 @@ def main():
                      "note": "P3D_STACK_PER_PIXEL: hit IDs as the literal frame, colours within 1e-4 of it on this scene"}
 
     gather_check = None
-    if dist_on and rank == 0:
+    if args.full and dist_on and rank == 0:
         # the last assembled frame must equal, bit for bit, what one GPU renders for the whole frame
         full = dev.full_tile()
         ref_pair = (torch.empty(p3d.packed_bytes(res * res), dtype=torch.uint8, device="cuda"),
@@ -469,55 +530,10 @@ def main():
 
     if rank == 0:
         value = rays_total * args.steps / dt / 1e6
-        alg_bytes_launch = st.algorithmic_bytes()  # rank 0's launch
-        dominant = "whitted_kernel" if whitted else "pt_kernel"
-        dom_ms = pass1_ms if literal else kernel_ms
-        alg_gbps = alg_bytes_launch / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # The nearest ceiling (DESIGN.md "Measurement"): the scene is LDS- or L2-resident, so HBM serves the
-        # framebuffer only.  What the dominant kernel spends is instruction issue: a wave64 VALU instruction takes its
-        # SIMD-32 for 2 cycles, 1024 SIMDs at 2.4 GHz = 1228.8 G wave-instructions/s.  Instruction and HBM byte counts come from the rocprofv3 PMC passes
-        # of this workload committed under profiles/r04/ — quoted only if taken from exactly these kernel sources.
-        summary, src = pmc_summary(workload, args.stack_mode) if not dist_on else (None, "PMC summaries are per single-GPU workload")
-        staged = os.path.getsize(scene_path) < 64 * 1024  # (the packaged small scenes: staged in LDS by the kernels)
-        roof = {"kernel": dominant, "kernel_ms": round(dom_ms, 4),
-                "algorithmic": {"bytes_per_launch": int(alg_bytes_launch), "GBps": round(alg_gbps, 1),
-                                "frac_vs_hbm": round(alg_gbps / HBM_PEAK_GBPS, 4),
-                                "frac_vs_lds": round(alg_gbps / LDS_PEAK_GBPS, 4) if staged else None,
-                                "note": "SURVEY.md 8(d) definition: bytes the algorithm looks at / dominant kernel's duration.  They are served by "
-                                        "LDS (staged scenes) or L2 / Infinity Cache, not by HBM: frac_vs_hbm is NOT a bound when > 1 (nothing is "
-                                        "skipped: counters equal the oracle's query by query); frac_vs_lds prices them against the LDS "
-                                        "bandwidth of the chip (128 B/clk/CU); measured HBM traffic is under `traffic` / `hbm`"}}
-        if summary:
-            k = summary["dominant"]
-            insts = k["SQ_INSTS_VALU"]
-            achieved = insts / (dom_ms * 1e-3) / 1e9  # G wave-instructions / s
-            peak = SIMDS * CLOCK_HZ / VALU_CYCLES / 1e9
-            traffic = k.get("hbm_bytes")
-            # every launch of a frame (hand-off launches included), not only the dominant one: the kernels of the summary that ran
-            # about once per traced frame (the one-off counting and schedule-building launches of the warm-up do not)
-            frame_insts = frame_valu_instructions(summary, literal) or insts
-            roof.update({"bound": "valu_issue", "achieved": round(achieved, 1), "peak": round(peak, 1), "unit": "Gwave-instr/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "hbm": {"achieved_GBps": round(traffic / (dom_ms * 1e-3) / 1e9, 1) if traffic else None, "peak_GBps": HBM_PEAK_GBPS,
-                                 "frac": round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None},
-                         "wave_instructions_valu": int(insts), "lane_utilisation": k.get("lane_utilisation"),
-                         "rocprof_avg_ms": k.get("avg_ms"), "source": src,
-                         "scope": "the dominant kernel of ONE frame on its own (kernel_ms live from HIP events, rocprof_avg_ms from "
-                                  "the committed trace of `bench.py --frames-in-flight 1`)",
-                         "timed_loop_frac_lower_bound": round(insts / (dt / args.steps) / 1e9 / peak, 4) if not dist_on else None,
-                         "timed_loop_frac": round(frame_insts / (dt / args.steps) / 1e9 / peak, 4) if not dist_on else None,
-                         "timed_loop_note": "VALU wave-instructions of ALL launches of one frame / ms_per_step / peak: what the chip issues "
-                                            "while `frames_in_flight` frames overlap (the lower bound counts the dominant kernel only)"})
-        else:
-            roof.update({"bound": "valu_issue", "achieved": None, "peak": round(SIMDS * CLOCK_HZ / VALU_CYCLES / 1e9, 1), "unit": "Gwave-instr/s",
-                         "frac": None, "traffic": None, "source": src})
         out = {
             "metric": "Mrays/s (primary+secondary)", "value": round(value, 1), "unit": "Mrays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
-            "ms_per_step_repeats": [round(d / args.steps * 1e3, 4) for d in dts],
-            "value_single_frame": round(rays_total_rank0 / (kernel_ms * 1e-3) / 1e6, 1) if not dist_on else None,
-            "latency_ms_single_frame": round(kernel_ms, 4),
             "scaling": "strong" if fixed else "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": desc, "resolution": [res, res], "rays_per_frame": int(rays_total),
@@ -531,27 +547,77 @@ def main():
                        "parallelism": "image rows in %d-row stripes, round-robin over %d GPU(s)%s"
                                       % (stripe_h, world,
                                          "; every frame's %s gathered to rank 0 over %s, %d frame(s) per collective, "
-                                         "double-buffered, %d frame(s) in flight per rank (one device scene and stream per gather slot); "
-                                         "gathered frame vs single-GPU frame: %s"
-                                         % ("u8 image" if gather == "u8" else "float RGB + hit IDs", "RCCL" if args.backend == "nccl" else "gloo (host-staged)", B, nfl, gather_check)
+                                         "double-buffered, %d frame(s) in flight per rank (one device scene and stream per gather slot)%s"
+                                         % ("u8 image" if gather == "u8" else "float RGB + hit IDs", "RCCL" if args.backend == "nccl" else "gloo (host-staged)", B, nfl,
+                                            "; gathered frame vs single-GPU frame: %s" % gather_check if gather_check else "")
                                          if dist_on else "")},
-            "value_note": "value = throughput of the timed loop (median of %d repeats of exactly --steps steps) with `frames_in_flight` frames "
-                          "overlapping on as many device scenes (streams: config.streams); value_single_frame / latency_ms_single_frame = ONE frame rendered "
-                          "alone (HIP events inside the library, mean of %d frames)" % (len(dts), n_probes),
-            "frame": {"kernel_ms": round(kernel_ms, 4), "pass1_ms": round(pass1_ms, 4), "handoff_ms": round(handoff_ms, 4),
-                      "cold_kernel_ms": round(cold.kernel_ms, 4), "handoff": handoff,
-                      "note": "ONE frame on its own: HIP events of the library on the launch stream (ms_per_step is the rate of the "
-                              "timed loop, with frames_in_flight frames overlapping); cold = first launch of this scene and config "
-                              "(image order, tile costs recorded), the timed frames use the recorded tile schedule"},
-            "roofline": roof,
+            "value_note": "value = throughput of the timed loop (%s exactly --steps steps) with `frames_in_flight` frames "
+                          "overlapping on as many device scenes (streams: config.streams)%s"
+                          % ("median of %d repeats of" % len(dts) if args.full else "one run of",
+                             "; value_single_frame / latency_ms_single_frame = ONE frame rendered alone (HIP events inside the library, "
+                             "mean of %d frames)" % n_probes if args.full else ""),
         }
-        if per_pixel:
-            out["per_pixel_stack"] = per_pixel
-        if dist_on:
-            single_gpu["value"] = round(rays_total / (single_gpu["ms_per_step"] * 1e-3) / 1e6, 1)
-            out["single_gpu_same_workload"] = single_gpu
-        if not args.no_cpu_baseline and not dist_on:
-            out["cpu_baseline"] = cpu_baseline(workload, scene_path, cfg, res)
+        if args.full:
+            alg_bytes_launch = st.algorithmic_bytes()  # rank 0's launch
+            dominant = "whitted_kernel" if whitted else "pt_kernel"
+            dom_ms = pass1_ms if literal else kernel_ms
+            alg_gbps = alg_bytes_launch / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            # The nearest ceiling (DESIGN.md "Measurement"): the scene is LDS- or L2-resident, so HBM serves the
+            # framebuffer only.  What the dominant kernel spends is instruction issue: a wave64 VALU instruction takes its
+            # SIMD-32 for 2 cycles, 1024 SIMDs at 2.4 GHz = 1228.8 G wave-instructions/s.  Instruction and HBM byte counts come from the rocprofv3 PMC passes
+            # of this workload committed under profiles/r04/ — quoted only if taken from exactly these kernel sources.
+            summary, src = pmc_summary(workload, args.stack_mode) if not dist_on else (None, "PMC summaries are per single-GPU workload")
+            staged = os.path.getsize(scene_path) < 64 * 1024  # (the packaged small scenes: staged in LDS by the kernels)
+            roof = {"kernel": dominant, "kernel_ms": round(dom_ms, 4),
+                    "algorithmic": {"bytes_per_launch": int(alg_bytes_launch), "GBps": round(alg_gbps, 1),
+                                    "frac_vs_hbm": round(alg_gbps / HBM_PEAK_GBPS, 4),
+                                    "frac_vs_lds": round(alg_gbps / LDS_PEAK_GBPS, 4) if staged else None,
+                                    "note": "SURVEY.md 8(d) definition: bytes the algorithm looks at / dominant kernel's duration.  They are served by "
+                                            "LDS (staged scenes) or L2 / Infinity Cache, not by HBM: frac_vs_hbm is NOT a bound when > 1 (nothing is "
+                                            "skipped: counters equal the oracle's query by query); frac_vs_lds prices them against the LDS "
+                                            "bandwidth of the chip (128 B/clk/CU); measured HBM traffic is under `traffic` / `hbm`"}}
+            if summary:
+                k = summary["dominant"]
+                insts = k["SQ_INSTS_VALU"]
+                achieved = insts / (dom_ms * 1e-3) / 1e9  # G wave-instructions / s
+                peak = SIMDS * CLOCK_HZ / VALU_CYCLES / 1e9
+                traffic = k.get("hbm_bytes")
+                # every launch of a frame (hand-off launches included), not only the dominant one: the kernels of the summary that ran
+                # about once per traced frame (the one-off counting and schedule-building launches of the warm-up do not)
+                frame_insts = frame_valu_instructions(summary, literal) or insts
+                roof.update({"bound": "valu_issue", "achieved": round(achieved, 1), "peak": round(peak, 1), "unit": "Gwave-instr/s",
+                             "frac": round(achieved / peak, 4), "traffic": traffic,
+                             "hbm": {"achieved_GBps": round(traffic / (dom_ms * 1e-3) / 1e9, 1) if traffic else None, "peak_GBps": HBM_PEAK_GBPS,
+                                     "frac": round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None},
+                             "wave_instructions_valu": int(insts), "lane_utilisation": k.get("lane_utilisation"),
+                             "rocprof_avg_ms": k.get("avg_ms"), "source": src,
+                             "scope": "the dominant kernel of ONE frame on its own (kernel_ms live from HIP events, rocprof_avg_ms from "
+                                      "the committed trace of `bench.py --frames-in-flight 1`)",
+                             "timed_loop_frac_lower_bound": round(insts / (dt / args.steps) / 1e9 / peak, 4) if not dist_on else None,
+                             "timed_loop_frac": round(frame_insts / (dt / args.steps) / 1e9 / peak, 4) if not dist_on else None,
+                             "timed_loop_note": "VALU wave-instructions of ALL launches of one frame / ms_per_step / peak: what the chip issues "
+                                                "while `frames_in_flight` frames overlap (the lower bound counts the dominant kernel only)"})
+            else:
+                roof.update({"bound": "valu_issue", "achieved": None, "peak": round(SIMDS * CLOCK_HZ / VALU_CYCLES / 1e9, 1), "unit": "Gwave-instr/s",
+                             "frac": None, "traffic": None, "source": src})
+            out.update({
+                "ms_per_step_repeats": [round(d / args.steps * 1e3, 4) for d in dts],
+                "value_single_frame": round(rays_total_rank0 / (kernel_ms * 1e-3) / 1e6, 1) if not dist_on else None,
+                "latency_ms_single_frame": round(kernel_ms, 4),
+                "frame": {"kernel_ms": round(kernel_ms, 4), "pass1_ms": round(pass1_ms, 4), "handoff_ms": round(handoff_ms, 4),
+                          "cold_kernel_ms": round(cold.kernel_ms, 4), "handoff": handoff,
+                          "note": "ONE frame on its own: HIP events of the library on the launch stream (ms_per_step is the rate of the "
+                                  "timed loop, with frames_in_flight frames overlapping); cold = first launch of this scene and config "
+                                  "(image order, tile costs recorded), the timed frames use the recorded tile schedule"},
+                "roofline": roof,
+            })
+            if per_pixel:
+                out["per_pixel_stack"] = per_pixel
+            if dist_on:
+                single_gpu["value"] = round(rays_total / (single_gpu["ms_per_step"] * 1e-3) / 1e6, 1)
+                out["single_gpu_same_workload"] = single_gpu
+            if not args.no_cpu_baseline and not dist_on:
+                out["cpu_baseline"] = cpu_baseline(workload, scene_path, cfg, res)
         print(json.dumps(out))
     if dist_on:
         dist.destroy_process_group()

@@ -15,7 +15,7 @@ mkdir -p $O
 cd $R
 # --frames-in-flight 1: one frame at a time, so that a kernel's duration in the trace is that kernel on its own (the
 # roofline block of bench.py is about the dominant kernel of ONE frame; the default timed loop overlaps two frames)
-B="python3 bench.py --workload $W --stack-mode $M --no-cpu-baseline --warmup $WU --frames-in-flight 1"
+B="python3 bench.py --full --workload $W --stack-mode $M --no-cpu-baseline --warmup $WU --frames-in-flight 1"
 timeout -k 10 ${PASS_TIMEOUT:-400} rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- $B --steps $K > $O/bench_under_rocprof.json 2> $O/trace.err
 timeout -k 10 ${PASS_TIMEOUT:-400} rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch --output-format csv -- $B --steps $PS > /dev/null 2> $O/pmc_fetch.err
 timeout -k 10 ${PASS_TIMEOUT:-400} rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write --output-format csv -- $B --steps $PS > /dev/null 2> $O/pmc_write.err
@@ -26,7 +26,7 @@ timeout -k 10 ${PASS_TIMEOUT:-400} rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_
 # (bench.py only quotes a summary taken from exactly these kernel sources), then once more to file the plain line next to them;
 # profiles/r04/ of the box travels back under gpurun_out/ (the only directory gpurun merges)
 python3 profiles/summarize_r04.py $W $M > $O/summary.log 2>&1 || cat $O/summary.log
-python3 bench.py --workload $W --stack-mode $M --no-cpu-baseline --warmup $WU --steps $K > $O/bench_plain.json 2> $O/bench_plain.err
+python3 bench.py --full --workload $W --stack-mode $M --no-cpu-baseline --warmup $WU --steps $K > $O/bench_plain.json 2> $O/bench_plain.err
 python3 profiles/summarize_r04.py $W $M > $O/summary.log 2>&1 || cat $O/summary.log
 python3 profiles/tools/frame_timeline.py $(ls -S $O/trace/*/*_kernel_trace.csv | head -1) > $O/frame_timeline.txt 2>&1 || true
 mkdir -p $R/gpurun_out/prof_r04/summary && cp profiles/r04/${W}_${M}_* $O/frame_timeline.txt $R/gpurun_out/prof_r04/summary/ 2>/dev/null; cp $O/frame_timeline.txt $R/gpurun_out/prof_r04/summary/${W}_${M}_frame_timeline.txt 2>/dev/null

@@ -1,7 +1,7 @@
 #!/bin/bash
 # ab_c4.sh NAME...: cfg4 per-pixel + literal (frames one at a time), product library against build/variants/libp3d_NAME.so
 out=$PWD/gpurun_out/ab_c4; rm -rf $out; mkdir -p $out
-run() { P3D_LIB=$2 python3 bench.py --workload cfg4 --stack-mode $3 --no-cpu-baseline --steps 6 --warmup 3 --frames-in-flight 1 2>$out/$1.err | tail -1 > $out/$1.json; }
+run() { P3D_LIB=$2 python3 bench.py --full --workload cfg4 --stack-mode $3 --no-cpu-baseline --steps 6 --warmup 3 --frames-in-flight 1 2>$out/$1.err | tail -1 > $out/$1.json; }
 V=$PWD/build/variants
 for rep in 1 2; do
   for mode in per_pixel literal; do

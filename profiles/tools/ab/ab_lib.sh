@@ -1,7 +1,7 @@
 #!/bin/bash
 # ab_lib.sh NAME... : bench (loop 1000 + 20 steps) for the tree's library and build/variants/libp3d_NAME.so, alternating
 out=$PWD/gpurun_out/ab_lib; rm -rf $out; mkdir -p $out
-run() { P3D_LIB=$2 python3 bench.py --no-cpu-baseline --steps $3 --warmup $4 2>$out/$1.err | tail -1 > $out/$1.json; }
+run() { P3D_LIB=$2 python3 bench.py --full --no-cpu-baseline --steps $3 --warmup $4 2>$out/$1.err | tail -1 > $out/$1.json; }
 for rep in 1 2; do
   run head_1000_$rep "" 1000 20
   for v in "$@"; do run ${v}_1000_$rep $PWD/build/variants/libp3d_$v.so 1000 20; done

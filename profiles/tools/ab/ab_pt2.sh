@@ -4,7 +4,7 @@ for rep in 1 2; do
   for w in cfg3 cfg4; do
     st=4; [ $w = cfg4 ] && st=6
     (cd build/r02tree && python3 bench.py --workload $w --no-cpu-baseline --steps $st --warmup 2 2>$out/r02.err | tail -n 1 > $out/${w}_r02_$rep.json)
-    python3 bench.py --workload $w --no-cpu-baseline --steps $st --warmup 2 2>$out/head.err | tail -n 1 > $out/${w}_head_$rep.json
+    python3 bench.py --full --workload $w --no-cpu-baseline --steps $st --warmup 2 2>$out/head.err | tail -n 1 > $out/${w}_head_$rep.json
   done
 done
 python3 - <<'PY'

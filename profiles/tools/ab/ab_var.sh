@@ -3,9 +3,9 @@
 out=$PWD/gpurun_out/ab_var; rm -rf $out; mkdir -p $out
 for rep in ${REPS:-1 2}; do
   (cd build/r02tree && python3 bench.py --no-cpu-baseline --steps ${STEPS:-200} --warmup 20 2>$out/r02.err | tail -1 > $out/00_r02_$rep.json)
-  python3 bench.py --no-cpu-baseline --steps ${STEPS:-200} --warmup 20 2>$out/head.err | tail -1 > $out/01_head_$rep.json
+  python3 bench.py --full --no-cpu-baseline --steps ${STEPS:-200} --warmup 20 2>$out/head.err | tail -1 > $out/01_head_$rep.json
   for v in "$@"; do
-    P3D_LIB=$PWD/build/variants/libp3d_$v.so python3 bench.py --no-cpu-baseline --steps ${STEPS:-200} --warmup 20 2>$out/$v.err | tail -1 > $out/10_${v}_$rep.json
+    P3D_LIB=$PWD/build/variants/libp3d_$v.so python3 bench.py --full --no-cpu-baseline --steps ${STEPS:-200} --warmup 20 2>$out/$v.err | tail -1 > $out/10_${v}_$rep.json
   done
 done
 python3 - <<'PY'

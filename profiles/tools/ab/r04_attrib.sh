@@ -4,7 +4,7 @@
 out=$PWD/gpurun_out/r04_attrib; rm -rf $out; mkdir -p $out
 V=$PWD/build/variants
 run() {  # name lib skip steps
-  P3D_LIB=$2 P3D_ABL_SKIP=$3 python3 bench.py --no-cpu-baseline --steps $4 --warmup 20 2>$out/$1.err | tail -1 > $out/$1.json
+  P3D_LIB=$2 P3D_ABL_SKIP=$3 python3 bench.py --full --no-cpu-baseline --steps $4 --warmup 20 2>$out/$1.err | tail -1 > $out/$1.json
 }
 for rep in 1 2; do
   for steps in 1000 20; do

@@ -2,7 +2,7 @@
 # ladder after the tile-ordered repair launch: P3D_ABL_SKIP 1 = no round-0 tile launch (check + repair), 4 = no round 1 / persistent
 out=$PWD/gpurun_out/r04_attrib2; rm -rf $out; mkdir -p $out
 V=$PWD/build/variants
-run() { P3D_LIB=$2 P3D_ABL_SKIP=$3 python3 bench.py --no-cpu-baseline --steps $4 --warmup 20 2>$out/$1.err | tail -1 > $out/$1.json; }
+run() { P3D_LIB=$2 P3D_ABL_SKIP=$3 python3 bench.py --full --no-cpu-baseline --steps $4 --warmup 20 2>$out/$1.err | tail -1 > $out/$1.json; }
 for rep in 1 2; do
   for steps in 1000 20; do
     run head_${steps}_$rep "" 0 $steps
@@ -21,6 +21,7 @@ for f in sorted(glob.glob('gpurun_out/r04_attrib2/*.json')):
     except Exception as e: print(f, 'ERR', e)
 PY
 export TMPDIR=/tmp
-rm -rf $PWD/gpurun_out/r04_trace; mkdir -p $PWD/gpurun_out/r04_trace
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $PWD/gpurun_out/r04_trace --output-format csv -- python3 bench.py --no-cpu-baseline --warmup 3 --frames-in-flight 1 --steps 20 > $PWD/gpurun_out/r04_trace/bench.json 2> $PWD/gpurun_out/r04_trace/err.log
-python3 profiles/tools/frame_timeline.py $(ls -S $PWD/gpurun_out/r04_trace/*/*_kernel_trace.csv | head -1)
+tr=$(dirname $out)/r04_trace  # next to this script's other output
+rm -rf $tr; mkdir -p $tr
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $tr --output-format csv -- python3 bench.py --full --no-cpu-baseline --warmup 3 --frames-in-flight 1 --steps 20 > $tr/bench.json 2> $tr/err.log
+python3 profiles/tools/frame_timeline.py $(ls -S $tr/*/*_kernel_trace.csv | head -1)

@@ -2,7 +2,7 @@
 # why do the tiny round-1 launches cost the loop 7 %?  skip 4 = not launched; 8 = launched, finds an empty list; w3 = list kernel without scratch
 out=$PWD/gpurun_out/r04_attrib3; rm -rf $out; mkdir -p $out
 V=$PWD/build/variants
-run() { P3D_LIB=$2 P3D_ABL_SKIP=$3 python3 bench.py --no-cpu-baseline --steps $4 --warmup 20 2>$out/$1.err | tail -1 > $out/$1.json; }
+run() { P3D_LIB=$2 P3D_ABL_SKIP=$3 python3 bench.py --full --no-cpu-baseline --steps $4 --warmup 20 2>$out/$1.err | tail -1 > $out/$1.json; }
 for rep in 1 2; do
   for steps in 1000; do
     run head_${steps}_$rep "" 0 $steps

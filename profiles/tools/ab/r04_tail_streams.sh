@@ -3,7 +3,7 @@
 out=$PWD/gpurun_out/ab_tail; rm -rf $out; mkdir -p $out
 run() { # name steps warm fif bulk tail [hwq]
   if [ -n "$7" ]; then export GPU_MAX_HW_QUEUES=$7; else unset GPU_MAX_HW_QUEUES; fi
-  python3 bench.py --no-cpu-baseline --steps $2 --warmup $3 --frames-in-flight $4 --bulk-streams $5 --tail-streams $6 2>$out/$1.err | tail -1 > $out/$1.json; }
+  python3 bench.py --full --no-cpu-baseline --steps $2 --warmup $3 --frames-in-flight $4 --bulk-streams $5 --tail-streams $6 2>$out/$1.err | tail -1 > $out/$1.json; }
 for rep in 1 2; do
   run base_f4_$rep 1000 20 4 2 0
   run t_f4_b2_t2_$rep 1000 20 4 2 2

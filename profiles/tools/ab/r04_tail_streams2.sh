@@ -1,6 +1,6 @@
 #!/bin/bash
 out=$PWD/gpurun_out/ab_tail; rm -rf $out; mkdir -p $out
-run() { python3 bench.py --no-cpu-baseline --steps $2 --warmup $3 --frames-in-flight $4 --bulk-streams $5 --tail-streams $6 2>$out/$1.err | tail -1 > $out/$1.json; }
+run() { python3 bench.py --full --no-cpu-baseline --steps $2 --warmup $3 --frames-in-flight $4 --bulk-streams $5 --tail-streams $6 2>$out/$1.err | tail -1 > $out/$1.json; }
 for rep in 1 2; do
   run base_f4_$rep 1000 20 4 2 0
   for f in 5 6 7 8 10 12 16; do run t_f${f}_b2_t2_$rep 1000 20 $f 2 2; done

@@ -1,6 +1,6 @@
 #!/bin/bash
 out=$PWD/gpurun_out/ab_tail; rm -rf $out; mkdir -p $out
-run() { python3 bench.py --no-cpu-baseline --steps $2 --warmup $3 --tail-streams $4 2>$out/$1.err | tail -1 > $out/$1.json; }
+run() { python3 bench.py --full --no-cpu-baseline --steps $2 --warmup $3 --tail-streams $4 2>$out/$1.err | tail -1 > $out/$1.json; }
 for rep in 1 2 3; do
   run tail_1000_$rep 1000 20 2
   run whole_1000_$rep 1000 20 0

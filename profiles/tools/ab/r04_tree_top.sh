@@ -3,7 +3,7 @@
 # variants built with mkvariant_src.sh from csrc + profiles/r04/experiments/tree_top_probe.patch.txt (topl: no flag; toprf: -DP3D_ABL_TOP_REFETCH=63)
 out=$PWD/gpurun_out/ab_top; rm -rf $out; mkdir -p $out
 run() { # name lib levels mode
-  P3D_LIB=$2 P3D_BFS_TOP_LEVELS=$3 python3 bench.py --workload cfg4 --stack-mode $4 --no-cpu-baseline --steps 6 --warmup 3 --frames-in-flight 1 2>$out/$1.err | tail -1 > $out/$1.json; }
+  P3D_LIB=$2 P3D_BFS_TOP_LEVELS=$3 python3 bench.py --full --workload cfg4 --stack-mode $4 --no-cpu-baseline --steps 6 --warmup 3 --frames-in-flight 1 2>$out/$1.err | tail -1 > $out/$1.json; }
 V=$PWD/build/variants
 for rep in 1 2; do
   for mode in per_pixel literal; do

@@ -1273,14 +1273,14 @@ def test_hand_off_launches_on_a_tail_stream_render_the_same_bits(tri5k_path):
 
 
 def test_bench_contract_json_line():
-    """bench.py prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline`.  The headline value is
+    """bench.py --full prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline`.  The headline value is
     the LITERAL frame (bit-identical to the reference's order); the roofline is a bound (frac <= 1 whenever the PMC
     summary of this workload matches the kernel sources, null otherwise — stale counters are not quoted)."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1313,11 +1313,42 @@ def test_bench_contract_json_line():
     assert len(cb["one_socket"]["runs"]) == 3 and cb["one_socket"]["cores"] <= cb["one_socket"]["logical_cpus"]
 
 
-def test_rccl_gather_path_runs_with_one_rank():
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps once and prints the headline only; --dump-outputs writes
+    the frame of the last timed step, and that frame is, bit for bit, what one scene renders for the same workload."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT, SCENES
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mrays/s (primary+secondary)" and d["unit"] == "Mrays/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert d["config"]["rays_per_frame"] == 4944908
+    assert abs(d["value"] - 4944908 / (d["ms_per_step"] * 1e3)) < 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "per_pixel_stack", "frame", "ms_per_step_repeats"):
+        assert k not in d, k
+    rgb, hit, rgb8 = (np.load(str(out / (n + ".npy"))) for n in ("rgb", "hit", "rgb8"))
+    assert rgb.dtype == np.float32 and hit.dtype == np.float64 and rgb8.dtype == np.float32
+    assert rgb.shape == (1024, 1024, 3) and hit.shape == (1024, 1024) and rgb8.shape == (1024, 1024, 3)
+    hs = p3d.HostScene(os.path.join(SCENES, "balls_low.p3f"))
+    hs.set_resolution(1024, 1024)
+    dev = p3d.DeviceScene(hs, bvh=True)
+    e_rgb, e_hit, e_rgb8, _ = dev.render(p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4), want_rgb8=True)
+    assert (hit == e_hit).all() and (rgb.view(np.uint32) == e_rgb.view(np.uint32)).all() and (rgb8 == e_rgb8).all()
+
+
+def test_rccl_gather_path_runs_with_one_rank(tri100k_path, tmp_path):
     """The production collective - torch.distributed backend "nccl" = RCCL, device tensors, bench.py's double-buffered
     send / finish / drain around p3d.gather_frame and p3d.assemble_frame - executed on this one-GPU box: `--force-dist`
     takes the N > 1 path with a single rank, launched the way the driver launches ranks.  The assembled frame must equal
-    the frame rendered directly, bit for bit (bench.py checks and reports that itself)."""
+    the frame rendered directly, bit for bit (bench.py checks and reports that itself), and so must the frame that
+    --dump-outputs writes from rank 0's assembled frames."""
     import json
     import subprocess
     import sys
@@ -1325,7 +1356,7 @@ def test_rccl_gather_path_runs_with_one_rank():
     port = 31500 + os.getpid() % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--backend", "nccl",
-           "--workload", "tri100k", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+           "--workload", "tri100k", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1334,6 +1365,13 @@ def test_rccl_gather_path_runs_with_one_rank():
     par = d["config"]["parallelism"]
     assert "RCCL" in par and "gathered frame vs single-GPU frame: ok" in par, par
     assert d["single_gpu_same_workload"]["value"] > 0 and d["value"] > 0
+    rgb, hit = np.load(str(tmp_path / "out" / "rgb.npy")), np.load(str(tmp_path / "out" / "hit.npy"))
+    assert sorted(os.listdir(str(tmp_path / "out"))) == ["hit.npy", "rgb.npy"]  # the f32 gather: no u8 image on rank 0
+    assert rgb.dtype == np.float32 and rgb.shape == (1024, 1024, 3) and hit.dtype == np.float64 and hit.shape == (1024, 1024)
+    hs = p3d.HostScene(tri100k_path)
+    hs.set_resolution(1024, 1024)
+    e_rgb, e_hit, _ = p3d.DeviceScene(hs, bvh=True).render(p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=6))
+    assert (hit == e_hit).all() and (rgb.view(np.uint32) == e_rgb.view(np.uint32)).all()
 
 
 def test_two_ranks_on_one_gpu_gather_the_single_gpu_frame():
@@ -1348,7 +1386,7 @@ def test_two_ranks_on_one_gpu_gather_the_single_gpu_frame():
     port = 29500 + os.getpid() % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "tri100k",
-           "--gather", "f32", "--steps", "3", "--warmup", "1"]
+           "--gather", "f32", "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -297,3 +297,34 @@ def test_bench_counts_the_instructions_of_a_frame_of_the_profiled_stack_mode_onl
                            "sched_build_kernel": k(2, 0.02), "__amd_rocclr_copyBuffer": k(100, 0.001)}}
     assert abs(bench.frame_valu_instructions(summary, True) - (60.0 + 7.0 + 2 * 0.5 + 0.25 + 0.011)) < 1e-9
     assert abs(bench.frame_valu_instructions(summary, False) - 58.0 * 1.01) < 1e-9
+
+
+def test_bench_dump_outputs_types_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files; above the size limit every array keeps the same seeded sample of
+    pixels, the same from run to run, with its pixel indices, and the files stay within the limit."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    h, w = 64, 48
+    frame = {"rgb": rng.random((h, w, 3), dtype=np.float32), "hit": rng.integers(-1, 1 << 30, (h, w), dtype=np.int32),
+             "rgb8": rng.integers(0, 256, (h, w, 3), dtype=np.uint8)}
+    shapes = bench.dump_outputs(str(tmp_path / "whole"), frame)
+    assert shapes == {"rgb": (h, w, 3), "hit": (h, w), "rgb8": (h, w, 3)}
+    got = {k: np.load(str(tmp_path / "whole" / (k + ".npy"))) for k in shapes}
+    assert got["rgb"].dtype == np.float32 and (got["rgb"] == frame["rgb"]).all()
+    assert got["hit"].dtype == np.float64 and (got["hit"] == frame["hit"]).all()
+    assert got["rgb8"].dtype == np.float32 and (got["rgb8"] == frame["rgb8"]).all()
+    limit = 40000
+    for run in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / run), frame, limit=limit)
+        assert set(shapes) == {"rgb", "hit", "rgb8", "pixel_index"}
+        assert sum(os.path.getsize(str(tmp_path / run / (k + ".npy"))) for k in shapes) <= limit
+    idx = np.load(str(tmp_path / "a" / "pixel_index.npy"))
+    assert idx.dtype == np.float64 and 0 < len(idx) < h * w and (np.diff(idx) > 0).all()
+    assert (idx == np.load(str(tmp_path / "b" / "pixel_index.npy"))).all()
+    flat = idx.astype(np.int64)
+    for k in ("rgb", "hit", "rgb8"):
+        a = np.load(str(tmp_path / "a" / (k + ".npy")))
+        assert (a == np.load(str(tmp_path / "b" / (k + ".npy")))).all()
+        assert (a == frame[k].reshape((h * w,) + frame[k].shape[2:])[flat]).all()
