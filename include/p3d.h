@@ -394,6 +394,43 @@ int p3d_scene_set_tail_stream(p3d_scene* scene, void* tail_hip_stream);
 int p3d_scene_join(p3d_scene* scene, void* hip_stream, int host_wait);
 
 /*
+ * Progressive accumulation: one anti-aliased frame rendered in passes over its samples, the image shown (or the frame
+ * stopped) after any of them - what the reference's drawModeEnabled display (main.cpp:45-48) does line by line, by sample
+ * instead.  A caller detects these entry points by the symbols being present (P3D_ABI_VERSION is unchanged).
+ *
+ * p3d_accum_create copies `cfg` and `tile` and allocates, on the scene's device, w*h running sums (3 float) and w*h first
+ * hits.  An accumulator belongs to its scene: destroy it before the scene.  Every pass renders samples [done, done + n) of
+ * every pixel of the tile, adds them to the running sums in sample order and advances `done`:
+ *   rgb    : sum / (float)done - after the last pass exactly sum / (float)(SPP*SPP), main.cpp:800
+ *   rgb8   : gamma + u8fromfloat of that value
+ *   hit_id : the first sample's primary hit, kept in the accumulator and written by every pass
+ * Exactness: every (pixel, sample) draws from its own RNG stream and a pixel's samples are added one at a time in sample
+ * order whatever the pass boundaries, so the pass that completes SPP*SPP samples writes the same bits as
+ * p3d_render_tile(_device) of the same cfg / tile, and any two partitions of samples [0, m) give the same bits after m.
+ * Summed over the passes of a frame, the rays_* / *_tests / shaded_hits counters equal the one-shot frame's; p3d_stats
+ * describes one pass (pixels = w*h per pass).
+ *
+ * Accepted: cfg->antialiasing = 1; every PATHTRACE configuration; WHITTED with P3D_STACK_PER_PIXEL or accel != BVH.
+ * Refused at create with P3D_ERR_UNSUPPORTED: antialiasing = 0 (no sample loop), and WHITTED + BVH + P3D_STACK_LITERAL
+ * (the serial order hands the hit_stack from pixel p's last sample to pixel p+1's first: no split over samples keeps it).
+ * A pass with n == 0 or done + n > SPP*SPP returns P3D_ERR_INVALID and changes nothing.  After a pass that returned an
+ * error the accumulator refuses passes (P3D_ERR_INVALID) until p3d_accum_reset, which goes back to 0 samples.
+ *
+ * p3d_accum_render is the host-buffer form (synchronous).  p3d_accum_render_device enqueues the pass on `hip_stream`
+ * under the scene's stream rules (p3d_render_tile_device): without `stats` it returns without waiting, and an error the
+ * device detects shows in p3d_scene_status - after such an error, reset every accumulator of the scene rendered since
+ * the last check.  Output pointers may be NULL.
+ */
+typedef struct p3d_accum p3d_accum;
+int p3d_accum_create(p3d_scene* scene, const p3d_config* cfg, const p3d_tile* tile, p3d_accum** out);
+void p3d_accum_destroy(p3d_accum* acc);
+int p3d_accum_reset(p3d_accum* acc);
+uint32_t p3d_accum_samples_done(const p3d_accum* acc);
+int p3d_accum_render(p3d_accum* acc, uint32_t n, float* rgb, int32_t* hit_id, uint8_t* rgb8, p3d_stats* stats);
+int p3d_accum_render_device(p3d_accum* acc, uint32_t n, float* d_rgb, int32_t* d_hit_id, uint8_t* d_rgb8,
+                            void* hip_stream, p3d_stats* stats);
+
+/*
  * Errors a kernel detects while it runs (a hit_stack leftover that outgrew its record, a work list of the hit_stack
  * hand-off that overflowed or did not run empty within its round bound, a row of a stripe or sub-rectangle whose
  * incoming hit_stack could not be established, a sample hand-out loop that reached its trip bound and would write pixels

@@ -37,6 +37,7 @@ EXPORTS = [
     "p3d_trace_closest", "p3d_trace_any", "p3d_host_scene_load", "p3d_host_scene_destroy",
     "p3d_host_scene_set_resolution", "p3d_host_scene_set_lens", "p3d_host_scene_replicate_lights",
     "p3d_host_scene_desc", "p3d_host_scene_bind_device", "p3d_host_scene_has_skybox", "p3d_host_scene_load_skybox", "p3d_host_scene_skybox_face",
+    "p3d_accum_create", "p3d_accum_destroy", "p3d_accum_reset", "p3d_accum_samples_done", "p3d_accum_render", "p3d_accum_render_device",
 ]
 
 
@@ -188,6 +189,15 @@ def lib():
         L.p3d_scene_set_tail_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.p3d_scene_join.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.p3d_debug_scene_limits.argtypes = [C.c_void_p, C.c_void_p]  # csrc/p3d_debug.h: not part of include/p3d.h
+        L.p3d_accum_create.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Tile), C.POINTER(C.c_void_p)]
+        L.p3d_accum_destroy.argtypes = [C.c_void_p]
+        L.p3d_accum_destroy.restype = None
+        L.p3d_accum_reset.argtypes = [C.c_void_p]
+        L.p3d_accum_samples_done.argtypes = [C.c_void_p]
+        L.p3d_accum_samples_done.restype = C.c_uint32
+        L.p3d_accum_render.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.p3d_accum_render_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(Stats)]
         _lib = L
     return _lib
 
@@ -384,6 +394,25 @@ class DeviceScene:
             return rgb, hit, rgb8, st
         return rgb, hit, st
 
+    def accumulator(self, cfg, tile=None):
+        """p3d_accum_create: an Accumulator that renders this frame (cfg, tile) in passes over its samples; the pass that
+        completes the SPP*SPP samples returns the same bits as render(cfg, tile).  Raises P3DError (P3D_ERR_UNSUPPORTED)
+        for antialiasing = 0 and for Whitted over the BVH with P3D_STACK_LITERAL."""
+        return Accumulator(self, cfg, tile or self.full_tile())
+
+    def render_progressive(self, cfg, samples_per_pass, tile=None, want_rgb8=False, stats=True):
+        """Renders the frame in passes of `samples_per_pass` samples (the last one takes what is left) and yields
+        (samples_done, render tuple) after every pass; the last one is the frame render(cfg, tile) returns."""
+        if samples_per_pass < 1:
+            raise ValueError("samples_per_pass must be at least 1")
+        acc = self.accumulator(cfg, tile)
+        try:
+            while acc.samples_done < acc.total:
+                out = acc.render(min(samples_per_pass, acc.total - acc.samples_done), want_rgb8=want_rgb8, stats=stats)
+                yield acc.samples_done, out
+        finally:
+            acc.close()
+
     def status(self):
         """p3d_scene_status: waits for the device, returns P3D_OK (0) or the code of a device-detected error of the
         asynchronous render_device calls since the last check (message: last_error())."""
@@ -454,6 +483,62 @@ class DeviceScene:
         occ = np.zeros(n, np.uint8)
         _check(self._L.p3d_trace_any(self._h, int(accel), n, o.ctypes.data, d.ctypes.data, occ.ctypes.data))
         return occ
+
+
+class Accumulator:
+    """p3d_accum (include/p3d.h): one anti-aliased frame of a DeviceScene rendered in passes over its samples, the running
+    sums kept on the device.  Every pass renders samples [samples_done, samples_done + n) of every pixel; rgb is the mean of
+    the samples so far, hit_id the first sample's hit.  Close it (or let it go) before the scene."""
+
+    def __init__(self, scene, cfg, tile):
+        self._L = scene._L
+        self.scene = scene  # (keeps the scene alive while the accumulator is)
+        self.cfg = cfg
+        self.tile = tile
+        self.total = int(cfg.spp_sqrt) ** 2
+        h = C.c_void_p()
+        _check(self._L.p3d_accum_create(scene._h, C.byref(cfg), C.byref(tile), C.byref(h)))
+        self._h = h
+
+    @property
+    def samples_done(self):
+        return int(self._L.p3d_accum_samples_done(self._h))
+
+    def reset(self):
+        """Back to 0 samples (also what lets an accumulator whose pass failed render again)."""
+        _check(self._L.p3d_accum_reset(self._h))
+
+    def render(self, n, want_rgb8=False, stats=True):
+        """p3d_accum_render: the next n samples; returns numpy arrays, the same tuple as DeviceScene.render."""
+        t = self.tile
+        rgb = np.zeros((t.h, t.w, 3), np.float32)
+        hit = np.zeros((t.h, t.w), np.int32)
+        rgb8 = np.zeros((t.h, t.w, 3), np.uint8) if want_rgb8 else None
+        st = Stats()
+        _check(self._L.p3d_accum_render(self._h, int(n), rgb.ctypes.data, hit.ctypes.data,
+                                        rgb8.ctypes.data if want_rgb8 else None, C.byref(st) if stats else None))
+        if want_rgb8:
+            return rgb, hit, rgb8, st
+        return rgb, hit, st
+
+    def render_device(self, n, d_rgb=0, d_hit=0, d_rgb8=0, stream=0, stats=None):
+        """p3d_accum_render_device: raw HBM addresses and a hipStream_t (or a torch.cuda.Stream); without stats the pass
+        is only enqueued - DeviceScene.status() reports what the device detected."""
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_accum_render_device(self._h, int(n), C.c_void_p(d_rgb or None), C.c_void_p(d_hit or None),
+                                               C.c_void_p(d_rgb8 or None), C.c_void_p(raw or None),
+                                               C.byref(stats) if stats is not None else None))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.p3d_accum_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def stripe_tile(res, rank, world, stripe_h=16):

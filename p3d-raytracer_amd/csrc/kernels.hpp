@@ -151,6 +151,13 @@ struct RenderParams {
   const uint32_t* wf_total;  // rays in the sorted queue this launch reads
   float4* wf_sorted;       // [units][2] the queue in bin order
   F3 wf_cell_origin, wf_cell_scale;  // cell = (origin - wf_cell_origin) * wf_cell_scale, clamped to [0, kWfCellsPerAxis)
+  // Sample range of this launch (anti-aliased kernels only; p3d_accum, include/p3d.h): samples [sample_begin, sample_end) of
+  // every pixel.  A whole frame is [0, SPP^2) with no accumulator.  With sample_begin > 0 a pixel's running sum and first
+  // hit start from accum_sum / accum_hit; with accum_sum set the raw sum and first hit are stored there at the end.  (Last in
+  // the struct: the kernarg offsets of every field above stay what they were.)
+  uint32_t sample_begin, sample_end;
+  float* accum_sum;        // [3 * pixel] running sum of the samples so far (before the division by the sample count)
+  int32_t* accum_hit;      // [pixel] first hit of global sample 0
 };
 
 // LDS map of one workgroup:  [ staged scene (lds_scene_f4 float4) | node stack (cap * 64 * 8 B) | per-pixel sample ring (PT, 4 lanes per pixel) ]
@@ -525,8 +532,8 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
   // per-pixel sample hand-out state behind the node stack (only allocated for SUB == 4); explicit LDS address space
   LdsPtPixelShared& shared = *(LdsPtPixelShared*)(smem + P.lds_scene_f4 + stack_lds_f4(SPILL, P.stack_cap));
   if (SUB == 4 && sub == 0) {
-    shared.next_start[px] = 0;
-    shared.next_add[px] = 0;
+    shared.next_start[px] = P.sample_begin;
+    shared.next_add[px] = P.sample_begin;
     shared.first_hit[px] = -1;
     shared.colour[0][px] = 0.0f; shared.colour[1][px] = 0.0f; shared.colour[2][px] = 0.0f;
     for (int k = 0; k < kPtRing; ++k) shared.tag[k][px] = 0;
@@ -638,19 +645,36 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
     if (EARLY_HIT) { if (P.hit_id && !(LIT != 0 && up.halo)) P.hit_id[(size_t)r * P.w + c] = (obj); }        \
     else first_hit = (obj);                                                                                  \
   } while (0)
-        if (SUB == 1) {
+        // a later pass of an accumulated frame goes on from the running sum and first hit the passes before it left
+        if (AA && LIT == 0 && P.sample_begin > 0 && (SUB == 1 || sub == 0)) {
+          const size_t k = (size_t)r * P.w + c;
+          color = f3(P.accum_sum[3 * k], P.accum_sum[3 * k + 1], P.accum_sum[3 * k + 2]);
+          first_hit = P.accum_hit[k];
+          if (SUB == 4) {
+            shared.colour[0][px] = color.x; shared.colour[1][px] = color.y; shared.colour[2][px] = color.z;
+            shared.first_hit[px] = first_hit;
+          }
+        }
+        if (SUB == 1 && !AA) {
           for (int si = 0; si < SPP; ++si) {
             for (int sj = 0; sj < SPP; ++sj) {
 #include "whitted_sample.inc"
               color = color + result;
             }
           }
+        } else if (SUB == 1) {  // samples [sample_begin, sample_end) in sample order
+          int si = (int)P.sample_begin / SPP, sj = (int)P.sample_begin - si * SPP;
+          for (int s = (int)P.sample_begin; s < (int)P.sample_end; ++s) {
+#include "whitted_sample.inc"
+            color = color + result;
+            if (++sj == SPP) { sj = 0; ++si; }
+          }
         } else {
           // Lanes of one wave wait for each other here (full ring, lane 0 waiting for the last samples of its pixel),
           // so the loop is wave-uniform — a ballot every lane takes part in decides its end, a waiting lane sits out
           // the rest of the trip — exactly as in pt_kernel (where a per-lane `continue` got split off as an inner loop).
-          const int n_samples = SPP * SPP;
-          const unsigned long long trips_max = P.debug_trip_bound ? (unsigned long long)P.debug_trip_bound : (unsigned long long)n_samples * 2ull + 1024ull;
+          const uint32_t s_end = P.sample_end;  // one past the last sample of this launch
+          const unsigned long long trips_max = P.debug_trip_bound ? (unsigned long long)P.debug_trip_bound : (unsigned long long)(s_end - P.sample_begin) * 2ull + 1024ull;
           uint32_t trips_left = trips_max > 0xffffffffull ? 0xffffffffu : (uint32_t)trips_max;
           const uint32_t spp_magic = (uint32_t)((0x100000000ull + (unsigned)SPP - 1) / (unsigned)SPP);
           bool done = false, holding = false;
@@ -664,13 +688,13 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
             if (done) continue;
             if (sub == 0) {  // add finished samples to the pixel colour, strictly in sample order
               uint32_t na = shared.next_add[px];
-              if (na < (uint32_t)n_samples && shared.tag[na % kPtRing][px] == na + 1) {
+              if (na < s_end && shared.tag[na % kPtRing][px] == na + 1) {
                 F3 sum = f3(shared.colour[0][px], shared.colour[1][px], shared.colour[2][px]);
                 do {
                   const int k = (int)(na % kPtRing);
                   sum = sum + f3(shared.radiance[k][0][px], shared.radiance[k][1][px], shared.radiance[k][2][px]);
                   ++na;
-                } while (na < (uint32_t)n_samples && shared.tag[na % kPtRing][px] == na + 1);
+                } while (na < s_end && shared.tag[na % kPtRing][px] == na + 1);
                 shared.colour[0][px] = sum.x; shared.colour[1][px] = sum.y; shared.colour[2][px] = sum.z;
                 shared.next_add[px] = na;
               }
@@ -679,8 +703,8 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
               s = (int)__hip_atomic_fetch_add(&shared.next_start[px], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               holding = true;
             }
-            if (s >= n_samples) {  // nothing left to start: finished, except lane 0 while samples remain to be added
-              done = sub != 0 || shared.next_add[px] >= (uint32_t)n_samples;
+            if ((uint32_t)s >= s_end) {  // nothing left to start: finished, except lane 0 while samples remain to be added
+              done = sub != 0 || shared.next_add[px] >= s_end;
               continue;
             }
             if ((uint32_t)s >= shared.next_add[px] + kPtRing) continue;  // wait for room in the ring
@@ -699,7 +723,12 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
           }
         }
 #undef P3D_FIRST_HIT
-        if (AA) color = color / (float)(SPP * SPP);  // main.cpp:800
+        if (AA && LIT == 0 && P.accum_sum && (SUB == 1 || sub == 0)) {  // the running sum and first hit for the next pass
+          const size_t k = (size_t)r * P.w + c;
+          P.accum_sum[3 * k] = color.x; P.accum_sum[3 * k + 1] = color.y; P.accum_sum[3 * k + 2] = color.z;
+          P.accum_hit[k] = first_hit;
+        }
+        if (AA) color = color / (float)P.sample_end;  // main.cpp:800 (sample_end = SPP * SPP on a frame's last pass)
 #ifdef P3D_PT_PROFILE
         PT_REGION(8)
         prof.flush();

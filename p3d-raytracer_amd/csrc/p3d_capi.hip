@@ -732,13 +732,8 @@ int finish_stats(p3d_scene* s, hipStream_t st, p3d_stats* stats, bool literal) {
   return check_status(s);
 }
 
-}  // namespace
-
-extern "C" {
-
-int p3d_render_tile_device(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float* d_rgb, int32_t* d_hit,
-                           uint8_t* d_rgb8, void* hip_stream, p3d_stats* stats) {
-  if (!s || !cfg || !tile) return fail(P3D_ERR_INVALID, "p3d_render_tile_device: null argument");
+// What every render call checks before it touches the device: the tile lies in the image, the options are known.
+int check_frame(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile) {
   if (int rc = check_accel(s, cfg->accel)) return rc;
   const DevCamera& cam = s->dev.cam;
   if (cam.res_x <= 0 || cam.res_y <= 0) return fail(P3D_ERR_INVALID, "scene has no camera");
@@ -762,6 +757,17 @@ int p3d_render_tile_device(p3d_scene* s, const p3d_config* cfg, const p3d_tile* 
     ;  // light replication (main.cpp:725-745) is a host-side scene edit: p3d_host_scene_replicate_lights
   if (cfg->accel == P3D_ACCEL_GRID && s->dev.n_objs == 0) return fail(P3D_ERR_UNSUPPORTED, "grid over an empty scene");
   if (cfg->skybox && !s->has_sky) return fail(P3D_ERR_INVALID, "config asks for SKYBOX but no cubemap was supplied (p3d_scene_set_skybox)");
+  return P3D_OK;
+}
+
+// The render path of p3d_render_tile_device (a whole frame: samples [0, SPP^2), no accumulator) and of p3d_accum_render_device
+// (samples [sample_begin, sample_end) of an anti-aliased frame whose running sums and first hits live in accum_sum /
+// accum_hit).  The sample range only reaches the anti-aliased sample loops; everything else is the same frame.
+int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float* d_rgb, int32_t* d_hit, uint8_t* d_rgb8,
+                void* hip_stream, p3d_stats* stats, uint32_t sample_begin, uint32_t sample_end, float* accum_sum, int32_t* accum_hit) {
+  if (int rc = check_frame(s, cfg, tile)) return rc;
+  const DevCamera& cam = s->dev.cam;
+  const int sh = tile->stripe_h > 0 ? tile->stripe_h : 1, ss = tile->stripe_h > 0 ? tile->stripe_stride : 1;
   P3D_HIP(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)hip_stream;
   s->last_status = 0;
@@ -822,11 +828,15 @@ int p3d_render_tile_device(p3d_scene* s, const p3d_config* cfg, const p3d_tile* 
   P.stack_cap = (int32_t)cap;
   P.stack_spills = lds_spill ? 1u : 0u;
   P.lds_scene_f4 = P.blob_f4;
-  // path tracer with >= 16 samples per pixel: four lanes per pixel, 4x4-pixel tiles (pt_kernel SUB = 4)
+  P.sample_begin = sample_begin;
+  P.sample_end = sample_end;
+  // path tracer with >= 16 samples per pixel in the launch: four lanes per pixel, 4x4-pixel tiles (pt_kernel SUB = 4)
   // ... and anti-aliased Whitted launches with >= 4 samples per pixel over a scene traversed from L2 (whitted_kernel SUB = 4),
-  // unless the samples of a pixel have to hand the stack to each other in order (LITERAL)
-  const bool sub4 = (pt && cfg->spp_sqrt >= kPtSub4MinSppSqrt) ||
-                    (!pt && !literal && !lds_scene && cfg->antialiasing && cfg->spp_sqrt >= kWhittedSub4MinSppSqrt);
+  // unless the samples of a pixel have to hand the stack to each other in order (LITERAL).  Counted in the samples of THIS
+  // launch (a pass of an accumulated frame may have fewer than the frame): both loops add the same values in the same order.
+  const uint32_t launch_samples = sample_end - sample_begin;
+  const bool sub4 = (pt && launch_samples >= kPtSub4MinSppSqrt * kPtSub4MinSppSqrt) ||
+                    (!pt && !literal && !lds_scene && cfg->antialiasing && launch_samples >= kWhittedSub4MinSppSqrt * kWhittedSub4MinSppSqrt);
   // ... and behind the node stack: the sample ring of the four-lanes-per-pixel kernels, or the cold shading state of the
   // Whitted kernels that traverse the scene from L2 without anti-aliasing (ColdState<true>, device_core.hpp)
   const bool cold_lds = !pt && !lds_scene && !cfg->antialiasing;
@@ -1082,6 +1092,8 @@ int p3d_render_tile_device(p3d_scene* s, const p3d_config* cfg, const p3d_tile* 
       P.rgb = d_rgb ? d_rgb + 3 * off : nullptr;
       P.hit_id = d_hit ? d_hit + off : nullptr;
       P.rgb8 = d_rgb8 ? d_rgb8 + 3 * off : nullptr;
+      P.accum_sum = accum_sum ? accum_sum + 3 * off : nullptr;
+      P.accum_hit = accum_hit ? accum_hit + off : nullptr;
       hipError_t e = hipSuccess;
       if (per_level && pass == 0) {
         // level 0 over the tiles (+ halo chains), then one launch per chain level over the queue the level above wrote,
@@ -1202,6 +1214,17 @@ int p3d_render_tile_device(p3d_scene* s, const p3d_config* cfg, const p3d_tile* 
   return P3D_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int p3d_render_tile_device(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float* d_rgb, int32_t* d_hit,
+                           uint8_t* d_rgb8, void* hip_stream, p3d_stats* stats) {
+  if (!s || !cfg || !tile) return fail(P3D_ERR_INVALID, "p3d_render_tile_device: null argument");
+  const uint32_t samples = cfg->antialiasing ? cfg->spp_sqrt * cfg->spp_sqrt : 1u;
+  return render_impl(s, cfg, tile, d_rgb, d_hit, d_rgb8, hip_stream, stats, 0, samples, nullptr, nullptr);
+}
+
 int p3d_scene_set_tail_stream(p3d_scene* s, void* hip_stream) {
   if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_set_tail_stream: null scene");
   P3D_HIP(hipSetDevice(s->device));
@@ -1264,6 +1287,100 @@ int p3d_render_tile(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, f
   if (hit_id) P3D_HIP(hipMemcpy(hit_id, s->out_hit.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (rgb8) P3D_HIP(hipMemcpy(rgb8, s->out_rgb8.p, n * 3, hipMemcpyDeviceToHost));
   return P3D_OK;  // device-detected errors were turned into a return code by finish_stats()
+}
+
+}  // extern "C"
+
+// Progressive accumulation (include/p3d.h): a frame's samples in passes, its running sums kept on the device between them.
+struct p3d_accum {
+  p3d_scene* s = nullptr;
+  int device = 0;       // (destroy needs no scene)
+  p3d_config cfg{};
+  p3d_tile tile{};
+  uint32_t total = 0;   // SPP^2
+  uint32_t done = 0;    // samples [0, done) of every pixel are in the sums
+  bool failed = false;  // a pass returned an error: the sums are unknown until p3d_accum_reset
+  Scratch sum, hit;     // [3 * pixel] float running sums, [pixel] first hits
+};
+
+extern "C" {
+
+int p3d_accum_create(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, p3d_accum** out) {
+  if (!s || !cfg || !tile || !out) return fail(P3D_ERR_INVALID, "p3d_accum_create: null argument");
+  *out = nullptr;
+  if (!cfg->antialiasing)
+    return fail(P3D_ERR_UNSUPPORTED, "p3d_accum_create: antialiasing = 0 renders one sample per pixel; there is nothing to accumulate");
+  if (cfg->integrator == P3D_WHITTED && cfg->accel == P3D_ACCEL_BVH && cfg->stack_mode == P3D_STACK_LITERAL)
+    return fail(P3D_ERR_UNSUPPORTED, "p3d_accum_create: Whitted over the BVH with P3D_STACK_LITERAL hands the hit_stack from a pixel's last "
+                                     "sample to the next pixel's first, so no split over samples keeps the reference's order; use P3D_STACK_PER_PIXEL");
+  if (int rc = check_frame(s, cfg, tile)) return rc;
+  P3D_HIP(hipSetDevice(s->device));
+  p3d_accum* a = new p3d_accum;
+  a->s = s;
+  a->device = s->device;
+  a->cfg = *cfg;
+  a->tile = *tile;
+  a->total = cfg->spp_sqrt * cfg->spp_sqrt;
+  const size_t n = (size_t)tile->w * tile->h;
+  int rc = a->sum.ensure(n * 3 * sizeof(float));
+  if (!rc) rc = a->hit.ensure(n * sizeof(int32_t));
+  if (rc) {
+    p3d_accum_destroy(a);
+    return rc;
+  }
+  *out = a;
+  return P3D_OK;
+}
+
+void p3d_accum_destroy(p3d_accum* a) {
+  if (!a) return;
+  (void)hipSetDevice(a->device);
+  a->sum.release();
+  a->hit.release();
+  delete a;
+}
+
+int p3d_accum_reset(p3d_accum* a) {
+  if (!a) return fail(P3D_ERR_INVALID, "p3d_accum_reset: null accumulator");
+  a->done = 0;
+  a->failed = false;
+  return P3D_OK;
+}
+
+uint32_t p3d_accum_samples_done(const p3d_accum* a) { return a ? a->done : 0u; }
+
+int p3d_accum_render_device(p3d_accum* a, uint32_t n, float* d_rgb, int32_t* d_hit, uint8_t* d_rgb8, void* hip_stream, p3d_stats* stats) {
+  if (!a) return fail(P3D_ERR_INVALID, "p3d_accum_render_device: null accumulator");
+  if (a->failed) return fail(P3D_ERR_INVALID, "p3d_accum_render: a previous pass failed; p3d_accum_reset starts the frame again");
+  if (n == 0 || n > a->total - a->done)
+    return fail(P3D_ERR_INVALID, "p3d_accum_render: " + std::to_string(n) + " samples asked, " + std::to_string(a->total - a->done) +
+                                     " of " + std::to_string(a->total) + " left (n must be at least 1)");
+  const int rc = render_impl(a->s, &a->cfg, &a->tile, d_rgb, d_hit, d_rgb8, hip_stream, stats, a->done, a->done + n,
+                             (float*)a->sum.p, (int32_t*)a->hit.p);
+  if (rc) {
+    a->failed = true;
+    return rc;
+  }
+  a->done += n;
+  return P3D_OK;
+}
+
+int p3d_accum_render(p3d_accum* a, uint32_t n, float* rgb, int32_t* hit_id, uint8_t* rgb8, p3d_stats* stats) {
+  if (!a) return fail(P3D_ERR_INVALID, "p3d_accum_render: null accumulator");
+  p3d_scene* s = a->s;
+  P3D_HIP(hipSetDevice(s->device));
+  const size_t px = (size_t)a->tile.w * a->tile.h;
+  if (rgb) if (int rc = s->out_rgb.ensure(px * 3 * sizeof(float))) return rc;
+  if (hit_id) if (int rc = s->out_hit.ensure(px * sizeof(int32_t))) return rc;
+  if (rgb8) if (int rc = s->out_rgb8.ensure(px * 3)) return rc;
+  p3d_stats local;  // (always with stats: the call waits for the pass and reports what the device detected)
+  if (int rc = p3d_accum_render_device(a, n, rgb ? (float*)s->out_rgb.p : nullptr, hit_id ? (int32_t*)s->out_hit.p : nullptr,
+                                       rgb8 ? (uint8_t*)s->out_rgb8.p : nullptr, nullptr, stats ? stats : &local))
+    return rc;
+  if (rgb) P3D_HIP(hipMemcpy(rgb, s->out_rgb.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (hit_id) P3D_HIP(hipMemcpy(hit_id, s->out_hit.p, px * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (rgb8) P3D_HIP(hipMemcpy(rgb8, s->out_rgb8.p, px * 3, hipMemcpyDeviceToHost));
+  return P3D_OK;
 }
 
 static int trace_common(p3d_scene* s, uint32_t accel, uint32_t n, const float* origin, const float* direction, int32_t* hit_id,

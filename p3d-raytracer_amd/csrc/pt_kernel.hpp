@@ -92,8 +92,8 @@ __global__ void __launch_bounds__(kBlock, P3D_PT_WAVES) pt_kernel(const RenderPa
   // pointer would compile to flat_load/flat_store, which are not ordered with the ds_* traffic
   LdsPtPixelShared& shared = *(LdsPtPixelShared*)(smem + P.lds_scene_f4 + stack_lds_f4(PT_STACK, P.stack_cap));
   if (SUB == 4 && sub == 0) {
-    shared.next_start[px] = 0;
-    shared.next_add[px] = 0;
+    shared.next_start[px] = P.sample_begin;
+    shared.next_add[px] = P.sample_begin;
     shared.first_hit[px] = -1;
     shared.colour[0][px] = 0.0f; shared.colour[1][px] = 0.0f; shared.colour[2][px] = 0.0f;
     for (int k = 0; k < kPtRing; ++k) shared.tag[k][px] = 0;
@@ -105,14 +105,23 @@ __global__ void __launch_bounds__(kBlock, P3D_PT_WAVES) pt_kernel(const RenderPa
     const int x = P.x0 + c;
     const int y = P.y0 + (r / sh) * sh * ss + (r % sh);
     const int SPP = (int)P.spp_sqrt;
-    const int n_samples = SPP * SPP;
+    const uint32_t s_end = P.sample_end;  // one past the last sample of this launch (a whole frame: SPP * SPP)
     const int MAXD = P.max_depth;
     if (sub == 0) ct.add(kPixels);
 
     F3 color = f3(0, 0, 0);  // pixel accumulator (main.cpp:792)
     int first_hit = -1;
-    int s = 0;               // SUB == 1: next sample to start; SUB == 4: the sample this lane is tracing
-    int si = 0, sj = 0;
+    int s = (int)P.sample_begin;  // SUB == 1: next sample to start; SUB == 4: the sample this lane is tracing
+    int si = s / SPP, sj = s - si * SPP;
+    const size_t k_out = (size_t)r * P.w + c;
+    if (P.sample_begin > 0 && sub == 0) {  // a later pass of an accumulated frame: go on from what the passes before it left
+      color = f3(P.accum_sum[3 * k_out], P.accum_sum[3 * k_out + 1], P.accum_sum[3 * k_out + 2]);
+      first_hit = P.accum_hit[k_out];
+      if (SUB == 4) {
+        shared.colour[0][px] = color.x; shared.colour[1][px] = color.y; shared.colour[2][px] = color.z;
+        shared.first_hit[px] = first_hit;
+      }
+    }
     bool alive = false, in_sample = false, first_ray = false;
     Rng rng;
     RayS ray;
@@ -130,7 +139,7 @@ __global__ void __launch_bounds__(kBlock, P3D_PT_WAVES) pt_kernel(const RenderPa
     // instantiations and the waiting lanes starved the working ones.)  The trip bound is a backstop:
     // no lane can need more trips than the pixel's whole sample set traced by one lane.
     const unsigned long long trips_max = P.debug_trip_bound ? (unsigned long long)P.debug_trip_bound
-                                                            : (unsigned long long)n_samples * (unsigned)(MAXD + 2) * 4ull + 1024ull;
+                                                            : (unsigned long long)(s_end - P.sample_begin) * (unsigned)(MAXD + 2) * 4ull + 1024ull;
     uint32_t trips_left = trips_max > 0xffffffffull ? 0xffffffffu : (uint32_t)trips_max;
     bool done = false, holding = false;
     const uint32_t spp_magic = (uint32_t)((0x100000000ull + (unsigned)SPP - 1) / (unsigned)SPP);
@@ -148,13 +157,13 @@ __global__ void __launch_bounds__(kBlock, P3D_PT_WAVES) pt_kernel(const RenderPa
       // whenever it is between two of its own samples, and every fourth trip while it traces one
       if (SUB == 4 && sub == 0 && (!alive || (trips_left & 3) == 0)) {
         uint32_t na = shared.next_add[px];
-        if (na < (uint32_t)n_samples && shared.tag[na % kPtRing][px] == na + 1) {
+        if (na < s_end && shared.tag[na % kPtRing][px] == na + 1) {
           F3 sum = f3(shared.colour[0][px], shared.colour[1][px], shared.colour[2][px]);
           do {
             const int k = (int)(na % kPtRing);
             sum = sum + f3(shared.radiance[k][0][px], shared.radiance[k][1][px], shared.radiance[k][2][px]);
             ++na;
-          } while (na < (uint32_t)n_samples && shared.tag[na % kPtRing][px] == na + 1);
+          } while (na < s_end && shared.tag[na % kPtRing][px] == na + 1);
           shared.colour[0][px] = sum.x; shared.colour[1][px] = sum.y; shared.colour[2][px] = sum.z;
           shared.next_add[px] = na;
         }
@@ -188,15 +197,15 @@ __global__ void __launch_bounds__(kBlock, P3D_PT_WAVES) pt_kernel(const RenderPa
               s = (int)__hip_atomic_fetch_add(&shared.next_start[px], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               holding = true;
             }
-            if (s >= n_samples) {  // nothing left to start: finished, except lane 0 while samples remain to be added
-              done = sub != 0 || shared.next_add[px] >= (uint32_t)n_samples;
+            if ((uint32_t)s >= s_end) {  // nothing left to start: finished, except lane 0 while samples remain to be added
+              done = sub != 0 || shared.next_add[px] >= s_end;
               continue;
             }
             if ((uint32_t)s >= shared.next_add[px] + kPtRing) continue;  // wait for room
             holding = false;
             si = (int)__umulhi((uint32_t)s, spp_magic);  // s / SPP (exact: s * SPP < 2^32)
             sj = s - si * SPP;
-          } else if (s == n_samples) {
+          } else if ((uint32_t)s == s_end) {
             break;
           }
           rng.seed_stream(P.seed, (uint32_t)(y * sc.cam.res_x + x), (uint32_t)s);
@@ -363,16 +372,22 @@ __global__ void __launch_bounds__(kBlock, P3D_PT_WAVES) pt_kernel(const RenderPa
         ct.add(kRaysBounce, 2);
       }
     }
-    if (SUB == 4 && sub == 0) color = f3(shared.colour[0][px], shared.colour[1][px], shared.colour[2][px]);
-    if (P.antialiasing) color = color / (float)(SPP * SPP);  // main.cpp:800
+    if (SUB == 4 && sub == 0) {
+      color = f3(shared.colour[0][px], shared.colour[1][px], shared.colour[2][px]);
+      first_hit = shared.first_hit[px];
+    }
+    if (P.accum_sum && sub == 0) {  // the running sum and first hit for the next pass
+      P.accum_sum[3 * k_out] = color.x; P.accum_sum[3 * k_out + 1] = color.y; P.accum_sum[3 * k_out + 2] = color.z;
+      P.accum_hit[k_out] = first_hit;
+    }
+    if (P.antialiasing) color = color / (float)s_end;  // main.cpp:800 (s_end = SPP * SPP on a frame's last pass)
 
 #ifdef P3D_PT_PROFILE
     PT_REGION(9)
     prof.flush();
 #endif
     if (sub == 0) {  // SUB == 4: lane 0 of the pixel holds its colour
-      if (SUB == 4) first_hit = shared.first_hit[px];
-      const size_t k = (size_t)r * P.w + c;
+      const size_t k = k_out;
       if (P.rgb) {
         P.rgb[3 * k] = color.x; P.rgb[3 * k + 1] = color.y; P.rgb[3 * k + 2] = color.z;
       }

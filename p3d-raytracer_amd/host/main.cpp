@@ -22,6 +22,10 @@
 //                               through a second ncclGather; GPU 0 then renders the whole frame alone and the gathered
 //                               frame is compared with it bit for bit - colours, hit IDs and the u8 image.  Prints the
 //                               verdict; a mismatch is exit code 3.
+//              [--passes K]     progressive: the frame's SPP*SPP samples in K passes of as-equal-as-possible size (p3d_accum,
+//                               include/p3d.h); --out is rewritten after every pass and one line per pass gives the samples
+//                               done and the pass time.  The last file is byte-identical to the one written without --passes.
+//                               Needs --aa 1 and, for --whitted over the BVH, --stack per_pixel; not with --gpus.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -255,6 +259,7 @@ int main(int argc, char** argv) {
   p3d_config_default(&cfg);
   std::string scene_path, skybox_dir, out = "RT_Output.png";  // main.cpp:851
   int res_w = 0, res_h = 0, device = 0, gpus = 0;
+  long passes = 0;  // --passes K (0: one call renders the frame)
   bool device_bvh = false, verify = false;
   uint32_t load_flags = 0;
   for (int i = 1; i < argc; ++i) {
@@ -285,8 +290,19 @@ int main(int argc, char** argv) {
     else if (a == "--device-bvh") device_bvh = true;
     else if (a == "--gpus") gpus = std::atoi(next("--gpus"));
     else if (a == "--verify") verify = true;
+    else if (a == "--passes") {
+      const char* v = next("--passes");
+      char* end = nullptr;
+      passes = std::strtol(v, &end, 10);
+      if (end == v || *end != 0 || passes < 1) { std::fprintf(stderr, "--passes needs a whole number of passes, at least 1 (got '%s')\n", v); return 2; }
+    }
     else if (a[0] != '-') scene_path = a;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+  }
+  if (passes > 0) {
+    if (gpus > 0) { std::fprintf(stderr, "--passes does not combine with --gpus (one frame's samples stay on one GPU)\n"); return 2; }
+    const long total = cfg.antialiasing ? (long)cfg.spp_sqrt * (long)cfg.spp_sqrt : 1;
+    if (cfg.antialiasing && passes > total) { std::fprintf(stderr, "--passes %ld: the frame has only %ld samples per pixel\n", passes, total); return 2; }
   }
   if (scene_path.empty()) {  // main.cpp:968-980: prompt for a name under P3D_Scenes/
     std::string name;
@@ -347,8 +363,36 @@ int main(int argc, char** argv) {
   p3d_tile tile{0, 0, W, H, 0, 1};
   p3d_stats st{};
   cfg.collect_stats = 1;
+  const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
   const auto t0 = std::chrono::high_resolution_clock::now();
-  if (p3d_render_tile(scene, &cfg, &tile, nullptr, nullptr, img.data(), &st) != P3D_OK) return die("render");
+  if (passes > 0) {  // progressive: the image refines pass by pass (p3d_accum), --out rewritten after every pass
+    p3d_accum* acc = nullptr;
+    if (const int rc = p3d_accum_create(scene, &cfg, &tile, &acc); rc != P3D_OK) {
+      if (rc != P3D_ERR_UNSUPPORTED) return die("accum_create");
+      std::fprintf(stderr, "--passes: %s\n", p3d_last_error());
+      return 2;
+    }
+    const uint32_t total = cfg.spp_sqrt * cfg.spp_sqrt;
+    for (long k = 0; k < passes; ++k) {
+      const uint32_t n = (uint32_t)(total / passes) + ((long)(total % passes) > k ? 1u : 0u);
+      p3d_stats ps{};
+      const auto p0 = std::chrono::high_resolution_clock::now();
+      if (p3d_accum_render(acc, n, nullptr, nullptr, img.data(), &ps) != P3D_OK) return die("render");
+      const double pass_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - p0).count();
+      std::printf("pass %ld/%ld: %u of %u samples done, %.3f ms\n", k + 1, passes, p3d_accum_samples_done(acc), total, pass_ms);
+      std::fflush(stdout);
+      st.rays_primary += ps.rays_primary; st.rays_shadow += ps.rays_shadow; st.rays_reflect += ps.rays_reflect;
+      st.rays_refract += ps.rays_refract; st.rays_bounce += ps.rays_bounce; st.rays_light += ps.rays_light;
+      st.kernel_ms += ps.kernel_ms;
+      if (!(ppm ? save_ppm(out, img, W, H) : save_png(out, img, W, H))) {
+        std::printf("Error saving Image file\n");
+        return 1;
+      }
+    }
+    p3d_accum_destroy(acc);
+  } else if (p3d_render_tile(scene, &cfg, &tile, nullptr, nullptr, img.data(), &st) != P3D_OK) {
+    return die("render");
+  }
   const auto t1 = std::chrono::high_resolution_clock::now();
   std::printf("Drawing finished!\n");
   const double secs = std::chrono::duration<double>(t1 - t0).count();
@@ -357,7 +401,6 @@ int main(int argc, char** argv) {
   std::printf("accel build + upload %.3f s; kernel %.3f ms; %llu rays; %.1f Mrays/s (kernel)\n",
               std::chrono::duration<double>(t_build1 - t_build0).count(), st.kernel_ms, (unsigned long long)rays,
               st.kernel_ms > 0 ? rays / (st.kernel_ms * 1e3) : 0.0);
-  const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
   if (!(ppm ? save_ppm(out, img, W, H) : save_png(out, img, W, H))) {
     std::printf("Error saving Image file\n");
     return 1;
