@@ -431,6 +431,55 @@ int p3d_accum_render_device(p3d_accum* acc, uint32_t n, float* d_rgb, int32_t* d
                             void* hip_stream, p3d_stats* stats);
 
 /*
+ * Adaptive sampling: a progressive path-traced frame (p3d_accum above) whose pixels stop taking samples once they have
+ * converged, so that later passes cost in proportion to the pixels still noisy.  Detected by its symbols, like p3d_accum.
+ *
+ * Passes.  A pass of n samples renders samples [done, done + n) of every ACTIVE pixel and then advances `done` by n, even
+ * when no pixel is active.  The rules of p3d_accum for n, for failures and for reset hold unchanged: n == 0 or
+ * done + n > SPP*SPP is P3D_ERR_INVALID and changes nothing; after a failed pass, passes are refused until
+ * p3d_adaptive_reset (0 samples, every pixel active again).  Every pass writes EVERY pixel of the tile to each non-NULL
+ * output:  rgb = sum / (float)samples_p,  rgb8 = gamma + u8fromfloat of that value,  hit_id = sample 0's primary hit,
+ *          samples = samples_p, the samples in the pixel's sum (w*h uint32).
+ * Exactness: a pixel that stopped after k samples holds exactly the bits a plain p3d_accum holds for it after k samples
+ * (same RNG streams, same additions in sample order, same epilogue); a pixel that never stops holds the one-shot frame's.
+ *
+ * Decision, at the end of a pass only: a pixel becomes inactive for good when samples_p >= min_samples and
+ * rel_err_p < rel_error (strict: rel_error = 0 never stops a pixel).
+ * Error metric, float32 on the device in this order, without contraction:
+ *   per sample radiance L added to the sum:  y = 0.2126f*L.x + 0.7152f*L.y + 0.0722f*L.z;  S2 += y*y  (sample order)
+ *   n = (float)samples_p;  Y = 0.2126f*S.x + 0.7152f*S.y + 0.0722f*S.z;  m = Y / n;
+ *   v = fmaxf((S2 - Y*m) / (n - 1.0f), 0.0f);  rel_err = sqrtf(v / n) / (m + 1.0e-3f)
+ *
+ * Refused at create: P3D_ERR_UNSUPPORTED for integrator = WHITTED (its anti-aliased frames have few, cheap samples) and
+ * antialiasing = 0; P3D_ERR_INVALID for a NaN or negative rel_error, min_samples outside [2, SPP*SPP], or non-zero
+ * reserved fields.  One device only.
+ * Stats describe one pass: pixels = the pixels rendered (the active ones); with collect_stats, rays_primary summed over
+ * a frame's passes equals the sum over pixels of samples_p.
+ *
+ * p3d_adaptive_render is the host-buffer form (synchronous).  p3d_adaptive_render_device follows
+ * p3d_accum_render_device's stream and error rules: without `stats` it returns without waiting for the device.
+ * p3d_adaptive_active_pixels (the pixels the next pass renders) and p3d_adaptive_read_state (per pixel: the running sum,
+ * 3 float; S2; samples_p; rel_err of the pixel's last pass) wait for the device.  Any output pointer may be NULL.
+ */
+typedef struct p3d_adaptive_params {
+  float rel_error;       /* a pixel stops once its rel_err is < rel_error; 0 = no pixel ever stops */
+  uint32_t min_samples;  /* no pixel stops before this many samples; 2 <= min_samples <= SPP*SPP */
+  uint32_t reserved[2];  /* must be 0 */
+} p3d_adaptive_params;
+typedef struct p3d_adaptive p3d_adaptive;
+int p3d_adaptive_create(p3d_scene* scene, const p3d_config* cfg, const p3d_tile* tile, const p3d_adaptive_params* params,
+                        p3d_adaptive** out);
+void p3d_adaptive_destroy(p3d_adaptive* ad);
+int p3d_adaptive_reset(p3d_adaptive* ad);
+uint32_t p3d_adaptive_samples_done(const p3d_adaptive* ad);
+int p3d_adaptive_active_pixels(p3d_adaptive* ad, uint32_t* n);
+int p3d_adaptive_render(p3d_adaptive* ad, uint32_t n, float* rgb, int32_t* hit_id, uint8_t* rgb8, uint32_t* samples,
+                        p3d_stats* stats);
+int p3d_adaptive_render_device(p3d_adaptive* ad, uint32_t n, float* d_rgb, int32_t* d_hit_id, uint8_t* d_rgb8,
+                               uint32_t* d_samples, void* hip_stream, p3d_stats* stats);
+int p3d_adaptive_read_state(p3d_adaptive* ad, float* sum, float* sum_y2, uint32_t* samples, float* rel_err);
+
+/*
  * Errors a kernel detects while it runs (a hit_stack leftover that outgrew its record, a work list of the hit_stack
  * hand-off that overflowed or did not run empty within its round bound, a row of a stripe or sub-rectangle whose
  * incoming hit_stack could not be established, a sample hand-out loop that reached its trip bound and would write pixels

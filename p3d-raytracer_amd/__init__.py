@@ -38,6 +38,8 @@ EXPORTS = [
     "p3d_host_scene_set_resolution", "p3d_host_scene_set_lens", "p3d_host_scene_replicate_lights",
     "p3d_host_scene_desc", "p3d_host_scene_bind_device", "p3d_host_scene_has_skybox", "p3d_host_scene_load_skybox", "p3d_host_scene_skybox_face",
     "p3d_accum_create", "p3d_accum_destroy", "p3d_accum_reset", "p3d_accum_samples_done", "p3d_accum_render", "p3d_accum_render_device",
+    "p3d_adaptive_create", "p3d_adaptive_destroy", "p3d_adaptive_reset", "p3d_adaptive_samples_done", "p3d_adaptive_active_pixels",
+    "p3d_adaptive_render", "p3d_adaptive_render_device", "p3d_adaptive_read_state",
 ]
 
 
@@ -112,6 +114,10 @@ class SkyboxDesc(C.Structure):
 class Tile(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
                 ("stripe_h", C.c_int32), ("stripe_stride", C.c_int32)]
+
+
+class AdaptiveParams(C.Structure):
+    _fields_ = [("rel_error", C.c_float), ("min_samples", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class Stats(C.Structure):
@@ -198,6 +204,19 @@ def lib():
         L.p3d_accum_render.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.p3d_accum_render_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(Stats)]
+        L.p3d_adaptive_create.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Tile), C.POINTER(AdaptiveParams),
+                                          C.POINTER(C.c_void_p)]
+        L.p3d_adaptive_destroy.argtypes = [C.c_void_p]
+        L.p3d_adaptive_destroy.restype = None
+        L.p3d_adaptive_reset.argtypes = [C.c_void_p]
+        L.p3d_adaptive_samples_done.argtypes = [C.c_void_p]
+        L.p3d_adaptive_samples_done.restype = C.c_uint32
+        L.p3d_adaptive_active_pixels.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.p3d_adaptive_render.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(Stats)]
+        L.p3d_adaptive_render_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(Stats)]
+        L.p3d_adaptive_read_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -413,6 +432,29 @@ class DeviceScene:
         finally:
             acc.close()
 
+    def adaptive(self, cfg, rel_error, min_samples=16, tile=None, reserved=(0, 0)):
+        """p3d_adaptive_create: an AdaptiveAccumulator - a progressive path-traced frame (cfg, tile) whose pixels stop
+        taking samples once their relative error is below rel_error (and they have at least min_samples).  Raises
+        P3DError: P3D_ERR_UNSUPPORTED for Whitted and antialiasing = 0, P3D_ERR_INVALID for bad parameters."""
+        return AdaptiveAccumulator(self, cfg, tile or self.full_tile(), rel_error, min_samples, reserved)
+
+    def render_adaptive(self, cfg, samples_per_pass, rel_error, min_samples=16, tile=None, want_rgb8=False, stats=True):
+        """Renders the frame in adaptive passes of `samples_per_pass` samples (the last one takes what is left) and yields
+        (samples_done, active_pixels, render tuple of AdaptiveAccumulator.render) after every pass, until no pixel is
+        active or every sample is done."""
+        if samples_per_pass < 1:
+            raise ValueError("samples_per_pass must be at least 1")
+        ad = self.adaptive(cfg, rel_error, min_samples, tile)
+        try:
+            while ad.samples_done < ad.total:
+                out = ad.render(min(samples_per_pass, ad.total - ad.samples_done), want_rgb8=want_rgb8, stats=stats)
+                active = ad.active_pixels
+                yield ad.samples_done, active, out
+                if active == 0:
+                    break
+        finally:
+            ad.close()
+
     def status(self):
         """p3d_scene_status: waits for the device, returns P3D_OK (0) or the code of a device-detected error of the
         asynchronous render_device calls since the last check (message: last_error())."""
@@ -532,6 +574,82 @@ class Accumulator:
     def close(self):
         if getattr(self, "_h", None):
             self._L.p3d_accum_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AdaptiveAccumulator:
+    """p3d_adaptive (include/p3d.h): a progressive path-traced frame whose pixels stop taking samples once converged.
+    Every pass renders samples [samples_done, samples_done + n) of the still-active pixels and writes every pixel: a
+    pixel that stopped after k samples holds the bits a plain Accumulator holds after k.  Close it before the scene."""
+
+    def __init__(self, scene, cfg, tile, rel_error, min_samples=16, reserved=(0, 0)):
+        self._L = scene._L
+        self.scene = scene
+        self.cfg = cfg
+        self.tile = tile
+        self.total = int(cfg.spp_sqrt) ** 2
+        prm = AdaptiveParams(float(rel_error), int(min_samples), (C.c_uint32 * 2)(*reserved))
+        h = C.c_void_p()
+        _check(self._L.p3d_adaptive_create(scene._h, C.byref(cfg), C.byref(tile), C.byref(prm), C.byref(h)))
+        self._h = h
+
+    @property
+    def samples_done(self):
+        return int(self._L.p3d_adaptive_samples_done(self._h))
+
+    @property
+    def active_pixels(self):
+        """Pixels the next pass renders (waits for the device)."""
+        n = C.c_uint32()
+        _check(self._L.p3d_adaptive_active_pixels(self._h, C.byref(n)))
+        return int(n.value)
+
+    def reset(self):
+        """Back to 0 samples, every pixel active (also what lets an object whose pass failed render again)."""
+        _check(self._L.p3d_adaptive_reset(self._h))
+
+    def render(self, n, want_rgb8=False, stats=True):
+        """p3d_adaptive_render: the next n samples of the active pixels -> (rgb, hit, samples, [rgb8,] stats)."""
+        t = self.tile
+        rgb = np.zeros((t.h, t.w, 3), np.float32)
+        hit = np.zeros((t.h, t.w), np.int32)
+        samples = np.zeros((t.h, t.w), np.uint32)
+        rgb8 = np.zeros((t.h, t.w, 3), np.uint8) if want_rgb8 else None
+        st = Stats()
+        _check(self._L.p3d_adaptive_render(self._h, int(n), rgb.ctypes.data, hit.ctypes.data,
+                                           rgb8.ctypes.data if want_rgb8 else None, samples.ctypes.data,
+                                           C.byref(st) if stats else None))
+        if want_rgb8:
+            return rgb, hit, samples, rgb8, st
+        return rgb, hit, samples, st
+
+    def render_device(self, n, d_rgb=0, d_hit=0, d_rgb8=0, d_samples=0, stream=0, stats=None):
+        """p3d_adaptive_render_device: raw HBM addresses and a hipStream_t (or a torch.cuda.Stream); without stats the
+        pass is only enqueued - DeviceScene.status() reports what the device detected."""
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_adaptive_render_device(self._h, int(n), C.c_void_p(d_rgb or None), C.c_void_p(d_hit or None),
+                                                  C.c_void_p(d_rgb8 or None), C.c_void_p(d_samples or None),
+                                                  C.c_void_p(raw or None), C.byref(stats) if stats is not None else None))
+
+    def read_state(self):
+        """p3d_adaptive_read_state (waits for the device): {"sum": (h, w, 3) float32, "sum_y2": (h, w) float32,
+        "samples": (h, w) uint32, "rel_err": (h, w) float32}."""
+        t = self.tile
+        out = {"sum": np.zeros((t.h, t.w, 3), np.float32), "sum_y2": np.zeros((t.h, t.w), np.float32),
+               "samples": np.zeros((t.h, t.w), np.uint32), "rel_err": np.zeros((t.h, t.w), np.float32)}
+        _check(self._L.p3d_adaptive_read_state(self._h, out["sum"].ctypes.data, out["sum_y2"].ctypes.data,
+                                               out["samples"].ctypes.data, out["rel_err"].ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.p3d_adaptive_destroy(self._h)
             self._h = None
 
     def __del__(self):

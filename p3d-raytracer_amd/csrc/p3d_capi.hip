@@ -18,6 +18,7 @@
 #include "p3d.h"
 #include "p3d_debug.h"
 #include "pt_kernel.hpp"
+#include "adaptive.hpp"
 
 using namespace p3d;
 
@@ -569,6 +570,27 @@ hipError_t launch_accel(bool pt, bool aa, bool sub4, bool lds_scene, bool stats,
   return stats ? launch_one<ACCEL, false, true>(pt, aa, sub4, P, blocks, lds, st) : launch_one<ACCEL, false, false>(pt, aa, sub4, P, blocks, lds, st);
 }
 
+// Adaptive passes (pt_adaptive_kernel): the grid is sized to the resident waves, not to the frame
+template <int ACCEL, bool LDS, bool STATS>
+hipError_t launch_adapt_one(bool sub4, const RenderParams& P, const PtAdaptParams& A, uint32_t blocks, size_t lds, hipStream_t st) {
+  if (sub4) hipLaunchKernelGGL((pt_adaptive_kernel<ACCEL, LDS, STATS, 4>), dim3(blocks), dim3(kBlock), lds, st, P, A);
+  else hipLaunchKernelGGL((pt_adaptive_kernel<ACCEL, LDS, STATS, 1>), dim3(blocks), dim3(kBlock), lds, st, P, A);
+  return hipGetLastError();
+}
+template <int ACCEL>
+hipError_t launch_adapt_accel(bool sub4, bool lds_scene, bool stats, const RenderParams& P, const PtAdaptParams& A, uint32_t blocks, size_t lds, hipStream_t st) {
+  if (lds_scene) return stats ? launch_adapt_one<ACCEL, true, true>(sub4, P, A, blocks, lds, st) : launch_adapt_one<ACCEL, true, false>(sub4, P, A, blocks, lds, st);
+  return stats ? launch_adapt_one<ACCEL, false, true>(sub4, P, A, blocks, lds, st) : launch_adapt_one<ACCEL, false, false>(sub4, P, A, blocks, lds, st);
+}
+
+// What render_impl needs for one pass of an adaptive frame (p3d_adaptive): the list the pass renders and the resolve /
+// decide / compact launch behind it.
+struct AdaptPass {
+  PtAdaptParams k;
+  AdaptResolveParams r;
+  uint32_t resident;  // workgroups the device holds at once (the grid of pt_adaptive_kernel at most)
+};
+
 // P3D_STACK_LITERAL launches (BVH only).  lit 1: pass 1; lit 2: work-list launch; lit 0: the check launch over the tiles; lit 3:
 // the check launch over pass 1's list; lit 4: check + repair over the tiles in one launch (whitted_kernel LIT = 3).
 // ghosts: the scene has zero-weight reflection rays to trace (a transmissive AND reflective material).
@@ -762,9 +784,11 @@ int check_frame(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile) {
 
 // The render path of p3d_render_tile_device (a whole frame: samples [0, SPP^2), no accumulator) and of p3d_accum_render_device
 // (samples [sample_begin, sample_end) of an anti-aliased frame whose running sums and first hits live in accum_sum /
-// accum_hit).  The sample range only reaches the anti-aliased sample loops; everything else is the same frame.
+// accum_hit).  The sample range only reaches the anti-aliased sample loops; everything else is the same frame.  With
+// `adapt` (p3d_adaptive_render_device, path tracer only) the pass renders the listed pixels and resolves the tile behind.
 int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float* d_rgb, int32_t* d_hit, uint8_t* d_rgb8,
-                void* hip_stream, p3d_stats* stats, uint32_t sample_begin, uint32_t sample_end, float* accum_sum, int32_t* accum_hit) {
+                void* hip_stream, p3d_stats* stats, uint32_t sample_begin, uint32_t sample_end, float* accum_sum, int32_t* accum_hit,
+                const AdaptPass* adapt = nullptr) {
   if (int rc = check_frame(s, cfg, tile)) return rc;
   const DevCamera& cam = s->dev.cam;
   const int sh = tile->stripe_h > 0 ? tile->stripe_h : 1, ss = tile->stripe_h > 0 ? tile->stripe_stride : 1;
@@ -896,7 +920,9 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
   const bool sched_ok = cfg->tile_order == P3D_TILE_ORDER_COST && cfg->max_depth > 0;
   // LITERAL: workgroups behind the tile grid of the first launch render the halo chains (8 chains of 8 pixels per wave)
   const uint32_t halo_blocks_max = literal ? ((uint32_t)tile->h * kHaloChain + kBlock - 1) / kBlock : 0;
-  const uint32_t max_threads = (blocks_for(tiles_x * bands_per_launch) + halo_blocks_max) * kBlock;
+  // (an adaptive pass: one launch of at most adapt->resident workgroups, each working through groups of the pixel list)
+  const uint32_t adapt_blocks = adapt ? std::max<uint32_t>(1, std::min<uint32_t>(adapt->resident, (uint32_t)(((size_t)tile->w * tile->h + (sub4 ? 15 : 63)) / (sub4 ? 16 : 64)))) : 0;
+  const uint32_t max_threads = adapt ? adapt_blocks * kBlock : (blocks_for(tiles_x * bands_per_launch) + halo_blocks_max) * kBlock;
   const size_t tile_units = (size_t)tile->h * ((size_t)tile->w + kHaloChain);  // upper bound of H.n_units
   // per-level launches keep one record per (level, unit); the work-list launches of a LITERAL frame behind them are the
   // megakernel and index [level][launch thread] with up to max_threads threads, whatever the size of the tile
@@ -1054,8 +1080,28 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
     on_tail = true;
     return P3D_OK;
   };
+  if (adapt) {  // the listed pixels over the whole tile in one launch, then resolve / decide / compact (adaptive.hpp)
+    P.x0 = tile->x0; P.y0 = tile->y0; P.w = tile->w; P.h = tile->h; P.row0 = 0;
+    P.tiles_x = tiles_x; P.tiles_y = total_bands; P.xcd_chunk = xcd_chunk;
+    P.sched = nullptr; P.tile_cost = nullptr;
+    P.tile_blocks = adapt_blocks;
+    P.level_stride = adapt_blocks * kBlock;
+    P.rgb = nullptr; P.hit_id = nullptr; P.rgb8 = nullptr;
+    P.accum_sum = accum_sum; P.accum_hit = accum_hit;
+    hipError_t e = hipSuccess;
+    switch (cfg->accel) {
+      case P3D_ACCEL_BVH: e = launch_adapt_accel<P3D_ACCEL_BVH>(sub4, lds_scene, want_counts, P, adapt->k, adapt_blocks, lds_bytes, st); break;
+      case P3D_ACCEL_GRID: e = launch_adapt_accel<P3D_ACCEL_GRID>(sub4, lds_scene, want_counts, P, adapt->k, adapt_blocks, lds_bytes, st); break;
+      default: e = launch_adapt_accel<P3D_ACCEL_NONE>(sub4, lds_scene, want_counts, P, adapt->k, adapt_blocks, lds_bytes, st); break;
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(adapt_resolve_kernel, dim3((adapt->r.slots + kAdaptResolveThreads - 1) / kAdaptResolveThreads), dim3(kAdaptResolveThreads), 0, st, adapt->r);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("adaptive pass launch: ") + hipGetErrorString(e));
+  }
   // pass: 0 = the render launches (LITERAL: pass 1, everything on an empty stack); 1 = LITERAL only: the check launches
-  for (int pass = 0; pass < (literal ? 2 : 1); ++pass) {
+  for (int pass = 0; pass < (adapt ? 0 : (literal ? 2 : 1)); ++pass) {
     if (pass == 1)
       if (int rc = to_tail()) return rc;
     if (pass == 1 && (abl_skip() & 1u)) break;
@@ -1380,6 +1426,188 @@ int p3d_accum_render(p3d_accum* a, uint32_t n, float* rgb, int32_t* hit_id, uint
   if (rgb) P3D_HIP(hipMemcpy(rgb, s->out_rgb.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
   if (hit_id) P3D_HIP(hipMemcpy(hit_id, s->out_hit.p, px * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (rgb8) P3D_HIP(hipMemcpy(rgb8, s->out_rgb8.p, px * 3, hipMemcpyDeviceToHost));
+  return P3D_OK;
+}
+
+}  // extern "C"
+
+// Adaptive sampling (include/p3d.h): a progressive path-traced frame whose pixels stop taking samples once converged.
+// Per pixel: the running sum, first hit, S2 and sample count; the list of the pixels the next pass renders and its count
+// live on the device (two counts: the pass reads one while its resolve builds the other).
+struct p3d_adaptive {
+  p3d_scene* s = nullptr;
+  int device = 0;
+  p3d_config cfg{};
+  p3d_tile tile{};
+  p3d_adaptive_params prm{};
+  uint32_t total = 0;     // SPP^2
+  uint32_t done = 0;      // samples of the passes so far
+  uint32_t passes = 0;    // passes since the reset: the list's count is counters[passes & 1]
+  uint32_t resident = 0;  // workgroups the device holds at once
+  bool failed = false;
+  Scratch sum, hit, sum_y2, samples, active, rel_err, list, counters;  // counters: count[2], ticket
+};
+
+namespace {
+
+size_t adapt_pixels(const p3d_adaptive* a) { return (size_t)a->tile.w * a->tile.h; }
+
+AdaptResolveParams adapt_resolve_params(p3d_adaptive* a, bool init) {
+  AdaptResolveParams R{};
+  uint32_t* ctr = (uint32_t*)a->counters.p;
+  R.sum = (const float*)a->sum.p; R.hit = (const int32_t*)a->hit.p; R.sum_y2 = (const float*)a->sum_y2.p;
+  R.samples = (uint32_t*)a->samples.p; R.active = (uint8_t*)a->active.p; R.rel_err = (float*)a->rel_err.p;
+  R.list_out = (uint32_t*)a->list.p;
+  R.count_out = ctr + ((a->passes + (init ? 0 : 1)) & 1u);
+  R.count_done = ctr + ((a->passes + (init ? 1 : 0)) & 1u);
+  R.ticket = ctr + 2;
+  R.w = a->tile.w; R.h = a->tile.h;
+  R.tiles8_x = ((uint32_t)a->tile.w + 7) / 8;
+  R.slots = R.tiles8_x * (((uint32_t)a->tile.h + 7) / 8) * 64;
+  R.min_samples = a->prm.min_samples; R.rel_error = a->prm.rel_error; R.gamma = a->cfg.gamma;
+  R.init = init ? 1u : 0u;
+  return R;
+}
+
+// Back to 0 samples with every pixel listed; returns when the device has done it
+int adapt_start(p3d_adaptive* a) {
+  P3D_HIP(hipSetDevice(a->device));
+  P3D_HIP(hipDeviceSynchronize());  // (no pass of this frame may still run; the caller's streams need not block on the null stream)
+  a->done = 0;
+  a->passes = 0;
+  a->failed = false;
+  P3D_HIP(hipMemsetAsync(a->counters.p, 0, 4 * sizeof(uint32_t), nullptr));
+  const AdaptResolveParams R = adapt_resolve_params(a, true);
+  hipLaunchKernelGGL(adapt_resolve_kernel, dim3((R.slots + kAdaptResolveThreads - 1) / kAdaptResolveThreads), dim3(kAdaptResolveThreads), 0, nullptr, R);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("adaptive reset launch: ") + hipGetErrorString(e));
+  P3D_HIP(hipDeviceSynchronize());
+  return P3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p3d_adaptive_create(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, const p3d_adaptive_params* prm, p3d_adaptive** out) {
+  if (!s || !cfg || !tile || !prm || !out) return fail(P3D_ERR_INVALID, "p3d_adaptive_create: null argument");
+  *out = nullptr;
+  if (cfg->integrator != P3D_PATHTRACE)
+    return fail(P3D_ERR_UNSUPPORTED, "p3d_adaptive_create: adaptive sampling is for the path tracer (Whitted frames have few, cheap samples per pixel)");
+  if (!cfg->antialiasing)
+    return fail(P3D_ERR_UNSUPPORTED, "p3d_adaptive_create: antialiasing = 0 renders one sample per pixel; there is nothing to adapt");
+  if (int rc = check_frame(s, cfg, tile)) return rc;
+  const uint32_t total = cfg->spp_sqrt * cfg->spp_sqrt;
+  if (!(prm->rel_error >= 0.0f)) return fail(P3D_ERR_INVALID, "p3d_adaptive_create: rel_error must be a number >= 0");
+  if (prm->min_samples < 2 || prm->min_samples > total)
+    return fail(P3D_ERR_INVALID, "p3d_adaptive_create: min_samples must lie in [2, SPP*SPP = " + std::to_string(total) + "]");
+  if (prm->reserved[0] || prm->reserved[1]) return fail(P3D_ERR_INVALID, "p3d_adaptive_create: reserved fields must be 0");
+  P3D_HIP(hipSetDevice(s->device));
+  int cus = 0;
+  P3D_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
+  p3d_adaptive* a = new p3d_adaptive;
+  a->s = s;
+  a->device = s->device;
+  a->cfg = *cfg;
+  a->tile = *tile;
+  a->prm = *prm;
+  a->total = total;
+  a->resident = (uint32_t)std::max(cus, 1) * 4 * P3D_PT_WAVES;  // 4 SIMDs per CU
+  const size_t n = adapt_pixels(a);
+  int rc = a->sum.ensure(n * 3 * sizeof(float));
+  if (!rc) rc = a->hit.ensure(n * sizeof(int32_t));
+  if (!rc) rc = a->sum_y2.ensure(n * sizeof(float));
+  if (!rc) rc = a->samples.ensure(n * sizeof(uint32_t));
+  if (!rc) rc = a->active.ensure(n);
+  if (!rc) rc = a->rel_err.ensure(n * sizeof(float));
+  if (!rc) rc = a->list.ensure(n * sizeof(uint32_t));
+  if (!rc) rc = a->counters.ensure(4 * sizeof(uint32_t));
+  if (!rc) rc = adapt_start(a);
+  if (rc) {
+    p3d_adaptive_destroy(a);
+    return rc;
+  }
+  *out = a;
+  return P3D_OK;
+}
+
+void p3d_adaptive_destroy(p3d_adaptive* a) {
+  if (!a) return;
+  (void)hipSetDevice(a->device);
+  for (Scratch* b : {&a->sum, &a->hit, &a->sum_y2, &a->samples, &a->active, &a->rel_err, &a->list, &a->counters}) b->release();
+  delete a;
+}
+
+int p3d_adaptive_reset(p3d_adaptive* a) {
+  if (!a) return fail(P3D_ERR_INVALID, "p3d_adaptive_reset: null object");
+  return adapt_start(a);
+}
+
+uint32_t p3d_adaptive_samples_done(const p3d_adaptive* a) { return a ? a->done : 0u; }
+
+int p3d_adaptive_active_pixels(p3d_adaptive* a, uint32_t* n) {
+  if (!a || !n) return fail(P3D_ERR_INVALID, "p3d_adaptive_active_pixels: null argument");
+  P3D_HIP(hipSetDevice(a->device));
+  P3D_HIP(hipDeviceSynchronize());
+  P3D_HIP(hipMemcpy(n, (uint32_t*)a->counters.p + (a->passes & 1u), sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return P3D_OK;
+}
+
+int p3d_adaptive_render_device(p3d_adaptive* a, uint32_t n, float* d_rgb, int32_t* d_hit, uint8_t* d_rgb8, uint32_t* d_samples,
+                               void* hip_stream, p3d_stats* stats) {
+  if (!a) return fail(P3D_ERR_INVALID, "p3d_adaptive_render_device: null object");
+  if (a->failed) return fail(P3D_ERR_INVALID, "p3d_adaptive_render: a previous pass failed; p3d_adaptive_reset starts the frame again");
+  if (n == 0 || n > a->total - a->done)
+    return fail(P3D_ERR_INVALID, "p3d_adaptive_render: " + std::to_string(n) + " samples asked, " + std::to_string(a->total - a->done) +
+                                     " of " + std::to_string(a->total) + " left (n must be at least 1)");
+  AdaptPass ap{};
+  uint32_t* ctr = (uint32_t*)a->counters.p;
+  ap.k.list = (const uint32_t*)a->list.p;
+  ap.k.count = ctr + (a->passes & 1u);
+  ap.k.ticket = ctr + 2;
+  ap.k.sum_y2 = (float*)a->sum_y2.p;
+  ap.r = adapt_resolve_params(a, false);
+  ap.r.n = n;
+  ap.r.rgb = d_rgb; ap.r.hit_id = d_hit; ap.r.rgb8 = d_rgb8; ap.r.samples_out = d_samples;
+  ap.resident = a->resident;
+  const int rc = render_impl(a->s, &a->cfg, &a->tile, nullptr, nullptr, nullptr, hip_stream, stats, a->done, a->done + n,
+                             (float*)a->sum.p, (int32_t*)a->hit.p, &ap);
+  if (rc) {
+    a->failed = true;
+    return rc;
+  }
+  a->done += n;
+  ++a->passes;
+  return P3D_OK;
+}
+
+int p3d_adaptive_render(p3d_adaptive* a, uint32_t n, float* rgb, int32_t* hit_id, uint8_t* rgb8, uint32_t* samples, p3d_stats* stats) {
+  if (!a) return fail(P3D_ERR_INVALID, "p3d_adaptive_render: null object");
+  p3d_scene* s = a->s;
+  P3D_HIP(hipSetDevice(s->device));
+  const size_t px = adapt_pixels(a);
+  if (rgb) if (int rc = s->out_rgb.ensure(px * 3 * sizeof(float))) return rc;
+  if (hit_id) if (int rc = s->out_hit.ensure(px * sizeof(int32_t))) return rc;
+  if (rgb8) if (int rc = s->out_rgb8.ensure(px * 3)) return rc;
+  p3d_stats local;  // (always with stats: the call waits for the pass and reports what the device detected)
+  if (int rc = p3d_adaptive_render_device(a, n, rgb ? (float*)s->out_rgb.p : nullptr, hit_id ? (int32_t*)s->out_hit.p : nullptr,
+                                          rgb8 ? (uint8_t*)s->out_rgb8.p : nullptr, nullptr, nullptr, stats ? stats : &local))
+    return rc;
+  if (rgb) P3D_HIP(hipMemcpy(rgb, s->out_rgb.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (hit_id) P3D_HIP(hipMemcpy(hit_id, s->out_hit.p, px * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (rgb8) P3D_HIP(hipMemcpy(rgb8, s->out_rgb8.p, px * 3, hipMemcpyDeviceToHost));
+  if (samples) P3D_HIP(hipMemcpy(samples, a->samples.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return P3D_OK;
+}
+
+int p3d_adaptive_read_state(p3d_adaptive* a, float* sum, float* sum_y2, uint32_t* samples, float* rel_err) {
+  if (!a) return fail(P3D_ERR_INVALID, "p3d_adaptive_read_state: null object");
+  P3D_HIP(hipSetDevice(a->device));
+  P3D_HIP(hipDeviceSynchronize());
+  const size_t px = adapt_pixels(a);
+  if (sum) P3D_HIP(hipMemcpy(sum, a->sum.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (sum_y2) P3D_HIP(hipMemcpy(sum_y2, a->sum_y2.p, px * sizeof(float), hipMemcpyDeviceToHost));
+  if (samples) P3D_HIP(hipMemcpy(samples, a->samples.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (rel_err) P3D_HIP(hipMemcpy(rel_err, a->rel_err.p, px * sizeof(float), hipMemcpyDeviceToHost));
   return P3D_OK;
 }
 

@@ -26,7 +26,13 @@
 //                               include/p3d.h); --out is rewritten after every pass and one line per pass gives the samples
 //                               done and the pass time.  The last file is byte-identical to the one written without --passes.
 //                               Needs --aa 1 and, for --whitted over the BVH, --stack per_pixel; not with --gpus.
+//              [--adaptive REL] with --passes and --pathtrace: adaptive sampling (p3d_adaptive, include/p3d.h) - a pixel
+//              [--min-spp M]    stops taking samples once its relative error is below REL and it has at least M samples
+//                               (default 16, or SPP*SPP when smaller).  One line per pass gives the samples done, the pixels
+//                               still active and the pass time; the passes end early once no pixel is active.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -260,6 +266,8 @@ int main(int argc, char** argv) {
   std::string scene_path, skybox_dir, out = "RT_Output.png";  // main.cpp:851
   int res_w = 0, res_h = 0, device = 0, gpus = 0;
   long passes = 0;  // --passes K (0: one call renders the frame)
+  float adaptive = -1.0f;  // --adaptive REL (< 0: off)
+  long min_spp = 0;        // --min-spp M (0: the default)
   bool device_bvh = false, verify = false;
   uint32_t load_flags = 0;
   for (int i = 1; i < argc; ++i) {
@@ -296,6 +304,20 @@ int main(int argc, char** argv) {
       passes = std::strtol(v, &end, 10);
       if (end == v || *end != 0 || passes < 1) { std::fprintf(stderr, "--passes needs a whole number of passes, at least 1 (got '%s')\n", v); return 2; }
     }
+    else if (a == "--adaptive") {
+      const char* v = next("--adaptive");
+      char* end = nullptr;
+      adaptive = std::strtof(v, &end);
+      if (end == v || *end != 0 || !(adaptive >= 0.0f) || adaptive == HUGE_VALF) {
+        std::fprintf(stderr, "--adaptive needs a relative error, a number >= 0 (got '%s')\n", v);
+        return 2;
+      }
+    } else if (a == "--min-spp") {
+      const char* v = next("--min-spp");
+      char* end = nullptr;
+      min_spp = std::strtol(v, &end, 10);
+      if (end == v || *end != 0 || min_spp < 2) { std::fprintf(stderr, "--min-spp needs a whole number of samples, at least 2 (got '%s')\n", v); return 2; }
+    }
     else if (a[0] != '-') scene_path = a;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
@@ -303,6 +325,15 @@ int main(int argc, char** argv) {
     if (gpus > 0) { std::fprintf(stderr, "--passes does not combine with --gpus (one frame's samples stay on one GPU)\n"); return 2; }
     const long total = cfg.antialiasing ? (long)cfg.spp_sqrt * (long)cfg.spp_sqrt : 1;
     if (cfg.antialiasing && passes > total) { std::fprintf(stderr, "--passes %ld: the frame has only %ld samples per pixel\n", passes, total); return 2; }
+  }
+  if (min_spp > 0 && adaptive < 0) { std::fprintf(stderr, "--min-spp goes with --adaptive\n"); return 2; }
+  if (adaptive >= 0) {
+    if (passes == 0) { std::fprintf(stderr, "--adaptive needs --passes K (the decisions are taken between passes)\n"); return 2; }
+    if (cfg.integrator != P3D_PATHTRACE) { std::fprintf(stderr, "--adaptive is for --pathtrace (not --whitted)\n"); return 2; }
+    if (gpus > 0) { std::fprintf(stderr, "--adaptive does not combine with --gpus\n"); return 2; }
+    const long total = (long)cfg.spp_sqrt * (long)cfg.spp_sqrt;
+    if (min_spp > total) { std::fprintf(stderr, "--min-spp %ld: the frame has only %ld samples per pixel\n", min_spp, total); return 2; }
+    if (min_spp == 0) min_spp = std::max(2L, std::min(16L, total));
   }
   if (scene_path.empty()) {  // main.cpp:968-980: prompt for a name under P3D_Scenes/
     std::string name;
@@ -365,7 +396,37 @@ int main(int argc, char** argv) {
   cfg.collect_stats = 1;
   const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
   const auto t0 = std::chrono::high_resolution_clock::now();
-  if (passes > 0) {  // progressive: the image refines pass by pass (p3d_accum), --out rewritten after every pass
+  if (passes > 0 && adaptive >= 0) {  // adaptive: converged pixels stop taking samples (p3d_adaptive)
+    p3d_adaptive* ad = nullptr;
+    const p3d_adaptive_params prm{adaptive, (uint32_t)min_spp, {0, 0}};
+    if (const int rc = p3d_adaptive_create(scene, &cfg, &tile, &prm, &ad); rc != P3D_OK) {
+      if (rc != P3D_ERR_UNSUPPORTED && rc != P3D_ERR_INVALID) return die("adaptive_create");
+      std::fprintf(stderr, "--adaptive: %s\n", p3d_last_error());
+      return 2;
+    }
+    const uint32_t total = cfg.spp_sqrt * cfg.spp_sqrt;
+    for (long k = 0; k < passes; ++k) {
+      const uint32_t n = (uint32_t)(total / passes) + ((long)(total % passes) > k ? 1u : 0u);
+      p3d_stats ps{};
+      uint32_t active = 0;
+      const auto p0 = std::chrono::high_resolution_clock::now();
+      if (p3d_adaptive_render(ad, n, nullptr, nullptr, img.data(), nullptr, &ps) != P3D_OK) return die("render");
+      if (p3d_adaptive_active_pixels(ad, &active) != P3D_OK) return die("adaptive_active_pixels");
+      const double pass_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - p0).count();
+      std::printf("pass %ld/%ld: %u of %u samples done, %u of %d pixels active, %.3f ms\n", k + 1, passes,
+                  p3d_adaptive_samples_done(ad), total, active, W * H, pass_ms);
+      std::fflush(stdout);
+      st.rays_primary += ps.rays_primary; st.rays_shadow += ps.rays_shadow; st.rays_reflect += ps.rays_reflect;
+      st.rays_refract += ps.rays_refract; st.rays_bounce += ps.rays_bounce; st.rays_light += ps.rays_light;
+      st.kernel_ms += ps.kernel_ms;
+      if (!(ppm ? save_ppm(out, img, W, H) : save_png(out, img, W, H))) {
+        std::printf("Error saving Image file\n");
+        return 1;
+      }
+      if (active == 0) break;  // every pixel has converged: later passes would change nothing
+    }
+    p3d_adaptive_destroy(ad);
+  } else if (passes > 0) {  // progressive: the image refines pass by pass (p3d_accum), --out rewritten after every pass
     p3d_accum* acc = nullptr;
     if (const int rc = p3d_accum_create(scene, &cfg, &tile, &acc); rc != P3D_OK) {
       if (rc != P3D_ERR_UNSUPPORTED) return die("accum_create");
