@@ -480,6 +480,82 @@ int p3d_adaptive_render_device(p3d_adaptive* ad, uint32_t n, float* d_rgb, int32
 int p3d_adaptive_read_state(p3d_adaptive* ad, float* sum, float* sum_y2, uint32_t* samples, float* rel_err);
 
 /*
+ * Denoising: feature buffers (AOVs) of a tile's primary rays, and an edge-avoiding a-trous wavelet filter (Dammertz et al.
+ * 2010; with a variance buffer, the luminance term of SVGF, Schied et al. 2017) that uses them - what a display loop runs
+ * behind every pass of a progressive frame.  Detected by its symbols, like p3d_accum (P3D_ABI_VERSION is unchanged).
+ *
+ * p3d_render_features traces the primary rays of samples [0, K) of every pixel of the tile - the rays the integrators trace:
+ * the (pixel, sample) RNG stream, the jitter / tent / lens sample of cfg, the closest-hit traversal of cfg->accel on an
+ * empty stack - and writes two w*h*4 float buffers, each averaged over the samples whose primary ray hit something:
+ *   normal_depth : (n.x, n.y, n.z, t)  n = the shading normal turned against the ray (main.cpp:366-368), the mean NOT
+ *                  renormalised (shorter than 1 on silhouettes); t = the traversal's closest-hit distance (p3d_trace_closest)
+ *   albedo_cov   : (diff_color, coverage)  coverage = the fraction of the K samples that hit; 0 = every component 0
+ * K = samples; 0 means min(16, SPP*SPP).  antialiasing = 0 has only the pixel-centre ray: K <= 1.  Either integrator,
+ * every accel.  P3D_ERR_INVALID for K > the frame's samples; P3D_ERR_UNSUPPORTED for a striped tile (stripe_stride > 1).
+ * The device form enqueues one launch on `hip_stream` under the scene's stream rules (p3d_render_tile_device) and
+ * returns without waiting; its buffers must be 16-byte aligned.
+ */
+int p3d_render_features(p3d_scene* scene, const p3d_config* cfg, const p3d_tile* tile, uint32_t samples, float* normal_depth,
+                        float* albedo_cov);
+int p3d_render_features_device(p3d_scene* scene, const p3d_config* cfg, const p3d_tile* tile, uint32_t samples,
+                               float* d_normal_depth, float* d_albedo_cov, void* hip_stream);
+
+/*
+ * The filter.  Iteration i = 0 .. iterations-1 has step s = 2^i; pixel p takes the taps q = p + s*(dx, dy), dx, dy in
+ * {-2 .. 2}, that lie in the w x h image, each with weight
+ *   h   = k[dx] k[dy],  k = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *   w_g = 1 if cov_p == 0 and cov_q == 0;  0 if exactly one of them is 0;  otherwise
+ *         max(0, n_p.n_q)^sigma_normal * exp(-|t_p - t_q| / (sigma_depth * s * t_p)) * exp(-|a_p - a_q|^2 / sigma_albedo^2)
+ *         (a term whose sigma is 0 is left out)
+ *   w_c = exp(-|Y_p - Y_q| / (sigma_luma * sqrt(v_p) + 1e-4))   with a variance buffer;  Y = 0.2126 R + 0.7152 G + 0.0722 B
+ *         exp(-|c_p - c_q|^2 * 4^i / sigma_color^2)              without one
+ *   w   = w_g * w_c, and 1 for the centre tap
+ *   c'_p = sum(h w c_q) / sum(h w),   v'_p = sum((h w)^2 v_q) / sum(h w)^2   (the next iteration filters c', v')
+ * in float32 (expf / powf / sqrtf, no contraction).  The last iteration writes out_rgb (w*h*3 float) and out_rgb8
+ * (gamma + u8fromfloat, the render calls' epilogue); either may be NULL, not both.  iterations = 0 copies the input: out_rgb
+ * is rgb, bit for bit, and out_rgb8 the rgb8 a render call writes for that rgb.
+ * Inputs: rgb w*h*3 float (linear, before gamma), var w*h float (NULL: the colour-distance term), normal_depth and
+ * albedo_cov as p3d_render_features writes them (required).  The outputs must not overlap the inputs.
+ * P3D_ERR_INVALID: iterations > 8, a NaN or negative sigma, sigma_color <= 0 without variance or sigma_luma <= 0 with it,
+ * gamma NaN or <= 0, non-zero reserved fields, null inputs.  p3d_denoise_params_default fills the defaults DESIGN.md
+ * chose on the Cornell box (5 iterations, sigma_color 4, sigma_luma 64, sigma_normal 128, sigma_depth 1, sigma_albedo 0.1;
+ * gamma 1 as p3d_config_default).
+ *
+ * A denoiser is made for one image size on one device: p3d_denoiser_create allocates the two float4 images the iterations
+ * ping-pong between, so p3d_denoise_device neither allocates nor waits: it enqueues one launch per iteration on `hip_stream`
+ * (behind a pass on that stream, or into a captured graph).  Its scratch is shared by its calls: enqueue the calls of one
+ * denoiser on one stream.  Device buffers are HBM addresses on the denoiser's device; the feature buffers 16-byte aligned.
+ * p3d_denoise is the host-buffer form (synchronous).
+ */
+typedef struct p3d_denoise_params {
+  uint32_t iterations;  /* 0 .. 8 */
+  float sigma_color;    /* colour distance, without a variance buffer (> 0) */
+  float sigma_luma;     /* luminance distance in standard deviations, with a variance buffer (> 0) */
+  float sigma_normal;   /* exponent of the normal term (0: off) */
+  float sigma_depth;    /* relative depth difference per unit of step (0: off) */
+  float sigma_albedo;   /* albedo distance (0: off) */
+  float gamma;          /* GAMMA of the rgb8 output, as p3d_config.gamma */
+  uint32_t reserved[2]; /* must be 0 */
+} p3d_denoise_params;
+void p3d_denoise_params_default(p3d_denoise_params* params);
+typedef struct p3d_denoiser p3d_denoiser;
+int p3d_denoiser_create(int device, int32_t w, int32_t h, p3d_denoiser** out);
+void p3d_denoiser_destroy(p3d_denoiser* dn);
+int p3d_denoise(p3d_denoiser* dn, const p3d_denoise_params* params, const float* rgb, const float* var, const float* normal_depth,
+                const float* albedo_cov, float* out_rgb, uint8_t* out_rgb8);
+int p3d_denoise_device(p3d_denoiser* dn, const p3d_denoise_params* params, const float* d_rgb, const float* d_var,
+                       const float* d_normal_depth, const float* d_albedo_cov, float* d_out_rgb, uint8_t* d_out_rgb8,
+                       void* hip_stream);
+/*
+ * The variance buffer of an adaptive frame: per pixel the variance of its mean luminance, v / n in the variables of the
+ * "Error metric" above (float32, that order); 0 for a pixel with fewer than 2 samples.  Reads the adaptive state and
+ * changes nothing.  Host form: waits for the device, writes w*h float.  Device form: one launch on `hip_stream`, enqueued
+ * behind the pass it describes.
+ */
+int p3d_denoise_variance(p3d_adaptive* ad, float* var);
+int p3d_denoise_variance_device(p3d_adaptive* ad, float* d_var, void* hip_stream);
+
+/*
  * Errors a kernel detects while it runs (a hit_stack leftover that outgrew its record, a work list of the hit_stack
  * hand-off that overflowed or did not run empty within its round bound, a row of a stripe or sub-rectangle whose
  * incoming hit_stack could not be established, a sample hand-out loop that reached its trip bound and would write pixels

@@ -40,6 +40,8 @@ EXPORTS = [
     "p3d_accum_create", "p3d_accum_destroy", "p3d_accum_reset", "p3d_accum_samples_done", "p3d_accum_render", "p3d_accum_render_device",
     "p3d_adaptive_create", "p3d_adaptive_destroy", "p3d_adaptive_reset", "p3d_adaptive_samples_done", "p3d_adaptive_active_pixels",
     "p3d_adaptive_render", "p3d_adaptive_render_device", "p3d_adaptive_read_state",
+    "p3d_render_features", "p3d_render_features_device", "p3d_denoise_params_default", "p3d_denoiser_create",
+    "p3d_denoiser_destroy", "p3d_denoise", "p3d_denoise_device", "p3d_denoise_variance", "p3d_denoise_variance_device",
 ]
 
 
@@ -118,6 +120,11 @@ class Tile(C.Structure):
 
 class AdaptiveParams(C.Structure):
     _fields_ = [("rel_error", C.c_float), ("min_samples", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_luma", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float), ("gamma", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
 class Stats(C.Structure):
@@ -217,6 +224,20 @@ def lib():
         L.p3d_adaptive_render_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.POINTER(Stats)]
         L.p3d_adaptive_read_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_render_features.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Tile), C.c_uint32, C.c_void_p, C.c_void_p]
+        L.p3d_render_features_device.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Tile), C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+        L.p3d_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
+        L.p3d_denoise_params_default.restype = None
+        L.p3d_denoiser_create.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.p3d_denoiser_destroy.argtypes = [C.c_void_p]
+        L.p3d_denoiser_destroy.restype = None
+        L.p3d_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]
+        L.p3d_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_denoise_variance.argtypes = [C.c_void_p, C.c_void_p]
+        L.p3d_denoise_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -239,6 +260,18 @@ def default_config(**kw):
             raise AttributeError(k)
         setattr(c, k, v)
     return c
+
+
+def denoise_params(**kw):
+    """p3d_denoise_params_default, then the fields given (iterations, sigma_color, sigma_luma, sigma_normal, sigma_depth,
+    sigma_albedo, gamma, reserved)."""
+    p = DenoiseParams()
+    lib().p3d_denoise_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_uint32 * 2)(*v) if k == "reserved" else v)
+    return p
 
 
 def whitted_config(accel=ACCEL_BVH, max_depth=4, **kw):
@@ -478,6 +511,23 @@ class DeviceScene:
         lim = (C.c_uint32 * 4)(trip_bound, max_rounds, halo_chain, leftover_pool)
         _check(self._L.p3d_debug_scene_limits(self._h, C.cast(lim, C.c_void_p)))
 
+    def render_features(self, cfg, samples=0, tile=None):
+        """p3d_render_features: the feature buffers of the primary rays of samples [0, K) (0: min(16, SPP*SPP)) ->
+        (normal_depth, albedo_cov), two (h, w, 4) float32 arrays: (n, t) and (diff_color, coverage), means over the samples
+        that hit."""
+        t = tile or self.full_tile()
+        nd = np.zeros((t.h, t.w, 4), np.float32)
+        ac = np.zeros((t.h, t.w, 4), np.float32)
+        _check(self._L.p3d_render_features(self._h, C.byref(cfg), C.byref(t), int(samples), nd.ctypes.data, ac.ctypes.data))
+        return nd, ac
+
+    def render_features_device(self, cfg, d_normal_depth, d_albedo_cov, samples=0, tile=None, stream=0):
+        """p3d_render_features_device: raw HBM addresses (16-byte aligned) and a hipStream_t (or a torch.cuda.Stream)."""
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_render_features_device(self._h, C.byref(cfg), C.byref(tile or self.full_tile()), int(samples),
+                                                  C.c_void_p(d_normal_depth or None), C.c_void_p(d_albedo_cov or None),
+                                                  C.c_void_p(raw or None)))
+
     def render_device(self, cfg, tile, d_rgb=0, d_hit=0, d_rgb8=0, stream=0, stats=None):
         """Device-buffer form: raw HBM addresses (e.g. torch.Tensor.data_ptr()) and a hipStream_t."""
         _check(self._L.p3d_render_tile_device(self._h, C.byref(cfg), C.byref(tile), C.c_void_p(d_rgb or None),
@@ -647,9 +697,74 @@ class AdaptiveAccumulator:
                                                out["samples"].ctypes.data, out["rel_err"].ctypes.data))
         return out
 
+    def variance(self):
+        """p3d_denoise_variance (waits for the device): per pixel the variance of its mean luminance, (h, w) float32 - the
+        variance buffer of Denoiser.run; 0 where a pixel has fewer than 2 samples."""
+        t = self.tile
+        var = np.zeros((t.h, t.w), np.float32)
+        _check(self._L.p3d_denoise_variance(self._h, var.ctypes.data))
+        return var
+
+    def variance_device(self, d_var, stream=0):
+        """p3d_denoise_variance_device: the same into HBM (w*h float), enqueued on `stream` behind the pass."""
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_denoise_variance_device(self._h, C.c_void_p(d_var or None), C.c_void_p(raw or None)))
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.p3d_adaptive_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Denoiser:
+    """p3d_denoiser (include/p3d.h): the edge-avoiding a-trous filter for w x h images on one device.  Inputs are the
+    linear rgb of a frame, its feature buffers (DeviceScene.render_features) and optionally a variance buffer
+    (AdaptiveAccumulator.variance); the device form neither allocates nor waits."""
+
+    def __init__(self, device, w, h):
+        self._L = lib()
+        self.w, self.h = int(w), int(h)
+        hd = C.c_void_p()
+        _check(self._L.p3d_denoiser_create(int(device), self.w, self.h, C.byref(hd)))
+        self._h = hd
+
+    def _shape(self, a, shape, dtype, what):
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != shape:
+            raise ValueError("%s: shape %s, the denoiser is for %s" % (what, a.shape, shape))
+        return a
+
+    def run(self, rgb, normal_depth, albedo_cov, variance=None, params=None, want_rgb8=False):
+        """p3d_denoise: -> rgb (h, w, 3) float32, and with want_rgb8 (rgb, rgb8)."""
+        h, w = self.h, self.w
+        rgb = self._shape(rgb, (h, w, 3), np.float32, "rgb")
+        nd = self._shape(normal_depth, (h, w, 4), np.float32, "normal_depth")
+        ac = self._shape(albedo_cov, (h, w, 4), np.float32, "albedo_cov")
+        var = None if variance is None else self._shape(variance, (h, w), np.float32, "variance")
+        prm = params if params is not None else denoise_params()
+        out = np.zeros((h, w, 3), np.float32)
+        out8 = np.zeros((h, w, 3), np.uint8) if want_rgb8 else None
+        _check(self._L.p3d_denoise(self._h, C.byref(prm), rgb.ctypes.data, var.ctypes.data if var is not None else None,
+                                   nd.ctypes.data, ac.ctypes.data, out.ctypes.data, out8.ctypes.data if want_rgb8 else None))
+        return (out, out8) if want_rgb8 else out
+
+    def run_device(self, d_rgb, d_normal_depth, d_albedo_cov, d_out_rgb=0, d_out_rgb8=0, d_var=0, params=None, stream=0):
+        """p3d_denoise_device: raw HBM addresses and a hipStream_t (or a torch.cuda.Stream); enqueued, not waited for."""
+        prm = params if params is not None else denoise_params()
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_denoise_device(self._h, C.byref(prm), C.c_void_p(d_rgb or None), C.c_void_p(d_var or None),
+                                          C.c_void_p(d_normal_depth or None), C.c_void_p(d_albedo_cov or None),
+                                          C.c_void_p(d_out_rgb or None), C.c_void_p(d_out_rgb8 or None), C.c_void_p(raw or None)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.p3d_denoiser_destroy(self._h)
             self._h = None
 
     def __del__(self):

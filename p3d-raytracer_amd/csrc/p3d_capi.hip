@@ -19,6 +19,8 @@
 #include "p3d_debug.h"
 #include "pt_kernel.hpp"
 #include "adaptive.hpp"
+#include "features.hpp"
+#include "denoise.hpp"
 
 using namespace p3d;
 
@@ -591,6 +593,16 @@ struct AdaptPass {
   uint32_t resident;  // workgroups the device holds at once (the grid of pt_adaptive_kernel at most)
 };
 
+// Feature buffers (p3d_render_features, features.hpp): one launch over the tile's 8x8 tiles with the frame's staging and stack
+template <int ACCEL>
+hipError_t launch_features(bool lds_scene, int stack_mode, const RenderParams& P, const FeatureParams& F, uint32_t blocks, size_t lds, hipStream_t st) {
+  if (!lds_scene) hipLaunchKernelGGL((feature_kernel<ACCEL, false, kStackWindow>), dim3(blocks), dim3(kBlock), lds, st, P, F);
+  else if (stack_mode == kStackLds8) hipLaunchKernelGGL((feature_kernel<ACCEL, true, kStackLds8>), dim3(blocks), dim3(kBlock), lds, st, P, F);
+  else if (stack_mode == kStackLds6) hipLaunchKernelGGL((feature_kernel<ACCEL, true, kStackLds6>), dim3(blocks), dim3(kBlock), lds, st, P, F);
+  else hipLaunchKernelGGL((feature_kernel<ACCEL, true, kStackWindow>), dim3(blocks), dim3(kBlock), lds, st, P, F);
+  return hipGetLastError();
+}
+
 // P3D_STACK_LITERAL launches (BVH only).  lit 1: pass 1; lit 2: work-list launch; lit 0: the check launch over the tiles; lit 3:
 // the check launch over pass 1's list; lit 4: check + repair over the tiles in one launch (whitted_kernel LIT = 3).
 // ghosts: the scene has zero-weight reflection rays to trace (a transmissive AND reflective material).
@@ -786,9 +798,11 @@ int check_frame(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile) {
 // (samples [sample_begin, sample_end) of an anti-aliased frame whose running sums and first hits live in accum_sum /
 // accum_hit).  The sample range only reaches the anti-aliased sample loops; everything else is the same frame.  With
 // `adapt` (p3d_adaptive_render_device, path tracer only) the pass renders the listed pixels and resolves the tile behind.
+// With `feat` (p3d_render_features_device) the launch traces the primary rays of samples [0, sample_end) and writes the
+// feature buffers instead: the same scene staging, stack and LDS as the frame, no shading.
 int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float* d_rgb, int32_t* d_hit, uint8_t* d_rgb8,
                 void* hip_stream, p3d_stats* stats, uint32_t sample_begin, uint32_t sample_end, float* accum_sum, int32_t* accum_hit,
-                const AdaptPass* adapt = nullptr) {
+                const AdaptPass* adapt = nullptr, const FeatureParams* feat = nullptr) {
   if (int rc = check_frame(s, cfg, tile)) return rc;
   const DevCamera& cam = s->dev.cam;
   const int sh = tile->stripe_h > 0 ? tile->stripe_h : 1, ss = tile->stripe_h > 0 ? tile->stripe_stride : 1;
@@ -859,8 +873,9 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
   // unless the samples of a pixel have to hand the stack to each other in order (LITERAL).  Counted in the samples of THIS
   // launch (a pass of an accumulated frame may have fewer than the frame): both loops add the same values in the same order.
   const uint32_t launch_samples = sample_end - sample_begin;
-  const bool sub4 = (pt && launch_samples >= kPtSub4MinSppSqrt * kPtSub4MinSppSqrt) ||
-                    (!pt && !literal && !lds_scene && cfg->antialiasing && launch_samples >= kWhittedSub4MinSppSqrt * kWhittedSub4MinSppSqrt);
+  // (feature launches: one lane per pixel, 8x8 tiles)
+  const bool sub4 = !feat && ((pt && launch_samples >= kPtSub4MinSppSqrt * kPtSub4MinSppSqrt) ||
+                              (!pt && !literal && !lds_scene && cfg->antialiasing && launch_samples >= kWhittedSub4MinSppSqrt * kWhittedSub4MinSppSqrt));
   // ... and behind the node stack: the sample ring of the four-lanes-per-pixel kernels, or the cold shading state of the
   // Whitted kernels that traverse the scene from L2 without anti-aliasing (ColdState<true>, device_core.hpp)
   const bool cold_lds = !pt && !lds_scene && !cfg->antialiasing;
@@ -869,7 +884,7 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
   // to keep the wave slots busy for several rounds (stripes of a multi-GPU frame, small frames): quarter waves are
   // shorter and four times as many, at the price of issue slots the chip then has to spare (tile_shape()).
   uint32_t tpw = sub4 ? 4 : 8, tph = sub4 ? 4 : 8;
-  if (!sub4 && !pt && !lds_scene && !cfg->antialiasing && cfg->chain_launch != P3D_CHAIN_PER_LEVEL) tile_shape((uint64_t)tile->w * tile->h, tpw, tph);
+  if (!feat && !sub4 && !pt && !lds_scene && !cfg->antialiasing && cfg->chain_launch != P3D_CHAIN_PER_LEVEL) tile_shape((uint64_t)tile->w * tile->h, tpw, tph);
   const uint32_t tp = tph;  // rows per tile band
   P.tile_w_shift = tpw == 8 ? 3 : 2;
   P.tile_h_shift = tph == 8 ? 3 : 2;
@@ -883,7 +898,7 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
   const uint32_t tiles_x = ((uint32_t)tile->w + tpw - 1) / tpw;
   // per-thread global scratch: Whitted level records (+ the zero-weight reflection rays a LITERAL launch puts aside),
   // or the path tracer's two deferred dielectric branches
-  const uint32_t levels = pt ? 2 * 3 : (uint32_t)cfg->max_depth;
+  const uint32_t levels = feat ? 0u : (pt ? 2 * 3 : (uint32_t)cfg->max_depth);
   const uint32_t deferred = (literal && s->zero_weight_reflections) ? 2u * (uint32_t)std::max(cfg->max_depth, 1) : 0u;
   // One launch per chain level (wf_level_kernel) where the lanes of a megakernel wave die off in the reflection levels:
   // Whitted without anti-aliasing over a BVH read from L2.  Not for the zero-weight reflection rays of LITERAL frames
@@ -922,7 +937,11 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
   const uint32_t halo_blocks_max = literal ? ((uint32_t)tile->h * kHaloChain + kBlock - 1) / kBlock : 0;
   // (an adaptive pass: one launch of at most adapt->resident workgroups, each working through groups of the pixel list)
   const uint32_t adapt_blocks = adapt ? std::max<uint32_t>(1, std::min<uint32_t>(adapt->resident, (uint32_t)(((size_t)tile->w * tile->h + (sub4 ? 15 : 63)) / (sub4 ? 16 : 64)))) : 0;
-  const uint32_t max_threads = adapt ? adapt_blocks * kBlock : (blocks_for(tiles_x * bands_per_launch) + halo_blocks_max) * kBlock;
+  // (feature buffers: one launch over every tile of the tile, one lane per pixel)
+  const uint32_t feat_blocks = feat ? blocks_for(tiles_x * total_bands) : 0;
+  if (feat && (uint64_t)feat_blocks * kBlock * std::max<uint32_t>(spill_entries, 1) > 0xffffffffull)  // (32-bit stack offsets, device_core.hpp Stack)
+    return fail(P3D_ERR_CAPACITY, "p3d_render_features: tile too large for one launch over a tree this deep (split the tile)");
+  const uint32_t max_threads = adapt ? adapt_blocks * kBlock : (feat ? feat_blocks * kBlock : (blocks_for(tiles_x * bands_per_launch) + halo_blocks_max) * kBlock);
   const size_t tile_units = (size_t)tile->h * ((size_t)tile->w + kHaloChain);  // upper bound of H.n_units
   // per-level launches keep one record per (level, unit); the work-list launches of a LITERAL frame behind them are the
   // megakernel and index [level][launch thread] with up to max_threads threads, whatever the size of the tile
@@ -1100,8 +1119,23 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
     }
     if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("adaptive pass launch: ") + hipGetErrorString(e));
   }
+  if (feat) {  // the primary rays of every pixel of the tile, one launch (features.hpp)
+    P.x0 = tile->x0; P.y0 = tile->y0; P.w = tile->w; P.h = tile->h; P.row0 = 0;
+    P.tiles_x = tiles_x; P.tiles_y = total_bands; P.xcd_chunk = xcd_chunk;
+    P.sched = nullptr; P.tile_cost = nullptr;
+    P.tile_blocks = feat_blocks;
+    P.level_stride = feat_blocks * kBlock;
+    const size_t feat_lds = (size_t)P.lds_scene_f4 * sizeof(float4) + (size_t)stack_lds_f4(stack_mode, cap) * sizeof(float4);
+    hipError_t e = hipSuccess;
+    switch (cfg->accel) {
+      case P3D_ACCEL_BVH: e = launch_features<P3D_ACCEL_BVH>(lds_scene, stack_mode, P, *feat, feat_blocks, feat_lds, st); break;
+      case P3D_ACCEL_GRID: e = launch_features<P3D_ACCEL_GRID>(lds_scene, stack_mode, P, *feat, feat_blocks, feat_lds, st); break;
+      default: e = launch_features<P3D_ACCEL_NONE>(lds_scene, stack_mode, P, *feat, feat_blocks, feat_lds, st); break;
+    }
+    if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("feature launch: ") + hipGetErrorString(e));
+  }
   // pass: 0 = the render launches (LITERAL: pass 1, everything on an empty stack); 1 = LITERAL only: the check launches
-  for (int pass = 0; pass < (adapt ? 0 : (literal ? 2 : 1)); ++pass) {
+  for (int pass = 0; pass < ((adapt || feat) ? 0 : (literal ? 2 : 1)); ++pass) {
     if (pass == 1)
       if (int rc = to_tail()) return rc;
     if (pass == 1 && (abl_skip() & 1u)) break;
@@ -1446,6 +1480,7 @@ struct p3d_adaptive {
   uint32_t resident = 0;  // workgroups the device holds at once
   bool failed = false;
   Scratch sum, hit, sum_y2, samples, active, rel_err, list, counters;  // counters: count[2], ticket
+  Scratch var;  // p3d_denoise_variance (host form): the device copy of its output
 };
 
 namespace {
@@ -1533,7 +1568,7 @@ int p3d_adaptive_create(p3d_scene* s, const p3d_config* cfg, const p3d_tile* til
 void p3d_adaptive_destroy(p3d_adaptive* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  for (Scratch* b : {&a->sum, &a->hit, &a->sum_y2, &a->samples, &a->active, &a->rel_err, &a->list, &a->counters}) b->release();
+  for (Scratch* b : {&a->sum, &a->hit, &a->sum_y2, &a->samples, &a->active, &a->rel_err, &a->list, &a->counters, &a->var}) b->release();
   delete a;
 }
 
@@ -1608,6 +1643,195 @@ int p3d_adaptive_read_state(p3d_adaptive* a, float* sum, float* sum_y2, uint32_t
   if (sum_y2) P3D_HIP(hipMemcpy(sum_y2, a->sum_y2.p, px * sizeof(float), hipMemcpyDeviceToHost));
   if (samples) P3D_HIP(hipMemcpy(samples, a->samples.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (rel_err) P3D_HIP(hipMemcpy(rel_err, a->rel_err.p, px * sizeof(float), hipMemcpyDeviceToHost));
+  return P3D_OK;
+}
+
+// ---- denoising (include/p3d.h): feature buffers, the a-trous filter, the variance of an adaptive frame ----
+
+int p3d_render_features_device(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, uint32_t samples, float* d_normal_depth,
+                               float* d_albedo_cov, void* hip_stream) {
+  if (!s || !cfg || !tile || !d_normal_depth || !d_albedo_cov) return fail(P3D_ERR_INVALID, "p3d_render_features: null argument");
+  if (((uintptr_t)d_normal_depth | (uintptr_t)d_albedo_cov) & 15u) return fail(P3D_ERR_INVALID, "p3d_render_features: the feature buffers must be 16-byte aligned");
+  if (tile->stripe_h > 0 && tile->stripe_stride > 1)
+    return fail(P3D_ERR_UNSUPPORTED, "p3d_render_features: striped tiles are not supported (the denoiser filters a buffer as one image)");
+  if (int rc = check_frame(s, cfg, tile)) return rc;
+  const uint32_t total = cfg->antialiasing ? cfg->spp_sqrt * cfg->spp_sqrt : 1u;
+  const uint32_t k = samples ? samples : std::min<uint32_t>(16, total);
+  if (k > total)
+    return fail(P3D_ERR_INVALID, "p3d_render_features: " + std::to_string(samples) + " samples asked, the frame has " + std::to_string(total) +
+                                     (cfg->antialiasing ? " per pixel" : " (antialiasing = 0: only the pixel-centre ray)"));
+  // primary rays on an empty stack, one launch: no hit_stack hand-off, no per-level chain, nothing counted
+  p3d_config fc = *cfg;
+  fc.stack_mode = P3D_STACK_PER_PIXEL;
+  fc.chain_launch = P3D_CHAIN_AUTO;
+  fc.collect_stats = 0;
+  FeatureParams F{};
+  F.normal_depth = (float4*)d_normal_depth;
+  F.albedo_cov = (float4*)d_albedo_cov;
+  F.samples = k;
+  return render_impl(s, &fc, tile, nullptr, nullptr, nullptr, hip_stream, nullptr, 0, k, nullptr, nullptr, nullptr, &F);
+}
+
+int p3d_render_features(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, uint32_t samples, float* normal_depth, float* albedo_cov) {
+  if (!s || !cfg || !tile || !normal_depth || !albedo_cov) return fail(P3D_ERR_INVALID, "p3d_render_features: null argument");
+  if (tile->w <= 0 || tile->h <= 0) return fail(P3D_ERR_INVALID, "empty tile");
+  P3D_HIP(hipSetDevice(s->device));
+  const size_t n = (size_t)tile->w * tile->h;
+  if (int rc = s->q_out.ensure(n * 2 * sizeof(float4))) return rc;
+  float* d_nd = (float*)s->q_out.p;
+  float* d_ac = d_nd + n * 4;
+  if (int rc = p3d_render_features_device(s, cfg, tile, samples, d_nd, d_ac, nullptr)) return rc;
+  P3D_HIP(hipMemcpy(normal_depth, d_nd, n * sizeof(float4), hipMemcpyDeviceToHost));
+  P3D_HIP(hipMemcpy(albedo_cov, d_ac, n * sizeof(float4), hipMemcpyDeviceToHost));
+  return P3D_OK;
+}
+
+void p3d_denoise_params_default(p3d_denoise_params* prm) {
+  if (!prm) return;
+  *prm = p3d_denoise_params{};
+  prm->iterations = 5;
+  prm->sigma_color = 4.0f;   // DESIGN.md "Denoising": chosen on the Cornell box, 16 against 1024 samples per pixel
+  prm->sigma_luma = 64.0f;
+  prm->sigma_normal = 128.0f;
+  prm->sigma_depth = 1.0f;
+  prm->sigma_albedo = 0.1f;
+  prm->gamma = 1.0f;  // p3d_config_default's GAMMA
+}
+
+}  // extern "C"
+
+// The denoiser: two float4 images (R, G, B, var) for the iterations to ping-pong between, made at create so that the
+// device-buffer call neither allocates nor waits; the host-buffer call keeps device copies of its arrays besides.
+struct p3d_denoiser {
+  int device = 0;
+  int32_t w = 0, h = 0;
+  Scratch ping, pong;
+  Scratch h_rgb, h_var, h_nd, h_ac, h_out, h_out8;
+};
+
+namespace {
+
+int check_denoise_params(const p3d_denoise_params* prm, bool has_var) {
+  if (prm->iterations > 8) return fail(P3D_ERR_INVALID, "p3d_denoise: iterations must be at most 8");
+  for (float v : {prm->sigma_color, prm->sigma_luma, prm->sigma_normal, prm->sigma_depth, prm->sigma_albedo})
+    if (!(v >= 0.0f)) return fail(P3D_ERR_INVALID, "p3d_denoise: every sigma must be a number >= 0");
+  if (has_var && !(prm->sigma_luma > 0.0f)) return fail(P3D_ERR_INVALID, "p3d_denoise: sigma_luma must be > 0 with a variance buffer");
+  if (!has_var && !(prm->sigma_color > 0.0f)) return fail(P3D_ERR_INVALID, "p3d_denoise: sigma_color must be > 0 without a variance buffer");
+  if (!(prm->gamma > 0.0f)) return fail(P3D_ERR_INVALID, "p3d_denoise: gamma must be a number > 0");
+  if (prm->reserved[0] || prm->reserved[1]) return fail(P3D_ERR_INVALID, "p3d_denoise: reserved fields must be 0");
+  return P3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p3d_denoiser_create(int device, int32_t w, int32_t h, p3d_denoiser** out) {
+  if (!out) return fail(P3D_ERR_INVALID, "p3d_denoiser_create: null argument");
+  *out = nullptr;
+  if (w <= 0 || h <= 0 || (uint64_t)w * (uint64_t)h > (1ull << 28)) return fail(P3D_ERR_INVALID, "p3d_denoiser_create: bad image size");
+  P3D_HIP(hipSetDevice(device));
+  p3d_denoiser* d = new p3d_denoiser;
+  d->device = device;
+  d->w = w;
+  d->h = h;
+  const size_t n = (size_t)w * h;
+  int rc = d->ping.ensure(n * sizeof(float4));
+  if (!rc) rc = d->pong.ensure(n * sizeof(float4));
+  if (rc) {
+    p3d_denoiser_destroy(d);
+    return rc;
+  }
+  *out = d;
+  return P3D_OK;
+}
+
+void p3d_denoiser_destroy(p3d_denoiser* d) {
+  if (!d) return;
+  (void)hipSetDevice(d->device);
+  for (Scratch* b : {&d->ping, &d->pong, &d->h_rgb, &d->h_var, &d->h_nd, &d->h_ac, &d->h_out, &d->h_out8}) b->release();
+  delete d;
+}
+
+int p3d_denoise_device(p3d_denoiser* d, const p3d_denoise_params* prm, const float* d_rgb, const float* d_var, const float* d_normal_depth,
+                       const float* d_albedo_cov, float* d_out_rgb, uint8_t* d_out_rgb8, void* hip_stream) {
+  if (!d || !prm || !d_rgb || !d_normal_depth || !d_albedo_cov) return fail(P3D_ERR_INVALID, "p3d_denoise: null argument");
+  if (!d_out_rgb && !d_out_rgb8) return fail(P3D_ERR_INVALID, "p3d_denoise: no output");
+  if (((uintptr_t)d_normal_depth | (uintptr_t)d_albedo_cov) & 15u) return fail(P3D_ERR_INVALID, "p3d_denoise: the feature buffers must be 16-byte aligned");
+  if (int rc = check_denoise_params(prm, d_var != nullptr)) return rc;
+  P3D_HIP(hipSetDevice(d->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  AtrousParams A{};
+  A.rgb_in = d_rgb; A.var_in = d_var;
+  A.nd = (const float4*)d_normal_depth; A.ac = (const float4*)d_albedo_cov;
+  A.rgb_out = d_out_rgb; A.rgb8_out = d_out_rgb8;
+  A.w = d->w; A.h = d->h;
+  A.has_var = d_var ? 1u : 0u;
+  A.sigma_luma = prm->sigma_luma; A.sigma_normal = prm->sigma_normal; A.sigma_depth = prm->sigma_depth; A.sigma_albedo = prm->sigma_albedo;
+  A.gamma = prm->gamma;
+  const dim3 grid(((uint32_t)d->w + kAtrousEdge - 1) / kAtrousEdge, ((uint32_t)d->h + kAtrousEdge - 1) / kAtrousEdge);
+  const uint32_t n_launch = std::max<uint32_t>(prm->iterations, 1);  // (iterations = 0: one launch that copies the input)
+  float4* buf[2] = {(float4*)d->ping.p, (float4*)d->pong.p};
+  for (uint32_t i = 0; i < n_launch; ++i) {
+    A.first = i == 0 ? 1u : 0u;
+    A.last = i + 1 == n_launch ? 1u : 0u;
+    A.in = buf[(i + 1) & 1u];
+    A.out = buf[i & 1u];
+    A.step = prm->iterations ? (int32_t)(1u << i) : 0;
+    A.color_scale = (float)((double)(1u << (2 * i)) / ((double)prm->sigma_color * (double)prm->sigma_color));
+    hipLaunchKernelGGL(atrous_kernel, grid, dim3(kAtrousThreads), 0, st, A);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("p3d_denoise launch: ") + hipGetErrorString(e));
+  }
+  return P3D_OK;
+}
+
+int p3d_denoise(p3d_denoiser* d, const p3d_denoise_params* prm, const float* rgb, const float* var, const float* normal_depth,
+                const float* albedo_cov, float* out_rgb, uint8_t* out_rgb8) {
+  if (!d || !prm || !rgb || !normal_depth || !albedo_cov) return fail(P3D_ERR_INVALID, "p3d_denoise: null argument");
+  if (!out_rgb && !out_rgb8) return fail(P3D_ERR_INVALID, "p3d_denoise: no output");
+  if (int rc = check_denoise_params(prm, var != nullptr)) return rc;
+  P3D_HIP(hipSetDevice(d->device));
+  const size_t n = (size_t)d->w * d->h;
+  if (int rc = d->h_rgb.ensure(n * 3 * sizeof(float))) return rc;
+  if (var) if (int rc = d->h_var.ensure(n * sizeof(float))) return rc;
+  if (int rc = d->h_nd.ensure(n * sizeof(float4))) return rc;
+  if (int rc = d->h_ac.ensure(n * sizeof(float4))) return rc;
+  if (out_rgb) if (int rc = d->h_out.ensure(n * 3 * sizeof(float))) return rc;
+  if (out_rgb8) if (int rc = d->h_out8.ensure(n * 3)) return rc;
+  P3D_HIP(hipMemcpy(d->h_rgb.p, rgb, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  if (var) P3D_HIP(hipMemcpy(d->h_var.p, var, n * sizeof(float), hipMemcpyHostToDevice));
+  P3D_HIP(hipMemcpy(d->h_nd.p, normal_depth, n * sizeof(float4), hipMemcpyHostToDevice));
+  P3D_HIP(hipMemcpy(d->h_ac.p, albedo_cov, n * sizeof(float4), hipMemcpyHostToDevice));
+  if (int rc = p3d_denoise_device(d, prm, (const float*)d->h_rgb.p, var ? (const float*)d->h_var.p : nullptr, (const float*)d->h_nd.p,
+                                  (const float*)d->h_ac.p, out_rgb ? (float*)d->h_out.p : nullptr, out_rgb8 ? (uint8_t*)d->h_out8.p : nullptr, nullptr))
+    return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  if (out_rgb) P3D_HIP(hipMemcpy(out_rgb, d->h_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (out_rgb8) P3D_HIP(hipMemcpy(out_rgb8, d->h_out8.p, n * 3, hipMemcpyDeviceToHost));
+  return P3D_OK;
+}
+
+int p3d_denoise_variance_device(p3d_adaptive* a, float* d_var, void* hip_stream) {
+  if (!a || !d_var) return fail(P3D_ERR_INVALID, "p3d_denoise_variance: null argument");
+  P3D_HIP(hipSetDevice(a->device));
+  VarianceParams V{};
+  V.sum = (const float*)a->sum.p; V.sum_y2 = (const float*)a->sum_y2.p; V.samples = (const uint32_t*)a->samples.p;
+  V.var = d_var;
+  V.n = (uint32_t)adapt_pixels(a);
+  hipLaunchKernelGGL(adapt_variance_kernel, dim3((V.n + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, V);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("p3d_denoise_variance launch: ") + hipGetErrorString(e));
+  return P3D_OK;
+}
+
+int p3d_denoise_variance(p3d_adaptive* a, float* var) {
+  if (!a || !var) return fail(P3D_ERR_INVALID, "p3d_denoise_variance: null argument");
+  P3D_HIP(hipSetDevice(a->device));
+  P3D_HIP(hipDeviceSynchronize());
+  const size_t px = adapt_pixels(a);
+  if (int rc = a->var.ensure(px * sizeof(float))) return rc;
+  if (int rc = p3d_denoise_variance_device(a, (float*)a->var.p, nullptr)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  P3D_HIP(hipMemcpy(var, a->var.p, px * sizeof(float), hipMemcpyDeviceToHost));
   return P3D_OK;
 }
 

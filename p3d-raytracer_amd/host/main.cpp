@@ -30,6 +30,11 @@
 //              [--min-spp M]    stops taking samples once its relative error is below REL and it has at least M samples
 //                               (default 16, or SPP*SPP when smaller).  One line per pass gives the samples done, the pixels
 //                               still active and the pass time; the passes end early once no pixel is active.
+//              [--denoise FILE] --pathtrace --aa 1: the final frame (the one-shot frame, or the last of --passes) denoised
+//              [--denoise-iter N]  with the edge-avoiding a-trous filter (p3d_denoise, include/p3d.h; N iterations, default 5,
+//              [--feature-spp K]   at most 8) over feature buffers of the first K samples' primary rays (default 0 = min(16,
+//                               SPP*SPP)); with --adaptive the filter uses the frame's variance.  FILE is PNG or PPM by
+//                               extension, as --out; --out is written as without --denoise.  Not with --whitted or --gpus.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -268,6 +273,9 @@ int main(int argc, char** argv) {
   long passes = 0;  // --passes K (0: one call renders the frame)
   float adaptive = -1.0f;  // --adaptive REL (< 0: off)
   long min_spp = 0;        // --min-spp M (0: the default)
+  std::string denoise_out;   // --denoise FILE (empty: off)
+  long denoise_iter = -1;    // --denoise-iter N (-1: the default)
+  long feature_spp = -1;     // --feature-spp K (-1: the default)
   bool device_bvh = false, verify = false;
   uint32_t load_flags = 0;
   for (int i = 1; i < argc; ++i) {
@@ -318,6 +326,18 @@ int main(int argc, char** argv) {
       min_spp = std::strtol(v, &end, 10);
       if (end == v || *end != 0 || min_spp < 2) { std::fprintf(stderr, "--min-spp needs a whole number of samples, at least 2 (got '%s')\n", v); return 2; }
     }
+    else if (a == "--denoise") denoise_out = next("--denoise");
+    else if (a == "--denoise-iter" || a == "--feature-spp") {
+      const char* v = next(a.c_str());
+      char* end = nullptr;
+      const long n = std::strtol(v, &end, 10);
+      const long hi = a == "--denoise-iter" ? 8 : 1L << 20;
+      if (end == v || *end != 0 || n < 0 || n > hi) {
+        std::fprintf(stderr, "%s needs a whole number from 0 to %ld (got '%s')\n", a.c_str(), hi, v);
+        return 2;
+      }
+      (a == "--denoise-iter" ? denoise_iter : feature_spp) = n;
+    }
     else if (a[0] != '-') scene_path = a;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
@@ -334,6 +354,19 @@ int main(int argc, char** argv) {
     const long total = (long)cfg.spp_sqrt * (long)cfg.spp_sqrt;
     if (min_spp > total) { std::fprintf(stderr, "--min-spp %ld: the frame has only %ld samples per pixel\n", min_spp, total); return 2; }
     if (min_spp == 0) min_spp = std::max(2L, std::min(16L, total));
+  }
+  if ((denoise_iter >= 0 || feature_spp >= 0) && denoise_out.empty()) {
+    std::fprintf(stderr, "%s goes with --denoise\n", denoise_iter >= 0 ? "--denoise-iter" : "--feature-spp");
+    return 2;
+  }
+  if (!denoise_out.empty()) {
+    if (cfg.integrator != P3D_PATHTRACE) { std::fprintf(stderr, "--denoise is for --pathtrace (not --whitted)\n"); return 2; }
+    if (gpus > 0) { std::fprintf(stderr, "--denoise does not combine with --gpus\n"); return 2; }
+    if (!cfg.antialiasing) { std::fprintf(stderr, "--denoise needs --aa 1 (a path-traced frame with samples to filter)\n"); return 2; }
+    if (feature_spp > (long)cfg.spp_sqrt * (long)cfg.spp_sqrt) {
+      std::fprintf(stderr, "--feature-spp %ld: the frame has only %ld samples per pixel\n", feature_spp, (long)cfg.spp_sqrt * (long)cfg.spp_sqrt);
+      return 2;
+    }
   }
   if (scene_path.empty()) {  // main.cpp:968-980: prompt for a name under P3D_Scenes/
     std::string name;
@@ -391,6 +424,8 @@ int main(int argc, char** argv) {
   const auto t_build1 = std::chrono::high_resolution_clock::now();
 
   std::vector<uint8_t> img((size_t)3 * W * H);
+  const bool denoise = !denoise_out.empty();
+  std::vector<float> lin(denoise ? (size_t)3 * W * H : 0), var;  // --denoise: the final frame's linear rgb (and variance)
   p3d_tile tile{0, 0, W, H, 0, 1};
   p3d_stats st{};
   cfg.collect_stats = 1;
@@ -410,7 +445,7 @@ int main(int argc, char** argv) {
       p3d_stats ps{};
       uint32_t active = 0;
       const auto p0 = std::chrono::high_resolution_clock::now();
-      if (p3d_adaptive_render(ad, n, nullptr, nullptr, img.data(), nullptr, &ps) != P3D_OK) return die("render");
+      if (p3d_adaptive_render(ad, n, denoise ? lin.data() : nullptr, nullptr, img.data(), nullptr, &ps) != P3D_OK) return die("render");
       if (p3d_adaptive_active_pixels(ad, &active) != P3D_OK) return die("adaptive_active_pixels");
       const double pass_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - p0).count();
       std::printf("pass %ld/%ld: %u of %u samples done, %u of %d pixels active, %.3f ms\n", k + 1, passes,
@@ -425,6 +460,10 @@ int main(int argc, char** argv) {
       }
       if (active == 0) break;  // every pixel has converged: later passes would change nothing
     }
+    if (denoise) {
+      var.resize((size_t)W * H);
+      if (p3d_denoise_variance(ad, var.data()) != P3D_OK) return die("denoise_variance");
+    }
     p3d_adaptive_destroy(ad);
   } else if (passes > 0) {  // progressive: the image refines pass by pass (p3d_accum), --out rewritten after every pass
     p3d_accum* acc = nullptr;
@@ -438,7 +477,7 @@ int main(int argc, char** argv) {
       const uint32_t n = (uint32_t)(total / passes) + ((long)(total % passes) > k ? 1u : 0u);
       p3d_stats ps{};
       const auto p0 = std::chrono::high_resolution_clock::now();
-      if (p3d_accum_render(acc, n, nullptr, nullptr, img.data(), &ps) != P3D_OK) return die("render");
+      if (p3d_accum_render(acc, n, denoise ? lin.data() : nullptr, nullptr, img.data(), &ps) != P3D_OK) return die("render");
       const double pass_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - p0).count();
       std::printf("pass %ld/%ld: %u of %u samples done, %.3f ms\n", k + 1, passes, p3d_accum_samples_done(acc), total, pass_ms);
       std::fflush(stdout);
@@ -451,7 +490,7 @@ int main(int argc, char** argv) {
       }
     }
     p3d_accum_destroy(acc);
-  } else if (p3d_render_tile(scene, &cfg, &tile, nullptr, nullptr, img.data(), &st) != P3D_OK) {
+  } else if (p3d_render_tile(scene, &cfg, &tile, denoise ? lin.data() : nullptr, nullptr, img.data(), &st) != P3D_OK) {
     return die("render");
   }
   const auto t1 = std::chrono::high_resolution_clock::now();
@@ -467,6 +506,30 @@ int main(int argc, char** argv) {
     return 1;
   }
   std::printf("Image file created\n");
+  if (denoise) {  // the final frame through the a-trous filter, over the primary rays' feature buffers
+    const auto d0 = std::chrono::high_resolution_clock::now();
+    std::vector<float> nd((size_t)4 * W * H), ac((size_t)4 * W * H);
+    if (p3d_render_features(scene, &cfg, &tile, feature_spp > 0 ? (uint32_t)feature_spp : 0u, nd.data(), ac.data()) != P3D_OK)
+      return die("render_features");
+    p3d_denoise_params prm;
+    p3d_denoise_params_default(&prm);
+    if (denoise_iter >= 0) prm.iterations = (uint32_t)denoise_iter;
+    prm.gamma = cfg.gamma;
+    p3d_denoiser* dn = nullptr;
+    if (p3d_denoiser_create(device, W, H, &dn) != P3D_OK) return die("denoiser_create");
+    std::vector<uint8_t> den((size_t)3 * W * H);
+    if (p3d_denoise(dn, &prm, lin.data(), var.empty() ? nullptr : var.data(), nd.data(), ac.data(), nullptr, den.data()) != P3D_OK)
+      return die("denoise");
+    p3d_denoiser_destroy(dn);
+    std::printf("denoised: %u iterations%s, features and filter %.3f ms\n", prm.iterations, var.empty() ? "" : " (adaptive variance)",
+                std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - d0).count());
+    const bool dppm = denoise_out.size() > 4 && denoise_out.compare(denoise_out.size() - 4, 4, ".ppm") == 0;
+    if (!(dppm ? save_ppm(denoise_out, den, W, H) : save_png(denoise_out, den, W, H))) {
+      std::printf("Error saving Image file\n");
+      return 1;
+    }
+    std::printf("Denoised image file created\n");
+  }
   p3d_scene_destroy(scene);
   p3d_host_scene_destroy(hs);
   return 0;

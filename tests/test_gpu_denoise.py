@@ -1,0 +1,357 @@
+"""Denoising on the GPU: feature buffers (p3d_render_features), the a-trous filter (p3d_denoise) against its float64 numpy
+statement (tests/atrous_reference.py), the variance of an adaptive frame (p3d_denoise_variance), the quality the default
+parameters reach on the Cornell box, and p3d_render --denoise."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import p3d_amd as p3d
+from atrous_reference import atrous, u8
+from conftest import ROOT, scene_path
+
+pytestmark = pytest.mark.gpu
+
+CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
+BALLS = scene_path("balls_low.p3f")
+TOL = 1e-5  # |gpu - ref| <= TOL * max(1, |ref|) per channel
+_scenes = {}
+
+
+def device_scene(path, res):
+    key = (path, res)
+    if key not in _scenes:
+        hs = p3d.HostScene(path)
+        hs.set_resolution(*res)
+        _scenes[key] = p3d.DeviceScene(hs, bvh=True, grid=True)
+    return _scenes[key]
+
+
+def cornell_cfg(spp=4, **kw):
+    return p3d.pathtrace_config(accel=kw.pop("accel", p3d.ACCEL_BVH), spp_sqrt=spp, max_depth=20, dof=0, seed=0x5EED, **kw)
+
+
+def same_bits(a, b):
+    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+
+
+def assert_close_to_reference(gpu, ref, what):
+    err = np.abs(gpu.astype(np.float64) - ref) / np.maximum(1.0, np.abs(ref))
+    assert np.isfinite(gpu).all(), what
+    assert err.max() <= TOL, "%s: worst relative error %.3g at %s" % (what, err.max(), np.unravel_index(err.argmax(), err.shape))
+
+
+# ---- feature buffers ----
+
+@pytest.mark.parametrize("path", [CORNELL, BALLS], ids=["cornell", "balls_low"])
+@pytest.mark.parametrize("accel", [p3d.ACCEL_BVH, p3d.ACCEL_GRID, p3d.ACCEL_NONE], ids=["bvh", "grid", "none"])
+def test_pixel_centre_features_match_the_traversal(path, accel):
+    from oracle import binding as ob
+    w, h = 40, 30
+    dev = device_scene(path, (w, h))
+    cfg = p3d.whitted_config(accel=accel, max_depth=2) if path == BALLS else cornell_cfg(accel=accel, antialiasing=0)
+    nd, ac = dev.render_features(cfg)
+    sc = ob.Scene(path)
+    sc.set_resolution(w, h)
+    rays = [sc.primary_ray(x + 0.5, y + 0.5) for y in range(h) for x in range(w)]
+    o = np.array([r[0] for r in rays], np.float32)
+    d = np.array([r[1] for r in rays], np.float32)
+    hit, hp, t = dev.trace_closest(accel, o, d, want_t=True)
+    hit, t, hp, d = hit.reshape(h, w), t.reshape(h, w), hp.reshape(h, w, 3), d.reshape(h, w, 3)
+    m = hit >= 0
+    assert m.any()
+    assert np.array_equal(ac[..., 3] == 1.0, m) and (ac[..., 3][~m] == 0).all()
+    assert (nd[~m] == 0).all() and (ac[~m] == 0).all()
+    assert same_bits(nd[..., 3][m], t[m])
+    arr = dev.host.arrays()
+    diff = arr["materials"][:, 0:3][arr["prim_material"][hit[m]]]
+    assert same_bits(ac[..., :3][m], diff)
+    norm = np.zeros((h, w, 3), np.float32)
+    for obj in np.unique(hit[m]):
+        sel = hit == obj
+        norm[sel] = dev.object_normal(int(obj), hp[sel])
+    f = np.float32
+    dn = (norm[..., 0] * d[..., 0] + norm[..., 1] * d[..., 1]) + norm[..., 2] * d[..., 2]
+    norml = np.where((dn < f(0))[..., None], norm, norm * f(-1.0))
+    decided = m & (np.abs(dn) >= 1e-6)  # (where the dot is ~0 the sign rule may fall either way)
+    assert same_bits(nd[..., :3][decided], norml[decided])
+    rest = m & ~decided
+    assert ((nd[..., :3][rest] == norm[rest]).all(-1) | (nd[..., :3][rest] == -norm[rest]).all(-1)).all()
+
+
+@pytest.mark.parametrize("accel", [p3d.ACCEL_BVH, p3d.ACCEL_GRID, p3d.ACCEL_NONE], ids=["bvh", "grid", "none"])
+def test_one_sample_features_follow_the_frames_first_hit(accel):
+    dev = device_scene(CORNELL, (96, 64))
+    cfg = cornell_cfg(spp=4, accel=accel)
+    tile = p3d.Tile(13, 9, 67, 45, 0, 1)
+    _, hit, _ = dev.render(cfg, tile=tile)
+    nd, ac = dev.render_features(cfg, samples=1, tile=tile)
+    assert np.array_equal(ac[..., 3] == 1.0, hit >= 0) and (ac[..., 3][hit < 0] == 0).all()
+    arr = dev.host.arrays()
+    m = hit >= 0
+    assert same_bits(ac[..., :3][m], arr["materials"][:, 0:3][arr["prim_material"][hit[m]]])
+    assert (nd[..., 3][m] > 0).all()
+
+
+@pytest.mark.parametrize("spp", [4, 5])
+def test_all_sample_features_are_sane(spp):
+    dev = device_scene(CORNELL, (96, 64))
+    cfg = cornell_cfg(spp=spp)
+    nd, ac = dev.render_features(cfg, samples=spp * spp)
+    assert np.isfinite(nd).all() and np.isfinite(ac).all()
+    cov = ac[..., 3]
+    assert ((cov >= 0) & (cov <= 1)).all()
+    assert np.allclose(cov * spp * spp, np.round(cov * spp * spp), atol=1e-4)
+    assert (np.linalg.norm(nd[..., :3].astype(np.float64), axis=-1) <= 1 + 1e-6).all()
+    assert (cov > 0).any()
+    d16, a16 = dev.render_features(cfg)  # samples = 0: min(16, SPP*SPP)
+    k16, ak16 = dev.render_features(cfg, samples=16)
+    assert same_bits(d16, k16) and same_bits(a16, ak16)
+
+
+# ---- the filter against its numpy statement ----
+
+def random_inputs(w, h, seed):
+    """Piecewise-constant features with noise (regions of a few normals, depths and albedos), uncovered patches and partial
+    coverage, noisy colours."""
+    rng = np.random.default_rng(seed)
+    region = (np.arange(h)[:, None] * 3 // max(h, 1)) * 3 + (np.arange(w)[None, :] * 3 // max(w, 1))
+    dirs = rng.normal(size=(9, 3))
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    n = dirs[region] + rng.normal(0, 0.02, (h, w, 3))
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    n *= rng.uniform(0.85, 1.0, (h, w, 1))
+    t = rng.uniform(2, 10, 9)[region] * rng.uniform(0.98, 1.02, (h, w))
+    alb = rng.uniform(0, 1, (9, 3))[region] + rng.normal(0, 0.01, (h, w, 3))
+    cov = np.where(rng.random((h, w)) < 0.2, rng.integers(1, 16, (h, w)) / 16.0, 1.0)
+    cov[region == 4] = 0.0  # an uncovered region
+    nd = np.concatenate([n, t[..., None]], -1).astype(np.float32)
+    ac = np.concatenate([alb, cov[..., None]], -1).astype(np.float32)
+    nd[cov == 0] = 0
+    ac[cov == 0] = 0
+    rgb = (alb * 0.8 + rng.normal(0, 0.15, (h, w, 3))).clip(0, None).astype(np.float32)
+    var = rng.uniform(0, 0.03, (h, w)).astype(np.float32)
+    return rgb, nd, ac, var
+
+
+def prm_kw(p):
+    return dict(iterations=p.iterations, sigma_color=p.sigma_color, sigma_luma=p.sigma_luma, sigma_normal=p.sigma_normal,
+                sigma_depth=p.sigma_depth, sigma_albedo=p.sigma_albedo)
+
+
+@pytest.mark.parametrize("w,h", [(67, 45), (1, 1), (3, 300)])
+@pytest.mark.parametrize("with_var", [False, True], ids=["colour", "variance"])
+def test_filter_matches_the_reference_on_random_inputs(w, h, with_var):
+    rgb, nd, ac, var = random_inputs(w, h, seed=w * 1000 + h)
+    dn = p3d.Denoiser(0, w, h)
+    for p in (p3d.denoise_params(), p3d.denoise_params(iterations=8, sigma_color=0.5, sigma_normal=16.0, sigma_depth=0.5,
+                                                       sigma_albedo=0.3, sigma_luma=2.0)):
+        out, out8 = dn.run(rgb, nd, ac, var if with_var else None, params=p, want_rgb8=True)
+        ref, _ = atrous(rgb, nd, ac, var if with_var else None, **prm_kw(p))
+        assert_close_to_reference(out, ref, "%dx%d %s" % (w, h, prm_kw(p)))
+        assert np.array_equal(out8, u8(out))
+    dn.close()
+
+
+@pytest.fixture(scope="module")
+def cornell_frame():
+    dev = device_scene(CORNELL, (96, 64))
+    cfg = cornell_cfg(spp=4)
+    ad = dev.adaptive(cfg, 0.0, min_samples=2)
+    try:
+        rgb, _, _, rgb8, _ = ad.render(16, want_rgb8=True)
+        var = ad.variance()
+    finally:
+        ad.close()
+    nd, ac = dev.render_features(cfg)
+    return dev, cfg, rgb, rgb8, var, nd, ac
+
+
+@pytest.mark.parametrize("with_var", [False, True], ids=["colour", "variance"])
+def test_filter_matches_the_reference_on_a_cornell_frame(cornell_frame, with_var):
+    dev, cfg, rgb, _, var, nd, ac = cornell_frame
+    dn = p3d.Denoiser(0, 96, 64)
+    p = p3d.denoise_params()
+    out = dn.run(rgb, nd, ac, var if with_var else None, params=p)
+    ref, _ = atrous(rgb, nd, ac, var if with_var else None, **prm_kw(p))
+    assert_close_to_reference(out, ref, "cornell")
+    assert not same_bits(out, rgb)
+
+
+def test_zero_iterations_copy_the_frame(cornell_frame):
+    dev, cfg, rgb, rgb8, var, nd, ac = cornell_frame
+    dn = p3d.Denoiser(0, 96, 64)
+    for v in (None, var):
+        out, out8 = dn.run(rgb, nd, ac, v, params=p3d.denoise_params(iterations=0), want_rgb8=True)
+        assert same_bits(out, rgb) and np.array_equal(out8, rgb8)
+    cfg_g = cornell_cfg(spp=4, gamma=2.2)
+    g_rgb, _, g_rgb8, _ = dev.render(cfg_g, want_rgb8=True)
+    out, out8 = dn.run(g_rgb, nd, ac, params=p3d.denoise_params(iterations=0, gamma=2.2), want_rgb8=True)
+    assert same_bits(out, g_rgb) and np.array_equal(out8, g_rgb8)
+
+
+def test_device_form_gives_the_host_forms_bits(cornell_frame):
+    import torch
+    dev, cfg, rgb, _, var, nd, ac = cornell_frame
+    dn = p3d.Denoiser(0, 96, 64)
+    p = p3d.denoise_params(gamma=2.2)
+    host, host8 = dn.run(rgb, nd, ac, var, params=p, want_rgb8=True)
+    t_rgb, t_var = torch.from_numpy(rgb).cuda(), torch.from_numpy(var).cuda()
+    t_nd = torch.zeros((64, 96, 4), dtype=torch.float32, device="cuda")
+    t_ac = torch.zeros((64, 96, 4), dtype=torch.float32, device="cuda")
+    out = torch.zeros((64, 96, 3), dtype=torch.float32, device="cuda")
+    out8 = torch.zeros((64, 96, 3), dtype=torch.uint8, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        dev.render_features_device(cfg, t_nd.data_ptr(), t_ac.data_ptr(), stream=s)
+        dn.run_device(t_rgb.data_ptr(), t_nd.data_ptr(), t_ac.data_ptr(), out.data_ptr(), out8.data_ptr(), t_var.data_ptr(),
+                      params=p, stream=s)
+    s.synchronize()
+    assert same_bits(t_nd.cpu().numpy(), nd) and same_bits(t_ac.cpu().numpy(), ac)
+    assert same_bits(out.cpu().numpy(), host) and np.array_equal(out8.cpu().numpy(), host8)
+
+
+def test_refusals(cornell_frame):
+    dev, cfg, rgb, _, var, nd, ac = cornell_frame
+    dn = p3d.Denoiser(0, 96, 64)
+    bad = [dict(iterations=9), dict(sigma_normal=float("nan")), dict(sigma_depth=-1.0), dict(sigma_color=0.0),
+           dict(gamma=0.0), dict(reserved=(0, 1))]
+    for kw in bad:
+        with pytest.raises(p3d.P3DError) as e:
+            dn.run(rgb, nd, ac, params=p3d.denoise_params(**kw))
+        assert e.value.code == -1, kw
+    with pytest.raises(p3d.P3DError) as e:
+        dn.run(rgb, nd, ac, var, params=p3d.denoise_params(sigma_luma=0.0))
+    assert e.value.code == -1
+    dn.run(rgb, nd, ac, var, params=p3d.denoise_params(sigma_color=0.0))  # (sigma_color is not used with a variance buffer)
+    with pytest.raises(ValueError):
+        dn.run(rgb[:10], nd, ac)
+    for wh in ((0, 5), (5, -1)):
+        with pytest.raises(p3d.P3DError) as e:
+            p3d.Denoiser(0, *wh)
+        assert e.value.code == -1
+    with pytest.raises(p3d.P3DError) as e:
+        dev.render_features(cfg, tile=p3d.stripe_tile((96, 64), 0, 2, stripe_h=8))
+    assert e.value.code == -3
+    with pytest.raises(p3d.P3DError) as e:
+        dev.render_features(cfg, samples=17)
+    assert e.value.code == -1
+    with pytest.raises(p3d.P3DError) as e:
+        dev.render_features(cornell_cfg(antialiasing=0), samples=2)
+    assert e.value.code == -1
+
+
+# ---- the variance of an adaptive frame ----
+
+def variance_numpy(state):
+    """include/p3d.h "Error metric" -> v / n, float32, the same operations in the same order; 0 below 2 samples."""
+    f = np.float32
+    with np.errstate(divide="ignore", invalid="ignore"):
+        S = state["sum"].astype(f)
+        n = state["samples"].astype(f)
+        Y = (f(0.2126) * S[..., 0] + f(0.7152) * S[..., 1]) + f(0.0722) * S[..., 2]
+        m = Y / n
+        v = np.fmax((state["sum_y2"] - Y * m) / (n - f(1.0)), f(0.0))
+        var = (v / n).astype(f)
+    return np.where(state["samples"] < 2, f(0), var)
+
+
+def test_adaptive_variance_is_the_error_metrics_variance():
+    import torch
+    dev = device_scene(CORNELL, (96, 64))
+    cfg = cornell_cfg(spp=8)
+    ad = dev.adaptive(cfg, 0.0, min_samples=2)
+    try:
+        ad.render(1)
+        assert (ad.variance() == 0).all()  # one sample each
+        for n in (3, 12, 16):
+            ad.render(n)
+            st = ad.read_state()
+            var = ad.variance()
+            assert same_bits(var, variance_numpy(st))
+        d_var = torch.full((64, 96), -1.0, dtype=torch.float32, device="cuda")
+        ad.variance_device(d_var.data_ptr())
+        torch.cuda.synchronize()
+        assert same_bits(d_var.cpu().numpy(), var)
+        assert (var > 0).any()
+    finally:
+        ad.close()
+    ad = dev.adaptive(cfg, 0.5, min_samples=4)  # some pixels stop: their variance is that of their own sample count
+    try:
+        for n in (4, 4, 8, 16):
+            ad.render(n)
+        st = ad.read_state()
+        assert len(np.unique(st["samples"])) > 1
+        assert same_bits(ad.variance(), variance_numpy(st))
+    finally:
+        ad.close()
+
+
+# ---- quality of the defaults on the Cornell box ----
+
+# measured with the defaults (DESIGN.md "Denoising"): MSE 7.3x lower without variance, 5.3x with the adaptive variance;
+# means +0.5 % and +0.04 % off the reference's (the noisy frame's, clamped: -9.7 %)
+MSE_GAIN_MIN = 4.0    # the denoised frame's MSE is at least this many times lower than the noisy frame's
+MEAN_SHIFT_MAX = 0.015
+
+
+def quality(dev, rgb, ref, hit, var, nd, ac):
+    arr = dev.host.arrays()
+    diffuse = (hit >= 0) & (arr["materials"][arr["prim_material"][np.maximum(hit, 0)], 3] == 1.0)
+    dn = p3d.Denoiser(0, rgb.shape[1], rgb.shape[0])
+    out = dn.run(rgb, nd, ac, var)
+    clamp = lambda a: np.clip(a[diffuse].astype(np.float64), 0, 1)
+    mse_noisy = ((clamp(rgb) - clamp(ref)) ** 2).mean()
+    mse_den = ((clamp(out) - clamp(ref)) ** 2).mean()
+    shift = abs(clamp(out).mean() / clamp(ref).mean() - 1)
+    return mse_noisy / mse_den, shift
+
+
+@pytest.mark.parametrize("mode", ["accumulator", "adaptive"])
+def test_default_parameters_denoise_the_cornell_box(mode):
+    dev = device_scene(CORNELL, (128, 128))
+    ref, _, _ = dev.render(cornell_cfg(spp=32))  # 1024 samples per pixel, same seed
+    cfg = cornell_cfg(spp=4)
+    if mode == "accumulator":
+        acc = dev.accumulator(cfg)
+        try:
+            rgb, hit, _ = acc.render(16)
+        finally:
+            acc.close()
+        var = None
+    else:
+        ad = dev.adaptive(cfg, 0.0, min_samples=2)
+        try:
+            rgb, hit, _, _ = ad.render(16)
+            var = ad.variance()
+        finally:
+            ad.close()
+    nd, ac = dev.render_features(cfg)
+    gain, shift = quality(dev, rgb, ref, hit, var, nd, ac)
+    print("quality %s: MSE gain %.2f, mean shift %.4f" % (mode, gain, shift))
+    assert gain >= MSE_GAIN_MIN, gain
+    assert shift <= MEAN_SHIFT_MAX, shift
+
+
+# ---- the front end ----
+
+def test_cli_denoise_writes_the_api_image(tmp_path):
+    from PIL import Image
+    exe = os.path.join(ROOT, "p3d-raytracer_amd", "p3d_render")
+    subprocess.check_call(["make", "-s", "-C", os.path.dirname(exe), "p3d_render"])
+    args = [exe, CORNELL, "--pathtrace", "--aa", "1", "--spp", "4", "--dof", "0", "--res", "64", "48", "--passes", "2"]
+    den, out, plain = str(tmp_path / "d.png"), str(tmp_path / "o.png"), str(tmp_path / "p.png")
+    r = subprocess.run(args + ["--out", out, "--denoise", den], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run(args + ["--out", plain], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert open(out, "rb").read() == open(plain, "rb").read()
+    dev = device_scene(CORNELL, (64, 48))
+    cfg = p3d.default_config(spp_sqrt=4, depth_of_field=0)
+    rgb, _, _ = dev.render(cfg)
+    nd, ac = dev.render_features(cfg)
+    _, rgb8 = p3d.Denoiser(0, 64, 48).run(rgb, nd, ac, params=p3d.denoise_params(gamma=cfg.gamma), want_rgb8=True)
+    img = np.asarray(Image.open(den).convert("RGB"))[::-1]  # file rows top-down, rgb8 bottom row first
+    assert np.array_equal(img, rgb8)
