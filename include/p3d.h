@@ -394,6 +394,31 @@ int p3d_scene_set_tail_stream(p3d_scene* scene, void* tail_hip_stream);
 int p3d_scene_join(p3d_scene* scene, void* hip_stream, int host_wait);
 
 /*
+ * Moving the camera of a device scene between frames - what a display loop does when the viewer moves - without a new .p3f,
+ * host scene, BVH or upload.  Detected by the symbols, like p3d_accum (P3D_ABI_VERSION is unchanged).
+ *
+ * p3d_camera_look_at runs the Camera constructor (camera.h:34-63) the .p3f loader runs for a `v` block - the same code, not a
+ * copy: with a scene's own `v` values (from, at, up, angle, resolution, aperture, focal) it gives, byte for byte, the
+ * p3d_camera p3d_host_scene_desc returns.  P3D_ERR_INVALID for a resolution <= 0.  Host only, no device needed.
+ * p3d_host_scene_view returns the `v` block a host scene was loaded with (after p3d_host_scene_set_lens: the lens it set).
+ *
+ * p3d_scene_set_camera replaces the scene's camera; frames enqueued after it render the new view, bit for bit as a scene
+ * created with that camera renders it.  It is a host call that WAITS: for the scene's tail stream (p3d_scene_join) and then for
+ * the whole device (hipDeviceSynchronize), because enqueued frames read the scene's memos; it therefore cannot be captured into
+ * a graph (and a graph captured before it keeps the camera it was captured with).  Then it forgets what was worked out for the
+ * old view's primary rays: the tile-cost schedules and the hit_stack hand-off's row chains and halo pixels.  Refused with
+ * P3D_ERR_INVALID: a scene created without a camera (res_x or res_y <= 0), a camera whose res_x / res_y differ from the scene's
+ * (the resolution is fixed at create), a non-finite field, w, h or plane_dist <= 0.  Setting the camera the scene already has
+ * changes nothing.  A p3d_accum or p3d_adaptive records the scene's camera at create and reset: a pass after the camera changed,
+ * without a reset in between, is refused with P3D_ERR_INVALID and changes nothing.
+ * p3d_scene_camera returns the scene's current camera (reserved = 0).
+ */
+int p3d_camera_look_at(const float from[3], const float at[3], const float up[3], float angle, int32_t res_x, int32_t res_y,
+                       float aperture_ratio, float focal_ratio, p3d_camera* out);
+int p3d_scene_set_camera(p3d_scene* scene, const p3d_camera* camera);
+int p3d_scene_camera(p3d_scene* scene, p3d_camera* out);
+
+/*
  * Progressive accumulation: one anti-aliased frame rendered in passes over its samples, the image shown (or the frame
  * stopped) after any of them - what the reference's drawModeEnabled display (main.cpp:45-48) does line by line, by sample
  * instead.  A caller detects these entry points by the symbols being present (P3D_ABI_VERSION is unchanged).
@@ -556,6 +581,73 @@ int p3d_denoise_variance(p3d_adaptive* ad, float* var);
 int p3d_denoise_variance_device(p3d_adaptive* ad, float* d_var, void* hip_stream);
 
 /*
+ * Temporal accumulation: the frames of a moving camera integrated over time - SVGF's history (Schied et al. 2017), the piece
+ * that makes a 1-spp path-traced frame watchable while the view moves.  Every pixel takes the previous frames' integrated colour
+ * wherever the same surface is still visible, and a luminance variance from temporal moments that goes into p3d_denoise's
+ * luminance term: (out_rgb, out_var) are the (rgb, var) of p3d_denoise / p3d_denoise_device.  Detected by its symbols.
+ *
+ * Inputs per frame: rgb (w*h*3 float, linear colour, from any render call or pass), normal_depth and albedo_cov as
+ * p3d_render_features writes them for that frame and camera, and `camera` - the camera the frame was rendered with
+ * (p3d_scene_camera).  The object keeps the previous frame's camera.  Per pixel p = (x, y) (y = 0 the bottom row):
+ *   point     d = the direction of primary_ray(camera, x + 0.5, y + 0.5) (float32, the render kernels' pixel-centre ray);
+ *             cov_p > 0: X = eye + t_p d;  cov_p == 0 (a miss): the point at infinity in direction d
+ *   project   into the previous camera (eye', u', v', n', w', h', plane_dist'): e = X - eye' (a miss: e = d);
+ *             a = e.u', b = e.v', c = e.n'; c >= 0: behind the previous camera, no history; otherwise
+ *             px' = (a (-plane_dist' / c) / w' + 0.5) res_x - 0.5,  py' = (b (-plane_dist' / c) / h' + 0.5) res_y - 0.5;
+ *             a previous camera identical to `camera` (every field, bit for bit) maps every pixel onto itself: px' = x, py' = y
+ *   taps      the four pixels q around (px', py') with bilinear weights; q is valid when it lies in the image, cov_p > 0 and
+ *             cov'_q > 0 or both are 0, and for hits |t'_q - |X - eye'|| <= depth_tolerance |X - eye'| and
+ *             n_p.n'_q >= normal_tolerance |n_p| |n'_q| (the features' normals, not renormalised)
+ *   history   W = the sum of the valid taps' weights.  W < 1e-3 (or the first frame since create / reset): n = 1, the colour
+ *             is c_p and the moments (Y, Y^2).  Otherwise c_hist, (m1, m2)_hist and n_prev are the weight-normalised sums over
+ *             the valid taps, n = min(n_prev + 1, max_history), a = max(alpha, 1/n), am = max(alpha_moments, 1/n):
+ *             c = (1 - a) c_hist + a c_p,  m1 = (1 - am) m1_hist + am Y,  m2 = (1 - am) m2_hist + am Y^2,
+ *             Y = 0.2126 R + 0.7152 G + 0.0722 B of c_p (the denoiser's luminance)
+ *   variance  n >= variance_min_history: var = max(0, m2 - m1^2).  Otherwise the same expression over moments averaged across
+ *             the 7x7 neighbourhood in the current frame (taps in the image) with the weights w_g of p3d_denoise at step 1
+ *             (sigma_normal, sigma_depth; the albedo term off) and 1 for the centre
+ * The state between frames - c, n, m1, m2, the coverage and normal_depth - is kept in float32; the projection and the blend
+ * are evaluated in float64 from those values and rounded once, the spatial weights in float32 (expf / powf), no contraction.
+ * n is rounded to float32 before it is used.  tests/temporal_reference.py is the float64 statement the kernels are checked
+ * against.  Outputs: out_rgb w*h*3 float, required; out_var w*h float and out_history w*h float (n), either may be NULL.
+ * The outputs must not overlap the inputs.
+ *
+ * Refused: P3D_ERR_UNSUPPORTED for a camera with aperture != 0 (the pinhole reprojection is not exact for a lens);
+ * P3D_ERR_INVALID for a camera whose resolution is not w x h or with a non-finite field or w, h, plane_dist <= 0, for alpha or
+ * alpha_moments outside [0, 1], max_history < 1, depth_tolerance <= 0, normal_tolerance outside [-1, 1], a negative or NaN
+ * sigma, non-zero reserved fields and null inputs.  A refused call changes nothing.
+ *
+ * An object is made for one image size (whole images only) on one device, like p3d_denoiser: p3d_temporal_create allocates
+ * two sets of three float4 images (96 bytes per pixel) that the frames ping-pong between, so p3d_temporal_accumulate_device
+ * neither allocates nor waits: it enqueues one launch (two with out_var) on `hip_stream`, behind a pass or inside a captured
+ * graph.  Enqueue the calls of one object on one stream.  p3d_temporal_accumulate is the host-buffer form (synchronous).
+ * p3d_temporal_reset forgets the history: the next frame is a first frame.  p3d_temporal_frames counts the frames since
+ * create / reset.  p3d_temporal_params_default fills the defaults DESIGN.md chose (alpha 0.2, alpha_moments 0.2,
+ * max_history 32, depth_tolerance 0.1, normal_tolerance 0.9, variance_min_history 4, sigma_normal 128, sigma_depth 1).
+ */
+typedef struct p3d_temporal_params {
+  float alpha;             /* floor of the new frame's colour weight (SVGF: 0.2); 0 = a plain running mean */
+  float alpha_moments;     /* the same for the luminance moments (SVGF: 0.2) */
+  float max_history;       /* cap on the history length n (>= 1) */
+  float depth_tolerance;   /* relative depth test of a reprojected tap (> 0) */
+  float normal_tolerance;  /* minimum cosine between the two normals (-1 .. 1) */
+  uint32_t variance_min_history; /* below this n the variance comes from a 7x7 spatial estimate (SVGF: 4) */
+  float sigma_normal, sigma_depth; /* weights of that spatial estimate, as p3d_denoise_params */
+  uint32_t reserved[2];    /* must be 0 */
+} p3d_temporal_params;
+typedef struct p3d_temporal p3d_temporal;
+void p3d_temporal_params_default(p3d_temporal_params* params);
+int p3d_temporal_create(int device, int32_t w, int32_t h, p3d_temporal** out);
+void p3d_temporal_destroy(p3d_temporal* tp);
+int p3d_temporal_reset(p3d_temporal* tp);
+uint32_t p3d_temporal_frames(const p3d_temporal* tp);
+int p3d_temporal_accumulate(p3d_temporal* tp, const p3d_temporal_params* params, const p3d_camera* camera, const float* rgb,
+                            const float* normal_depth, const float* albedo_cov, float* out_rgb, float* out_var, float* out_history);
+int p3d_temporal_accumulate_device(p3d_temporal* tp, const p3d_temporal_params* params, const p3d_camera* camera,
+                                   const float* d_rgb, const float* d_normal_depth, const float* d_albedo_cov, float* d_out_rgb,
+                                   float* d_out_var, float* d_out_history, void* hip_stream);
+
+/*
  * Errors a kernel detects while it runs (a hit_stack leftover that outgrew its record, a work list of the hit_stack
  * hand-off that overflowed or did not run empty within its round bound, a row of a stripe or sub-rectangle whose
  * incoming hit_stack could not be established, a sample hand-out loop that reached its trip bound and would write pixels
@@ -632,6 +724,10 @@ int p3d_host_scene_bind_device(p3d_host_scene* hs, p3d_scene* scene);
 /* 1 if a cubemap is loaded: the `.p3f` had an `env <dir>` line (scene.cpp:605-610) and the folder was found (relative to
  * the working directory, as in the reference, or next to the scene file), or p3d_host_scene_load_skybox was called. */
 int p3d_host_scene_has_skybox(p3d_host_scene* hs);
+/* The `v` block as loaded (from, at, up, angle; the aperture / focal ratios, as p3d_host_scene_set_lens left them): the
+ * arguments of p3d_camera_look_at that rebuild the scene's camera.  P3D_ERR_INVALID without a `v` block. */
+int p3d_host_scene_view(p3d_host_scene* hs, float from[3], float at[3], float up[3], float* angle, float* aperture_ratio,
+                        float* focal_ratio);
 /* Scene::LoadSkybox (scene.cpp:329-377): <sky_dir>/{right,left,top,bottom,front,back}.jpg, decoded by the library
  * (baseline JPEG - sequential DCT, Huffman, 8 bit, grey or YCbCr with 1x1 / 2x1 / 2x2 luma sampling - following the IJG
  * library's default path: the six shipped faces come out byte for byte as PIL's libjpeg-turbo decodes them; DevIL's own

@@ -42,6 +42,9 @@ EXPORTS = [
     "p3d_adaptive_render", "p3d_adaptive_render_device", "p3d_adaptive_read_state",
     "p3d_render_features", "p3d_render_features_device", "p3d_denoise_params_default", "p3d_denoiser_create",
     "p3d_denoiser_destroy", "p3d_denoise", "p3d_denoise_device", "p3d_denoise_variance", "p3d_denoise_variance_device",
+    "p3d_camera_look_at", "p3d_scene_set_camera", "p3d_scene_camera", "p3d_host_scene_view",
+    "p3d_temporal_params_default", "p3d_temporal_create", "p3d_temporal_destroy", "p3d_temporal_reset", "p3d_temporal_frames",
+    "p3d_temporal_accumulate", "p3d_temporal_accumulate_device",
 ]
 
 
@@ -125,6 +128,12 @@ class AdaptiveParams(C.Structure):
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_luma", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float), ("gamma", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("max_history", C.c_float), ("depth_tolerance", C.c_float),
+                ("normal_tolerance", C.c_float), ("variance_min_history", C.c_uint32), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
 class Stats(C.Structure):
@@ -238,6 +247,23 @@ def lib():
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.p3d_denoise_variance.argtypes = [C.c_void_p, C.c_void_p]
         L.p3d_denoise_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        F3 = C.c_float * 3
+        L.p3d_camera_look_at.argtypes = [F3, F3, F3, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float, C.POINTER(Camera)]
+        L.p3d_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.p3d_scene_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.p3d_host_scene_view.argtypes = [C.c_void_p, F3, F3, F3, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.p3d_temporal_params_default.argtypes = [C.POINTER(TemporalParams)]
+        L.p3d_temporal_params_default.restype = None
+        L.p3d_temporal_create.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.p3d_temporal_destroy.argtypes = [C.c_void_p]
+        L.p3d_temporal_destroy.restype = None
+        L.p3d_temporal_reset.argtypes = [C.c_void_p]
+        L.p3d_temporal_frames.argtypes = [C.c_void_p]
+        L.p3d_temporal_frames.restype = C.c_uint32
+        L.p3d_temporal_accumulate.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(Camera), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(Camera), C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -272,6 +298,34 @@ def denoise_params(**kw):
             raise AttributeError(k)
         setattr(p, k, (C.c_uint32 * 2)(*v) if k == "reserved" else v)
     return p
+
+
+def temporal_params(**kw):
+    """p3d_temporal_params_default, then the fields given (alpha, alpha_moments, max_history, depth_tolerance,
+    normal_tolerance, variance_min_history, sigma_normal, sigma_depth, reserved)."""
+    p = TemporalParams()
+    lib().p3d_temporal_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_uint32 * 2)(*v) if k == "reserved" else v)
+    return p
+
+
+def _f3(v):
+    v = [float(x) for x in v]
+    if len(v) != 3:
+        raise ValueError("a 3-vector is needed, got %r" % (v,))
+    return (C.c_float * 3)(*v)
+
+
+def look_at(from_, at, up, angle, res, aperture_ratio=0.0, focal_ratio=1.0):
+    """p3d_camera_look_at: the Camera the .p3f loader builds for a `v` block with these values (camera.h:34-63);
+    res = (res_x, res_y)."""
+    cam = Camera()
+    _check(lib().p3d_camera_look_at(_f3(from_), _f3(at), _f3(up), float(angle), int(res[0]), int(res[1]), float(aperture_ratio),
+                                    float(focal_ratio), C.byref(cam)))
+    return cam
 
 
 def whitted_config(accel=ACCEL_BVH, max_depth=4, **kw):
@@ -333,6 +387,14 @@ class HostScene:
         w, h = C.c_uint32(), C.c_uint32()
         _check(self._L.p3d_host_scene_skybox_face(self._h, int(face), C.byref(img), C.byref(w), C.byref(h)))
         return np.ctypeslib.as_array(img, shape=(h.value, w.value, 3)).copy()
+
+    def view(self):
+        """p3d_host_scene_view: the `v` block -> dict(from_, at, up, angle, aperture_ratio, focal_ratio), the arguments of
+        look_at that rebuild the scene's camera (float32 values as the loader read them)."""
+        f, a, u = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 3)()
+        ang, ap, fr = C.c_float(), C.c_float(), C.c_float()
+        _check(self._L.p3d_host_scene_view(self._h, f, a, u, C.byref(ang), C.byref(ap), C.byref(fr)))
+        return dict(from_=tuple(f), at=tuple(a), up=tuple(u), angle=ang.value, aperture_ratio=ap.value, focal_ratio=fr.value)
 
     def desc(self, bvh=False, grid=False):
         p = C.POINTER(SceneDesc)()
@@ -432,6 +494,18 @@ class DeviceScene:
 
     def full_tile(self):
         return Tile(0, 0, self.res[0], self.res[1], 0, 1)
+
+    @property
+    def camera(self):
+        """p3d_scene_camera: the scene's current Camera."""
+        cam = Camera()
+        _check(self._L.p3d_scene_camera(self._h, C.byref(cam)))
+        return cam
+
+    def set_camera(self, cam):
+        """p3d_scene_set_camera: frames rendered after it see `cam` (a Camera of the scene's resolution, e.g. from look_at).
+        Waits for the device.  Accumulators of this scene refuse passes until they are reset."""
+        _check(self._L.p3d_scene_set_camera(self._h, C.byref(cam)))
 
     def render(self, cfg, tile=None, want_rgb8=False, stats=True):
         """Host-buffer form (p3d_render_tile): returns numpy arrays."""
@@ -765,6 +839,71 @@ class Denoiser:
     def close(self):
         if getattr(self, "_h", None):
             self._L.p3d_denoiser_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Temporal:
+    """p3d_temporal (include/p3d.h): temporal accumulation of w x h frames on one device - every frame's colour blended with
+    the previous frames' history reprojected into its view, plus a luminance variance for Denoiser.run.  Inputs per frame:
+    the Camera the frame was rendered with (DeviceScene.camera), its linear rgb and its feature buffers
+    (DeviceScene.render_features).  The device form neither allocates nor waits."""
+
+    def __init__(self, device, w, h):
+        self._L = lib()
+        self.w, self.h = int(w), int(h)
+        hd = C.c_void_p()
+        _check(self._L.p3d_temporal_create(int(device), self.w, self.h, C.byref(hd)))
+        self._h = hd
+
+    @property
+    def frames(self):
+        """Frames accumulated since create / reset."""
+        return int(self._L.p3d_temporal_frames(self._h))
+
+    def reset(self):
+        """Forget the history: the next frame starts it again."""
+        _check(self._L.p3d_temporal_reset(self._h))
+
+    def _shape(self, a, shape, what):
+        a = np.ascontiguousarray(a, np.float32)
+        if a.shape != shape:
+            raise ValueError("%s: shape %s, the object is for %s" % (what, a.shape, shape))
+        return a
+
+    def run(self, camera, rgb, normal_depth, albedo_cov, params=None):
+        """p3d_temporal_accumulate -> (rgb (h, w, 3), var (h, w), history (h, w)), float32."""
+        h, w = self.h, self.w
+        rgb = self._shape(rgb, (h, w, 3), "rgb")
+        nd = self._shape(normal_depth, (h, w, 4), "normal_depth")
+        ac = self._shape(albedo_cov, (h, w, 4), "albedo_cov")
+        prm = params if params is not None else temporal_params()
+        out = np.zeros((h, w, 3), np.float32)
+        var = np.zeros((h, w), np.float32)
+        hist = np.zeros((h, w), np.float32)
+        _check(self._L.p3d_temporal_accumulate(self._h, C.byref(prm), C.byref(camera), rgb.ctypes.data, nd.ctypes.data,
+                                               ac.ctypes.data, out.ctypes.data, var.ctypes.data, hist.ctypes.data))
+        return out, var, hist
+
+    def run_device(self, camera, d_rgb, d_normal_depth, d_albedo_cov, d_out_rgb, d_out_var=0, d_out_history=0, params=None,
+                   stream=0):
+        """p3d_temporal_accumulate_device: raw HBM addresses and a hipStream_t (or a torch.cuda.Stream); enqueued, not waited
+        for."""
+        prm = params if params is not None else temporal_params()
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_temporal_accumulate_device(self._h, C.byref(prm), C.byref(camera), C.c_void_p(d_rgb or None),
+                                                      C.c_void_p(d_normal_depth or None), C.c_void_p(d_albedo_cov or None),
+                                                      C.c_void_p(d_out_rgb or None), C.c_void_p(d_out_var or None),
+                                                      C.c_void_p(d_out_history or None), C.c_void_p(raw or None)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.p3d_temporal_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -21,6 +21,7 @@
 #include "adaptive.hpp"
 #include "features.hpp"
 #include "denoise.hpp"
+#include "temporal.hpp"
 
 using namespace p3d;
 
@@ -183,7 +184,31 @@ struct p3d_scene {
   hipStream_t tail_stream = nullptr;
   hipEvent_t ev_tail_go = nullptr, ev_tail_done = nullptr;
   bool tail_pending = false;  // ev_tail_done was recorded by the last frame: the next launch on this scene waits for it
+  uint64_t cam_gen = 0;       // bumped by every p3d_scene_set_camera that changes the camera (p3d_accum / p3d_adaptive check it)
 };
+
+namespace {
+
+// Forgets the memoised tile schedules (their costs were recorded for one camera, among other things).
+void drop_schedules(p3d_scene* s) {
+  for (SchedEntry& e : s->sched) {
+    e.cost.release();
+    e.sched.release();
+    if (e.ready) (void)hipEventDestroy(e.ready);
+  }
+  s->sched.clear();
+}
+
+// Every float field of a camera is finite, and the view window and plane distance are positive
+bool camera_usable(const p3d_camera& c) {
+  const float f[17] = {c.eye[0], c.eye[1], c.eye[2], c.u[0], c.u[1], c.u[2], c.v[0], c.v[1], c.v[2], c.n[0], c.n[1], c.n[2],
+                       c.plane_dist, c.w, c.h, c.focal_ratio, c.aperture};
+  for (float x : f)
+    if (!std::isfinite(x)) return false;
+  return c.w > 0.0f && c.h > 0.0f && c.plane_dist > 0.0f;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -203,11 +228,7 @@ void p3d_scene_destroy(p3d_scene* s) {
   if (s->d_emitters) (void)hipFree(s->d_emitters);
   if (s->d_stats) (void)hipFree(s->d_stats);
   for (uint32_t*& f : s->d_sky) if (f) (void)hipFree(f);
-  for (SchedEntry& e : s->sched) {
-    e.cost.release();
-    e.sched.release();
-    if (e.ready) (void)hipEventDestroy(e.ready);
-  }
+  drop_schedules(s);
   s->levels.release(); s->spill.release(); s->deferred.release(); s->wf_rays.release(); s->wf_keys.release(); s->wf_sorted.release(); s->wf_final.release(); s->out_rgb.release(); s->out_hit.release();
   s->ho_where.release(); s->ho_entries.release(); s->ho_meta.release(); s->ho_first.release(); s->ho_first_sample.release(); s->ho_touched.release();
   s->ho_lists.release(); s->ho_check.release(); s->ho_counters.release(); s->ho_row_chain.release(); s->ho_halo_pix.release(); s->ho_ucount.release();
@@ -1051,8 +1072,8 @@ int render_impl(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, float
   if (literal && H.halo) {
     halo_blocks = (H.rows * kHaloChain + kBlock - 1) / kBlock;
     // The chain flags and the pixels in front of every chain row are a function of the tile and of what shapes the
-    // primary rays (the scene and its camera are fixed): worked out by two launches on this stream when any of that
-    // changes, kept otherwise (the frames of a sequence find them ready).
+    // primary rays (the scene is fixed; p3d_scene_set_camera clears the key when the camera changes): worked out by two
+    // launches on this stream when any of that changes, kept otherwise (the frames of a sequence find them ready).
     const uint32_t max_chain = s->dbg.halo_chain ? std::min<uint32_t>(s->dbg.halo_chain, kHaloChain) : kHaloChain;
     const std::vector<int64_t> key = {tile->x0, tile->y0, tile->w, tile->h, tile->stripe_h, tile->stripe_stride, cam.res_x, cam.res_y,
                                       cfg->antialiasing ? 1 : 0, cfg->antialiasing ? (int64_t)cfg->spp_sqrt : 1, (int64_t)cfg->seed,
@@ -1325,6 +1346,45 @@ int p3d_scene_join(p3d_scene* s, void* hip_stream, int host_wait) {
   return P3D_OK;
 }
 
+int p3d_scene_camera(p3d_scene* s, p3d_camera* out) {
+  if (!s || !out) return fail(P3D_ERR_INVALID, "p3d_scene_camera: null argument");
+  const DevCamera& c = s->dev.cam;
+  *out = p3d_camera{};
+  const F3* src[4] = {&c.eye, &c.u, &c.v, &c.n};
+  float* dst[4] = {out->eye, out->u, out->v, out->n};
+  for (int i = 0; i < 4; ++i) {
+    dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z;
+  }
+  out->plane_dist = c.plane_dist; out->w = c.w; out->h = c.h; out->focal_ratio = c.focal_ratio; out->aperture = c.aperture;
+  out->res_x = c.res_x; out->res_y = c.res_y;
+  return P3D_OK;
+}
+
+int p3d_scene_set_camera(p3d_scene* s, const p3d_camera* cam) {
+  if (!s || !cam) return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: null argument");
+  DevCamera& c = s->dev.cam;
+  if (c.res_x <= 0 || c.res_y <= 0) return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: the scene was created without a camera");
+  if (cam->res_x != c.res_x || cam->res_y != c.res_y)
+    return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: the camera is for " + std::to_string(cam->res_x) + "x" + std::to_string(cam->res_y) +
+                                     ", the scene renders " + std::to_string(c.res_x) + "x" + std::to_string(c.res_y) + " (fixed at create)");
+  if (!camera_usable(*cam)) return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: every field must be finite, and w, h and plane_dist > 0");
+  P3D_HIP(hipSetDevice(s->device));
+  // The scene's scratch and memos may still be in use by enqueued work: its tail stream and the caller's streams
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  DevCamera n{};
+  n.eye = to_f3(cam->eye); n.u = to_f3(cam->u); n.v = to_f3(cam->v); n.n = to_f3(cam->n);
+  n.w = cam->w; n.h = cam->h; n.plane_dist = cam->plane_dist; n.focal_ratio = cam->focal_ratio; n.aperture = cam->aperture;
+  n.res_x = cam->res_x; n.res_y = cam->res_y;
+  if (std::memcmp(&n, &c, sizeof(DevCamera)) == 0) return P3D_OK;  // the same view: nothing to forget
+  c = n;
+  ++s->cam_gen;
+  // what was worked out for the primary rays of the old view: tile costs, the hit_stack hand-off's row chains and halos
+  drop_schedules(s);
+  s->ho_chain_key.clear();
+  return P3D_OK;
+}
+
 int p3d_scene_status(p3d_scene* s) {
   if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_status: null argument");
   P3D_HIP(hipSetDevice(s->device));
@@ -1380,6 +1440,7 @@ struct p3d_accum {
   uint32_t total = 0;   // SPP^2
   uint32_t done = 0;    // samples [0, done) of every pixel are in the sums
   bool failed = false;  // a pass returned an error: the sums are unknown until p3d_accum_reset
+  uint64_t cam_gen = 0; // the scene's camera generation at create / reset
   Scratch sum, hit;     // [3 * pixel] float running sums, [pixel] first hits
 };
 
@@ -1401,6 +1462,7 @@ int p3d_accum_create(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, 
   a->cfg = *cfg;
   a->tile = *tile;
   a->total = cfg->spp_sqrt * cfg->spp_sqrt;
+  a->cam_gen = s->cam_gen;
   const size_t n = (size_t)tile->w * tile->h;
   int rc = a->sum.ensure(n * 3 * sizeof(float));
   if (!rc) rc = a->hit.ensure(n * sizeof(int32_t));
@@ -1424,6 +1486,7 @@ int p3d_accum_reset(p3d_accum* a) {
   if (!a) return fail(P3D_ERR_INVALID, "p3d_accum_reset: null accumulator");
   a->done = 0;
   a->failed = false;
+  a->cam_gen = a->s->cam_gen;
   return P3D_OK;
 }
 
@@ -1432,6 +1495,8 @@ uint32_t p3d_accum_samples_done(const p3d_accum* a) { return a ? a->done : 0u; }
 int p3d_accum_render_device(p3d_accum* a, uint32_t n, float* d_rgb, int32_t* d_hit, uint8_t* d_rgb8, void* hip_stream, p3d_stats* stats) {
   if (!a) return fail(P3D_ERR_INVALID, "p3d_accum_render_device: null accumulator");
   if (a->failed) return fail(P3D_ERR_INVALID, "p3d_accum_render: a previous pass failed; p3d_accum_reset starts the frame again");
+  if (a->cam_gen != a->s->cam_gen)
+    return fail(P3D_ERR_INVALID, "p3d_accum_render: the scene's camera changed since the frame began; p3d_accum_reset starts it again in the new view");
   if (n == 0 || n > a->total - a->done)
     return fail(P3D_ERR_INVALID, "p3d_accum_render: " + std::to_string(n) + " samples asked, " + std::to_string(a->total - a->done) +
                                      " of " + std::to_string(a->total) + " left (n must be at least 1)");
@@ -1479,6 +1544,7 @@ struct p3d_adaptive {
   uint32_t passes = 0;    // passes since the reset: the list's count is counters[passes & 1]
   uint32_t resident = 0;  // workgroups the device holds at once
   bool failed = false;
+  uint64_t cam_gen = 0;   // the scene's camera generation at create / reset
   Scratch sum, hit, sum_y2, samples, active, rel_err, list, counters;  // counters: count[2], ticket
   Scratch var;  // p3d_denoise_variance (host form): the device copy of its output
 };
@@ -1511,6 +1577,7 @@ int adapt_start(p3d_adaptive* a) {
   a->done = 0;
   a->passes = 0;
   a->failed = false;
+  a->cam_gen = a->s->cam_gen;
   P3D_HIP(hipMemsetAsync(a->counters.p, 0, 4 * sizeof(uint32_t), nullptr));
   const AdaptResolveParams R = adapt_resolve_params(a, true);
   hipLaunchKernelGGL(adapt_resolve_kernel, dim3((R.slots + kAdaptResolveThreads - 1) / kAdaptResolveThreads), dim3(kAdaptResolveThreads), 0, nullptr, R);
@@ -1591,6 +1658,8 @@ int p3d_adaptive_render_device(p3d_adaptive* a, uint32_t n, float* d_rgb, int32_
                                void* hip_stream, p3d_stats* stats) {
   if (!a) return fail(P3D_ERR_INVALID, "p3d_adaptive_render_device: null object");
   if (a->failed) return fail(P3D_ERR_INVALID, "p3d_adaptive_render: a previous pass failed; p3d_adaptive_reset starts the frame again");
+  if (a->cam_gen != a->s->cam_gen)
+    return fail(P3D_ERR_INVALID, "p3d_adaptive_render: the scene's camera changed since the frame began; p3d_adaptive_reset starts it again in the new view");
   if (n == 0 || n > a->total - a->done)
     return fail(P3D_ERR_INVALID, "p3d_adaptive_render: " + std::to_string(n) + " samples asked, " + std::to_string(a->total - a->done) +
                                      " of " + std::to_string(a->total) + " left (n must be at least 1)");
@@ -1832,6 +1901,181 @@ int p3d_denoise_variance(p3d_adaptive* a, float* var) {
   if (int rc = p3d_denoise_variance_device(a, (float*)a->var.p, nullptr)) return rc;
   P3D_HIP(hipDeviceSynchronize());
   P3D_HIP(hipMemcpy(var, a->var.p, px * sizeof(float), hipMemcpyDeviceToHost));
+  return P3D_OK;
+}
+
+}  // extern "C"
+
+// ---- temporal accumulation (include/p3d.h, csrc/temporal.hpp) ----
+
+// Per pixel three float4 images (colour + history, moments + coverage, normal_depth), twice: the frame of parity k writes set
+// k & 1 and reads the other.  The previous frame's camera is kept here and handed to the kernel by value.
+struct p3d_temporal {
+  int device = 0;
+  int32_t w = 0, h = 0;
+  uint32_t frames = 0;  // frames since create / reset
+  p3d_camera prev{};    // the camera of the last frame (frames > 0)
+  Scratch col[2], mom[2], nd[2];
+  Scratch h_rgb, h_nd, h_ac, h_out, h_var, h_hist;  // the host-buffer call's device copies
+};
+
+namespace {
+
+int check_temporal_params(const p3d_temporal_params* prm) {
+  if (!(prm->alpha >= 0.0f && prm->alpha <= 1.0f) || !(prm->alpha_moments >= 0.0f && prm->alpha_moments <= 1.0f))
+    return fail(P3D_ERR_INVALID, "p3d_temporal: alpha and alpha_moments must lie in [0, 1]");
+  if (!(prm->max_history >= 1.0f)) return fail(P3D_ERR_INVALID, "p3d_temporal: max_history must be a number >= 1");
+  if (!(prm->depth_tolerance > 0.0f) || !std::isfinite(prm->depth_tolerance))
+    return fail(P3D_ERR_INVALID, "p3d_temporal: depth_tolerance must be a finite number > 0");
+  if (!(prm->normal_tolerance >= -1.0f && prm->normal_tolerance <= 1.0f))
+    return fail(P3D_ERR_INVALID, "p3d_temporal: normal_tolerance must lie in [-1, 1]");
+  if (prm->variance_min_history > (1u << 24)) return fail(P3D_ERR_INVALID, "p3d_temporal: variance_min_history must be at most 2^24");
+  if (!(prm->sigma_normal >= 0.0f) || !(prm->sigma_depth >= 0.0f) || !std::isfinite(prm->sigma_normal) || !std::isfinite(prm->sigma_depth))
+    return fail(P3D_ERR_INVALID, "p3d_temporal: sigma_normal and sigma_depth must be finite numbers >= 0");
+  if (prm->reserved[0] || prm->reserved[1]) return fail(P3D_ERR_INVALID, "p3d_temporal: reserved fields must be 0");
+  return P3D_OK;
+}
+
+int check_temporal_camera(const p3d_temporal* tp, const p3d_camera* cam) {
+  if (cam->res_x != tp->w || cam->res_y != tp->h)
+    return fail(P3D_ERR_INVALID, "p3d_temporal: the camera renders " + std::to_string(cam->res_x) + "x" + std::to_string(cam->res_y) +
+                                     ", the object is for " + std::to_string(tp->w) + "x" + std::to_string(tp->h));
+  if (!camera_usable(*cam)) return fail(P3D_ERR_INVALID, "p3d_temporal: every camera field must be finite, and w, h and plane_dist > 0");
+  if (cam->aperture != 0.0f)
+    return fail(P3D_ERR_UNSUPPORTED, "p3d_temporal: a lens camera (aperture != 0) is not supported: the pinhole reprojection is not exact for it");
+  return P3D_OK;
+}
+
+DevCamera dev_camera(const p3d_camera& c) {
+  DevCamera d{};
+  d.eye = to_f3(c.eye); d.u = to_f3(c.u); d.v = to_f3(c.v); d.n = to_f3(c.n);
+  d.w = c.w; d.h = c.h; d.plane_dist = c.plane_dist; d.focal_ratio = c.focal_ratio; d.aperture = c.aperture;
+  d.res_x = c.res_x; d.res_y = c.res_y;
+  return d;
+}
+
+}  // namespace
+
+extern "C" {
+
+void p3d_temporal_params_default(p3d_temporal_params* prm) {
+  if (!prm) return;
+  *prm = p3d_temporal_params{};
+  prm->alpha = 0.2f;  // SVGF's
+  prm->alpha_moments = 0.2f;
+  prm->max_history = 32.0f;
+  prm->depth_tolerance = 0.1f;
+  prm->normal_tolerance = 0.9f;
+  prm->variance_min_history = 4;
+  prm->sigma_normal = 128.0f;  // p3d_denoise_params_default's
+  prm->sigma_depth = 1.0f;
+}
+
+int p3d_temporal_create(int device, int32_t w, int32_t h, p3d_temporal** out) {
+  if (!out) return fail(P3D_ERR_INVALID, "p3d_temporal_create: null argument");
+  *out = nullptr;
+  if (w <= 0 || h <= 0 || (uint64_t)w * (uint64_t)h > (1ull << 28)) return fail(P3D_ERR_INVALID, "p3d_temporal_create: bad image size");
+  P3D_HIP(hipSetDevice(device));
+  p3d_temporal* t = new p3d_temporal;
+  t->device = device;
+  t->w = w;
+  t->h = h;
+  const size_t n = (size_t)w * h;
+  int rc = P3D_OK;
+  for (int k = 0; k < 2 && !rc; ++k) {
+    rc = t->col[k].ensure(n * sizeof(float4));
+    if (!rc) rc = t->mom[k].ensure(n * sizeof(float4));
+    if (!rc) rc = t->nd[k].ensure(n * sizeof(float4));
+  }
+  if (rc) {
+    p3d_temporal_destroy(t);
+    return rc;
+  }
+  *out = t;
+  return P3D_OK;
+}
+
+void p3d_temporal_destroy(p3d_temporal* t) {
+  if (!t) return;
+  (void)hipSetDevice(t->device);
+  for (Scratch* b : {&t->col[0], &t->col[1], &t->mom[0], &t->mom[1], &t->nd[0], &t->nd[1], &t->h_rgb, &t->h_nd, &t->h_ac, &t->h_out,
+                     &t->h_var, &t->h_hist})
+    b->release();
+  delete t;
+}
+
+int p3d_temporal_reset(p3d_temporal* t) {
+  if (!t) return fail(P3D_ERR_INVALID, "p3d_temporal_reset: null object");
+  t->frames = 0;
+  t->prev = p3d_camera{};
+  return P3D_OK;
+}
+
+uint32_t p3d_temporal_frames(const p3d_temporal* t) { return t ? t->frames : 0u; }
+
+int p3d_temporal_accumulate_device(p3d_temporal* t, const p3d_temporal_params* prm, const p3d_camera* cam, const float* d_rgb,
+                                   const float* d_normal_depth, const float* d_albedo_cov, float* d_out_rgb, float* d_out_var,
+                                   float* d_out_history, void* hip_stream) {
+  if (prm) if (int rc = check_temporal_params(prm)) return rc;
+  if (!t || !prm || !cam || !d_rgb || !d_normal_depth || !d_albedo_cov || !d_out_rgb)
+    return fail(P3D_ERR_INVALID, "p3d_temporal_accumulate: null argument");
+  if (((uintptr_t)d_normal_depth | (uintptr_t)d_albedo_cov) & 15u)
+    return fail(P3D_ERR_INVALID, "p3d_temporal_accumulate: the feature buffers must be 16-byte aligned");
+  if (int rc = check_temporal_camera(t, cam)) return rc;
+  P3D_HIP(hipSetDevice(t->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const uint32_t cur = t->frames & 1u, prv = cur ^ 1u;
+  TemporalParams T{};
+  T.cam = dev_camera(*cam);
+  T.prev = dev_camera(t->prev);
+  T.rgb = d_rgb; T.nd = (const float4*)d_normal_depth; T.ac = (const float4*)d_albedo_cov;
+  T.col_prev = (const float4*)t->col[prv].p; T.mom_prev = (const float4*)t->mom[prv].p; T.nd_prev = (const float4*)t->nd[prv].p;
+  T.col = (float4*)t->col[cur].p; T.mom = (float4*)t->mom[cur].p; T.ndc = (float4*)t->nd[cur].p;
+  T.out_rgb = d_out_rgb; T.out_history = d_out_history; T.out_var = d_out_var;
+  T.w = t->w; T.h = t->h;
+  T.has_prev = t->frames > 0 ? 1u : 0u;
+  T.same_view = T.has_prev && std::memcmp(&T.cam, &T.prev, sizeof(DevCamera)) == 0 ? 1u : 0u;
+  T.alpha = prm->alpha; T.alpha_moments = prm->alpha_moments; T.max_history = prm->max_history;
+  T.depth_tolerance = prm->depth_tolerance; T.normal_tolerance = prm->normal_tolerance;
+  T.variance_min_history = (float)prm->variance_min_history;
+  T.sigma_normal = prm->sigma_normal; T.sigma_depth = prm->sigma_depth;
+  const dim3 grid(((uint32_t)t->w + kTemporalEdge - 1) / kTemporalEdge, ((uint32_t)t->h + kTemporalEdge - 1) / kTemporalEdge);
+  hipLaunchKernelGGL(temporal_reproject_kernel, grid, dim3(kTemporalThreads), 0, st, T);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("p3d_temporal launch: ") + hipGetErrorString(e));
+  if (d_out_var) {
+    hipLaunchKernelGGL(temporal_variance_kernel, grid, dim3(kTemporalThreads), 0, st, T);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("p3d_temporal launch: ") + hipGetErrorString(e));
+  }
+  ++t->frames;
+  t->prev = *cam;
+  return P3D_OK;
+}
+
+int p3d_temporal_accumulate(p3d_temporal* t, const p3d_temporal_params* prm, const p3d_camera* cam, const float* rgb,
+                            const float* normal_depth, const float* albedo_cov, float* out_rgb, float* out_var, float* out_history) {
+  if (prm) if (int rc = check_temporal_params(prm)) return rc;  // (first: the parameters are checked without an object)
+  if (!t || !prm || !cam || !rgb || !normal_depth || !albedo_cov || !out_rgb)
+    return fail(P3D_ERR_INVALID, "p3d_temporal_accumulate: null argument");
+  if (int rc = check_temporal_camera(t, cam)) return rc;
+  P3D_HIP(hipSetDevice(t->device));
+  const size_t n = (size_t)t->w * t->h;
+  if (int rc = t->h_rgb.ensure(n * 3 * sizeof(float))) return rc;
+  if (int rc = t->h_nd.ensure(n * sizeof(float4))) return rc;
+  if (int rc = t->h_ac.ensure(n * sizeof(float4))) return rc;
+  if (int rc = t->h_out.ensure(n * 3 * sizeof(float))) return rc;
+  if (out_var) if (int rc = t->h_var.ensure(n * sizeof(float))) return rc;
+  if (out_history) if (int rc = t->h_hist.ensure(n * sizeof(float))) return rc;
+  P3D_HIP(hipMemcpy(t->h_rgb.p, rgb, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  P3D_HIP(hipMemcpy(t->h_nd.p, normal_depth, n * sizeof(float4), hipMemcpyHostToDevice));
+  P3D_HIP(hipMemcpy(t->h_ac.p, albedo_cov, n * sizeof(float4), hipMemcpyHostToDevice));
+  if (int rc = p3d_temporal_accumulate_device(t, prm, cam, (const float*)t->h_rgb.p, (const float*)t->h_nd.p, (const float*)t->h_ac.p,
+                                              (float*)t->h_out.p, out_var ? (float*)t->h_var.p : nullptr,
+                                              out_history ? (float*)t->h_hist.p : nullptr, nullptr))
+    return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  P3D_HIP(hipMemcpy(out_rgb, t->h_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (out_var) P3D_HIP(hipMemcpy(out_var, t->h_var.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (out_history) P3D_HIP(hipMemcpy(out_history, t->h_hist.p, n * sizeof(float), hipMemcpyDeviceToHost));
   return P3D_OK;
 }
 

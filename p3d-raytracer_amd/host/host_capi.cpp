@@ -23,6 +23,17 @@ struct p3d_host_scene {
 
 namespace {
 
+// The p3d_camera of a constructed Camera (camera.h:34-63): what p3d_host_scene_desc and p3d_camera_look_at hand out.
+void pack_camera(const p3d::Camera& c, p3d_camera& k) {
+  k = p3d_camera{};
+  k.eye[0] = c.eye.x; k.eye[1] = c.eye.y; k.eye[2] = c.eye.z;
+  k.u[0] = c.u.x; k.u[1] = c.u.y; k.u[2] = c.u.z;
+  k.v[0] = c.v.x; k.v[1] = c.v.y; k.v[2] = c.v.z;
+  k.n[0] = c.n.x; k.n[1] = c.n.y; k.n[2] = c.n.z;
+  k.plane_dist = c.plane_dist; k.w = c.w; k.h = c.h; k.focal_ratio = c.focal_ratio;
+  k.aperture = c.aperture; k.res_x = c.res_x; k.res_y = c.res_y;
+}
+
 void flatten(p3d_host_scene& hs) {
   using namespace p3d;
   const Scene& S = hs.scene;
@@ -66,15 +77,7 @@ void flatten(p3d_host_scene& hs) {
   d.prims = hs.prims.data();
   d.materials = hs.materials.data();
   d.lights = hs.lights.data();
-  if (const Camera* c = S.GetCamera()) {
-    p3d_camera& k = d.camera;
-    k.eye[0] = c->eye.x; k.eye[1] = c->eye.y; k.eye[2] = c->eye.z;
-    k.u[0] = c->u.x; k.u[1] = c->u.y; k.u[2] = c->u.z;
-    k.v[0] = c->v.x; k.v[1] = c->v.y; k.v[2] = c->v.z;
-    k.n[0] = c->n.x; k.n[1] = c->n.y; k.n[2] = c->n.z;
-    k.plane_dist = c->plane_dist; k.w = c->w; k.h = c->h; k.focal_ratio = c->focal_ratio;
-    k.aperture = c->aperture; k.res_x = c->res_x; k.res_y = c->res_y;
-  }
+  if (const Camera* c = S.GetCamera()) pack_camera(*c, d.camera);
   const Color bg = S.GetBackgroundColor();
   d.background[0] = bg.r(); d.background[1] = bg.g(); d.background[2] = bg.b();
   if (hs.bvh) {
@@ -170,6 +173,34 @@ int p3d_host_scene_desc(p3d_host_scene* hs, int build_bvh, int build_grid, const
   }
   if (!hs->flat_valid) flatten(*hs);
   *out = &hs->desc;
+  return P3D_OK;
+}
+
+int p3d_host_scene_view(p3d_host_scene* hs, float from[3], float at[3], float up[3], float* angle, float* aperture_ratio,
+                        float* focal_ratio) {
+  if (!hs || !from || !at || !up || !angle || !aperture_ratio || !focal_ratio)
+    return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_view: null argument");
+  const p3d::Scene::ViewBlock& v = hs->scene.view;
+  if (!v.present) return p3d::fail(P3D_ERR_INVALID, "scene has no camera (`v` block)");
+  const p3d::Vector* src[3] = {&v.from, &v.at, &v.up};
+  float* dst[3] = {from, at, up};
+  for (int i = 0; i < 3; ++i) {
+    dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z;
+  }
+  *angle = v.angle;
+  *aperture_ratio = v.aperture;
+  *focal_ratio = v.focal;
+  return P3D_OK;
+}
+
+// camera.h:34-63 as the loader runs it for a `v` block (Scene::rebuildCamera); hither / yon leave no trace in p3d_camera
+int p3d_camera_look_at(const float from[3], const float at[3], const float up[3], float angle, int32_t res_x, int32_t res_y,
+                       float aperture_ratio, float focal_ratio, p3d_camera* out) {
+  if (!from || !at || !up || !out) return p3d::fail(P3D_ERR_INVALID, "p3d_camera_look_at: null argument");
+  if (res_x <= 0 || res_y <= 0) return p3d::fail(P3D_ERR_INVALID, "p3d_camera_look_at: the resolution must be positive");
+  const p3d::Camera c(p3d::Vector(from[0], from[1], from[2]), p3d::Vector(at[0], at[1], at[2]), p3d::Vector(up[0], up[1], up[2]), angle,
+                      0.0f, 0.0f, res_x, res_y, aperture_ratio, focal_ratio);
+  pack_camera(c, *out);
   return P3D_OK;
 }
 

@@ -35,6 +35,13 @@
 //              [--feature-spp K]   at most 8) over feature buffers of the first K samples' primary rays (default 0 = min(16,
 //                               SPP*SPP)); with --adaptive the filter uses the frame's variance.  FILE is PNG or PPM by
 //                               extension, as --out; --out is written as without --denoise.  Not with --whitted or --gpus.
+//              [--frames N]     N frames of a moving camera (one-shot renders): frame k turns the view k * DEG degrees about
+//              [--orbit DEG]    the `up` axis through `at` (p3d_camera_look_at, p3d_scene_set_camera) and uses seed + k.  Frame k
+//                               is written to <out>_%03d.<ext> (and <denoise>_%03d.<ext>), and one line per frame prints its
+//                               from / at / up (%.9g).  Frame 0 is the scene's own view.  Not with --passes or --gpus.
+//              [--temporal]     with --frames, --pathtrace and --denoise: every frame goes through the temporal accumulator
+//                               (p3d_temporal, default parameters) and the variance-term filter at sigma_luma = 4 (SVGF's
+//                               value: the temporal variance is per sample; DESIGN.md "Temporal reprojection").
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -263,6 +270,100 @@ int render_multi_gpu(const p3d_scene_desc* desc, bool device_bvh, p3d_config cfg
   return verdict;
 }
 
+bool save_image(const std::string& path, const std::vector<uint8_t>& rgb8, int w, int h) {
+  const bool ppm = path.size() > 4 && path.compare(path.size() - 4, 4, ".ppm") == 0;
+  return ppm ? save_ppm(path, rgb8, w, h) : save_png(path, rgb8, w, h);
+}
+
+// <base>_%03d<.ext>: the frame number before the extension (none: appended)
+std::string frame_name(const std::string& path, long k) {
+  char num[16];
+  std::snprintf(num, sizeof(num), "_%03ld", k);
+  const size_t slash = path.find_last_of('/'), dot = path.find_last_of('.');
+  if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return path + num;
+  return path.substr(0, dot) + num + path.substr(dot);
+}
+
+// --frames N --orbit DEG: frame k sees the scene from `from` turned k * DEG degrees about the `up` axis through `at` (Rodrigues'
+// rotation in double, rounded to float once), rendered with seed + k; with --denoise every frame is filtered, with --temporal
+// after the temporal accumulator.  Returns the exit code.
+int render_frames(p3d_host_scene* hs, p3d_scene* scene, p3d_config cfg, long frames, double orbit, bool temporal, const std::string& out,
+                  const std::string& denoise_out, long denoise_iter, long feature_spp, int device) {
+  float from[3], at[3], up[3], angle, aperture_ratio, focal_ratio;
+  if (p3d_host_scene_view(hs, from, at, up, &angle, &aperture_ratio, &focal_ratio) != P3D_OK) return die("view");
+  p3d_camera cam0;
+  if (p3d_scene_camera(scene, &cam0) != P3D_OK) return die("camera");
+  const int W = cam0.res_x, H = cam0.res_y;
+  const size_t px = (size_t)W * H;
+  const bool denoise = !denoise_out.empty();
+  std::vector<uint8_t> img(px * 3), den(denoise ? px * 3 : 0);
+  std::vector<float> lin(denoise ? px * 3 : 0), nd(denoise ? px * 4 : 0), ac(denoise ? px * 4 : 0), trgb, tvar;
+  p3d_denoiser* dn = nullptr;
+  p3d_temporal* tp = nullptr;
+  if (denoise && p3d_denoiser_create(device, W, H, &dn) != P3D_OK) return die("denoiser_create");
+  if (temporal) {
+    if (p3d_temporal_create(device, W, H, &tp) != P3D_OK) return die("temporal_create");
+    trgb.resize(px * 3);
+    tvar.resize(px);
+  }
+  p3d_denoise_params dprm;
+  p3d_denoise_params_default(&dprm);
+  if (denoise_iter >= 0) dprm.iterations = (uint32_t)denoise_iter;
+  dprm.gamma = cfg.gamma;
+  if (temporal) dprm.sigma_luma = 4.0f;  // the per-sample variance of the temporal moments, as SVGF's
+  p3d_temporal_params tprm;
+  p3d_temporal_params_default(&tprm);
+  const p3d_tile tile{0, 0, W, H, 0, 1};
+  const uint64_t seed0 = cfg.seed;
+  double ax = up[0], ay = up[1], az = up[2];
+  const double al = std::sqrt(ax * ax + ay * ay + az * az);
+  if (!(al > 0)) { std::fprintf(stderr, "--orbit: the scene's up vector is zero\n"); return 1; }
+  ax /= al; ay /= al; az /= al;
+  for (long k = 0; k < frames; ++k) {
+    float f[3] = {from[0], from[1], from[2]};
+    if (k > 0) {  // v' = v cos + (a x v) sin + a (a.v)(1 - cos), v = from - at
+      const double th = (double)k * orbit * 3.14159265358979323846 / 180.0, c = std::cos(th), s = std::sin(th);
+      const double vx = (double)from[0] - at[0], vy = (double)from[1] - at[1], vz = (double)from[2] - at[2];
+      const double dt = ax * vx + ay * vy + az * vz;
+      const double rx = vx * c + (ay * vz - az * vy) * s + ax * dt * (1 - c);
+      const double ry = vy * c + (az * vx - ax * vz) * s + ay * dt * (1 - c);
+      const double rz = vz * c + (ax * vy - ay * vx) * s + az * dt * (1 - c);
+      f[0] = (float)(at[0] + rx); f[1] = (float)(at[1] + ry); f[2] = (float)(at[2] + rz);
+      p3d_camera cam;
+      if (p3d_camera_look_at(f, at, up, angle, W, H, aperture_ratio, focal_ratio, &cam) != P3D_OK || p3d_scene_set_camera(scene, &cam) != P3D_OK)
+        return die("set_camera");
+    }
+    std::printf("frame %ld: from %.9g %.9g %.9g at %.9g %.9g %.9g up %.9g %.9g %.9g\n", k, f[0], f[1], f[2], at[0], at[1], at[2], up[0], up[1], up[2]);
+    cfg.seed = seed0 + (uint64_t)k;
+    p3d_stats st{};
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    if (p3d_render_tile(scene, &cfg, &tile, denoise ? lin.data() : nullptr, nullptr, img.data(), &st) != P3D_OK) return die("render");
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    if (!save_image(frame_name(out, k), img, W, H)) { std::printf("Error saving Image file\n"); return 1; }
+    if (denoise) {
+      if (p3d_render_features(scene, &cfg, &tile, feature_spp > 0 ? (uint32_t)feature_spp : 0u, nd.data(), ac.data()) != P3D_OK)
+        return die("render_features");
+      if (temporal) {
+        p3d_camera cam;
+        if (p3d_scene_camera(scene, &cam) != P3D_OK) return die("camera");
+        if (const int t = p3d_temporal_accumulate(tp, &tprm, &cam, lin.data(), nd.data(), ac.data(), trgb.data(), tvar.data(), nullptr); t != P3D_OK) {
+          if (t != P3D_ERR_UNSUPPORTED) return die("temporal");
+          std::fprintf(stderr, "--temporal: %s\n", p3d_last_error());
+          return 2;
+        }
+      }
+      if (p3d_denoise(dn, &dprm, temporal ? trgb.data() : lin.data(), temporal ? tvar.data() : nullptr, nd.data(), ac.data(), nullptr, den.data()) != P3D_OK)
+        return die("denoise");
+      if (!save_image(frame_name(denoise_out, k), den, W, H)) { std::printf("Error saving Image file\n"); return 1; }
+    }
+    std::printf("frame %ld: %.3f ms (render call), seed %llu\n", k, ms, (unsigned long long)cfg.seed);
+    std::fflush(stdout);
+  }
+  if (tp) p3d_temporal_destroy(tp);
+  if (dn) p3d_denoiser_destroy(dn);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -276,6 +377,9 @@ int main(int argc, char** argv) {
   std::string denoise_out;   // --denoise FILE (empty: off)
   long denoise_iter = -1;    // --denoise-iter N (-1: the default)
   long feature_spp = -1;     // --feature-spp K (-1: the default)
+  long frames = 0;           // --frames N (0: one frame, the usual output names)
+  double orbit = 0.0;        // --orbit DEG (degrees per frame)
+  bool orbit_set = false, temporal = false;
   bool device_bvh = false, verify = false;
   uint32_t load_flags = 0;
   for (int i = 1; i < argc; ++i) {
@@ -327,6 +431,18 @@ int main(int argc, char** argv) {
       if (end == v || *end != 0 || min_spp < 2) { std::fprintf(stderr, "--min-spp needs a whole number of samples, at least 2 (got '%s')\n", v); return 2; }
     }
     else if (a == "--denoise") denoise_out = next("--denoise");
+    else if (a == "--frames") {
+      const char* v = next("--frames");
+      char* end = nullptr;
+      frames = std::strtol(v, &end, 10);
+      if (end == v || *end != 0 || frames < 1 || frames > 1000) { std::fprintf(stderr, "--frames needs a whole number from 1 to 1000 (got '%s')\n", v); return 2; }
+    } else if (a == "--orbit") {
+      const char* v = next("--orbit");
+      char* end = nullptr;
+      orbit = std::strtod(v, &end);
+      if (end == v || *end != 0 || !std::isfinite(orbit)) { std::fprintf(stderr, "--orbit needs a finite number of degrees (got '%s')\n", v); return 2; }
+      orbit_set = true;
+    } else if (a == "--temporal") temporal = true;
     else if (a == "--denoise-iter" || a == "--feature-spp") {
       const char* v = next(a.c_str());
       char* end = nullptr;
@@ -367,6 +483,15 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "--feature-spp %ld: the frame has only %ld samples per pixel\n", feature_spp, (long)cfg.spp_sqrt * (long)cfg.spp_sqrt);
       return 2;
     }
+  }
+  if (orbit_set && frames == 0) { std::fprintf(stderr, "--orbit goes with --frames\n"); return 2; }
+  if (temporal) {
+    if (frames == 0) { std::fprintf(stderr, "--temporal needs --frames N (it integrates a sequence)\n"); return 2; }
+    if (denoise_out.empty()) { std::fprintf(stderr, "--temporal needs --denoise FILE (its output goes through the variance-term filter)\n"); return 2; }
+  }
+  if (frames > 0) {
+    if (passes > 0) { std::fprintf(stderr, "--frames does not combine with --passes (every frame is one render call)\n"); return 2; }
+    if (gpus > 0) { std::fprintf(stderr, "--frames does not combine with --gpus\n"); return 2; }
   }
   if (scene_path.empty()) {  // main.cpp:968-980: prompt for a name under P3D_Scenes/
     std::string name;
@@ -422,6 +547,12 @@ int main(int argc, char** argv) {
     cfg.skybox = 1;
   }
   const auto t_build1 = std::chrono::high_resolution_clock::now();
+  if (frames > 0) {
+    const int rc = render_frames(hs, scene, cfg, frames, orbit, temporal, out, denoise_out, denoise_iter, feature_spp, device);
+    p3d_scene_destroy(scene);
+    p3d_host_scene_destroy(hs);
+    return rc;
+  }
 
   std::vector<uint8_t> img((size_t)3 * W * H);
   const bool denoise = !denoise_out.empty();
