@@ -419,6 +419,40 @@ int p3d_scene_set_camera(p3d_scene* scene, const p3d_camera* camera);
 int p3d_scene_camera(p3d_scene* scene, p3d_camera* out);
 
 /*
+ * Moving the OBJECTS of a device scene between frames, without a new scene.  Detected by the symbols (P3D_ABI_VERSION is
+ * unchanged).  Only for scenes of p3d_scene_create_device_bvh: the linear BVH is brought up to date on the device, in place.
+ *
+ * p3d_scene_update_prims replaces the `n` objects object[0..n) by prims[0..n) (whole p3d_prim records: geometry, normal and
+ * box, as p3d_host_scene_desc hands them out after p3d_host_scene_set_geometry) and then
+ *   P3D_UPDATE_REFIT   keeps the tree's topology and leaf order and recomputes every node box bottom-up: cheap, exact for the
+ *                      tree it keeps, but the tree fits the scene less well the further objects have moved;
+ *   P3D_UPDATE_REBUILD runs the whole build again in a workspace the scene keeps (no allocation per call): node and leaf
+ *                      arrays are, bit for bit, those p3d_scene_create_device_bvh builds for the updated descriptor.
+ *                      n = 0 is allowed: it re-sorts a tree that many refits have degraded.
+ * Frames enqueued after the call see the new geometry.  Like p3d_scene_set_camera it is a host call that WAITS (tail stream,
+ * then the whole device, then for its own launches) and cannot be captured into a graph.  It forgets the tile-cost schedules
+ * and the hit_stack hand-off's row chains and halo pixels, refreshes the root box, and a p3d_accum or p3d_adaptive refuses
+ * passes (P3D_ERR_INVALID, nothing changed) until it is reset.  p3d_temporal knows nothing of it: it reprojects with the camera
+ * only, so the caller resets it or accepts ghosting on moved objects.  The first update of a scene allocates the builder's
+ * state (about 150 bytes per object), which p3d_scene_destroy frees.
+ * *update_ms (may be NULL): GPU time between two events around the staging copy and the launches.
+ * Refused with P3D_ERR_INVALID, nothing changed: a scene of p3d_scene_create; a scene that carries a grid (it would go stale);
+ * an object index out of range or repeated within the call; a record whose type or material differs from the object's
+ * (emitter list and kernel selection stay valid); a non-finite or inverted bmin / bmax; an unknown mode; NULL arrays with n > 0.
+ *
+ * p3d_scene_export_bvh returns the scene's current device-built tree in the descriptor's format (p3d_bvh_node: children
+ * adjacent and behind their parent, leaves as ranges of prim_index), relabelled on the host by a depth-first walk from the
+ * root, left child first: exactly what p3d_scene_create accepts as bvh_nodes / bvh_prim_index / bvh_max_depth.  *n_nodes and
+ * *n_prim_index hold the capacities of the arrays on entry and the sizes on return; with nodes == NULL only the sizes are
+ * returned.  P3D_ERR_CAPACITY if an array is too small, P3D_ERR_INVALID for a scene of p3d_scene_create.  max_depth may be NULL.
+ */
+typedef enum p3d_update_mode { P3D_UPDATE_REFIT = 0, P3D_UPDATE_REBUILD = 1 } p3d_update_mode;
+int p3d_scene_update_prims(p3d_scene* scene, uint32_t n, const uint32_t* object, const p3d_prim* prims,
+                           uint32_t mode, float* update_ms);
+int p3d_scene_export_bvh(p3d_scene* scene, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index,
+                         uint32_t* n_prim_index, uint32_t* max_depth);
+
+/*
  * Progressive accumulation: one anti-aliased frame rendered in passes over its samples, the image shown (or the frame
  * stopped) after any of them - what the reference's drawModeEnabled display (main.cpp:45-48) does line by line, by sample
  * instead.  A caller detects these entry points by the symbols being present (P3D_ABI_VERSION is unchanged).
@@ -704,6 +738,15 @@ void p3d_host_scene_destroy(p3d_host_scene* hs);
 int p3d_host_scene_set_resolution(p3d_host_scene* hs, int32_t res_x, int32_t res_y);
 /* Same for the `aperture` / `focal` entries of the `v` block. */
 int p3d_host_scene_set_lens(p3d_host_scene* hs, float aperture_ratio, float focal_ratio);
+/*
+ * Replaces the nine geometry floats of the objects object[0..n): v + 9 i means what p3d_prim.v means for the object's kind
+ * (sphere: centre and radius, triangle: three vertices, box: min and max).  The objects are constructed again by the
+ * constructors the .p3f loader runs (the same code), so the triangle normal, Min / Max -/+ EPSILON and the sphere box come out
+ * as a scene file with these numbers would give them; material and index stay.  Planes are refused (P3D_ERR_INVALID), as are
+ * an index out of range and NULL arrays with n > 0; nothing is changed then.  Drops the host BVH and grid - the next
+ * p3d_host_scene_desc builds them again - and invalidates the flattened arrays.  Host only, no device needed.
+ */
+int p3d_host_scene_set_geometry(p3d_host_scene* hs, uint32_t n, const uint32_t* object, const float* v /* n x 9 */);
 /* Replaces every light by SPP x SPP jittered copies (main.cpp:725-745); used for
  * SOFT_SHADOWS without ANTIALIASING. */
 int p3d_host_scene_replicate_lights(p3d_host_scene* hs, uint32_t spp_sqrt, float light_side);

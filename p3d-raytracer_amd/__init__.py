@@ -29,6 +29,7 @@ SAMPLE_JITTER, SAMPLE_TENT = 0, 1
 LOAD_LEGACY_F11 = 1
 DEBUG_NONE, DEBUG_TEST_INTERSECT, DEBUG_DEPTH_MAP = 0, 1, 2
 HANDOFF_COMPACT, HANDOFF_DENSE = 0, 1
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 
 EXPORTS = [
     "p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_config_default",
@@ -45,6 +46,7 @@ EXPORTS = [
     "p3d_camera_look_at", "p3d_scene_set_camera", "p3d_scene_camera", "p3d_host_scene_view",
     "p3d_temporal_params_default", "p3d_temporal_create", "p3d_temporal_destroy", "p3d_temporal_reset", "p3d_temporal_frames",
     "p3d_temporal_accumulate", "p3d_temporal_accumulate_device",
+    "p3d_scene_update_prims", "p3d_scene_export_bvh", "p3d_host_scene_set_geometry",
 ]
 
 
@@ -264,6 +266,10 @@ def lib():
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.p3d_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(Camera), C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_scene_update_prims.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        L.p3d_scene_export_bvh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint32)]
+        L.p3d_host_scene_set_geometry.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -373,6 +379,15 @@ class HostScene:
     def replicate_lights(self, spp_sqrt, light_side):
         _check(self._L.p3d_host_scene_replicate_lights(self._h, int(spp_sqrt), float(light_side)))
 
+    def set_geometry(self, objects, v):
+        """p3d_host_scene_set_geometry: the nine geometry floats `v[i]` (what prim_v holds for the object's kind) replace those of
+        object `objects[i]`, through the loader's constructors.  Planes are refused.  Drops the host BVH and grid."""
+        obj = np.ascontiguousarray(objects, np.uint32).reshape(-1)
+        g = np.ascontiguousarray(v, np.float32).reshape(-1, 9)
+        if len(g) != len(obj):
+            raise ValueError("set_geometry: %d objects, %d rows of nine floats" % (len(obj), len(g)))
+        _check(self._L.p3d_host_scene_set_geometry(self._h, len(obj), obj.ctypes.data, g.ctypes.data))
+
     def has_skybox(self):
         """A cubemap is loaded: the folder of the scene's `env` line was found, or load_skybox was called (p3d_host_scene_has_skybox)."""
         return bool(self._L.p3d_host_scene_has_skybox(self._h))
@@ -449,12 +464,28 @@ class DeviceScene:
 
     def __init__(self, host_scene, bvh=True, grid=False, device=0):
         """bvh: True = the reference-exact tree built on the host (BVH::build), "device" = a linear BVH built
-        on the GPU (p3d_scene_create_device_bvh: correct closest hits, not the reference's tree), False = none."""
+        on the GPU (p3d_scene_create_device_bvh: correct closest hits, not the reference's tree), False = none,
+        a dict with the bvh_* keys of HostScene.arrays(bvh=True) (e.g. from export_bvh) = that tree over the
+        host scene's current objects."""
         self._L = lib()
         self.host = host_scene
         self.device_bvh_ms = None
         h = C.c_void_p()
-        if bvh == "device":
+        if isinstance(bvh, dict):
+            src = host_scene.desc(False, grid)
+            d = SceneDesc.from_buffer_copy(src)  # the host scene's descriptor with the tree swapped in
+            n = len(bvh["bvh_index"])
+            nodes = np.zeros((n, 8), np.uint32)
+            nodes[:, 0:3] = np.ascontiguousarray(bvh["bvh_bmin"], np.float32).reshape(n, 3).view(np.uint32)
+            nodes[:, 3] = bvh["bvh_index"]
+            nodes[:, 4:7] = np.ascontiguousarray(bvh["bvh_bmax"], np.float32).reshape(n, 3).view(np.uint32)
+            nodes[:, 7] = bvh["bvh_count_leaf"]
+            order = np.ascontiguousarray(bvh["bvh_order"], np.uint32)
+            d.n_bvh_nodes, d.n_bvh_prim_index, d.bvh_max_depth = n, len(order), int(bvh["bvh_max_depth"])
+            d.bvh_nodes = C.cast(nodes.ctypes.data, C.POINTER(BvhNode))
+            d.bvh_prim_index = C.cast(order.ctypes.data, C.POINTER(C.c_uint32))
+            _check(self._L.p3d_scene_create(C.byref(d), int(device), C.byref(h)))
+        elif bvh == "device":
             d = host_scene.desc(False, grid)
             ms = C.c_float(0)
             _check(self._L.p3d_scene_create_device_bvh(C.byref(d), int(device), C.byref(h), C.byref(ms)))
@@ -506,6 +537,33 @@ class DeviceScene:
         """p3d_scene_set_camera: frames rendered after it see `cam` (a Camera of the scene's resolution, e.g. from look_at).
         Waits for the device.  Accumulators of this scene refuse passes until they are reset."""
         _check(self._L.p3d_scene_set_camera(self._h, C.byref(cam)))
+
+    def update_prims(self, objects, mode=UPDATE_REFIT):
+        """p3d_scene_update_prims: the records of `objects` are taken from the bound host scene's current descriptor (after
+        HostScene.set_geometry) and the device BVH is refitted or rebuilt.  Waits for the device; returns update_ms.
+        Accumulators of this scene refuse passes until they are reset."""
+        obj = np.ascontiguousarray(objects, np.uint32).reshape(-1)
+        d = self.host.desc(False, False)
+        if len(obj) and int(obj.max()) >= d.n_prims:
+            raise P3DError(-1, "update_prims: object index out of range")
+        recs = (Prim * max(len(obj), 1))()
+        for i, o in enumerate(obj):
+            recs[i] = d.prims[int(o)]
+        ms = C.c_float(0)
+        _check(self._L.p3d_scene_update_prims(self._h, len(obj), obj.ctypes.data if len(obj) else None,
+                                              C.cast(recs, C.c_void_p) if len(obj) else None, int(mode), C.byref(ms)))
+        return ms.value
+
+    def export_bvh(self):
+        """p3d_scene_export_bvh: the current device-built tree as numpy arrays, with the bvh_* keys of HostScene.arrays(bvh=True)
+        (children adjacent and behind their parent): DeviceScene(hs, bvh=that dict) uploads it again."""
+        n, m, depth = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(self._L.p3d_scene_export_bvh(self._h, None, C.byref(n), None, C.byref(m), C.byref(depth)))
+        buf = np.zeros((n.value, 8), np.uint32)
+        order = np.zeros(m.value, np.uint32)
+        _check(self._L.p3d_scene_export_bvh(self._h, buf.ctypes.data, C.byref(n), order.ctypes.data, C.byref(m), C.byref(depth)))
+        return dict(bvh_bmin=buf[:, 0:3].view(np.float32), bvh_index=buf[:, 3].copy(), bvh_bmax=buf[:, 4:7].view(np.float32),
+                    bvh_count_leaf=buf[:, 7].copy(), bvh_order=order, bvh_max_depth=depth.value)
 
     def render(self, cfg, tile=None, want_rgb8=False, stats=True):
         """Host-buffer form (p3d_render_tile): returns numpy arrays."""

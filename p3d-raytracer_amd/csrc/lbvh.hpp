@@ -180,6 +180,33 @@ __global__ void emit(const unsigned long long* keys, uint32_t n, const uint2* ch
   }
 }
 
+// One object of p3d_scene_update_prims as it is staged for scatter_prims: the caller's record and the object it replaces
+struct UpdateRecord {
+  p3d_prim prim;
+  uint32_t object;
+  uint32_t pad[3];
+};
+static_assert(sizeof(UpdateRecord) == 112, "UpdateRecord is read as seven float4");
+
+// Replaces objects in place: the object-order geometry (packed as create_impl's geom_of packs it), the shading normal and
+// the object's box.  One thread per record; the host has checked that every index is < n_objs and appears once.
+__global__ void scatter_prims(const UpdateRecord* recs, uint32_t n, uint32_t n_objs, float4* ogeom, float4* normals, float4* boxes) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const float4* r = reinterpret_cast<const float4*>(recs + i);
+  const float4 a = r[0], b = r[1], c = r[2], d = r[3], e = r[4], f = r[5], g = r[6];
+  // p3d_prim: v[0..8] = a.xyzw b.xyzw c.x, type = c.y, material = c.z, n = d.xyz, bmin = e.xyz, bmax = f.xyz
+  const uint32_t obj = __float_as_uint(g.x);
+  if (obj >= n_objs) return;
+  const uint32_t tm = __float_as_uint(c.y) | (__float_as_uint(c.z) << 8);
+  ogeom[3 * obj] = a;
+  ogeom[3 * obj + 1] = b;
+  ogeom[3 * obj + 2] = make_float4(c.x, __uint_as_float(tm), __uint_as_float(obj), 0.f);
+  normals[obj] = make_float4(d.x, d.y, d.z, 0.f);
+  boxes[2 * obj] = make_float4(e.x, e.y, e.z, 0.f);
+  boxes[2 * obj + 1] = make_float4(f.x, f.y, f.z, 0.f);
+}
+
 struct Result {
   uint32_t n_nodes = 0, max_depth = 0;
   float build_ms = 0;
@@ -191,58 +218,89 @@ struct Result {
     if (e_ != hipSuccess) return e_;       \
   } while (0)
 
+// The builder's intermediate state for n objects.  lbvh::build makes one for the length of a call; a scene that is
+// updated (p3d_scene_update_prims) keeps one, with the object boxes, from its first update to its destruction: sorted,
+// children and parent then ARE the topology of the tree in the scene's node array.
+struct Workspace {
+  uint32_t n = 0;
+  float4* boxes = nullptr;  // 2 n, only with alloc(n, true)
+  uint32_t* bounds = nullptr;
+  unsigned long long *keys = nullptr, *sorted = nullptr;
+  uint2* children = nullptr;
+  uint32_t *parent = nullptr, *visits = nullptr, *depth = nullptr;
+  float4* node_box = nullptr;
+  void* temp = nullptr;
+  size_t temp_bytes = 0;
+
+  hipError_t alloc(uint32_t n_objs, bool with_boxes) {
+    n = n_objs;
+    if (with_boxes) P3D_LBVH_HIP(hipMalloc((void**)&boxes, (size_t)2 * n * sizeof(float4)));
+    P3D_LBVH_HIP(hipMalloc((void**)&bounds, 6 * sizeof(uint32_t)));
+    P3D_LBVH_HIP(hipMalloc((void**)&keys, (size_t)n * 8));
+    P3D_LBVH_HIP(hipMalloc((void**)&sorted, (size_t)n * 8));
+    P3D_LBVH_HIP(hipMalloc((void**)&children, (size_t)n * sizeof(uint2)));
+    P3D_LBVH_HIP(hipMalloc((void**)&parent, (size_t)2 * n * sizeof(uint32_t)));
+    P3D_LBVH_HIP(hipMalloc((void**)&visits, (size_t)n * sizeof(uint32_t)));
+    P3D_LBVH_HIP(hipMalloc((void**)&depth, sizeof(uint32_t)));
+    P3D_LBVH_HIP(hipMalloc((void**)&node_box, (size_t)4 * n * sizeof(float4)));
+    P3D_LBVH_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, temp_bytes, keys, sorted, (int)n));
+    P3D_LBVH_HIP(hipMalloc(&temp, temp_bytes ? temp_bytes : 16));
+    return hipSuccess;
+  }
+  void release() {
+    for (void* p : {(void*)boxes, (void*)bounds, (void*)keys, (void*)sorted, (void*)children, (void*)parent, (void*)visits,
+                    (void*)depth, (void*)node_box, temp})
+      if (p) (void)hipFree(p);
+    *this = Workspace{};
+  }
+};
+
+// Steps 1 to 3 on the null stream: centre bounds, Morton keys, radix sort, Karras hierarchy -> sorted, children, parent
+inline hipError_t enqueue_topology(Workspace& w, const float4* d_boxes) {
+  const uint32_t n = w.n, blocks = (n + kThreads - 1) / kThreads;
+  P3D_LBVH_HIP(hipMemsetAsync(w.bounds, 0xff, 3 * sizeof(uint32_t), 0));  // min of centres: the largest ordered uint
+  P3D_LBVH_HIP(hipMemsetAsync(w.bounds + 3, 0, 3 * sizeof(uint32_t), 0));
+  hipLaunchKernelGGL(centre_bounds, dim3(blocks), dim3(kThreads), 0, 0, d_boxes, n, w.bounds);
+  hipLaunchKernelGGL(morton_keys, dim3(blocks), dim3(kThreads), 0, 0, d_boxes, n, w.bounds, w.keys);
+  P3D_LBVH_HIP(hipcub::DeviceRadixSort::SortKeys(w.temp, w.temp_bytes, w.keys, w.sorted, (int)n));
+  if (n > 1) hipLaunchKernelGGL(build_internal, dim3(blocks), dim3(kThreads), 0, 0, w.sorted, n, w.children, w.parent);
+  return hipGetLastError();
+}
+
+// Steps 4 and 5 over the topology in w: node boxes bottom-up from d_boxes, then the node records and the leaf-order geometry
+inline hipError_t enqueue_fit(Workspace& w, const float4* d_boxes, const float4* d_ogeom, float4* d_nodes, float4* d_bgeom) {
+  const uint32_t n = w.n, blocks = (n + kThreads - 1) / kThreads;
+  P3D_LBVH_HIP(hipMemsetAsync(w.visits, 0, (size_t)n * sizeof(uint32_t), 0));
+  P3D_LBVH_HIP(hipMemsetAsync(w.depth, 0, sizeof(uint32_t), 0));
+  hipLaunchKernelGGL(refit, dim3(blocks), dim3(kThreads), 0, 0, w.sorted, d_boxes, n, w.children, w.parent, w.visits, w.node_box, w.depth);
+  hipLaunchKernelGGL(emit, dim3(blocks), dim3(kThreads), 0, 0, w.sorted, n, w.children, w.node_box, d_ogeom, d_nodes, d_bgeom);
+  return hipGetLastError();
+}
+
 // d_boxes: 2 n float4 (GetBoundingBox of every object).  d_nodes: room for 2 (2 n - 1) float4, d_bgeom: 3 n float4.
 inline hipError_t build(const float4* d_boxes, const float4* d_ogeom, uint32_t n, float4* d_nodes, float4* d_bgeom, Result* out) {
   *out = Result{};
   if (n == 0) return hipSuccess;
-  const uint32_t blocks = (n + kThreads - 1) / kThreads;
-  uint32_t* d_bounds = nullptr;
-  unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
-  uint2* d_children = nullptr;
-  uint32_t *d_parent = nullptr, *d_visits = nullptr, *d_depth = nullptr;
-  float4* d_node_box = nullptr;
-  void* d_temp = nullptr;
-  size_t temp_bytes = 0;
+  Workspace w;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t rc = hipSuccess;
   auto body = [&]() -> hipError_t {
-    P3D_LBVH_HIP(hipMalloc((void**)&d_bounds, 6 * sizeof(uint32_t)));
-    P3D_LBVH_HIP(hipMalloc((void**)&d_keys, (size_t)n * 8));
-    P3D_LBVH_HIP(hipMalloc((void**)&d_sorted, (size_t)n * 8));
-    P3D_LBVH_HIP(hipMalloc((void**)&d_children, (size_t)n * sizeof(uint2)));
-    P3D_LBVH_HIP(hipMalloc((void**)&d_parent, (size_t)2 * n * sizeof(uint32_t)));
-    P3D_LBVH_HIP(hipMalloc((void**)&d_visits, (size_t)n * sizeof(uint32_t)));
-    P3D_LBVH_HIP(hipMalloc((void**)&d_depth, sizeof(uint32_t)));
-    P3D_LBVH_HIP(hipMalloc((void**)&d_node_box, (size_t)4 * n * sizeof(float4)));
-    P3D_LBVH_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, temp_bytes, d_keys, d_sorted, (int)n));
-    P3D_LBVH_HIP(hipMalloc(&d_temp, temp_bytes ? temp_bytes : 16));
+    P3D_LBVH_HIP(w.alloc(n, false));
     P3D_LBVH_HIP(hipEventCreate(&e0));
     P3D_LBVH_HIP(hipEventCreate(&e1));
-    const uint32_t init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    P3D_LBVH_HIP(hipMemcpy(d_bounds, init, sizeof(init), hipMemcpyHostToDevice));
     P3D_LBVH_HIP(hipEventRecord(e0, 0));
-    P3D_LBVH_HIP(hipMemsetAsync(d_visits, 0, (size_t)n * sizeof(uint32_t), 0));
-    P3D_LBVH_HIP(hipMemsetAsync(d_depth, 0, sizeof(uint32_t), 0));
-    hipLaunchKernelGGL(centre_bounds, dim3(blocks), dim3(kThreads), 0, 0, d_boxes, n, d_bounds);
-    hipLaunchKernelGGL(morton_keys, dim3(blocks), dim3(kThreads), 0, 0, d_boxes, n, d_bounds, d_keys);
-    P3D_LBVH_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp, temp_bytes, d_keys, d_sorted, (int)n));
-    if (n > 1) hipLaunchKernelGGL(build_internal, dim3(blocks), dim3(kThreads), 0, 0, d_sorted, n, d_children, d_parent);
-    hipLaunchKernelGGL(refit, dim3(blocks), dim3(kThreads), 0, 0, d_sorted, d_boxes, n, d_children, d_parent, d_visits, d_node_box, d_depth);
-    hipLaunchKernelGGL(emit, dim3(blocks), dim3(kThreads), 0, 0, d_sorted, n, d_children, d_node_box, d_ogeom, d_nodes, d_bgeom);
-    P3D_LBVH_HIP(hipGetLastError());
+    P3D_LBVH_HIP(enqueue_topology(w, d_boxes));
+    P3D_LBVH_HIP(enqueue_fit(w, d_boxes, d_ogeom, d_nodes, d_bgeom));
     P3D_LBVH_HIP(hipEventRecord(e1, 0));
     P3D_LBVH_HIP(hipEventSynchronize(e1));
     P3D_LBVH_HIP(hipEventElapsedTime(&out->build_ms, e0, e1));
-    P3D_LBVH_HIP(hipMemcpy(&out->max_depth, d_depth, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    P3D_LBVH_HIP(hipMemcpy(&out->max_depth, w.depth, sizeof(uint32_t), hipMemcpyDeviceToHost));
     out->n_nodes = 2 * n - 1;
     return hipSuccess;
   };
-  rc = body();
+  const hipError_t rc = body();
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  for (void* p : {(void*)d_bounds, (void*)d_keys, (void*)d_sorted, (void*)d_children, (void*)d_parent, (void*)d_visits,
-                  (void*)d_depth, (void*)d_node_box, d_temp})
-    if (p) (void)hipFree(p);
+  w.release();
   return rc;
 }
 

@@ -185,6 +185,15 @@ struct p3d_scene {
   hipEvent_t ev_tail_go = nullptr, ev_tail_done = nullptr;
   bool tail_pending = false;  // ev_tail_done was recorded by the last frame: the next launch on this scene waits for it
   uint64_t cam_gen = 0;       // bumped by every p3d_scene_set_camera that changes the camera (p3d_accum / p3d_adaptive check it)
+  // p3d_scene_update_prims (scenes of p3d_scene_create_device_bvh only)
+  bool device_bvh = false;
+  uint64_t geom_gen = 0;               // bumped by every update; checked like cam_gen
+  std::vector<uint32_t> obj_tm;        // type | material << 8 of every object: what an update may not change
+  std::vector<float4> create_boxes;    // the object boxes the tree was built from, until the first update moves them to the device
+  lbvh::Workspace lbvh_ws;             // allocated by the first update: object boxes and the topology of the tree in d_blob
+  bool lbvh_topology = false;          // lbvh_ws.sorted / children / parent describe the tree in d_blob
+  Scratch upd_stage;                   // lbvh::UpdateRecord[n] of the update in progress
+  std::vector<lbvh::UpdateRecord> upd_host;
 };
 
 namespace {
@@ -235,6 +244,7 @@ void p3d_scene_destroy(p3d_scene* s) {
   if (s->d_status) (void)hipFree(s->d_status);
   if (s->d_halo_verdict) (void)hipFree(s->d_halo_verdict);
   s->out_rgb8.release(); s->q_in.release(); s->q_out.release();
+  s->lbvh_ws.release(); s->upd_stage.release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   if (s->ev_mid) (void)hipEventDestroy(s->ev_mid);
@@ -479,7 +489,11 @@ static int create_impl(const p3d_scene_desc* d_in, int device, bool device_bvh, 
     s->has_bvh = true;
     s->bvh_max_depth = built.max_depth;
     s->device_bvh_ms = built.build_ms;
+    s->create_boxes = std::move(boxes);
+    s->obj_tm.resize(d->n_prims);
+    for (uint32_t i = 0; i < d->n_prims; ++i) s->obj_tm[i] = d->prims[i].type | (d->prims[i].material << 8);
   }
+  s->device_bvh = device_bvh;
   // The node-stack capacity (LDS + spill) is derived from the tree depth: never trust the caller's
   // number below what the node array really contains (child indices were validated above:
   // children lie behind their parent, so this walk terminates).
@@ -1385,6 +1399,161 @@ int p3d_scene_set_camera(p3d_scene* s, const p3d_camera* cam) {
   return P3D_OK;
 }
 
+int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, const p3d_prim* prims, uint32_t mode, float* update_ms) {
+  if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null scene");
+  if (n && (!object || !prims)) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null array with n > 0");
+  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: unknown mode");
+  if (!s->device_bvh)
+    return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
+  if (s->has_grid) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene carries a grid, which would go stale");
+  const uint32_t n_objs = s->dev.n_objs;
+  if (n > n_objs) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: more records than objects (an index is repeated)");
+  {
+    std::vector<uint8_t> seen(n_objs, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+      const p3d_prim& p = prims[i];
+      if (object[i] >= n_objs) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object index out of range");
+      if (seen[object[i]]) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " appears twice");
+      seen[object[i]] = 1;
+      if (p.type > 0xffu || p.material > 0xffffffu || (p.type | (p.material << 8)) != s->obj_tm[object[i]])
+        return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " changes its type or material");
+      for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p.bmin[k]) || !std::isfinite(p.bmax[k]) || !(p.bmin[k] <= p.bmax[k]))
+          return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " has a non-finite or inverted box");
+    }
+  }
+  if (update_ms) *update_ms = 0.0f;
+  if (n_objs == 0) return P3D_OK;
+  P3D_HIP(hipSetDevice(s->device));
+  // enqueued frames read the geometry, the tree and the scene's memos: the tail stream, then the whole device
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  auto hip_fail = [](const char* what, hipError_t e) { return fail(P3D_ERR_NO_DEVICE, std::string("p3d_scene_update_prims: ") + what + ": " + hipGetErrorString(e)); };
+  lbvh::Workspace& w = s->lbvh_ws;
+  if (!w.n) {  // first update: the builder's state, with the boxes the tree in d_blob was built from
+    hipError_t e = w.alloc(n_objs, true);
+    if (e == hipSuccess) e = hipMemcpy(w.boxes, s->create_boxes.data(), s->create_boxes.size() * sizeof(float4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      w.release();
+      return hip_fail("workspace", e);
+    }
+    std::vector<float4>().swap(s->create_boxes);
+    s->lbvh_topology = false;
+  }
+  if (n) {
+    if (int rc = s->upd_stage.ensure((size_t)n * sizeof(lbvh::UpdateRecord))) return rc;
+    s->upd_host.assign(n, lbvh::UpdateRecord{});
+    for (uint32_t i = 0; i < n; ++i) {
+      s->upd_host[i].prim = prims[i];
+      s->upd_host[i].object = object[i];
+    }
+  }
+  if (mode == P3D_UPDATE_REFIT && !s->lbvh_topology) {
+    // the keys, children and parents of the tree in d_blob, from the boxes it was built from: the build's own first half
+    // (deterministic: unique keys), outside the timed part - a scene pays it once
+    if (hipError_t e = lbvh::enqueue_topology(w, w.boxes); e != hipSuccess) return hip_fail("topology", e);
+    P3D_HIP(hipDeviceSynchronize());
+    s->lbvh_topology = true;
+  }
+  // from here on the scene changes
+  float4* blob = s->d_blob;
+  hipError_t e = hipEventRecord(s->ev0, 0);
+  if (e == hipSuccess && n) {
+    e = hipMemcpyAsync(s->upd_stage.p, s->upd_host.data(), (size_t)n * sizeof(lbvh::UpdateRecord), hipMemcpyHostToDevice, 0);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(lbvh::scatter_prims, dim3((n + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
+                         (const lbvh::UpdateRecord*)s->upd_stage.p, n, n_objs, blob + s->off_ogeom, blob + s->off_normals, w.boxes);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess && mode == P3D_UPDATE_REBUILD) {
+    s->lbvh_topology = false;
+    e = lbvh::enqueue_topology(w, w.boxes);
+  }
+  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom);
+  if (e == hipSuccess) e = hipEventRecord(s->ev1, 0);
+  if (e == hipSuccess) e = hipEventSynchronize(s->ev1);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  float ms = 0.0f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, s->ev0, s->ev1);
+  uint32_t depth = 0;
+  float4 root[2];
+  if (e == hipSuccess) e = hipMemcpy(&depth, w.depth, sizeof(depth), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(root, blob + s->off_nodes, sizeof(root), hipMemcpyDeviceToHost);
+  // whatever happened, the old geometry's memos are void
+  ++s->geom_gen;
+  drop_schedules(s);
+  s->ho_chain_key.clear();
+  if (e != hipSuccess) return hip_fail("update", e);
+  if (mode == P3D_UPDATE_REBUILD) {
+    s->lbvh_topology = true;
+    s->bvh_max_depth = depth;
+  }
+  s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
+  s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
+  if (update_ms) *update_ms = ms;
+  return P3D_OK;
+}
+
+int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {
+  if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: null scene");
+  if (!n_nodes || !n_prim_index) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: null size argument");
+  if (nodes && !prim_index) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: nodes without prim_index");
+  if (!s->device_bvh) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: the scene was not created by p3d_scene_create_device_bvh");
+  const uint32_t n = s->dev.n_objs;
+  if (max_depth) *max_depth = s->bvh_max_depth;
+  if (n == 0) {
+    *n_nodes = *n_prim_index = 0;
+    return P3D_OK;
+  }
+  P3D_HIP(hipSetDevice(s->device));
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  const uint32_t n_rec = 2 * n - 1;
+  std::vector<float4> rec((size_t)2 * n_rec), geom((size_t)3 * n);
+  P3D_HIP(hipMemcpy(rec.data(), s->d_blob + s->off_nodes, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  P3D_HIP(hipMemcpy(geom.data(), s->d_blob + s->off_bgeom, geom.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  // The device numbering (children of Karras node i at 1 + 2 i, 2 + 2 i) does not put children behind their parent, and a
+  // pair of leaves emitted as one leaf leaves its child records unused: relabel by a depth-first walk, left child first
+  std::vector<p3d_bvh_node> out;
+  out.reserve(n_rec);
+  out.push_back(p3d_bvh_node{});
+  std::vector<std::pair<uint32_t, uint32_t>> todo{{0u, 0u}};  // (record on the device, index in `out`)
+  while (!todo.empty()) {
+    const auto [at, id] = todo.back();
+    todo.pop_back();
+    const float4 lo = rec[2 * (size_t)at], hi = rec[2 * (size_t)at + 1];
+    uint32_t desc;
+    std::memcpy(&desc, &lo.w, 4);
+    p3d_bvh_node b{};
+    b.bmin[0] = lo.x; b.bmin[1] = lo.y; b.bmin[2] = lo.z;
+    b.bmax[0] = hi.x; b.bmax[1] = hi.y; b.bmax[2] = hi.z;
+    if (desc & kDescLeaf) {
+      b.index = desc_index(desc);
+      b.count_leaf = P3D_BVH_LEAF | desc_count(desc);
+      if ((uint64_t)b.index + desc_count(desc) > n) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: leaf range out of bounds on the device");
+    } else {
+      if ((uint64_t)desc + 1 >= n_rec || out.size() + 2 > n_rec) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: child index out of bounds on the device");
+      b.index = (uint32_t)out.size();
+      b.count_leaf = 0;
+      out.push_back(p3d_bvh_node{});
+      out.push_back(p3d_bvh_node{});
+      todo.push_back({desc + 1, b.index + 1});
+      todo.push_back({desc, b.index});  // on top: the left subtree is numbered first
+    }
+    out[id] = b;
+  }
+  const uint32_t have_nodes = *n_nodes, have_prims = *n_prim_index;
+  *n_nodes = (uint32_t)out.size();
+  *n_prim_index = n;
+  if (!nodes) return P3D_OK;
+  if (have_nodes < out.size() || have_prims < n)
+    return fail(P3D_ERR_CAPACITY, "p3d_scene_export_bvh: the arrays are too small (call with nodes = NULL for the sizes)");
+  std::memcpy(nodes, out.data(), out.size() * sizeof(p3d_bvh_node));
+  for (uint32_t i = 0; i < n; ++i) std::memcpy(&prim_index[i], &geom[3 * (size_t)i + 2].z, 4);  // geom_of: the object index
+  return P3D_OK;
+}
+
 int p3d_scene_status(p3d_scene* s) {
   if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_status: null argument");
   P3D_HIP(hipSetDevice(s->device));
@@ -1441,6 +1610,7 @@ struct p3d_accum {
   uint32_t done = 0;    // samples [0, done) of every pixel are in the sums
   bool failed = false;  // a pass returned an error: the sums are unknown until p3d_accum_reset
   uint64_t cam_gen = 0; // the scene's camera generation at create / reset
+  uint64_t geom_gen = 0; // ... and its geometry generation (p3d_scene_update_prims)
   Scratch sum, hit;     // [3 * pixel] float running sums, [pixel] first hits
 };
 
@@ -1463,6 +1633,7 @@ int p3d_accum_create(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, 
   a->tile = *tile;
   a->total = cfg->spp_sqrt * cfg->spp_sqrt;
   a->cam_gen = s->cam_gen;
+  a->geom_gen = s->geom_gen;
   const size_t n = (size_t)tile->w * tile->h;
   int rc = a->sum.ensure(n * 3 * sizeof(float));
   if (!rc) rc = a->hit.ensure(n * sizeof(int32_t));
@@ -1487,6 +1658,7 @@ int p3d_accum_reset(p3d_accum* a) {
   a->done = 0;
   a->failed = false;
   a->cam_gen = a->s->cam_gen;
+  a->geom_gen = a->s->geom_gen;
   return P3D_OK;
 }
 
@@ -1497,6 +1669,8 @@ int p3d_accum_render_device(p3d_accum* a, uint32_t n, float* d_rgb, int32_t* d_h
   if (a->failed) return fail(P3D_ERR_INVALID, "p3d_accum_render: a previous pass failed; p3d_accum_reset starts the frame again");
   if (a->cam_gen != a->s->cam_gen)
     return fail(P3D_ERR_INVALID, "p3d_accum_render: the scene's camera changed since the frame began; p3d_accum_reset starts it again in the new view");
+  if (a->geom_gen != a->s->geom_gen)
+    return fail(P3D_ERR_INVALID, "p3d_accum_render: the scene's objects moved since the frame began; p3d_accum_reset starts it again");
   if (n == 0 || n > a->total - a->done)
     return fail(P3D_ERR_INVALID, "p3d_accum_render: " + std::to_string(n) + " samples asked, " + std::to_string(a->total - a->done) +
                                      " of " + std::to_string(a->total) + " left (n must be at least 1)");
@@ -1545,6 +1719,7 @@ struct p3d_adaptive {
   uint32_t resident = 0;  // workgroups the device holds at once
   bool failed = false;
   uint64_t cam_gen = 0;   // the scene's camera generation at create / reset
+  uint64_t geom_gen = 0;  // ... and its geometry generation (p3d_scene_update_prims)
   Scratch sum, hit, sum_y2, samples, active, rel_err, list, counters;  // counters: count[2], ticket
   Scratch var;  // p3d_denoise_variance (host form): the device copy of its output
 };
@@ -1578,6 +1753,7 @@ int adapt_start(p3d_adaptive* a) {
   a->passes = 0;
   a->failed = false;
   a->cam_gen = a->s->cam_gen;
+  a->geom_gen = a->s->geom_gen;
   P3D_HIP(hipMemsetAsync(a->counters.p, 0, 4 * sizeof(uint32_t), nullptr));
   const AdaptResolveParams R = adapt_resolve_params(a, true);
   hipLaunchKernelGGL(adapt_resolve_kernel, dim3((R.slots + kAdaptResolveThreads - 1) / kAdaptResolveThreads), dim3(kAdaptResolveThreads), 0, nullptr, R);
@@ -1660,6 +1836,8 @@ int p3d_adaptive_render_device(p3d_adaptive* a, uint32_t n, float* d_rgb, int32_
   if (a->failed) return fail(P3D_ERR_INVALID, "p3d_adaptive_render: a previous pass failed; p3d_adaptive_reset starts the frame again");
   if (a->cam_gen != a->s->cam_gen)
     return fail(P3D_ERR_INVALID, "p3d_adaptive_render: the scene's camera changed since the frame began; p3d_adaptive_reset starts it again in the new view");
+  if (a->geom_gen != a->s->geom_gen)
+    return fail(P3D_ERR_INVALID, "p3d_adaptive_render: the scene's objects moved since the frame began; p3d_adaptive_reset starts it again");
   if (n == 0 || n > a->total - a->done)
     return fail(P3D_ERR_INVALID, "p3d_adaptive_render: " + std::to_string(n) + " samples asked, " + std::to_string(a->total - a->done) +
                                      " of " + std::to_string(a->total) + " left (n must be at least 1)");

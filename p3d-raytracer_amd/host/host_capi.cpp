@@ -133,6 +133,35 @@ int p3d_host_scene_set_lens(p3d_host_scene* hs, float aperture_ratio, float foca
   return P3D_OK;
 }
 
+int p3d_host_scene_set_geometry(p3d_host_scene* hs, uint32_t n, const uint32_t* object, const float* v) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_geometry: null scene");
+  if (n && (!object || !v)) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_geometry: null array with n > 0");
+  using namespace p3d;
+  const uint32_t n_objs = static_cast<uint32_t>(hs->scene.getNumObjects());
+  for (uint32_t i = 0; i < n; ++i) {  // all or nothing
+    if (object[i] >= n_objs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_geometry: object index out of range");
+    if (hs->scene.getObject(object[i])->kind() == Kind::Plane)
+      return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_geometry: object " + std::to_string(object[i]) + " is a plane (three points make one; its nine floats are not them)");
+  }
+  if (n == 0) return P3D_OK;
+  hs->bvh.reset();  // they hold pointers to the objects, and were built for the old boxes
+  hs->grid.reset();
+  hs->flat_valid = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* g = v + 9 * static_cast<size_t>(i);
+    // what the loader's `s`, `p` and `box` handlers run (Scene::load_p3f)
+    switch (hs->scene.getObject(object[i])->kind()) {
+      case Kind::Sphere: hs->scene.replaceObject(object[i], new Sphere(Vector(g[0], g[1], g[2]), g[3])); break;
+      case Kind::Triangle:
+        hs->scene.replaceObject(object[i], new Triangle(Vector(g[0], g[1], g[2]), Vector(g[3], g[4], g[5]), Vector(g[6], g[7], g[8])));
+        break;
+      case Kind::Box: hs->scene.replaceObject(object[i], new aaBox(Vector(g[0], g[1], g[2]), Vector(g[3], g[4], g[5]))); break;
+      case Kind::Plane: break;
+    }
+  }
+  return P3D_OK;
+}
+
 // main.cpp:725-745: SPP x SPP copies of every light on a LIGHT_SIDE square, colour / SPP^2
 int p3d_host_scene_replicate_lights(p3d_host_scene* hs, uint32_t spp_sqrt, float light_side) {
   if (!hs || spp_sqrt == 0) return p3d::fail(P3D_ERR_INVALID, "replicate_lights: bad argument");

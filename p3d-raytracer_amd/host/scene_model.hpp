@@ -262,6 +262,13 @@ class Scene {
   int getNumObjects() const { return static_cast<int>(objects.size()); }
   void addObject(Object* o) { o->bind(dev_, static_cast<uint32_t>(objects.size())); objects.emplace_back(o); }
   Object* getObject(unsigned i) const { return i < objects.size() ? objects[i].get() : nullptr; }
+  // A newly constructed object in the place of objects[i] (p3d_host_scene_set_geometry): material, device binding and hit ID stay.
+  // Whoever holds Object pointers (BVH, Grid) must be dropped first.
+  void replaceObject(unsigned i, Object* o) {
+    o->SetMaterial(objects[i]->GetMaterial());
+    o->bind(dev_, i);
+    objects[i].reset(o);
+  }
   int getNumLights() const { return static_cast<int>(lights.size()); }
   void addLight(Light* l) { lights.emplace_back(l); }
   Light* getLight(unsigned i) const { return i < lights.size() ? lights[i].get() : nullptr; }
