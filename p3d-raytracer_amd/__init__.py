@@ -161,15 +161,25 @@ class Stats(C.Structure):
 
 
 def build(force=False):
-    """Compile libp3d.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(HERE, "host", f) for f in os.listdir(os.path.join(HERE, "host")) if f.endswith((".cpp", ".hpp"))]
-    srcs.append(os.path.join(HERE, "..", "include", "p3d.h"))
-    stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
-    if force or stale:
-        if not os.path.exists("/opt/rocm/bin/hipcc"):
-            raise RuntimeError("libp3d.so is missing/stale and hipcc is not available to build it")
-        subprocess.check_call(["make", "-C", HERE, "libp3d.so"], stdout=subprocess.DEVNULL)
+    """Compile libp3d.so for gfx950 in-tree (hipcc cross-compiles without a GPU).  What is stale is the Makefile's
+    decision (its prerequisites are every source under csrc/ and host/): `make` does nothing when the library is up to
+    date, and without hipcc `make -q` only asks."""
+    if os.environ.get("P3D_LIB"):  # a variant library (`make variant`) is not this Makefile target: it only has to exist
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError("P3D_LIB names %s, which does not exist (build it with `make variant`)" % LIB_PATH)
+        return LIB_PATH
+    make = ["make", "-C", HERE, "libp3d.so"]
+    if os.path.exists("/opt/rocm/bin/hipcc"):
+        subprocess.check_call(make, stdout=subprocess.DEVNULL)
+        return LIB_PATH
+    stale = force or not os.path.exists(LIB_PATH)
+    if not stale:
+        try:
+            stale = subprocess.call(make + ["-q"], stdout=subprocess.DEVNULL) != 0
+        except OSError:  # no make either: nothing can say more than that the library is there
+            pass
+    if stale:
+        raise RuntimeError("libp3d.so is missing/stale and hipcc is not available to build it")
     return LIB_PATH
 
 

@@ -1,0 +1,105 @@
+// capi_query.hpp — batched single-ray and per-object queries (p3d_trace_*, p3d_object_*, p3d_skybox_color)
+#pragma once
+#include "capi_common.hpp"
+
+extern "C" {
+
+static int trace_common(p3d_scene* s, uint32_t accel, uint32_t n, const float* origin, const float* direction, int32_t* hit_id,
+                        float* t_host, float* hit_point, uint8_t* occluded, bool any) {
+  if (!s || !origin || !direction || (any ? !occluded : !hit_id)) return fail(P3D_ERR_INVALID, "p3d_trace: null argument");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (accel == P3D_ACCEL_GRID && s->dev.n_objs == 0) return fail(P3D_ERR_UNSUPPORTED, "grid over an empty scene");
+  if (n == 0) return P3D_OK;
+  P3D_HIP(hipSetDevice(s->device));
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;  // (the queries use the scene's scratch on the null stream)
+  const size_t in_bytes = (size_t)n * 6 * sizeof(float);
+  const size_t out_bytes = (size_t)n * (sizeof(int32_t) + 4 * sizeof(float) + 1) + 256;
+  if (int rc = s->q_in.ensure(in_bytes)) return rc;
+  if (int rc = s->q_out.ensure(out_bytes)) return rc;
+  float* d_o = (float*)s->q_in.p;
+  float* d_d = d_o + (size_t)n * 3;
+  int32_t* d_hit = (int32_t*)s->q_out.p;
+  float* d_hp = (float*)(d_hit + n);
+  float* d_t = d_hp + (size_t)n * 3;
+  uint8_t* d_occ = (uint8_t*)(d_t + n);
+  P3D_HIP(hipMemcpy(d_o, origin, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  P3D_HIP(hipMemcpy(d_d, direction, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
+  const uint32_t cap = 16;  // LDS window of the spilling stack (a power of two), the rest in the backing array
+  const uint32_t blocks = (n + kBlock - 1) / kBlock;
+  if ((uint64_t)(bound > cap ? bound : 0) * blocks * kBlock > 0xffffffffull)  // entries are addressed with 32-bit offsets (device_core.hpp Stack)
+    return fail(P3D_ERR_CAPACITY, "p3d_trace: too many rays for one call over a tree this deep (split the batch)");
+  if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)(bound > cap ? bound : 0) * blocks * kBlock * sizeof(uint2)))) return rc;
+  TraceParams P{};
+  P.sc = s->dev; P.n = n; P.origin = d_o; P.direction = d_d; P.hit_id = d_hit; P.hit_point = d_hp; P.occluded = d_occ;
+  P.t = t_host ? d_t : nullptr; P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
+  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
+  (void)with_accel(accel, [&](auto A) {
+    if (any) hipLaunchKernelGGL((trace_kernel<decltype(A)::value, true>), dim3(blocks), dim3(kBlock), lds, 0, P);
+    else hipLaunchKernelGGL((trace_kernel<decltype(A)::value, false>), dim3(blocks), dim3(kBlock), lds, 0, P);
+    return hipSuccess;
+  });
+  P3D_HIP(hipGetLastError());
+  P3D_HIP(hipDeviceSynchronize());
+  if (any) {
+    P3D_HIP(hipMemcpy(occluded, d_occ, n, hipMemcpyDeviceToHost));
+  } else {
+    P3D_HIP(hipMemcpy(hit_id, d_hit, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (hit_point) P3D_HIP(hipMemcpy(hit_point, d_hp, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (t_host) P3D_HIP(hipMemcpy(t_host, d_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return P3D_OK;
+}
+
+int p3d_trace_closest(p3d_scene* s, uint32_t accel, uint32_t n, const float* origin, const float* direction, int32_t* hit_id,
+                      float* t, float* hit_point) {
+  return trace_common(s, accel, n, origin, direction, hit_id, t, hit_point, nullptr, false);
+}
+int p3d_trace_any(p3d_scene* s, uint32_t accel, uint32_t n, const float* origin, const float* direction, uint8_t* occluded) {
+  return trace_common(s, accel, n, origin, direction, nullptr, nullptr, nullptr, occluded, true);
+}
+
+static int object_query(p3d_scene* s, int what, uint32_t object, uint32_t n, const float* a, float* b, uint8_t* hit, float* t) {
+  if (!s || !a || !b || (what == 0 && (!hit || !t))) return fail(P3D_ERR_INVALID, "p3d object query: null argument");
+  if (what != 2 && object >= s->dev.n_objs) return fail(P3D_ERR_INVALID, "p3d object query: no such object");
+  if (what == 2 && !s->has_sky) return fail(P3D_ERR_INVALID, "p3d_skybox_color: no cubemap was supplied (p3d_scene_set_skybox)");
+  if (n == 0) return P3D_OK;
+  P3D_HIP(hipSetDevice(s->device));
+  const size_t vec = (size_t)n * 3 * sizeof(float);
+  if (int rc = s->q_in.ensure(vec)) return rc;
+  if (int rc = s->q_out.ensure(vec + (size_t)n * (sizeof(float) + 1) + 64)) return rc;
+  float* d_a = (float*)s->q_in.p;
+  float* d_b = (float*)s->q_out.p;
+  float* d_t = d_b + (size_t)n * 3;
+  uint8_t* d_hit = (uint8_t*)(d_t + n);
+  P3D_HIP(hipMemcpy(d_a, a, vec, hipMemcpyHostToDevice));
+  if (what == 0) {
+    P3D_HIP(hipMemcpy(d_b, b, vec, hipMemcpyHostToDevice));
+    P3D_HIP(hipMemcpy(d_t, t, (size_t)n * sizeof(float), hipMemcpyHostToDevice));  // untouched where the test fails
+  }
+  ObjectQueryParams Q{};
+  Q.sc = s->dev; Q.object = object; Q.n = n; Q.a = d_a; Q.b = d_b; Q.hit = d_hit; Q.t = d_t;
+  const uint32_t blocks = (n + kBlock - 1) / kBlock;
+  if (what == 0) hipLaunchKernelGGL((object_query_kernel<0>), dim3(blocks), dim3(kBlock), 0, 0, Q);
+  else if (what == 1) hipLaunchKernelGGL((object_query_kernel<1>), dim3(blocks), dim3(kBlock), 0, 0, Q);
+  else hipLaunchKernelGGL((object_query_kernel<2>), dim3(blocks), dim3(kBlock), 0, 0, Q);
+  P3D_HIP(hipGetLastError());
+  P3D_HIP(hipDeviceSynchronize());
+  P3D_HIP(hipMemcpy(b, d_b, vec, hipMemcpyDeviceToHost));
+  if (what == 0) {
+    P3D_HIP(hipMemcpy(hit, d_hit, n, hipMemcpyDeviceToHost));
+    P3D_HIP(hipMemcpy(t, d_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return P3D_OK;
+}
+int p3d_object_intercepts(p3d_scene* s, uint32_t object, uint32_t n, const float* origin, float* direction, uint8_t* hit, float* t) {
+  return object_query(s, 0, object, n, origin, direction, hit, t);
+}
+int p3d_object_normal(p3d_scene* s, uint32_t object, uint32_t n, const float* point, float* normal) {
+  return object_query(s, 1, object, n, point, normal, nullptr, nullptr);
+}
+int p3d_skybox_color(p3d_scene* s, uint32_t n, const float* direction, float* rgb) {
+  return object_query(s, 2, 0, n, direction, rgb, nullptr, nullptr);
+}
+
+}  // extern "C"

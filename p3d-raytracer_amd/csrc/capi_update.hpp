@@ -1,0 +1,198 @@
+// capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims), and the export of a device-built tree
+#pragma once
+#include "capi_common.hpp"
+
+extern "C" {
+
+int p3d_scene_camera(p3d_scene* s, p3d_camera* out) {
+  if (!s || !out) return fail(P3D_ERR_INVALID, "p3d_scene_camera: null argument");
+  const DevCamera& c = s->dev.cam;
+  *out = p3d_camera{};
+  const F3* src[4] = {&c.eye, &c.u, &c.v, &c.n};
+  float* dst[4] = {out->eye, out->u, out->v, out->n};
+  for (int i = 0; i < 4; ++i) {
+    dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z;
+  }
+  out->plane_dist = c.plane_dist; out->w = c.w; out->h = c.h; out->focal_ratio = c.focal_ratio; out->aperture = c.aperture;
+  out->res_x = c.res_x; out->res_y = c.res_y;
+  return P3D_OK;
+}
+
+int p3d_scene_set_camera(p3d_scene* s, const p3d_camera* cam) {
+  if (!s || !cam) return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: null argument");
+  DevCamera& c = s->dev.cam;
+  if (c.res_x <= 0 || c.res_y <= 0) return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: the scene was created without a camera");
+  if (cam->res_x != c.res_x || cam->res_y != c.res_y)
+    return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: the camera is for " + std::to_string(cam->res_x) + "x" + std::to_string(cam->res_y) +
+                                     ", the scene renders " + std::to_string(c.res_x) + "x" + std::to_string(c.res_y) + " (fixed at create)");
+  if (!camera_usable(*cam)) return fail(P3D_ERR_INVALID, "p3d_scene_set_camera: every field must be finite, and w, h and plane_dist > 0");
+  P3D_HIP(hipSetDevice(s->device));
+  // The scene's scratch and memos may still be in use by enqueued work: its tail stream and the caller's streams
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  const DevCamera n = dev_camera(*cam);
+  if (std::memcmp(&n, &c, sizeof(DevCamera)) == 0) return P3D_OK;  // the same view: nothing to forget
+  c = n;
+  ++s->cam_gen;
+  // what was worked out for the primary rays of the old view: tile costs, the hit_stack hand-off's row chains and halos
+  drop_schedules(s);
+  s->ho_chain_key.clear();
+  return P3D_OK;
+}
+
+int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, const p3d_prim* prims, uint32_t mode, float* update_ms) {
+  if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null scene");
+  if (n && (!object || !prims)) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null array with n > 0");
+  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: unknown mode");
+  if (!s->device_bvh)
+    return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
+  if (s->has_grid) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene carries a grid, which would go stale");
+  const uint32_t n_objs = s->dev.n_objs;
+  if (n > n_objs) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: more records than objects (an index is repeated)");
+  {
+    std::vector<uint8_t> seen(n_objs, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+      const p3d_prim& p = prims[i];
+      if (object[i] >= n_objs) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object index out of range");
+      if (seen[object[i]]) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " appears twice");
+      seen[object[i]] = 1;
+      if (p.type > 0xffu || p.material > 0xffffffu || (p.type | (p.material << 8)) != s->obj_tm[object[i]])
+        return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " changes its type or material");
+      for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p.bmin[k]) || !std::isfinite(p.bmax[k]) || !(p.bmin[k] <= p.bmax[k]))
+          return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " has a non-finite or inverted box");
+    }
+  }
+  if (update_ms) *update_ms = 0.0f;
+  if (n_objs == 0) return P3D_OK;
+  P3D_HIP(hipSetDevice(s->device));
+  // enqueued frames read the geometry, the tree and the scene's memos: the tail stream, then the whole device
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  auto hip_fail = [](const char* what, hipError_t e) { return fail(P3D_ERR_NO_DEVICE, std::string("p3d_scene_update_prims: ") + what + ": " + hipGetErrorString(e)); };
+  lbvh::Workspace& w = s->lbvh_ws;
+  if (!w.n) {  // first update: the builder's state, with the boxes the tree in d_blob was built from
+    hipError_t e = w.alloc(n_objs, true);
+    if (e == hipSuccess) e = hipMemcpy(w.boxes, s->create_boxes.data(), s->create_boxes.size() * sizeof(float4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      w.release();
+      return hip_fail("workspace", e);
+    }
+    std::vector<float4>().swap(s->create_boxes);
+    s->lbvh_topology = false;
+  }
+  if (n) {
+    if (int rc = s->upd_stage.ensure((size_t)n * sizeof(lbvh::UpdateRecord))) return rc;
+    s->upd_host.assign(n, lbvh::UpdateRecord{});
+    for (uint32_t i = 0; i < n; ++i) {
+      s->upd_host[i].prim = prims[i];
+      s->upd_host[i].object = object[i];
+    }
+  }
+  if (mode == P3D_UPDATE_REFIT && !s->lbvh_topology) {
+    // the keys, children and parents of the tree in d_blob, from the boxes it was built from: the build's own first half
+    // (deterministic: unique keys), outside the timed part - a scene pays it once
+    if (hipError_t e = lbvh::enqueue_topology(w, w.boxes); e != hipSuccess) return hip_fail("topology", e);
+    P3D_HIP(hipDeviceSynchronize());
+    s->lbvh_topology = true;
+  }
+  // from here on the scene changes
+  float4* blob = s->d_blob;
+  hipError_t e = hipEventRecord(s->ev0, 0);
+  if (e == hipSuccess && n) {
+    e = hipMemcpyAsync(s->upd_stage.p, s->upd_host.data(), (size_t)n * sizeof(lbvh::UpdateRecord), hipMemcpyHostToDevice, 0);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(lbvh::scatter_prims, dim3((n + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
+                         (const lbvh::UpdateRecord*)s->upd_stage.p, n, n_objs, blob + s->off_ogeom, blob + s->off_normals, w.boxes);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess && mode == P3D_UPDATE_REBUILD) {
+    s->lbvh_topology = false;
+    e = lbvh::enqueue_topology(w, w.boxes);
+  }
+  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom);
+  if (e == hipSuccess) e = hipEventRecord(s->ev1, 0);
+  if (e == hipSuccess) e = hipEventSynchronize(s->ev1);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  float ms = 0.0f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, s->ev0, s->ev1);
+  uint32_t depth = 0;
+  float4 root[2];
+  if (e == hipSuccess) e = hipMemcpy(&depth, w.depth, sizeof(depth), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(root, blob + s->off_nodes, sizeof(root), hipMemcpyDeviceToHost);
+  // whatever happened, the old geometry's memos are void
+  ++s->geom_gen;
+  drop_schedules(s);
+  s->ho_chain_key.clear();
+  if (e != hipSuccess) return hip_fail("update", e);
+  if (mode == P3D_UPDATE_REBUILD) {
+    s->lbvh_topology = true;
+    s->bvh_max_depth = depth;
+  }
+  s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
+  s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
+  if (update_ms) *update_ms = ms;
+  return P3D_OK;
+}
+
+int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {
+  if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: null scene");
+  if (!n_nodes || !n_prim_index) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: null size argument");
+  if (nodes && !prim_index) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: nodes without prim_index");
+  if (!s->device_bvh) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: the scene was not created by p3d_scene_create_device_bvh");
+  const uint32_t n = s->dev.n_objs;
+  if (max_depth) *max_depth = s->bvh_max_depth;
+  if (n == 0) {
+    *n_nodes = *n_prim_index = 0;
+    return P3D_OK;
+  }
+  P3D_HIP(hipSetDevice(s->device));
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  const uint32_t n_rec = 2 * n - 1;
+  std::vector<float4> rec((size_t)2 * n_rec), geom((size_t)3 * n);
+  P3D_HIP(hipMemcpy(rec.data(), s->d_blob + s->off_nodes, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  P3D_HIP(hipMemcpy(geom.data(), s->d_blob + s->off_bgeom, geom.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  // The device numbering (children of Karras node i at 1 + 2 i, 2 + 2 i) does not put children behind their parent, and a
+  // pair of leaves emitted as one leaf leaves its child records unused: relabel by a depth-first walk, left child first
+  std::vector<p3d_bvh_node> out;
+  out.reserve(n_rec);
+  out.push_back(p3d_bvh_node{});
+  std::vector<std::pair<uint32_t, uint32_t>> todo{{0u, 0u}};  // (record on the device, index in `out`)
+  while (!todo.empty()) {
+    const auto [at, id] = todo.back();
+    todo.pop_back();
+    const float4 lo = rec[2 * (size_t)at], hi = rec[2 * (size_t)at + 1];
+    uint32_t desc;
+    std::memcpy(&desc, &lo.w, 4);
+    p3d_bvh_node b{};
+    b.bmin[0] = lo.x; b.bmin[1] = lo.y; b.bmin[2] = lo.z;
+    b.bmax[0] = hi.x; b.bmax[1] = hi.y; b.bmax[2] = hi.z;
+    if (desc & kDescLeaf) {
+      b.index = desc_index(desc);
+      b.count_leaf = P3D_BVH_LEAF | desc_count(desc);
+      if ((uint64_t)b.index + desc_count(desc) > n) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: leaf range out of bounds on the device");
+    } else {
+      if ((uint64_t)desc + 1 >= n_rec || out.size() + 2 > n_rec) return fail(P3D_ERR_INVALID, "p3d_scene_export_bvh: child index out of bounds on the device");
+      b.index = (uint32_t)out.size();
+      b.count_leaf = 0;
+      out.push_back(p3d_bvh_node{});
+      out.push_back(p3d_bvh_node{});
+      todo.push_back({desc + 1, b.index + 1});
+      todo.push_back({desc, b.index});  // on top: the left subtree is numbered first
+    }
+    out[id] = b;
+  }
+  const uint32_t have_nodes = *n_nodes, have_prims = *n_prim_index;
+  *n_nodes = (uint32_t)out.size();
+  *n_prim_index = n;
+  if (!nodes) return P3D_OK;
+  if (have_nodes < out.size() || have_prims < n)
+    return fail(P3D_ERR_CAPACITY, "p3d_scene_export_bvh: the arrays are too small (call with nodes = NULL for the sizes)");
+  std::memcpy(nodes, out.data(), out.size() * sizeof(p3d_bvh_node));
+  for (uint32_t i = 0; i < n; ++i) std::memcpy(&prim_index[i], &geom[3 * (size_t)i + 2].z, 4);  // geom_of: the object index
+  return P3D_OK;
+}
+
+}  // extern "C"

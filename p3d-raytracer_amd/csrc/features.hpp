@@ -3,8 +3,8 @@
 // One lane per pixel, one wave per 8x8 tile (the tile map of the render kernels, tile_of_block).  Every lane traces the
 // primary rays of samples [0, K) of its pixel - the rays the integrators trace: the same RNG stream per (pixel, sample),
 // make_primary, and the closest-hit traversal of the configured accel on an empty stack - and averages what the samples
-// that hit something saw.  Scene staging, stack mode and LDS size are the ones render_impl picks for the frame
-// (p3d_capi.hip); the kernel has no shading, so it is short and its registers do not limit occupancy.
+// that hit something saw.  Scene staging, stack mode and LDS size are the ones plan_frame picks for the frame
+// (capi_frame_plan.hpp); the kernel has no shading, so it is short and its registers do not limit occupancy.
 #pragma once
 
 #include "kernels.hpp"

@@ -94,7 +94,7 @@
                     const float kd = (0.0f > nl) ? 0.0f : nl;
                     const float kb = (0.0f > bn) ? 0.0f : bn;
                     // (a material whose specular term is multiplied by Ks == 0 in main.cpp:232 and cannot be anything but a finite
-                    // non-negative number - flagged at upload, p3d_capi.hip - does not need its value: for 0 <= kb <= 1 the power is in
+                    // non-negative number - flagged at upload, capi_scene_layout.hpp - does not need its value: for 0 <= kb <= 1 the power is in
                     // [0, 1], the product a finite number >= +0, and leaving it out of a sum of such numbers changes no bit of
                     // diff * Kd + spec * 0.  A NaN cosine fails kb <= 1 and takes the full path.)
                     const bool dead_spec = dead_spec_mat && kb <= 1.0f;

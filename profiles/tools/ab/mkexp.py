@@ -29,9 +29,9 @@ for e in edits:
             'return !(ax < INFINITY) || !(ay < INFINITY) || !(az < INFINITY);')
         sub('device_core.hpp', '(!sc.odd_boxes && !__any(ray.odd_inv))', '(!__any(ray.odd_inv))', 0)
     elif e == 'nopad':
-        sub('p3d_capi.hip', '''  blob.push_back(make_float4(0, 0, 0, 0));
+        sub('capi_scene_layout.hpp', '''  blob.push_back(make_float4(0, 0, 0, 0));
   blob.push_back(make_float4(0, 0, 0, 0));
-  s->off_nodes''', '  s->off_nodes')
+  L.off_nodes''', '  L.off_nodes')
     elif e == 'oddinv':
         sub('device_core.hpp', 'return !(ax < INFINITY && ax >= 0.75f) || !(ay < INFINITY && ay >= 0.75f) || !(az < INFINITY && az >= 0.75f);',
             'return !(ax < INFINITY) || !(ay < INFINITY) || !(az < INFINITY);')
@@ -47,9 +47,9 @@ for e in edits:
 ''')
         sub('device_core.hpp', 'return cap * kBlock * (spill ? 8u : 6u) / 16u;', 'return cap * kBlock * 8u / 16u;')
     elif e == 'pad8k':
-        sub('p3d_capi.hip', '(sub4 ? sizeof(PtPixelShared) : 0) + (cold_lds ? (size_t)kColdDwords * kBlock * sizeof(float) : 0);', '(sub4 ? sizeof(PtPixelShared) : 0) + (cold_lds ? (size_t)kColdDwords * kBlock * sizeof(float) : 0) + (lds_scene ? 576 : 0);')
+        sub('capi_frame_plan.hpp', '(sub4 ? sizeof(PtPixelShared) : 0) + (cold_lds ? (size_t)kColdDwords * kBlock * sizeof(float) : 0);', '(sub4 ? sizeof(PtPixelShared) : 0) + (cold_lds ? (size_t)kColdDwords * kBlock * sizeof(float) : 0) + (lds_scene ? 576 : 0);')
     elif e.startswith('wide'):
-        sub('p3d_capi.hip', 'std::max<uint32_t>(64, H.n_units / kBlock)));', 'std::max<uint32_t>(64, std::min<uint32_t>(H.n_units / kBlock, %su))));' % e[4:])
+        sub('capi_frame.hpp', 'std::max<uint32_t>(64, H.n_units / kBlock)));', 'std::max<uint32_t>(64, std::min<uint32_t>(H.n_units / kBlock, %su))));' % e[4:])
     elif e.startswith('nv'):
         sub('kernels.hpp', '__global__ void __launch_bounds__(kBlock, LIT == 2 ? P3D_LIST_WAVES : ((LDS || AA) ? P3D_WHITTED_WAVES : P3D_WHITTED_GLOBAL_WAVES)) whitted_kernel(',
             '__global__ void __launch_bounds__(kBlock, LIT == 2 ? P3D_LIST_WAVES : ((LDS || AA) ? P3D_WHITTED_WAVES : P3D_WHITTED_GLOBAL_WAVES)) __attribute__((amdgpu_num_vgpr((LDS && LIT == 1 && !AA && !STATS) ? %s : 0))) whitted_kernel(' % e[2:])
@@ -61,14 +61,14 @@ for e in edits:
     elif e == 'ptnofast':
         sub('pt_kernel.hpp', 'closest_hit<ACCEL, PT_STACK, !LDS, true>', 'closest_hit<ACCEL, PT_STACK, !LDS, !LDS>', 0)
     elif e == 'pt6':
-        sub('pt_kernel.hpp', 'constexpr int PT_STACK = LDS ? kStackLds8 : kStackWindow;', 'constexpr int PT_STACK = LDS ? kStackLds6 : kStackWindow;')
-        sub('p3d_capi.hip', '(pt ? kStackLds8 : kStackLds6)', 'kStackLds6')
+        sub('pt_body.inc', 'constexpr int PT_STACK = LDS ? kStackLds8 : kStackWindow;', 'constexpr int PT_STACK = LDS ? kStackLds6 : kStackWindow;')
+        sub('capi_frame_plan.hpp', '(pt ? kStackLds8 : kStackLds6)', 'kStackLds6')
     elif e == 'ldirlit':
         sub('whitted_level.inc', 'if (COLD) {  // the light direction', 'if (COLD || (LIT == 1)) {  // the light direction')
     elif e == 'ldirall':
         sub('whitted_level.inc', 'if (COLD) {  // the light direction', 'if (true) {  // the light direction')
     elif e == 'cap12':
-        sub('p3d_capi.hip', 'const uint32_t cap = cfg->accel == P3D_ACCEL_BVH ? (spilling ? window : bound) : 1;', 'const uint32_t cap = cfg->accel == P3D_ACCEL_BVH ? (spilling ? window : std::min<uint32_t>(bound, 12)) : 1;')
+        sub('capi_frame_plan.hpp', 'const uint32_t cap = cfg->accel == P3D_ACCEL_BVH ? (spilling ? window : bound) : 1;', 'const uint32_t cap = cfg->accel == P3D_ACCEL_BVH ? (spilling ? window : std::min<uint32_t>(bound, 12)) : 1;')
     else:
         raise SystemExit('unknown edit ' + e)
 print(dst)

@@ -826,7 +826,7 @@ def test_planes_boxes_and_glass(accel):
 
 
 @pytest.mark.parametrize("matte,lights", [
-    ("0.8 0.7 0.2 0.9  0.3 0.6 0.9 0 40", "0.9 0.8 0.7"),      # Ks = 0: the kernels leave the Blinn power out (p3d_capi.hip material flag)
+    ("0.8 0.7 0.2 0.9  0.3 0.6 0.9 0 40", "0.9 0.8 0.7"),      # Ks = 0: the kernels leave the Blinn power out (capi_scene_layout.hpp material flag)
     ("0.8 0.7 0.2 0.9  0.3 0.6 0.9 0 1e30", "0.9 0.8 0.7"),    # ... also for a shine that drives every power below 1 to zero
     ("0.8 0.7 0.2 0.9  0.3 0.6 0.9 0 0", "0.9 0.8 0.7"),       # ... and for shine 0 (pow(x, 0) = 1, pow(0, 0) = 1)
     ("0.8 0.7 0.2 0.9  0.3 0.6 0.9 -0.0 40", "0.9 0.8 0.7"),   # Ks = -0 compares equal to 0: flagged as well, the products' signs must survive
