@@ -78,14 +78,7 @@ __global__ void __launch_bounds__(kAdaptResolveThreads) adapt_resolve_kernel(con
       R.rgb[3 * p] = color.x; R.rgb[3 * p + 1] = color.y; R.rgb[3 * p + 2] = color.z;
     }
     if (R.hit_id) R.hit_id[p] = R.hit[p];
-    if (R.rgb8) {
-      F3 gc = color;
-      if (R.gamma != 1.0f) {
-        const double ig = (double)(1 / R.gamma);
-        gc = f3((float)pow_spec((double)color.x, ig), (float)pow_spec((double)color.y, ig), (float)pow_spec((double)color.z, ig));
-      }
-      R.rgb8[3 * p] = u8fromfloat(gc.x); R.rgb8[3 * p + 1] = u8fromfloat(gc.y); R.rgb8[3 * p + 2] = u8fromfloat(gc.z);
-    }
+    if (R.rgb8) store_rgb8(R.rgb8 + 3 * p, color, R.gamma);
     if (R.samples_out) R.samples_out[p] = sp;
   }
   // wave-ballot compaction: one atomic per wave, the wave's pixels in slot order

@@ -17,6 +17,8 @@
 #include "lbvh.hpp"
 #include "p3d.h"
 #include "p3d_debug.h"
+#include "wavefront.hpp"
+#include "queries.hpp"
 #include "pt_kernel.hpp"
 #include "adaptive.hpp"
 #include "features.hpp"

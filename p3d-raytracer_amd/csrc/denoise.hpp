@@ -117,14 +117,7 @@ __global__ void __launch_bounds__(kAtrousThreads) atrous_kernel(const AtrousPara
   if (A.rgb_out) {
     A.rgb_out[3 * p] = res.x; A.rgb_out[3 * p + 1] = res.y; A.rgb_out[3 * p + 2] = res.z;
   }
-  if (A.rgb8_out) {  // the render kernels' epilogue (pt_body.inc): gamma, then u8fromfloat
-    F3 gc = f3(res.x, res.y, res.z);
-    if (A.gamma != 1.0f) {
-      const double ig = (double)(1 / A.gamma);
-      gc = f3((float)pow_spec((double)res.x, ig), (float)pow_spec((double)res.y, ig), (float)pow_spec((double)res.z, ig));
-    }
-    A.rgb8_out[3 * p] = u8fromfloat(gc.x); A.rgb8_out[3 * p + 1] = u8fromfloat(gc.y); A.rgb8_out[3 * p + 2] = u8fromfloat(gc.z);
-  }
+  if (A.rgb8_out) store_rgb8(A.rgb8_out + 3 * p, f3(res.x, res.y, res.z), A.gamma);  // the render kernels' epilogue
 }
 
 // Variance of every pixel's mean luminance for p3d_denoise_variance: include/p3d.h "Error metric", float32 in that order.

@@ -1025,5 +1025,13 @@ __device__ __forceinline__ uint8_t u8fromfloat(float x) {  // maths.h:81-86
   const float s = x * 255.99f;
   return s >= 255.0f ? (uint8_t)255 : (uint8_t)s;
 }
+// main.cpp:814-820, the end of every frame writer: colour -> gamma -> the three bytes of a pixel
+__device__ __forceinline__ void store_rgb8(uint8_t* out, F3 c, float gamma) {
+  if (gamma != 1.0f) {
+    const double ig = (double)(1 / gamma);
+    c = f3((float)pow_spec((double)c.x, ig), (float)pow_spec((double)c.y, ig), (float)pow_spec((double)c.z, ig));
+  }
+  out[0] = u8fromfloat(c.x); out[1] = u8fromfloat(c.y); out[2] = u8fromfloat(c.z);
+}
 
 }  // namespace p3d

@@ -1,11 +1,10 @@
-// kernels.hpp — the HIP kernels of the hot path (gfx950).
+// kernels.hpp — what every render kernel shares (launch parameters, scene staging, tile schedule, pixel samples, the
+// four-lanes-per-pixel ring) and the Whitted megakernel (gfx950).
 //
 //   whitted_kernel : primary ray -> closest hit -> Blinn-Phong with shadow feelers ->
 //                    reflect / refract chain with per-level clamp      (main.cpp:92-309 + 753-820)
-//   pt_kernel      : the smallpt-style Radiance loop as a persistent per-lane bounce loop
-//                    (main.cpp:313-516 + 758-800)
-//   trace_kernel   : batched closest / any-hit queries (bvh.cpp:198-340, grid.cpp:71-208,
-//                    main.cpp:116-124,208-216)
+//   elsewhere      : pt_kernel.hpp (path tracer), handoff_kernels.hpp (hit_stack hand-off), wavefront.hpp (one launch
+//                    per chain level), queries.hpp (batched queries)
 //
 // One workgroup = one wavefront = an 8x8 pixel block.  See device_core.hpp for the
 // traversal conventions and DESIGN.md for the kernel-by-kernel roofline discussion.
@@ -15,25 +14,17 @@
 #include "handoff.hpp"
 #include "p3d.h"
 
-// minimum waves per SIMD the register allocator must leave room for (2nd __launch_bounds__ arg)
+// Minimum waves per SIMD the register allocator must leave room for (2nd __launch_bounds__ argument): whitted_waves() below
+// says which instantiation gets which.
 #ifndef P3D_WHITTED_WAVES
 #define P3D_WHITTED_WAVES 2
 #endif
-// Same for the no-AA instantiations that traverse the scene from L2: they wait on memory, not on the VALU, and
-// trade registers for waves.  100k triangles 1024x1024 / 2048x2048 with 16 / 12 / 12 / 10 / 8 LDS stack entries:
-// 4 waves (111 VGPRs) 8.44 / 22.9 ms, 5 (96) 7.69 / 20.7, 6 (80 VGPRs, 46 spilled dwords) 7.26 / 19.4,
-// 7 (72) 7.40 / 18.7, 8 (64) 7.37 / 18.7.
-// The work-list launches of the hit_stack hand-off (LIT == 2) are short lists of unrelated deep pixels: every wave waits
-// on its own dependent chain, so what counts is how many waves are resident at once, not registers per wave.
 #ifndef P3D_LIST_WAVES
 #define P3D_LIST_WAVES 4
 #endif
 #ifndef P3D_WHITTED_GLOBAL_WAVES
 #define P3D_WHITTED_GLOBAL_WAVES 6
 #endif
-// One-sample-per-pixel instantiations over an LDS-staged scene: 96 VGPRs = five waves per SIMD.  The per-pixel kernel needs
-// exactly that; the literal pass 1 needs 99 without the zero-weight-reflection machinery (GHOSTS = false) and is held to 96
-// without a spilled dword (with it: 107, and holding it to 96 spills 12 dwords - profiles/r03/experiments §13).
 #ifndef P3D_WHITTED_LDS_WAVES
 #define P3D_WHITTED_LDS_WAVES 5
 #endif
@@ -337,116 +328,25 @@ struct PtPixelShared {       // [..][pixel]: the 16 pixels of the tile are the f
 };
 
 typedef __attribute__((address_space(3))) volatile PtPixelShared LdsPtPixelShared;
-
-// Where a unit of the hand-off (handoff.hpp) lies in the image: tile pixels and, in front of every row, the halo slots.
-struct UnitPlace {
-  int c, r, x, y;  // tile column / tile row (output index), image pixel
-  bool halo;       // a frame pixel rendered only for what it leaves on the stack: no output
-  bool valid;
-};
-__device__ __forceinline__ int image_row(const RenderParams& P, int r) {
-  const int sh = P.stripe_h > 0 ? P.stripe_h : 1, ss = P.stripe_h > 0 ? P.stripe_stride : 1;
-  return P.y0 + (r / sh) * sh * ss + (r % sh);
+__device__ __forceinline__ void ring_init(LdsPtPixelShared& shared, uint32_t px, uint32_t sample_begin) {
+  shared.next_start[px] = sample_begin;
+  shared.next_add[px] = sample_begin;
+  shared.first_hit[px] = -1;
+  shared.colour[0][px] = 0.0f; shared.colour[1][px] = 0.0f; shared.colour[2][px] = 0.0f;
+  for (int k = 0; k < kPtRing; ++k) shared.tag[k][px] = 0;
 }
-__device__ __forceinline__ UnitPlace place_of_unit(const RenderParams& P, uint32_t unit) {
-  const Handoff& H = P.hand;
-  UnitPlace u;
-  const uint32_t row = unit / H.row_units, j = unit - row * H.row_units;
-  u.r = (int)row - P.row0;
-  u.halo = j < H.halo;
-  u.valid = true;
-  if (u.halo) {
-    const uint32_t fp = H.halo_pix[row * H.halo + j];
-    u.valid = fp != kNoUnit;
-    u.c = 0;
-    u.x = (int)(fp % (uint32_t)P.sc.cam.res_x);
-    u.y = (int)(fp / (uint32_t)P.sc.cam.res_x);
-  } else {
-    u.c = (int)(j - H.halo);
-    u.x = P.x0 + u.c;
-    u.y = image_row(P, u.r);
-  }
-  return u;
-}
-// pass 1 / check: the unit of a lane of a halo workgroup (8 chains of kHaloChain slots per wave)
-__device__ __forceinline__ bool halo_unit_of_lane(const RenderParams& P, uint32_t lane, uint32_t& unit) {
-  const Handoff& H = P.hand;
-  const uint32_t slot = (blockIdx.x - P.tile_blocks) * kBlock + lane;
-  const uint32_t row = slot / kHaloChain, j = slot % kHaloChain;
-  if (H.halo == 0 || row >= H.rows || !H.row_chain[row]) return false;
-  unit = row * H.row_units + j;
-  return H.halo_pix[row * H.halo + j] != kNoUnit;
+// post finished sample s; its ring slot is free (guaranteed when the sample was handed out)
+__device__ __forceinline__ void ring_post(LdsPtPixelShared& shared, uint32_t px, int s, F3 radiance) {
+  const int k = s % kPtRing;
+  shared.radiance[k][0][px] = radiance.x; shared.radiance[k][1][px] = radiance.y; shared.radiance[k][2][px] = radiance.z;
+  shared.tag[k][px] = (uint32_t)s + 1;
 }
 
-template <bool SPILL, class CT>
-__device__ __forceinline__ void seed_stack(Stack& st, const Handoff& H, uint32_t pred, uint32_t slot_count, CT& ct) {
-  stack_clear(st);
-  const uint32_t n = slot_count & 0xffffu, slot = slot_count >> 16;
-  const uint32_t at = n ? leftover_at(H, slot, pred) : 0u;
-  for (uint32_t e = 0; e < n; ++e) {
-    const uint2 v = H.entries[at + e];
-    push<SPILL>(st, v.x, __uint_as_float(v.y), ct);
-  }
-}
-// collect_stats under P3D_STACK_LITERAL (handoff.hpp: ucount / uch0).  The deepest stack goes straight to the global
-// maximum: it is taken over everything that was traced, speculative passes included.
-template <bool STATS>
-__device__ __forceinline__ void store_unit_counters(const Handoff& H, uint32_t unit, const Counters<STATS>& ct, const uint32_t* ch0,
-                                                    unsigned long long* stats) {
-  if (!STATS) return;
-  for (int s = 0; s < kNumStats; ++s)
-    if (s != kMaxStack) H.ucount[(size_t)s * H.n_units + unit] = ct.get(s);
-  for (int k = 0; k < kCh0Counters; ++k) H.uch0[(size_t)k * H.n_units + unit] = ch0[k];
-  atomicMax(&stats[kMaxStack], (unsigned long long)ct.get(kMaxStack));
-}
-// a unit whose first closest hit was re-traced on a new leftover and came out the same: only that query's tests change
-template <bool STATS>
-__device__ __forceinline__ void replace_ch0_counters(const Handoff& H, uint32_t unit, const Counters<STATS>& cc, unsigned long long* stats) {
-  if (!STATS) return;
-  for (int k = 0; k < kCh0Counters; ++k) {
-    const size_t at = (size_t)k * H.n_units + unit;
-    const uint32_t now = cc.get(kNodeTests + k);
-    H.ucount[(size_t)(kNodeTests + k) * H.n_units + unit] += now - H.uch0[at];
-    H.uch0[at] = now;
-  }
-  atomicMax(&stats[kMaxStack], (unsigned long long)cc.get(kMaxStack));
-}
-// sum of the unit counters over the pixels of the tile (halo units are not pixels of the tile)
-__global__ void __launch_bounds__(256) ucount_reduce_kernel(const Handoff H, uint32_t w, unsigned long long* stats) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  const uint32_t n_pix = w * H.rows;
-  for (int s = 0; s < kNumStats; ++s) {
-    if (s == kMaxStack) continue;
-    unsigned long long v = 0;
-    for (uint32_t p = i; p < n_pix; p += gridDim.x * 256) {
-      const uint32_t unit = (p / w) * H.row_units + H.halo + (p % w);
-      v += H.ucount[(size_t)s * H.n_units + unit];
-    }
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&stats[s], v);
-  }
-}
+}  // namespace p3d
 
-__device__ __forceinline__ bool same_first(float4 a, float4 b) {
-  return __float_as_uint(a.x) == __float_as_uint(b.x) && __float_as_uint(a.y) == __float_as_uint(b.y) &&
-         __float_as_uint(a.z) == __float_as_uint(b.z) && __float_as_uint(a.w) == __float_as_uint(b.w);
-}
-// The first closest hit of a unit's first touching sample, traced on whatever the stack holds (bvh.cpp:198-276).
-template <bool SPILL, bool VOTE, class CT>
-__device__ __forceinline__ float4 first_closest_hit(const RenderParams& P, const DevScene& sc, Stack& st, int x, int y, uint32_t sample, CT& ct) {
-  Rng rng;
-  rng.state = 0; rng.inc = 1;
-  const int SPP = P.antialiasing ? (int)P.spp_sqrt : 1;
-  const int si = (int)sample / SPP, sj = (int)sample % SPP;
-  if (P.antialiasing) rng.seed_stream(P.seed, (uint32_t)(y * sc.cam.res_x + x), sample);
-  F3 o, d, Pn;
-  make_primary(P, sc.cam, x, y, si, sj, rng, o, d);
-  RayS ray;
-  ray_set(ray, o, d);
-  Geom g;
-  const int obj = closest_hit<P3D_ACCEL_BVH, SPILL, VOTE>(sc, st, ray, Pn, g, ct);
-  return obj < 0 ? make_float4(0.f, 0.f, 0.f, __int_as_float(-1)) : make_float4(Pn.x, Pn.y, Pn.z, __int_as_float(obj));
-}
+#include "handoff_kernels.hpp"  // uses the above; whitted_kernel uses its steps
+
+namespace p3d {
 
 // ---------------------------------------------------------------------------
 // Whitted megakernel
@@ -469,8 +369,22 @@ __device__ __forceinline__ float4 first_closest_hit(const RenderParams& P, const
 // GHOSTS: the scene has a material that is transmissive AND reflective, i.e. LITERAL frames trace zero-weight reflection rays
 // (whitted_sample.inc); without one the machinery is compiled out (pass 1 over the bench scene: 107 -> 96 VGPRs, five waves
 // per SIMD like the per-pixel kernel).
+constexpr int whitted_waves(bool AA, bool LDS, int LIT, bool GHOSTS) {
+  // The work-list launches of the hit_stack hand-off (LIT == 2) are short lists of unrelated deep pixels: every wave waits on
+  // its own dependent chain, so what counts is how many waves are resident at once, not registers per wave.
+  if (LIT >= 2) return P3D_LIST_WAVES;
+  if (AA) return P3D_WHITTED_WAVES;
+  // The no-AA instantiations that traverse the scene from L2 wait on memory, not on the VALU, and trade registers for waves.
+  // 100k triangles 1024x1024 / 2048x2048 with 16 / 12 / 12 / 10 / 8 LDS stack entries: 4 waves (111 VGPRs) 8.44 / 22.9 ms,
+  // 5 (96) 7.69 / 20.7, 6 (80 VGPRs, 46 spilled dwords) 7.26 / 19.4, 7 (72) 7.40 / 18.7, 8 (64) 7.37 / 18.7.
+  if (!LDS) return P3D_WHITTED_GLOBAL_WAVES;
+  // One sample per pixel over an LDS-staged scene: 96 VGPRs = five waves per SIMD.  The per-pixel kernel needs exactly that; the
+  // literal pass 1 needs 99 without the zero-weight-reflection machinery (GHOSTS = false) and is held to 96 without a spilled
+  // dword (with it: 107, and holding it to 96 spills 12 dwords - profiles/r03/experiments §13).
+  return (LIT == 1 && GHOSTS) ? P3D_WHITTED_WAVES : P3D_WHITTED_LDS_WAVES;
+}
 template <int ACCEL, bool LDS, bool STATS, bool AA, bool SPILL = !LDS, int SUB = 1, int LIT = 0, bool GHOSTS = true>
-__global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_WHITTED_WAVES : (LDS ? ((LIT == 1 && GHOSTS) ? P3D_WHITTED_WAVES : P3D_WHITTED_LDS_WAVES) : P3D_WHITTED_GLOBAL_WAVES))) whitted_kernel(const RenderParams P) {
+__global__ void __launch_bounds__(kBlock, whitted_waves(AA, LDS, LIT, GHOSTS)) whitted_kernel(const RenderParams P) {
   static_assert(SUB == 1 || AA, "four lanes per pixel need more than one sample per pixel");
   static_assert(LIT == 0 || (ACCEL == P3D_ACCEL_BVH && SUB == 1), "only the BVH has a stack to hand on; one lane per pixel");
   constexpr bool REDO = LIT >= 2;               // launches that render units again, seeded with their predecessor's leftover
@@ -479,11 +393,8 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
   uint32_t tx = 0, ty = 0;
   const bool halo_block = (LIT == 1 || LIT == 3) && blockIdx.x >= P.tile_blocks;
   if (LIT != 2 && !halo_block && !tile_of_block(P, tx, ty)) return;
-  if (LIT == 2) {  // nothing on the list for this workgroup: leave before the scene is staged
-    uint32_t n0 = __hip_atomic_load(P.hand.n_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    n0 = n0 > P.hand.list_cap ? P.hand.list_cap : n0;
-    if ((size_t)blockIdx.x * P.hand.lanes >= n0) return;
-  }
+  // LIT == 2: nothing on the list for this workgroup: leave before the scene is staged
+  if (LIT == 2 && (size_t)blockIdx.x * P.hand.lanes >= list_count(P.hand.n_in, P.hand.list_cap)) return;
   const uint32_t lane = threadIdx.x;
   const uint32_t tws = SUB == 4 ? 2u : P.tile_w_shift, ths = SUB == 4 ? 2u : P.tile_h_shift;  // tile = (1 << tws) x (1 << ths) pixels
   // LIT == 3: which lanes have anything to re-trace is known before the scene is staged, and most waves leave here.  The
@@ -492,19 +403,11 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
   uint32_t t_unit = 0, t_pred = 0, t_slot_count = 0;
   bool t_need = false;
   if (LIT == 3) {
-    const Handoff& H0 = P.hand;
-    bool act;
-    if (halo_block) {
-      act = halo_unit_of_lane(P, lane, t_unit);
-    } else {
-      const int c = (int)((tx << tws) + (lane & ((1u << tws) - 1u))), r = (int)((ty << ths) + (lane >> tws));
-      act = lane < (1u << (tws + ths)) && c < P.w && r < P.h;
-      t_unit = (uint32_t)(P.row0 + r) * H0.row_units + H0.halo + (uint32_t)c;
-    }
-    if (act && handoff_touched(H0, t_unit)) {
-      const int pred = handoff_pred(H0, t_unit);
+    const bool act = unit_of_lane(P, halo_block, tx, ty, tws, ths, lane, t_unit);
+    if (act && handoff_touched(P.hand, t_unit)) {  // (twin: handoff_check_kernel, which reads meta)
+      const int pred = handoff_pred(P.hand, t_unit);
       if (pred >= 0) {
-        const uint32_t pm = H0.meta0[pred];
+        const uint32_t pm = P.hand.meta0[pred];
         t_need = (pm & 0xffffu) != 0;  // otherwise the predecessor left nothing: pass 1's empty stack was right
         t_pred = (uint32_t)pred;
         t_slot_count = pm & 0x1ffffu;
@@ -531,13 +434,7 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
   cold.bind(smem, P.lds_scene_f4 + stack_lds_f4(SPILL, P.stack_cap), lane);
   // per-pixel sample hand-out state behind the node stack (only allocated for SUB == 4); explicit LDS address space
   LdsPtPixelShared& shared = *(LdsPtPixelShared*)(smem + P.lds_scene_f4 + stack_lds_f4(SPILL, P.stack_cap));
-  if (SUB == 4 && sub == 0) {
-    shared.next_start[px] = P.sample_begin;
-    shared.next_add[px] = P.sample_begin;
-    shared.first_hit[px] = -1;
-    shared.colour[0][px] = 0.0f; shared.colour[1][px] = 0.0f; shared.colour[2][px] = 0.0f;
-    for (int k = 0; k < kPtRing; ++k) shared.tag[k][px] = 0;
-  }
+  if (SUB == 4 && sub == 0) ring_init(shared, px, P.sample_begin);
 
   const Handoff& H = P.hand;
   uint4* list_in = H.list_in;
@@ -547,8 +444,7 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
   for (uint32_t round = 0;; ++round) {  // LIT == 2 in one persistent workgroup: a trip per round; otherwise one trip
     uint32_t n_in = 0;
     if (LIT == 2) {
-      n_in = __hip_atomic_load(n_in_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      n_in = n_in > H.list_cap ? H.list_cap : n_in;
+      n_in = list_count(n_in_p, H.list_cap);
       if (n_in == 0) break;
       if (H.round_base + round >= H.max_rounds) {  // work left after the last round allowed: the frame is not the serial one
         if (lane == 0) atomicOr(P.status, kHoErrNoFixedPoint);
@@ -561,43 +457,33 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
     }
     for (uint32_t chunk = blockIdx.x;; chunk += gridDim.x) {  // LIT == 2: 64 list entries per trip
       bool active;
-      UnitPlace up;
+      UnitPlace up = no_place();
       uint32_t unit = 0, pred = 0, pred_slot_count = 0, flags = 0;
       if (LIT == 2) {
         if ((size_t)chunk * H.lanes >= n_in) break;
         const uint32_t i = chunk * H.lanes + lane;
         active = lane < H.lanes && i < n_in;
-        up.c = up.r = up.x = up.y = 0; up.halo = false; up.valid = false;
         if (active) {
-          const uint32_t* e = reinterpret_cast<const uint32_t*>(list_in + i);
-          unit = __hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          pred = __hip_atomic_load(e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          pred_slot_count = __hip_atomic_load(e + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          flags = __hip_atomic_load(e + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          up = place_of_unit(P, unit);
-          active = up.valid;
+          const uint4 e = list_entry(list_in, i);
+          unit = e.x; pred = e.y; pred_slot_count = e.z; flags = e.w;
         }
       } else if (LIT == 3) {  // the tile's lanes that start on a non-empty leftover: check first, like a list entry with flag 1
         active = t_need;
         unit = t_unit; pred = t_pred; pred_slot_count = t_slot_count; flags = 1u;
-        up.c = up.r = up.x = up.y = 0; up.halo = false; up.valid = false;
-        if (active) {
-          up = place_of_unit(P, unit);
-          active = up.valid;
-        }
       } else if (halo_block) {
         active = halo_unit_of_lane(P, lane, unit);
-        up.c = up.r = up.x = up.y = 0; up.halo = true; up.valid = active;
+        up.halo = true;
         if (active) up = place_of_unit(P, unit);
       } else {
-        up.c = (int)((tx << tws) + (px & ((1u << tws) - 1u)));
-        up.r = (int)((ty << ths) + (px >> tws));
-        up.halo = false;
-        active = px < (1u << (tws + ths)) && up.c < P.w && up.r < P.h;
+        active = tile_pixel(P, tx, ty, tws, ths, px, up.c, up.r);
         up.valid = active;
         up.x = P.x0 + up.c;
         up.y = image_row(P, up.r);
-        if (LIT == 1) unit = (uint32_t)(P.row0 + up.r) * H.row_units + H.halo + (uint32_t)up.c;
+        if (LIT == 1) unit = unit_of_pixel(P, up.c, up.r);
+      }
+      if (REDO && active) {
+        up = place_of_unit(P, unit);
+        active = up.valid;
       }
 
       bool unit_touched = false;
@@ -605,7 +491,7 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
       if (STATS && LIT != 0) ct.clear();  // LITERAL: counters per unit (store_unit_counters), not per lane
       if (REDO && active) {  // seed with the predecessor's leftover; re-trace the first closest hit if asked to
         seed_stack<SPILL>(st, H, pred, pred_slot_count, ct);
-        if (flags & 1u) {
+        if (flags & 1u) {  // (twin: first_hit_unchanged; calling it here spills more SGPRs in three LIT == 2 instantiations)
           if (H.count) atomicAdd(&H.counters[kHoChecked], 1u);
           const float4 now = first_closest_hit<SPILL, !LDS>(P, sc, st, up.x, up.y, AA ? H.first_sample[unit] : 0u, ct);
           if (same_first(now, H.first[unit])) {  // nothing this unit computes can differ
@@ -713,9 +599,7 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
             const int sj = s - si * SPP;
 #include "whitted_sample.inc"
             if (s == 0) shared.first_hit[px] = first_hit;
-            const int k = s % kPtRing;
-            shared.radiance[k][0][px] = result.x; shared.radiance[k][1][px] = result.y; shared.radiance[k][2][px] = result.z;
-            shared.tag[k][px] = (uint32_t)s + 1;
+            ring_post(shared, px, s, result);
           }
           if (sub == 0) {
             color = f3(shared.colour[0][px], shared.colour[1][px], shared.colour[2][px]);
@@ -740,14 +624,7 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
             P.rgb[3 * k] = color.x; P.rgb[3 * k + 1] = color.y; P.rgb[3 * k + 2] = color.z;
           }
           if (!EARLY_HIT && P.hit_id) P.hit_id[k] = first_hit;
-          if (P.rgb8) {  // main.cpp:814-820
-            F3 gc = color;
-            if (P.gamma != 1.0f) {
-              const double ig = (double)(1 / P.gamma);
-              gc = f3((float)pow_spec((double)color.x, ig), (float)pow_spec((double)color.y, ig), (float)pow_spec((double)color.z, ig));
-            }
-            P.rgb8[3 * k] = u8fromfloat(gc.x); P.rgb8[3 * k + 1] = u8fromfloat(gc.y); P.rgb8[3 * k + 2] = u8fromfloat(gc.z);
-          }
+          if (P.rgb8) store_rgb8(P.rgb8 + 3 * k, color, P.gamma);
         }
 
 #ifndef P3D_ABL_NO_RECORDS  // (timing ablation only: pass 1 keeps no records, the frame is the per-pixel one)
@@ -819,357 +696,4 @@ __global__ void __launch_bounds__(kBlock, LIT >= 2 ? P3D_LIST_WAVES : (AA ? P3D_
   P3D_TL_END()
 }
 
-// Object::intercepts / Object::getNormal / Scene::GetSkyboxColor for batches (host-class forwarding, unit parity)
-struct ObjectQueryParams {
-  DevScene sc;
-  uint32_t object, n;
-  const float* a;   // origins | points | directions
-  float* b;         // directions (in/out) | normals | rgb
-  uint8_t* hit;
-  float* t;
-};
-template <int WHAT>  // 0 intercepts, 1 normal, 2 skybox colour
-__global__ void __launch_bounds__(kBlock) object_query_kernel(const ObjectQueryParams P) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= P.n) return;
-  Counters<false> ct;
-  if (WHAT == 0) {
-    const Geom g = load_geom(P.sc.ogeom, P.object);
-    RayS ray;
-    ray_set(ray, f3(P.a[3 * i], P.a[3 * i + 1], P.a[3 * i + 2]), f3(P.b[3 * i], P.b[3 * i + 1], P.b[3 * i + 2]));
-    float t = 0.0f;
-    const bool h = intercepts(g, ray, t, ct);
-    P.hit[i] = h ? 1 : 0;
-    if (h) P.t[i] = t;
-    P.b[3 * i] = ray.d.x; P.b[3 * i + 1] = ray.d.y; P.b[3 * i + 2] = ray.d.z;
-  } else if (WHAT == 1) {
-    const Geom g = load_geom(P.sc.ogeom, P.object);
-    const F3 nrm = get_normal(g, P.sc.normals, f3(P.a[3 * i], P.a[3 * i + 1], P.a[3 * i + 2]));
-    P.b[3 * i] = nrm.x; P.b[3 * i + 1] = nrm.y; P.b[3 * i + 2] = nrm.z;
-  } else {
-    const F3 c = skybox_color(P.sc, f3(P.a[3 * i], P.a[3 * i + 1], P.a[3 * i + 2]));
-    P.b[3 * i] = c.x; P.b[3 * i + 1] = c.y; P.b[3 * i + 2] = c.z;
-  }
-}
-
-// For every tile row that starts a chain of its own (its predecessor in the FRAME is not the end of the tile row above:
-// first row of a stripe, any row of a sub-rectangle, a tile that does not start at the frame's first pixel): the frame
-// pixels in front of the row whose leftovers have to be known for the row's first pixel to start on the right stack.
-//
-// A pixel "touches" the stack if the primary ray of one of its samples gets past the root test (bvh.cpp:203-205).  What
-// the row starts on is the leftover of the last touching pixel before it, which depends on ITS predecessor's leftover,
-// and so on back to the frame's first pixel - but only through the result of each pixel's first closest hit
-// (handoff.hpp).  The chain can therefore be cut at a pixel whose first closest hit provably does not depend on the
-// stack it finds.  The stale entries of a found stack are popped AFTER the query's own traversal and the popped
-// subtrees are walked with the query's ray (bvh.cpp:256-265); that changes the result only if (a) one of the primitive
-// tests it runs returns a hit nearer than the own traversal's, or (b) a sphere test re-normalises the ray's direction
-// (scene.cpp:156, ray.h:16-18).  So a pixel is CERTIFIED if, after its own traversal on an empty stack,
-//   (a) NO primitive of the scene - all of them are tested, whatever boxes they sit in - is hit nearer than tmin by the
-//       ray as the traversal left it, and
-//   (b) the scene has no sphere, or normalising that ray's direction once more leaves its bits unchanged (then every
-//       further normalisation is the identity).
-// Under (a) and (b) no sequence of stale subtree walks can change tmin, the hit or the direction, whatever the stack
-// held: the pixel rendered on an empty stack is the pixel of the serial frame, its leftover included.  The kernel walks
-// back from the row, takes the touching pixels most recent first, and stops at the first one it can certify (or at the
-// frame's first touching pixel, whose stack IS empty); the pixels it collected are rendered in front of the row for
-// their leftovers, the oldest on an empty stack, each next one checked against its predecessor's leftover like any
-// other unit.  If `max_chain` (<= kHaloChain) pixels are collected without a certificate and an older touching pixel
-// exists, the row cannot be started exactly: kHoErrHalo is raised and the call fails (P3D_ERR_CAPACITY) instead of
-// returning a frame that is only probably right.
-//
-// One workgroup per row.  Every thread looks at one pixel of the kHaloFindThreads before the row; candidates are taken
-// one at a time: wave 0 runs the own traversal (all lanes the same ray), all threads share the all-primitives test.
-constexpr int kHaloFindThreads = 1024;
-struct HaloFindShared {
-  unsigned long long touched[kHaloFindThreads / kBlock];
-  float tmin, dx, dy, dz;
-  uint32_t settled, closer;
-};
-__device__ __forceinline__ bool pixel_first_touching_ray(const RenderParams& P, const NodeRec& root, long long f, RayS& ray) {
-  const DevScene& sc = P.sc;
-  const int res_x = sc.cam.res_x, SPP = P.antialiasing ? (int)P.spp_sqrt : 1;
-  const int x = (int)(f % res_x), y = (int)(f / res_x);
-  for (int s = 0; s < SPP * SPP; ++s) {
-    Rng rng;
-    rng.state = 0; rng.inc = 1;
-    if (P.antialiasing) rng.seed_stream(P.seed, (uint32_t)(y * res_x + x), (uint32_t)s);
-    F3 o, d;
-    make_primary(P, sc.cam, x, y, s / SPP, s % SPP, rng, o, d);
-    ray_set(ray, o, d);
-    float t;
-    if (aabb_intercepts(xyz(root.lo), xyz(root.hi), ray, t, false)) return true;
-  }
-  return false;
-}
-// Which rows of a tile start a chain of their own: a function of the tile alone, worked out on the launch stream so
-// that two tiles queued on one stream cannot see each other's flags.  Also resets the verdict of the search that follows.
-struct RowChainParams {
-  uint8_t* chain;
-  uint32_t* verdict;
-  int32_t rows, x0, y0, w, res_x, sh, ss;
-};
-__global__ void __launch_bounds__(256) row_chain_kernel(const RowChainParams C) {
-  const int r = (int)(blockIdx.x * 256 + threadIdx.x);
-  if (r == 0) *C.verdict = 0;
-  if (r >= C.rows) return;
-  auto image_y = [&](int row) { return (long long)C.y0 + (long long)(row / C.sh) * C.sh * C.ss + (row % C.sh); };
-  const long long y = image_y(r);
-  const bool full_width = C.x0 == 0 && C.w == C.res_x;
-  C.chain[r] = r == 0 ? !(C.x0 == 0 && y == 0) : !(full_width && y == image_y(r - 1) + 1);
-}
-
-__global__ void __launch_bounds__(kHaloFindThreads) halo_find_kernel(const RenderParams P, uint32_t* halo_pix, uint32_t* verdict, uint32_t max_chain,
-                                                                     uint32_t has_spheres, uint32_t window, uint32_t backing_stride) {
-  extern __shared__ float4 smem[];  // wave 0's node stack: window * 64 entries
-  __shared__ HaloFindShared sh;
-  const Handoff& H = P.hand;
-  const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  if (row >= H.rows || !H.row_chain[row]) return;
-  const DevScene& sc = P.sc;
-  const long long f0 = (long long)image_row(P, (int)row) * sc.cam.res_x + P.x0;  // the row's first pixel: search below it
-  const NodeRec root = load_node(sc.nodes, 0);
-  Counters<false> ct;
-  uint32_t found = 0;
-  bool certified = false, older_exists = false;
-  for (long long base = f0; base > 0 && !certified && !older_exists; base -= kHaloFindThreads) {
-    const long long f = base - 1 - (long long)tid;  // thread 0 looks at the most recent pixel
-    RayS ray;
-    const bool touched = f >= 0 && pixel_first_touching_ray(P, root, f, ray);
-    const unsigned long long m = __ballot(touched);
-    if (lane == 0) sh.touched[wave] = m;
-    __syncthreads();
-    for (uint32_t w = 0; w < kHaloFindThreads / kBlock && !certified && !older_exists; ++w) {
-      unsigned long long mask = sh.touched[w];
-      while (mask && !certified && !older_exists) {  // workgroup-uniform
-        const int l = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        if (found == max_chain) {  // the chain is full and here is a touching pixel it would still need
-          older_exists = true;
-          break;
-        }
-        const long long pix = base - 1 - (long long)(w * kBlock + (uint32_t)l);
-        if (tid == 0) halo_pix[row * kHaloChain + (kHaloChain - 1 - found)] = (uint32_t)pix;
-        ++found;
-        // ---- certificate ----
-        pixel_first_touching_ray(P, root, pix, ray);  // (every thread: the same ray)
-        if (wave == 0) {
-          Stack st;
-          stack_bind(st, smem, 0, lane, (int)window, P.spill, backing_stride, blockIdx.x * kBlock + lane);
-          F3 hp;
-          Geom g;
-          float tmin = FLT_MAX;
-          RayS left;
-          bvh_closest<true>(sc, st, ray, hp, g, ct, nullptr, &tmin, &left);
-          if (lane == 0) {
-            sh.tmin = tmin;
-            sh.dx = left.d.x; sh.dy = left.d.y; sh.dz = left.d.z;
-            sh.settled = same_bits(normalized(left.d), left.d) ? 1u : 0u;
-            sh.closer = 0;
-          }
-        }
-        __syncthreads();
-        const float tmin = sh.tmin;
-        const bool settled = sh.settled != 0;
-        bool closer = false;
-        if (settled || !has_spheres) {
-          RayS r = ray;
-          r.d = f3(sh.dx, sh.dy, sh.dz);
-          r.inv = f3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
-          r.odd_inv = inv_is_odd(r.inv);
-          r.settled = settled;  // a settled direction is returned as it is by the sphere test (ray.h:16-18 would give the same bits)
-          for (uint32_t i = tid; i < sc.n_objs && !closer; i += kHaloFindThreads) {
-            const Geom g = load_geom(sc.ogeom, i);
-            float t;
-            closer = intercepts(g, r, t, ct) && t < tmin;
-          }
-        }
-        if (closer) sh.closer = 1;  // (benign race: every writer stores the same value)
-        __syncthreads();
-        certified = (settled || !has_spheres) && sh.closer == 0;
-        __syncthreads();
-      }
-    }
-    __syncthreads();
-  }
-  if (older_exists && !certified && tid == 0) atomicOr(verdict, kHoErrHalo);
-  if (tid < kHaloChain - found) halo_pix[row * kHaloChain + tid] = kNoUnit;
-}
-
-// The check of round 0 of the hand-off for a whole launch: every unit that touched the stack and whose predecessor left something
-// re-traces its first closest hit on that leftover; the units whose hit changed go on the work list of the redo launch.
-template <bool LDS, bool SPILL, bool STATS = false>
-__global__ void __launch_bounds__(kBlock) handoff_check_kernel(const RenderParams P) {
-  extern __shared__ float4 smem[];
-  uint32_t tx = 0, ty = 0;
-  const bool halo_block = blockIdx.x >= P.tile_blocks;
-  if (!halo_block && !tile_of_block(P, tx, ty)) return;
-  const uint32_t lane = threadIdx.x;
-  const Handoff& H = P.hand;
-  uint32_t unit = 0;
-  bool active;
-  if (halo_block) {
-    active = halo_unit_of_lane(P, lane, unit);
-  } else {
-    const uint32_t tws = P.tile_w_shift, ths = P.tile_h_shift;
-    const int c = (int)((tx << tws) + (lane & ((1u << tws) - 1u))), r = (int)((ty << ths) + (lane >> tws));
-    active = lane < (1u << (tws + ths)) && c < P.w && r < P.h;
-    unit = (uint32_t)(P.row0 + r) * H.row_units + H.halo + (uint32_t)c;
-  }
-  // which lanes have anything to re-trace is known before the scene is staged: most waves leave here
-  int pred = -1;
-  uint32_t pm = 0;
-  if (active && handoff_touched(H, unit)) {
-    pred = handoff_pred(H, unit);
-    if (pred >= 0) pm = H.meta[pred];
-  }
-  const bool need = (pm & 0xffffu) != 0;  // otherwise the predecessor left nothing: pass 1's empty stack was right
-  if (__ballot(need) == 0) return;
-  DevScene sc = P.sc;
-  stage_scene<LDS, false>(sc, P, smem);  // (the hand-off exists for the BVH only)
-  if (!need) return;
-  Counters<STATS> ct;
-  ct.clear();
-  Stack st;
-  stack_bind(st, smem, P.lds_scene_f4, lane, P.stack_cap, P.spill, P.level_stride, blockIdx.x * kBlock + lane);
-  const UnitPlace up = place_of_unit(P, unit);
-  const uint32_t slot_count = pm & 0x1ffffu;
-  seed_stack<SPILL>(st, H, (uint32_t)pred, slot_count, ct);
-  if (H.count) atomicAdd(&H.counters[kHoChecked], 1u);
-  const float4 now = first_closest_hit<SPILL, !LDS>(P, sc, st, up.x, up.y, P.antialiasing ? H.first_sample[unit] : 0u, ct);
-  if (!same_first(now, H.first[unit]))
-    handoff_append(H.list_out, H.n_out, H.list_cap, P.status, make_uint4(unit, (uint32_t)pred, slot_count, 0u));
-  else
-    replace_ch0_counters<STATS>(H, unit, ct, P.stats);
-}
-
-// The same round over the list pass 1 wrote (Handoff::check_list: the units that left something): entry -> the unit that starts on
-// that leftover (the next one that touched the stack) -> re-trace its first closest hit on it.  Every lane has work; one launch
-// for the whole tile however many launches pass 1 took.
-template <bool LDS, bool SPILL, bool STATS = false>
-__global__ void __launch_bounds__(kBlock) handoff_check_list_kernel(const RenderParams P) {
-  extern __shared__ float4 smem[];
-  const Handoff& H = P.hand;
-  uint32_t n = __hip_atomic_load(H.check_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  n = n > H.n_units ? H.n_units : n;
-  if ((size_t)blockIdx.x * kBlock >= n) return;  // nothing on the list for this workgroup: leave before the scene is staged
-  const uint32_t lane = threadIdx.x;
-  DevScene sc = P.sc;
-  stage_scene<LDS, false>(sc, P, smem);
-  Stack st;
-  stack_bind(st, smem, P.lds_scene_f4, lane, P.stack_cap, P.spill, P.level_stride, blockIdx.x * kBlock + lane);
-  for (uint32_t chunk = blockIdx.x; (size_t)chunk * kBlock < n; chunk += gridDim.x) {
-    const uint32_t i = chunk * kBlock + lane;
-    if (i >= n) continue;
-    const uint32_t pred = H.check_list[i];
-    const uint32_t pm = H.meta[pred];
-    const int succ = handoff_succ(H, pred);
-    if (succ < 0 || (pm & 0xffffu) == 0) continue;  // nobody starts on it (end of a chain) / the pool was full (the call fails)
-    const uint32_t unit = (uint32_t)succ;
-    Counters<STATS> ct;
-    ct.clear();
-    const UnitPlace up = place_of_unit(P, unit);
-    const uint32_t slot_count = pm & 0x1ffffu;
-    seed_stack<SPILL>(st, H, pred, slot_count, ct);
-    if (H.count) atomicAdd(&H.counters[kHoChecked], 1u);
-    const float4 now = first_closest_hit<SPILL, !LDS>(P, sc, st, up.x, up.y, P.antialiasing ? H.first_sample[unit] : 0u, ct);
-    if (!same_first(now, H.first[unit]))
-      handoff_append(H.list_out, H.n_out, H.list_cap, P.status, make_uint4(unit, pred, slot_count, 0u));
-    else
-      replace_ch0_counters<STATS>(H, unit, ct, P.stats);
-  }
-}
-
-// Round 1 of the hand-off as a LIGHT launch.  List B holds the successors of the units whose leftover changed in round 0; nearly
-// all of them only need their first closest hit re-traced on the new leftover to find that nothing changes.  Until round 4 that was
-// done by the work-list instantiation of whitted_kernel (LIT = 2: the whole Whitted chain, 128 VGPRs + scratch), whose few waves had
-// to wait for a double-width slot among the other frames' pass-1 waves; this kernel only checks, and passes the rare entry whose hit
-// does change (or that asks for no check) on to list C, which the persistent workgroup behind it renders again.
-template <bool LDS, bool SPILL, bool STATS = false>
-__global__ void __launch_bounds__(kBlock) handoff_check_entries_kernel(const RenderParams P) {
-  extern __shared__ float4 smem[];
-  const Handoff& H = P.hand;
-  uint32_t n = __hip_atomic_load(H.n_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  n = n > H.list_cap ? H.list_cap : n;
-  if ((size_t)blockIdx.x * H.lanes >= n) return;  // nothing on the list for this workgroup: leave before the scene is staged
-  const uint32_t lane = threadIdx.x;
-  if (H.round_base >= H.max_rounds) {  // work left after the last round allowed: the frame is not the serial one
-    if (lane == 0) atomicOr(P.status, kHoErrNoFixedPoint);
-    return;
-  }
-  if (H.count && blockIdx.x == 0 && lane == 0) atomicOr(&H.counters[kHoRound1], 1u);
-  DevScene sc = P.sc;
-  stage_scene<LDS, false>(sc, P, smem);
-  Stack st;
-  stack_bind(st, smem, P.lds_scene_f4, lane, P.stack_cap, P.spill, P.level_stride, blockIdx.x * kBlock + lane);
-  for (uint32_t chunk = blockIdx.x; (size_t)chunk * H.lanes < n; chunk += gridDim.x) {
-    const uint32_t i = chunk * H.lanes + lane;
-    if (lane >= H.lanes || i >= n) continue;
-    const uint32_t* e = reinterpret_cast<const uint32_t*>(H.list_in + i);
-    const uint32_t unit = __hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t pred = __hip_atomic_load(e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t slot_count = __hip_atomic_load(e + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t flags = __hip_atomic_load(e + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const UnitPlace up = place_of_unit(P, unit);
-    if (!up.valid) continue;
-    if (flags & 1u) {
-      Counters<STATS> ct;
-      ct.clear();
-      seed_stack<SPILL>(st, H, pred, slot_count, ct);
-      if (H.count) atomicAdd(&H.counters[kHoChecked], 1u);
-      const float4 now = first_closest_hit<SPILL, !LDS>(P, sc, st, up.x, up.y, P.antialiasing ? H.first_sample[unit] : 0u, ct);
-      if (same_first(now, H.first[unit])) {  // nothing this unit computes can differ
-        replace_ch0_counters<STATS>(H, unit, ct, P.stats);
-        continue;
-      }
-    }
-    handoff_append(H.list_out, H.n_out, H.list_cap, P.status, make_uint4(unit, pred, slot_count, 0u));  // rendered again by the launch behind this one
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Batched queries (unit-level parity of the traversal back ends)
-// ---------------------------------------------------------------------------
-struct TraceParams {
-  DevScene sc;
-  uint32_t n;
-  const float* origin;
-  const float* direction;
-  int32_t* hit_id;
-  float* t;
-  float* hit_point;
-  uint8_t* occluded;
-  uint2* spill;
-  uint32_t spill_stride;
-  int32_t stack_cap;
-};
-
-template <int ACCEL, bool ANY>
-__global__ void __launch_bounds__(kBlock) trace_kernel(const TraceParams P) {
-  extern __shared__ float4 smem[];
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  Stack st;
-  stack_bind(st, smem, 0, threadIdx.x, P.stack_cap, P.spill, P.spill_stride, i);
-  if (i >= P.n) return;
-  Counters<false> ct;
-  RayS ray;
-  ray_set(ray, f3(P.origin[3 * i], P.origin[3 * i + 1], P.origin[3 * i + 2]),
-          f3(P.direction[3 * i], P.direction[3 * i + 1], P.direction[3 * i + 2]));
-  if (ANY) {
-    P.occluded[i] = any_hit<ACCEL, true, true>(P.sc, st, ray, ct) ? 1 : 0;
-  } else {
-    F3 hp = f3(0, 0, 0);
-    Geom g;
-    float t = FLT_MAX;
-    const int obj = closest_hit<ACCEL, true, true>(P.sc, st, ray, hp, g, ct, nullptr, &t);
-    P.hit_id[i] = obj;
-    if (P.t) P.t[i] = obj < 0 ? FLT_MAX : t;
-    if (obj < 0) hp = f3(0, 0, 0);
-    if (P.hit_point) {
-      P.hit_point[3 * i] = hp.x; P.hit_point[3 * i + 1] = hp.y; P.hit_point[3 * i + 2] = hp.z;
-    }
-  }
-}
-
 }  // namespace p3d
-
-#include "wavefront.hpp"

@@ -46,19 +46,12 @@
     }
     const int c = ADAPT ? (int)(pix % (uint32_t)P.w) : (int)(tx * TP + (px % TP));
     const int r = ADAPT ? (int)(pix / (uint32_t)P.w) : (int)(ty * TP + (px / TP));
-    if (SUB == 4 && sub == 0) {
-      shared.next_start[px] = P.sample_begin;
-      shared.next_add[px] = P.sample_begin;
-      shared.first_hit[px] = -1;
-      shared.colour[0][px] = 0.0f; shared.colour[1][px] = 0.0f; shared.colour[2][px] = 0.0f;
-      for (int k = 0; k < kPtRing; ++k) shared.tag[k][px] = 0;
-    }
+    if (SUB == 4 && sub == 0) ring_init(shared, px, P.sample_begin);
 
     const bool active = ADAPT ? listed : (c < P.w && r < P.h);
     if (active) {
-      const int sh = P.stripe_h > 0 ? P.stripe_h : 1, ss = P.stripe_h > 0 ? P.stripe_stride : 1;
       const int x = P.x0 + c;
-      const int y = P.y0 + (r / sh) * sh * ss + (r % sh);
+      const int y = image_row(P, r);
       const int SPP = (int)P.spp_sqrt;
       const uint32_t s_end = P.sample_end;  // one past the last sample of this launch (a whole frame: SPP * SPP)
       const int MAXD = P.max_depth;
@@ -140,9 +133,7 @@
           } else {
             if (in_sample) {
               if (SUB == 4) {  // post the finished sample; its ring slot is free (guaranteed when it was handed out)
-                const int k = s % kPtRing;
-                shared.radiance[k][0][px] = L.x; shared.radiance[k][1][px] = L.y; shared.radiance[k][2][px] = L.z;
-                shared.tag[k][px] = (uint32_t)s + 1;
+                ring_post(shared, px, s, L);
               } else {
                 color = color + L;
                 if constexpr (ADAPT) s2 = s2 + luma_sq(L);
@@ -354,14 +345,7 @@
             P.rgb[3 * k] = color.x; P.rgb[3 * k + 1] = color.y; P.rgb[3 * k + 2] = color.z;
           }
           if (P.hit_id) P.hit_id[k] = first_hit;
-          if (P.rgb8) {
-            F3 gc = color;
-            if (P.gamma != 1.0f) {
-              const double ig = (double)(1 / P.gamma);
-              gc = f3((float)pow_spec((double)color.x, ig), (float)pow_spec((double)color.y, ig), (float)pow_spec((double)color.z, ig));
-            }
-            P.rgb8[3 * k] = u8fromfloat(gc.x); P.rgb8[3 * k + 1] = u8fromfloat(gc.y); P.rgb8[3 * k + 2] = u8fromfloat(gc.z);
-          }
+          if (P.rgb8) store_rgb8(P.rgb8 + 3 * k, color, P.gamma);
         }
       }
     }

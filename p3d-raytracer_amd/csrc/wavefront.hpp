@@ -1,7 +1,9 @@
 // wavefront.hpp — the Whitted chain as one launch per level with ray compaction and binning between levels
-// (p3d_config.chain_launch = P3D_CHAIN_PER_LEVEL).  Included at the end of kernels.hpp: uses its RenderParams, tile map,
-// unit placement and the per-level body whitted_level.inc.
+// (p3d_config.chain_launch = P3D_CHAIN_PER_LEVEL).  Uses the RenderParams and tile map of kernels.hpp, the unit placement of
+// handoff_kernels.hpp and the per-level body whitted_level.inc.
 #pragma once
+
+#include "kernels.hpp"
 
 namespace p3d {
 
@@ -96,7 +98,7 @@ __global__ void __launch_bounds__(kBlock, P3D_WF_WAVES) wf_level_kernel(const Re
         up.valid = active;
         up.x = P.x0 + up.c;
         up.y = image_row(P, up.r);
-        unit = (uint32_t)(P.row0 + up.r) * H.row_units + H.halo + (uint32_t)up.c;
+        unit = unit_of_pixel(P, up.c, up.r);
       }
       if (active) {
         F3 o, d;
@@ -247,14 +249,7 @@ __global__ void __launch_bounds__(256) wf_fold_kernel(const RenderParams P) {
   if (P.rgb) {
     P.rgb[3 * (size_t)i] = result.x; P.rgb[3 * (size_t)i + 1] = result.y; P.rgb[3 * (size_t)i + 2] = result.z;
   }
-  if (P.rgb8) {  // main.cpp:814-820
-    F3 gc = result;
-    if (P.gamma != 1.0f) {
-      const double ig = (double)(1 / P.gamma);
-      gc = f3((float)pow_spec((double)result.x, ig), (float)pow_spec((double)result.y, ig), (float)pow_spec((double)result.z, ig));
-    }
-    P.rgb8[3 * (size_t)i] = u8fromfloat(gc.x); P.rgb8[3 * (size_t)i + 1] = u8fromfloat(gc.y); P.rgb8[3 * (size_t)i + 2] = u8fromfloat(gc.z);
-  }
+  if (P.rgb8) store_rgb8(P.rgb8 + 3 * (size_t)i, result, P.gamma);
 }
 
 }  // namespace p3d
