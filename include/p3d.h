@@ -436,7 +436,11 @@ int p3d_scene_camera(p3d_scene* scene, p3d_camera* out);
  * only, so the caller resets it or accepts ghosting on moved objects.  The first update of a scene allocates the builder's
  * state (about 150 bytes per object), which p3d_scene_destroy frees.
  * *update_ms (may be NULL): GPU time between two events around the staging copy and the launches.
- * Refused with P3D_ERR_INVALID, nothing changed: a scene of p3d_scene_create; a scene that carries a grid (it would go stale);
+ * A scene with a device-built grid (p3d_scene_build_grid, below) keeps it: in both modes the grid is rebuilt in full after the
+ * BVH work, inside *update_ms.  If that rebuild fails the call returns its error (P3D_ERR_CAPACITY, P3D_ERR_NO_DEVICE): the
+ * geometry and the BVH ARE updated, and the scene has no grid until p3d_scene_build_grid succeeds again.
+ * Refused with P3D_ERR_INVALID, nothing changed: a scene of p3d_scene_create; a scene created with the host's grid in its
+ * descriptor (it would go stale);
  * an object index out of range or repeated within the call; a record whose type or material differs from the object's
  * (emitter list and kernel selection stay valid); a non-finite or inverted bmin / bmax; an unknown mode; NULL arrays with n > 0.
  *
@@ -451,6 +455,37 @@ int p3d_scene_update_prims(p3d_scene* scene, uint32_t n, const uint32_t* object,
                            uint32_t mode, float* update_ms);
 int p3d_scene_export_bvh(p3d_scene* scene, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index,
                          uint32_t* n_prim_index, uint32_t* max_depth);
+
+/*
+ * The uniform grid of a live scene, built on the device.  Detected by the symbols (P3D_ABI_VERSION is unchanged).  Only for
+ * scenes of p3d_scene_create_device_bvh, which keep their objects' boxes on the device and accept updates.
+ *
+ * p3d_scene_build_grid builds, or builds again, the scene's grid from the current object boxes: bounds, cell counts,
+ * cell_start and cell_items are, bit for bit, those of Grid::Build (grid.cpp:3-68; p3d_host_scene_desc with build_grid = 1)
+ * for the same objects, every cell's list in ascending object index.  After it accel = P3D_ACCEL_GRID works on the scene in
+ * every render, accumulate, adaptive, feature and query entry point, with the results of a scene created with the host's grid,
+ * and p3d_scene_update_prims rebuilds the grid with every update.  Like an update it is a host call that WAITS (tail stream,
+ * then the whole device, then for its own launches) and cannot be captured into a graph; it forgets the tile-cost schedules.
+ * The first build allocates the builder's state (that of the first update, if none has run, and about 40 bytes per object
+ * plus 16 bytes per cell item); the cell arrays and that state grow when a later build needs more, are kept otherwise - a
+ * rebuild that fits allocates nothing - and are freed by p3d_scene_destroy.
+ * *build_ms (may be NULL): GPU time between two events around the launches.
+ * Refused with P3D_ERR_INVALID, nothing changed: a null scene; a scene of p3d_scene_create; a scene whose descriptor carried a
+ * grid at create (it has the host's grid, and stays refused by updates).  P3D_ERR_UNSUPPORTED: a scene with no objects; a
+ * scene created with a non-finite or inverted box.  P3D_ERR_CAPACITY: a cell count along an axis that does not fit an int;
+ * more than 2^28 cells in all (a stated limit, not a measured one: 1 GiB of cell_start); more cell items than a uint32
+ * counts; an allocation that fails.  After a failed build the scene has NO grid (accel = P3D_ACCEL_GRID is refused as for a
+ * scene created without one); its BVH is untouched.
+ *
+ * p3d_scene_export_grid returns the device-built grid in the descriptor's format.  *n_cell_start and *n_cell_items hold the
+ * capacities of the arrays on entry and the sizes (n_cells + 1, n_items) on return; `info` receives nx, ny, nz, bmin, bmax,
+ * n_cells and n_items, its pointers are NULL.  With cell_start == NULL only `info` and the sizes are returned.
+ * P3D_ERR_CAPACITY if an array is too small (nothing is written to the arrays), P3D_ERR_INVALID for a scene without a
+ * device-built grid.
+ */
+int p3d_scene_build_grid(p3d_scene* scene, float* build_ms /* may be NULL */);
+int p3d_scene_export_grid(p3d_scene* scene, p3d_grid_desc* info, uint32_t* cell_start, uint32_t* n_cell_start,
+                          uint32_t* cell_items, uint32_t* n_cell_items);
 
 /*
  * Progressive accumulation: one anti-aliased frame rendered in passes over its samples, the image shown (or the frame

@@ -47,6 +47,7 @@ EXPORTS = [
     "p3d_temporal_params_default", "p3d_temporal_create", "p3d_temporal_destroy", "p3d_temporal_reset", "p3d_temporal_frames",
     "p3d_temporal_accumulate", "p3d_temporal_accumulate_device",
     "p3d_scene_update_prims", "p3d_scene_export_bvh", "p3d_host_scene_set_geometry",
+    "p3d_scene_build_grid", "p3d_scene_export_grid",
 ]
 
 
@@ -280,6 +281,9 @@ def lib():
         L.p3d_scene_export_bvh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32),
                                            C.POINTER(C.c_uint32)]
         L.p3d_host_scene_set_geometry.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.p3d_scene_build_grid.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.p3d_scene_export_grid.argtypes = [C.c_void_p, C.POINTER(GridDesc), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
+                                            C.POINTER(C.c_uint32)]
         _lib = L
     return _lib
 
@@ -476,10 +480,20 @@ class DeviceScene:
         """bvh: True = the reference-exact tree built on the host (BVH::build), "device" = a linear BVH built
         on the GPU (p3d_scene_create_device_bvh: correct closest hits, not the reference's tree), False = none,
         a dict with the bvh_* keys of HostScene.arrays(bvh=True) (e.g. from export_bvh) = that tree over the
-        host scene's current objects."""
+        host scene's current objects.
+        grid: True = the host's grid (Grid::Build) uploaded with the scene, "device" = the same grid built on the GPU after
+        create (p3d_scene_build_grid; needs bvh="device"): it follows update_prims, an uploaded one refuses them."""
         self._L = lib()
         self.host = host_scene
         self.device_bvh_ms = None
+        self.device_grid_ms = None
+        device_grid = isinstance(grid, str) and grid == "device"
+        if device_grid and not (isinstance(bvh, str) and bvh == "device"):
+            raise P3DError(-1, 'DeviceScene: grid="device" needs bvh="device" (only those scenes keep their boxes on the GPU)')
+        if isinstance(grid, str) and not device_grid:
+            raise P3DError(-1, 'DeviceScene: grid is True, False or "device"')
+        if device_grid:
+            grid = False
         h = C.c_void_p()
         if isinstance(bvh, dict):
             src = host_scene.desc(False, grid)
@@ -495,8 +509,11 @@ class DeviceScene:
             d.bvh_nodes = C.cast(nodes.ctypes.data, C.POINTER(BvhNode))
             d.bvh_prim_index = C.cast(order.ctypes.data, C.POINTER(C.c_uint32))
             _check(self._L.p3d_scene_create(C.byref(d), int(device), C.byref(h)))
-        elif bvh == "device":
+        elif isinstance(bvh, str) and bvh == "device":
             d = host_scene.desc(False, grid)
+            if device_grid:  # a host scene that has built its grid once keeps it in its descriptor: this scene builds its own
+                d = SceneDesc.from_buffer_copy(d)
+                d.has_grid = 0
             ms = C.c_float(0)
             _check(self._L.p3d_scene_create_device_bvh(C.byref(d), int(device), C.byref(h), C.byref(ms)))
             self.device_bvh_ms = ms.value
@@ -506,6 +523,8 @@ class DeviceScene:
         self.res = (d.camera.res_x, d.camera.res_y)
         self._h = h
         self.device = device
+        if device_grid:
+            self.device_grid_ms = self.build_grid()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -574,6 +593,25 @@ class DeviceScene:
         _check(self._L.p3d_scene_export_bvh(self._h, buf.ctypes.data, C.byref(n), order.ctypes.data, C.byref(m), C.byref(depth)))
         return dict(bvh_bmin=buf[:, 0:3].view(np.float32), bvh_index=buf[:, 3].copy(), bvh_bmax=buf[:, 4:7].view(np.float32),
                     bvh_count_leaf=buf[:, 7].copy(), bvh_order=order, bvh_max_depth=depth.value)
+
+    def build_grid(self):
+        """p3d_scene_build_grid: builds (or builds again) the uniform grid on the GPU from the scene's current object boxes - the
+        grid Grid::Build gives, to the bit.  Only for bvh="device" scenes created without a grid.  Waits for the device; returns
+        build_ms.  From then on update_prims rebuilds it."""
+        ms = C.c_float(0)
+        _check(self._L.p3d_scene_build_grid(self._h, C.byref(ms)))
+        return ms.value
+
+    def export_grid(self):
+        """p3d_scene_export_grid: the device-built grid as numpy arrays, with the grid_* keys of HostScene.arrays(grid=True)."""
+        g = GridDesc()
+        n, m = C.c_uint32(0), C.c_uint32(0)
+        _check(self._L.p3d_scene_export_grid(self._h, C.byref(g), None, C.byref(n), None, C.byref(m)))
+        start = np.zeros(n.value, np.uint32)
+        items = np.zeros(max(m.value, 1), np.uint32)
+        _check(self._L.p3d_scene_export_grid(self._h, C.byref(g), start.ctypes.data, C.byref(n), items.ctypes.data, C.byref(m)))
+        return dict(grid_n=(g.nx, g.ny, g.nz), grid_bmin=np.array(g.bmin[:], np.float32), grid_bmax=np.array(g.bmax[:], np.float32),
+                    grid_cell_start=start, grid_cell_items=items[:m.value].copy())
 
     def render(self, cfg, tile=None, want_rgb8=False, stats=True):
         """Host-buffer form (p3d_render_tile): returns numpy arrays."""

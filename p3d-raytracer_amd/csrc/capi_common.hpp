@@ -15,6 +15,7 @@
 #include "../host/p3d_error.hpp"
 #include "kernels.hpp"
 #include "lbvh.hpp"
+#include "grid_build.hpp"
 #include "p3d.h"
 #include "p3d_debug.h"
 #include "wavefront.hpp"
@@ -133,6 +134,11 @@ struct p3d_scene {
   bool lbvh_topology = false;          // lbvh_ws.sorted / children / parent describe the tree in d_blob
   Scratch upd_stage;                   // lbvh::UpdateRecord[n] of the update in progress
   std::vector<lbvh::UpdateRecord> upd_host;
+  // p3d_scene_build_grid (the same scenes): d_cell_start / d_cell_items above are then the device-built grid
+  bool uploaded_grid = false;          // the descriptor carried the host's grid: it cannot follow updates and is never rebuilt
+  uint64_t cell_start_cap = 0, cell_items_cap = 0;  // words allocated; they grow when a build needs more and are kept otherwise
+  uint32_t grid_items = 0;             // cell_start[n_cells] of the device-built grid
+  grid_build::Workspace grid_ws;       // allocated by the first build
 };
 
 namespace {

@@ -19,6 +19,7 @@ void p3d_scene_destroy(p3d_scene* s) {
     if (p) (void)hipFree(p);
   drop_schedules(s);
   s->lbvh_ws.release();
+  s->grid_ws.release();
   for (hipEvent_t e : {s->ev0, s->ev1, s->ev_mid, s->ev_p1, s->ev_tail_go, s->ev_tail_done})
     if (e) (void)hipEventDestroy(e);
   delete s;  // (every Scratch of the scene frees itself here)
@@ -69,7 +70,7 @@ int upload_grid(p3d_scene* s, const p3d_grid_desc& g) {
   v.grid.bmin = to_f3(g.bmin); v.grid.bmax = to_f3(g.bmax);
   v.grid.nx = g.nx; v.grid.ny = g.ny; v.grid.nz = g.nz;
   v.grid.cell_start = s->d_cell_start; v.grid.cell_items = s->d_cell_items;
-  s->has_grid = true;
+  s->has_grid = s->uploaded_grid = true;
   return P3D_OK;
 }
 

@@ -1,6 +1,6 @@
 // capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims), and the export of a device-built tree
 #pragma once
-#include "capi_common.hpp"
+#include "capi_grid.hpp"
 
 extern "C" {
 
@@ -46,7 +46,7 @@ int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, con
   if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: unknown mode");
   if (!s->device_bvh)
     return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
-  if (s->has_grid) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene carries a grid, which would go stale");
+  if (s->uploaded_grid) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene carries the host's grid, which would go stale");
   const uint32_t n_objs = s->dev.n_objs;
   if (n > n_objs) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: more records than objects (an index is repeated)");
   {
@@ -70,17 +70,8 @@ int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, con
   if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
   P3D_HIP(hipDeviceSynchronize());
   auto hip_fail = [](const char* what, hipError_t e) { return fail(P3D_ERR_NO_DEVICE, std::string("p3d_scene_update_prims: ") + what + ": " + hipGetErrorString(e)); };
+  if (int rc = ensure_box_workspace(s, "p3d_scene_update_prims")) return rc;  // first update: the builder's state
   lbvh::Workspace& w = s->lbvh_ws;
-  if (!w.n) {  // first update: the builder's state, with the boxes the tree in d_blob was built from
-    hipError_t e = w.alloc(n_objs, true);
-    if (e == hipSuccess) e = hipMemcpy(w.boxes, s->create_boxes.data(), s->create_boxes.size() * sizeof(float4), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      w.release();
-      return hip_fail("workspace", e);
-    }
-    std::vector<float4>().swap(s->create_boxes);
-    s->lbvh_topology = false;
-  }
   if (n) {
     if (int rc = s->upd_stage.ensure((size_t)n * sizeof(lbvh::UpdateRecord))) return rc;
     s->upd_host.assign(n, lbvh::UpdateRecord{});
@@ -112,6 +103,9 @@ int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, con
     e = lbvh::enqueue_topology(w, w.boxes);
   }
   if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom);
+  // a device-built grid follows in full, in both modes; if that fails the grid is dropped and the rest of the update stands
+  int grid_rc = P3D_OK;
+  if (e == hipSuccess && s->has_grid) grid_rc = rebuild_grid(s, "p3d_scene_update_prims");
   if (e == hipSuccess) e = hipEventRecord(s->ev1, 0);
   if (e == hipSuccess) e = hipEventSynchronize(s->ev1);
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -133,7 +127,7 @@ int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, con
   s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
   s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
   if (update_ms) *update_ms = ms;
-  return P3D_OK;
+  return grid_rc;  // (rebuild_grid has recorded its message)
 }
 
 int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {

@@ -11,7 +11,6 @@
 namespace p3d {
 
 namespace {
-inline double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }  // maths.h:46-49
 inline void put3(float dst[3], const Vector& v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; }
 }  // namespace
 
@@ -261,7 +260,7 @@ void BVH::emit_top(Top& t, uint32_t node) {
 //   * each object goes into every cell its box overlaps; cell lists keep object order
 // ---------------------------------------------------------------------------
 void Grid::Build() {
-  const float kEps = 0.0001f;
+  const float kEps = kGridEps;
   Vector p0(FLT_MAX, FLT_MAX, FLT_MAX), p1(-FLT_MAX, -FLT_MAX, -FLT_MAX);
   for (Object* o : objects_) {
     const AABB b = o->GetBoundingBox();
@@ -279,9 +278,9 @@ void Grid::Build() {
   const Vector w = p1 - p0;
   const int num_obj = getNumObjects();
   const float s = powf(num_obj / (w.x * w.y * w.z), 1 / 3);  // == 1, kept for NaN/inf fidelity
-  nx = static_cast<int>(truncf(m * w.x * s) + 1);
-  ny = static_cast<int>(truncf(m * w.y * s) + 1);
-  nz = static_cast<int>(truncf(m * w.z * s) + 1);
+  nx = static_cast<int>(grid_axis_cells(m, w.x, s));  // (grid_rule.hpp: shared with the device build)
+  ny = static_cast<int>(grid_axis_cells(m, w.y, s));
+  nz = static_cast<int>(grid_axis_cells(m, w.z, s));
 
   const size_t n_cells = static_cast<size_t>(nx) * ny * nz;
   struct Span { int x0, x1, y0, y1, z0, z1; };
@@ -290,12 +289,12 @@ void Grid::Build() {
   for (int j = 0; j < num_obj; ++j) {
     const AABB b = objects_[j]->GetBoundingBox();
     Span sp;
-    sp.x0 = static_cast<int>(clampd((b.min.x - p0.x) * nx / (p1.x - p0.x), 0, nx - 1));
-    sp.y0 = static_cast<int>(clampd((b.min.y - p0.y) * ny / (p1.y - p0.y), 0, ny - 1));
-    sp.z0 = static_cast<int>(clampd((b.min.z - p0.z) * nz / (p1.z - p0.z), 0, nz - 1));
-    sp.x1 = static_cast<int>(clampd((b.max.x - p0.x) * nx / (p1.x - p0.x), 0, nx - 1));
-    sp.y1 = static_cast<int>(clampd((b.max.y - p0.y) * ny / (p1.y - p0.y), 0, ny - 1));
-    sp.z1 = static_cast<int>(clampd((b.max.z - p0.z) * nz / (p1.z - p0.z), 0, nz - 1));
+    sp.x0 = grid_axis_cell(b.min.x, p0.x, p1.x, nx);
+    sp.y0 = grid_axis_cell(b.min.y, p0.y, p1.y, ny);
+    sp.z0 = grid_axis_cell(b.min.z, p0.z, p1.z, nz);
+    sp.x1 = grid_axis_cell(b.max.x, p0.x, p1.x, nx);
+    sp.y1 = grid_axis_cell(b.max.y, p0.y, p1.y, ny);
+    sp.z1 = grid_axis_cell(b.max.z, p0.z, p1.z, nz);
     spans[j] = sp;
     for (int iz = sp.z0; iz <= sp.z1; ++iz)
       for (int iy = sp.y0; iy <= sp.y1; ++iy)

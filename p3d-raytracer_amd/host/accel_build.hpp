@@ -11,6 +11,7 @@
 #include <memory>
 #include <vector>
 
+#include "grid_rule.hpp"
 #include "p3d.h"
 #include "scene_model.hpp"
 
@@ -81,7 +82,7 @@ class Grid {
   std::vector<Object*> objects_;
   std::vector<uint32_t> cell_start_, cell_items_;
   int nx = 0, ny = 0, nz = 0;
-  float m = 2.0f;  // grid.h:33
+  float m = kGridDensity;  // grid.h:33
   AABB bbox;
   ::p3d_scene* dev_ = nullptr;
 };

@@ -11,6 +11,8 @@
 //              [--stack literal|per_pixel]   p3d_config.stack_mode (default literal: the reference's one hit_stack)
 //              [--device-bvh]   build a linear BVH on the GPU instead of the reference's tree on the host
 //                               (p3d_scene_create_device_bvh: same closest hits, shadow feelers may differ)
+//              [--device-grid]  build the uniform grid on the GPU after create (p3d_scene_build_grid: the host's grid to the
+//                               bit, same image as without the flag); implies --device-bvh; for --accel grid
 //              [--skybox DIR]   DIR/{right,left,top,bottom,front,back}.jpg (baseline JPEG, decoded by the library as
 //                               Scene::LoadSkybox asks DevIL to; .ppm accepted too) -> SKYBOX true.  A scene's own
 //                               `env <dir>` line does the same when the folder is found.
@@ -143,7 +145,7 @@ constexpr int kNcclUint8 = 1;  // rccl.h: ncclUint8
 constexpr int kStripeRows = 8;
 
 // Renders the frame on n GPUs into `img` (bottom row first, 3 bytes per pixel).  Returns 0, or 1 after printing why not.
-int render_multi_gpu(const p3d_scene_desc* desc, bool device_bvh, p3d_config cfg, int n, bool verify, std::vector<uint8_t>& img, double* secs) {
+int render_multi_gpu(const p3d_scene_desc* desc, bool device_bvh, bool device_grid, p3d_config cfg, int n, bool verify, std::vector<uint8_t>& img, double* secs) {
   const int W = desc->camera.res_x, H = desc->camera.res_y;
   int ndev = p3d_device_count();
   if (n > ndev) { std::fprintf(stderr, "--gpus %d: this node shows %d HIP device(s)\n", n, ndev); return 1; }
@@ -163,8 +165,9 @@ int render_multi_gpu(const p3d_scene_desc* desc, bool device_bvh, p3d_config cfg
   uint8_t* d_all = nullptr;
   cfg.collect_stats = 0;
   for (int d = 0; d < n; ++d) {
-    const int rc = device_bvh && cfg.accel == P3D_ACCEL_BVH ? p3d_scene_create_device_bvh(desc, d, &scenes[d], nullptr) : p3d_scene_create(desc, d, &scenes[d]);
+    const int rc = device_grid || (device_bvh && cfg.accel == P3D_ACCEL_BVH) ? p3d_scene_create_device_bvh(desc, d, &scenes[d], nullptr) : p3d_scene_create(desc, d, &scenes[d]);
     if (rc != P3D_OK) return die("scene_create");
+    if (device_grid && p3d_scene_build_grid(scenes[d], nullptr) != P3D_OK) return die("scene_build_grid");
     if (!hip_ok(hipSetDevice(d), "hipSetDevice") || !hip_ok(hipStreamCreate(&streams[d]), "hipStreamCreate") ||
         !hip_ok(hipMalloc((void**)&d_part[d], part), "hipMalloc"))
       return 1;
@@ -380,7 +383,7 @@ int main(int argc, char** argv) {
   long frames = 0;           // --frames N (0: one frame, the usual output names)
   double orbit = 0.0;        // --orbit DEG (degrees per frame)
   bool orbit_set = false, temporal = false;
-  bool device_bvh = false, verify = false;
+  bool device_bvh = false, device_grid = false, verify = false;
   uint32_t load_flags = 0;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -408,6 +411,7 @@ int main(int argc, char** argv) {
     else if (a == "--stack") cfg.stack_mode = std::string(next("--stack")) == "per_pixel" ? P3D_STACK_PER_PIXEL : P3D_STACK_LITERAL;
     else if (a == "--device") device = std::atoi(next("--device"));
     else if (a == "--device-bvh") device_bvh = true;
+    else if (a == "--device-grid") device_grid = device_bvh = true;
     else if (a == "--gpus") gpus = std::atoi(next("--gpus"));
     else if (a == "--verify") verify = true;
     else if (a == "--passes") {
@@ -512,14 +516,14 @@ int main(int argc, char** argv) {
 
   const auto t_build0 = std::chrono::high_resolution_clock::now();
   const p3d_scene_desc* desc = nullptr;
-  if (p3d_host_scene_desc(hs, cfg.accel == P3D_ACCEL_BVH && !device_bvh, cfg.accel == P3D_ACCEL_GRID, &desc) != P3D_OK) return die("flatten");
+  if (p3d_host_scene_desc(hs, cfg.accel == P3D_ACCEL_BVH && !device_bvh, cfg.accel == P3D_ACCEL_GRID && !device_grid, &desc) != P3D_OK) return die("flatten");
   const int W = desc->camera.res_x, H = desc->camera.res_y;
   std::printf("\nResolutionX = %d  ResolutionY= %d.\n", W, H);  // main.cpp:986
   if (gpus > 0) {  // several GPUs of this node (or one, through the same path): stripes + one RCCL gather
     if (!skybox_dir.empty()) { std::fprintf(stderr, "--gpus with --skybox is not wired up in this front end\n"); return 2; }
     std::vector<uint8_t> img((size_t)3 * W * H);
     double secs = 0;
-    if (const int rc = render_multi_gpu(desc, device_bvh, cfg, gpus, verify, img, &secs)) return rc;
+    if (const int rc = render_multi_gpu(desc, device_bvh, device_grid, cfg, gpus, verify, img, &secs)) return rc;
     std::printf("Drawing finished!\n\nDone: %.2f (sec)\n", secs);
     std::printf("%d GPU(s): stripes of %d rows, one ncclGather of %zu bytes per GPU; second frame %.3f ms (render + gather)\n", gpus, kStripeRows,
                 (size_t)3 * W * (H / gpus), secs * 1e3);
@@ -530,10 +534,14 @@ int main(int argc, char** argv) {
     return 0;
   }
   p3d_scene* scene = nullptr;
-  if (device_bvh && cfg.accel == P3D_ACCEL_BVH) {
+  if (device_grid || (device_bvh && cfg.accel == P3D_ACCEL_BVH)) {  // (a device-built grid needs the scene kind that keeps its boxes on the GPU)
     float build_ms = 0;
     if (p3d_scene_create_device_bvh(desc, device, &scene, &build_ms) != P3D_OK) return die("scene_create_device_bvh");
     std::printf("BVH built on the GPU in %.2f ms\n", build_ms);
+    if (device_grid) {
+      if (p3d_scene_build_grid(scene, &build_ms) != P3D_OK) return die("scene_build_grid");
+      std::printf("Grid built on the GPU in %.2f ms\n", build_ms);
+    }
   } else if (p3d_scene_create(desc, device, &scene) != P3D_OK) {
     return die("scene_create");
   }
