@@ -457,6 +457,50 @@ int p3d_scene_export_bvh(p3d_scene* scene, p3d_bvh_node* nodes, uint32_t* n_node
                          uint32_t* n_prim_index, uint32_t* max_depth);
 
 /*
+ * Moving objects by TRANSFORMS, applied on the device.  Detected by the symbol (P3D_ABI_VERSION is unchanged).  The same
+ * scenes as p3d_scene_update_prims, and the same call from the BVH work onwards; what differs is where the new geometry comes
+ * from: the caller sends 64 bytes per transform and 16 bytes per range of objects, and a kernel moves the objects and does
+ * what the host's constructors do (triangle normal, boxes).
+ *
+ * Rest pose.  Every object has a REST geometry: the nine floats it was created with or was last given by
+ * p3d_scene_update_prims.  p3d_scene_transform_prims sets every object of ranges[i] = [first, first + count) to
+ * xforms[ranges[i].xform](rest) - never to T(current): calling it every frame with that frame's absolute pose accumulates no
+ * rounding.  Objects that no range names keep their current geometry.  The rest copy (48 bytes per object) is made by the
+ * first call from the scene's geometry of that moment and freed by p3d_scene_destroy; from then on p3d_scene_update_prims
+ * writes it too for the objects it replaces.
+ *
+ * Arithmetic: float32, left to right, no contraction (host/prim_rule.hpp, shared with the host's constructors).
+ *   point    x' = ((m[0] x + m[1] y) + m[2] z) + m[3], y' from m[4..7], z' from m[8..11]
+ *   triangle the three vertices as points; normal and box as the loader computes them from those vertices
+ *   sphere   the centre as a point; radius' = radius * sphere_scale; box = centre -+ radius'
+ *   box      min and max as points; accepted only if m[0], m[5], m[10] > 0 and the six off-diagonal entries are exactly 0
+ * The result is, bit for bit, what p3d_host_scene_set_geometry + p3d_scene_update_prims give for the same numbers.  (The
+ * identity returns the rest bits except that a coordinate -0 comes back as +0: 1 * -0 + 0 is +0.)
+ *
+ * Behaviour: modes, the device-grid rebuild inside *update_ms, the waits, the forgotten schedules and row chains, the root
+ * box, and accumulators refusing passes until reset are those of p3d_scene_update_prims.  n_ranges = 0 is allowed.  The
+ * staging for ranges and transforms grows when needed and is kept: a second call of the same size allocates nothing.
+ * Overflow: finite inputs can still overflow.  An object whose new box would be non-finite or inverted is NOT written and
+ * keeps its current geometry; the other objects are updated, the BVH and grid work runs, and the call returns
+ * P3D_ERR_INVALID with the number of such objects in p3d_last_error.
+ * Refused with P3D_ERR_INVALID, nothing changed: a null scene; a scene of p3d_scene_create; a scene with an uploaded grid;
+ * NULL arrays with non-zero counts; an unknown mode; a range with count = 0, first + count > the object count,
+ * xform >= n_xforms or reserved != 0; ranges that overlap (their order is free); a non-finite m or sphere_scale;
+ * sphere_scale <= 0; reserved != 0 in a transform; a range that covers a plane; a range that covers a box with a transform
+ * that is not positive-diagonal.
+ */
+typedef struct p3d_xform { /* 64 bytes */
+  float m[12];             /* row-major 3x4 */
+  float sphere_scale;      /* radius' = radius * sphere_scale; > 0 */
+  uint32_t reserved[3];    /* must be 0 */
+} p3d_xform;
+typedef struct p3d_xform_range { /* objects [first, first + count) take xforms[xform] */
+  uint32_t first, count, xform, reserved;
+} p3d_xform_range;
+int p3d_scene_transform_prims(p3d_scene* scene, uint32_t n_ranges, const p3d_xform_range* ranges, uint32_t n_xforms,
+                              const p3d_xform* xforms, uint32_t mode, float* update_ms);
+
+/*
  * The uniform grid of a live scene, built on the device.  Detected by the symbols (P3D_ABI_VERSION is unchanged).  Only for
  * scenes of p3d_scene_create_device_bvh, which keep their objects' boxes on the device and accept updates.
  *

@@ -47,7 +47,7 @@ EXPORTS = [
     "p3d_temporal_params_default", "p3d_temporal_create", "p3d_temporal_destroy", "p3d_temporal_reset", "p3d_temporal_frames",
     "p3d_temporal_accumulate", "p3d_temporal_accumulate_device",
     "p3d_scene_update_prims", "p3d_scene_export_bvh", "p3d_host_scene_set_geometry",
-    "p3d_scene_build_grid", "p3d_scene_export_grid",
+    "p3d_scene_build_grid", "p3d_scene_export_grid", "p3d_scene_transform_prims",
 ]
 
 
@@ -61,6 +61,14 @@ class Prim(C.Structure):
     _fields_ = [("v", C.c_float * 9), ("type", C.c_uint32), ("material", C.c_uint32), ("reserved0", C.c_uint32),
                 ("n", C.c_float * 3), ("reserved1", C.c_uint32), ("bmin", C.c_float * 3), ("reserved2", C.c_uint32),
                 ("bmax", C.c_float * 3), ("reserved3", C.c_uint32)]
+
+
+class Xform(C.Structure):
+    _fields_ = [("m", C.c_float * 12), ("sphere_scale", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class XformRange(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("xform", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Material(C.Structure):
@@ -284,6 +292,8 @@ def lib():
         L.p3d_scene_build_grid.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.p3d_scene_export_grid.argtypes = [C.c_void_p, C.POINTER(GridDesc), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
                                             C.POINTER(C.c_uint32)]
+        L.p3d_scene_transform_prims.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -361,6 +371,58 @@ def pathtrace_config(accel=ACCEL_BVH, spp_sqrt=16, max_depth=20, dof=0, **kw):
                 depth_of_field=dof, sample_disk=1, soft_shadows=0)
     base.update(kw)
     return default_config(**base)
+
+
+def _xform_arrays(ranges, xforms, sphere_scale):
+    """(ranges as (n, 3) int64, xforms as (k, 12) float32, sphere_scale as (k,) float32) of the arguments of
+    transformed / DeviceScene.transform_prims"""
+    r = np.asarray(list(ranges), np.int64).reshape(-1, 3)
+    m = np.ascontiguousarray(xforms, np.float32)
+    if m.ndim == 3 and m.shape[1:] == (3, 4):
+        m = m.reshape(-1, 12)
+    if m.ndim != 2 or m.shape[1] != 12:
+        raise ValueError("xforms: an (n, 3, 4) or (n, 12) array is needed, got shape %r" % (m.shape,))
+    sc = np.ones(len(m), np.float32) if sphere_scale is None else np.ascontiguousarray(sphere_scale, np.float32).reshape(-1)
+    if len(sc) != len(m):
+        raise ValueError("sphere_scale: %d values for %d transforms" % (len(sc), len(m)))
+    return r, m, sc
+
+
+def transformed(prim_type, prim_v, ranges, xforms, sphere_scale=None):
+    """What p3d_scene_transform_prims computes for the nine geometry floats, stated in numpy float32, one rounded operation
+    at a time: -> (objects, new_v), the arguments of HostScene.set_geometry that bring a host scene along.  `ranges`: an
+    iterable of (first, count, xform); `xforms`: (n, 3, 4) or (n, 12) float32, row-major; `sphere_scale`: n values, default
+    1.  A point: x' = ((m0 x + m1 y) + m2 z) + m3; the vertices of a triangle, the centre of a sphere (radius' = radius *
+    sphere_scale) and min / max of a box are points.  prim_v holds the REST geometry.  Planes are refused, and boxes unless
+    the transform is a positive scale per axis and a translation."""
+    r, m, sc = _xform_arrays(ranges, xforms, sphere_scale)
+    prim_type = np.asarray(prim_type)
+    v = np.ascontiguousarray(prim_v, np.float32).reshape(-1, 9)
+    objects, rows = [], []
+    for first, count, x in r:
+        if count <= 0 or first < 0 or first + count > len(v) or not 0 <= x < len(m):
+            raise ValueError("transformed: bad range (%d, %d, %d)" % (first, count, x))
+        idx = np.arange(first, first + count)
+        kind = prim_type[idx]
+        if (kind == 3).any():
+            raise ValueError("transformed: range (%d, %d) covers a plane" % (first, count))
+        t = m[x].reshape(3, 4)
+        if (kind == 2).any() and not ((np.diag(t[:, :3]) > 0).all() and (t[:, :3][~np.eye(3, dtype=bool)] == 0).all()):
+            raise ValueError("transformed: range (%d, %d) covers a box, and transform %d is not positive-diagonal" % (first, count, x))
+        out = v[idx].copy()
+        for cols, k in (((0,), 0), ((0, 3, 6), 1), ((0, 3), 2)):
+            sel = kind == k
+            for c in cols:
+                px, py, pz = v[idx, c][sel], v[idx, c + 1][sel], v[idx, c + 2][sel]
+                for row in range(3):
+                    out[sel, c + row] = ((t[row, 0] * px + t[row, 1] * py) + t[row, 2] * pz) + t[row, 3]
+        sph = kind == 0
+        out[sph, 3] = v[idx, 3][sph] * sc[x]
+        objects.append(idx)
+        rows.append(out)
+    if not objects:
+        return np.zeros(0, np.uint32), np.zeros((0, 9), np.float32)
+    return np.concatenate(objects).astype(np.uint32), np.concatenate(rows).astype(np.float32)
 
 
 class HostScene:
@@ -581,6 +643,27 @@ class DeviceScene:
         ms = C.c_float(0)
         _check(self._L.p3d_scene_update_prims(self._h, len(obj), obj.ctypes.data if len(obj) else None,
                                               C.cast(recs, C.c_void_p) if len(obj) else None, int(mode), C.byref(ms)))
+        return ms.value
+
+    def transform_prims(self, ranges, xforms, mode=UPDATE_REFIT, sphere_scale=None):
+        """p3d_scene_transform_prims: the objects of every (first, count, xform) in `ranges` are set, on the device, to
+        xforms[xform] of their REST geometry (what they were created with or last given by update_prims), and the device BVH
+        is refitted or rebuilt.  `xforms`: (n, 3, 4) or (n, 12) float32; `sphere_scale`: n radius factors, default 1.  Waits
+        for the device; returns update_ms.  The bound host scene is not touched: HostScene.set_geometry(*transformed(...)) of
+        the rest prim_v brings it along.  Accumulators of this scene refuse passes until they are reset."""
+        r, m, sc = _xform_arrays(ranges, xforms, sphere_scale)
+        if len(r) and (r.min() < 0 or r.max() > 0xffffffff):
+            raise P3DError(-1, "transform_prims: a range does not fit uint32")
+        rg = (XformRange * max(len(r), 1))()
+        for i, (first, count, x) in enumerate(r):
+            rg[i] = XformRange(int(first), int(count), int(x), 0)
+        xf = (Xform * max(len(m), 1))()
+        for i in range(len(m)):
+            xf[i].m[:] = m[i].tolist()
+            xf[i].sphere_scale = float(sc[i])
+        ms = C.c_float(0)
+        _check(self._L.p3d_scene_transform_prims(self._h, len(r), C.cast(rg, C.c_void_p) if len(r) else None, len(m),
+                                                 C.cast(xf, C.c_void_p) if len(m) else None, int(mode), C.byref(ms)))
         return ms.value
 
     def export_bvh(self):

@@ -1,6 +1,66 @@
-// capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims), and the export of a device-built tree
+// capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims, p3d_scene_transform_prims), and the export of a device-built tree
 #pragma once
 #include "capi_grid.hpp"
+
+namespace {
+
+// What every geometry update does before the scene changes: the waits, the builder's state, and for a refit the topology
+int begin_update(p3d_scene* s, uint32_t mode, const char* who) {
+  P3D_HIP(hipSetDevice(s->device));
+  // enqueued frames read the geometry, the tree and the scene's memos: the tail stream, then the whole device
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  if (int rc = ensure_box_workspace(s, who)) return rc;  // first update: the builder's state
+  lbvh::Workspace& w = s->lbvh_ws;
+  if (mode == P3D_UPDATE_REFIT && !s->lbvh_topology) {
+    // the keys, children and parents of the tree in d_blob, from the boxes it was built from: the build's own first half
+    // (deterministic: unique keys), outside the timed part - a scene pays it once
+    if (hipError_t e = lbvh::enqueue_topology(w, w.boxes); e != hipSuccess)
+      return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": topology: " + hipGetErrorString(e));
+    P3D_HIP(hipDeviceSynchronize());
+    s->lbvh_topology = true;
+  }
+  return P3D_OK;
+}
+
+// What every geometry update does behind the kernel that wrote the new object-order geometry, normals and boxes (`e`: what
+// enqueueing that gave; ev0 is recorded): the BVH, the device-built grid, the waits and the scene's bookkeeping
+int finish_update(p3d_scene* s, uint32_t mode, hipError_t e, const char* who, float* update_ms) {
+  lbvh::Workspace& w = s->lbvh_ws;
+  float4* blob = s->d_blob;
+  if (e == hipSuccess && mode == P3D_UPDATE_REBUILD) {
+    s->lbvh_topology = false;
+    e = lbvh::enqueue_topology(w, w.boxes);
+  }
+  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom);
+  // a device-built grid follows in full, in both modes; if that fails the grid is dropped and the rest of the update stands
+  int grid_rc = P3D_OK;
+  if (e == hipSuccess && s->has_grid) grid_rc = rebuild_grid(s, who);
+  if (e == hipSuccess) e = hipEventRecord(s->ev1, 0);
+  if (e == hipSuccess) e = hipEventSynchronize(s->ev1);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  float ms = 0.0f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, s->ev0, s->ev1);
+  uint32_t depth = 0;
+  float4 root[2];
+  if (e == hipSuccess) e = hipMemcpy(&depth, w.depth, sizeof(depth), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(root, blob + s->off_nodes, sizeof(root), hipMemcpyDeviceToHost);
+  // whatever happened, the old geometry's memos are void
+  ++s->geom_gen;
+  drop_schedules(s);
+  s->ho_chain_key.clear();
+  if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": update: " + hipGetErrorString(e));
+  if (mode == P3D_UPDATE_REBUILD) {
+    s->lbvh_topology = true;
+    s->bvh_max_depth = depth;
+  }
+  s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
+  s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
+  if (update_ms) *update_ms = ms;
+  return grid_rc;  // (rebuild_grid has recorded its message)
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -41,6 +101,7 @@ int p3d_scene_set_camera(p3d_scene* s, const p3d_camera* cam) {
 }
 
 int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, const p3d_prim* prims, uint32_t mode, float* update_ms) {
+  const char* who = "p3d_scene_update_prims";
   if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null scene");
   if (n && (!object || !prims)) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null array with n > 0");
   if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: unknown mode");
@@ -65,28 +126,14 @@ int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, con
   }
   if (update_ms) *update_ms = 0.0f;
   if (n_objs == 0) return P3D_OK;
-  P3D_HIP(hipSetDevice(s->device));
-  // enqueued frames read the geometry, the tree and the scene's memos: the tail stream, then the whole device
-  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
-  P3D_HIP(hipDeviceSynchronize());
-  auto hip_fail = [](const char* what, hipError_t e) { return fail(P3D_ERR_NO_DEVICE, std::string("p3d_scene_update_prims: ") + what + ": " + hipGetErrorString(e)); };
-  if (int rc = ensure_box_workspace(s, "p3d_scene_update_prims")) return rc;  // first update: the builder's state
-  lbvh::Workspace& w = s->lbvh_ws;
-  if (n) {
+  if (n) s->upd_host.assign(n, lbvh::UpdateRecord{});
+  for (uint32_t i = 0; i < n; ++i) {
+    s->upd_host[i].prim = prims[i];
+    s->upd_host[i].object = object[i];
+  }
+  if (int rc = begin_update(s, mode, who)) return rc;
+  if (n)
     if (int rc = s->upd_stage.ensure((size_t)n * sizeof(lbvh::UpdateRecord))) return rc;
-    s->upd_host.assign(n, lbvh::UpdateRecord{});
-    for (uint32_t i = 0; i < n; ++i) {
-      s->upd_host[i].prim = prims[i];
-      s->upd_host[i].object = object[i];
-    }
-  }
-  if (mode == P3D_UPDATE_REFIT && !s->lbvh_topology) {
-    // the keys, children and parents of the tree in d_blob, from the boxes it was built from: the build's own first half
-    // (deterministic: unique keys), outside the timed part - a scene pays it once
-    if (hipError_t e = lbvh::enqueue_topology(w, w.boxes); e != hipSuccess) return hip_fail("topology", e);
-    P3D_HIP(hipDeviceSynchronize());
-    s->lbvh_topology = true;
-  }
   // from here on the scene changes
   float4* blob = s->d_blob;
   hipError_t e = hipEventRecord(s->ev0, 0);
@@ -94,40 +141,98 @@ int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, con
     e = hipMemcpyAsync(s->upd_stage.p, s->upd_host.data(), (size_t)n * sizeof(lbvh::UpdateRecord), hipMemcpyHostToDevice, 0);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(lbvh::scatter_prims, dim3((n + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
-                         (const lbvh::UpdateRecord*)s->upd_stage.p, n, n_objs, blob + s->off_ogeom, blob + s->off_normals, w.boxes);
+                         (const lbvh::UpdateRecord*)s->upd_stage.p, n, n_objs, blob + s->off_ogeom, blob + s->off_normals, s->lbvh_ws.boxes,
+                         (float4*)s->rest.p);
       e = hipGetLastError();
     }
   }
-  if (e == hipSuccess && mode == P3D_UPDATE_REBUILD) {
-    s->lbvh_topology = false;
-    e = lbvh::enqueue_topology(w, w.boxes);
+  return finish_update(s, mode, e, who, update_ms);
+}
+
+int p3d_scene_transform_prims(p3d_scene* s, uint32_t n_ranges, const p3d_xform_range* ranges, uint32_t n_xforms, const p3d_xform* xforms,
+                              uint32_t mode, float* update_ms) {
+  const char* who = "p3d_scene_transform_prims";
+  const std::string pre = std::string(who) + ": ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if ((n_ranges && !ranges) || (n_xforms && !xforms)) return fail(P3D_ERR_INVALID, pre + "null array with a non-zero count");
+  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, pre + "unknown mode");
+  if (!s->device_bvh)
+    return fail(P3D_ERR_INVALID, pre + "the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
+  if (s->uploaded_grid) return fail(P3D_ERR_INVALID, pre + "the scene carries the host's grid, which would go stale");
+  const uint32_t n_objs = s->dev.n_objs;
+  if (n_ranges > n_objs) return fail(P3D_ERR_INVALID, pre + "more ranges than objects (ranges overlap or are empty)");
+  std::vector<uint8_t> diagonal(n_xforms, 0);  // the transform may move a box
+  for (uint32_t x = 0; x < n_xforms; ++x) {
+    const p3d_xform& t = xforms[x];
+    for (int k = 0; k < 12; ++k)
+      if (!std::isfinite(t.m[k])) return fail(P3D_ERR_INVALID, pre + "transform " + std::to_string(x) + " has a non-finite entry");
+    if (!std::isfinite(t.sphere_scale) || !(t.sphere_scale > 0.0f))
+      return fail(P3D_ERR_INVALID, pre + "transform " + std::to_string(x) + ": sphere_scale must be finite and > 0");
+    if (t.reserved[0] | t.reserved[1] | t.reserved[2]) return fail(P3D_ERR_INVALID, pre + "transform " + std::to_string(x) + ": reserved must be 0");
+    diagonal[x] = xform_is_positive_diagonal(t.m) ? 1 : 0;
   }
-  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom);
-  // a device-built grid follows in full, in both modes; if that fails the grid is dropped and the rest of the update stands
-  int grid_rc = P3D_OK;
-  if (e == hipSuccess && s->has_grid) grid_rc = rebuild_grid(s, "p3d_scene_update_prims");
-  if (e == hipSuccess) e = hipEventRecord(s->ev1, 0);
-  if (e == hipSuccess) e = hipEventSynchronize(s->ev1);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  float ms = 0.0f;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, s->ev0, s->ev1);
-  uint32_t depth = 0;
-  float4 root[2];
-  if (e == hipSuccess) e = hipMemcpy(&depth, w.depth, sizeof(depth), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(root, blob + s->off_nodes, sizeof(root), hipMemcpyDeviceToHost);
-  // whatever happened, the old geometry's memos are void
-  ++s->geom_gen;
-  drop_schedules(s);
-  s->ho_chain_key.clear();
-  if (e != hipSuccess) return hip_fail("update", e);
-  if (mode == P3D_UPDATE_REBUILD) {
-    s->lbvh_topology = true;
-    s->bvh_max_depth = depth;
+  // sorted by `first`, with the objects covered in front of each: what the kernel searches
+  std::vector<xform::StagedRange> sorted(n_ranges);
+  for (uint32_t r = 0; r < n_ranges; ++r) {
+    const p3d_xform_range& g = ranges[r];
+    const std::string at = pre + "range " + std::to_string(r);
+    if (g.count == 0) return fail(P3D_ERR_INVALID, at + " is empty");
+    if ((uint64_t)g.first + g.count > n_objs) return fail(P3D_ERR_INVALID, at + " ends behind the last object");
+    if (g.xform >= n_xforms) return fail(P3D_ERR_INVALID, at + " names a transform that is not there");
+    if (g.reserved) return fail(P3D_ERR_INVALID, at + ": reserved must be 0");
+    sorted[r] = xform::StagedRange{g.first, g.count, g.xform, 0u};
   }
-  s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
-  s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
-  if (update_ms) *update_ms = ms;
-  return grid_rc;  // (rebuild_grid has recorded its message)
+  std::sort(sorted.begin(), sorted.end(), [](const xform::StagedRange& a, const xform::StagedRange& b) { return a.first < b.first; });
+  uint32_t total = 0;
+  for (uint32_t r = 0; r < n_ranges; ++r) {
+    xform::StagedRange& g = sorted[r];
+    if (r && sorted[r - 1].first + sorted[r - 1].count > g.first)
+      return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(g.first) + " is in two ranges");
+    g.before = total;
+    total += g.count;  // (disjoint ranges inside n_objs: no overflow)
+    for (uint32_t o = g.first; o < g.first + g.count; ++o) {
+      const uint32_t type = s->obj_tm[o] & 0xffu;
+      if (type == P3D_PRIM_PLANE) return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(o) + " is a plane");
+      if (type == P3D_PRIM_BOX && !diagonal[g.xform])
+        return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(o) + " is a box, and transform " + std::to_string(g.xform) +
+                                         " is not a positive scale per axis and a translation");
+    }
+  }
+  if (update_ms) *update_ms = 0.0f;
+  if (n_objs == 0) return P3D_OK;
+  // one upload: the counter (zero), the ranges, the transforms
+  static_assert(sizeof(p3d_xform) == 64 && sizeof(p3d_xform_range) == 16, "p3d_xform is read as four float4, a range as one uint4");
+  const size_t words = 1 + (size_t)n_ranges + 4 * (size_t)n_xforms;
+  s->xf_host.assign(words, make_uint4(0, 0, 0, 0));
+  if (n_ranges) std::memcpy(s->xf_host.data() + 1, sorted.data(), (size_t)n_ranges * sizeof(uint4));
+  if (n_xforms) std::memcpy(s->xf_host.data() + 1 + n_ranges, xforms, (size_t)n_xforms * sizeof(p3d_xform));
+  if (int rc = begin_update(s, mode, who)) return rc;
+  if (int rc = s->xf_stage.ensure(words * sizeof(uint4))) return rc;
+  if (!s->rest.p) {  // no transform has run: the object-order geometry IS the rest pose
+    const size_t bytes = (size_t)3 * n_objs * sizeof(float4);
+    if (int rc = s->rest.ensure(bytes)) return rc;
+    if (hipError_t e = hipMemcpy(s->rest.p, s->d_blob + s->off_ogeom, bytes, hipMemcpyDeviceToDevice); e != hipSuccess) {
+      s->rest.release();
+      return fail(P3D_ERR_NO_DEVICE, pre + "rest copy: " + hipGetErrorString(e));
+    }
+  }
+  // from here on the scene changes
+  float4* blob = s->d_blob;
+  const uint4* stage = (const uint4*)s->xf_stage.p;
+  hipError_t e = hipEventRecord(s->ev0, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(s->xf_stage.p, s->xf_host.data(), words * sizeof(uint4), hipMemcpyHostToDevice, 0);
+  if (e == hipSuccess && total) {
+    hipLaunchKernelGGL(xform::transform_prims, dim3((total + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
+                       (const float4*)s->rest.p, stage + 1, n_ranges, (const float4*)(stage + 1 + n_ranges), n_xforms, total, n_objs,
+                       blob + s->off_ogeom, blob + s->off_normals, s->lbvh_ws.boxes, (uint32_t*)s->xf_stage.p);
+    e = hipGetLastError();
+  }
+  const int rc = finish_update(s, mode, e, who, update_ms);
+  if (rc == P3D_ERR_NO_DEVICE) return rc;
+  uint32_t skipped = 0;
+  P3D_HIP(hipMemcpy(&skipped, s->xf_stage.p, sizeof(skipped), hipMemcpyDeviceToHost));
+  if (rc || !skipped) return rc;  // (a failed grid rebuild has recorded its message)
+  return fail(P3D_ERR_INVALID, pre + std::to_string(skipped) + " object(s) would have a non-finite or inverted box and keep their geometry; the others are updated");
 }
 
 int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {

@@ -190,7 +190,8 @@ static_assert(sizeof(UpdateRecord) == 112, "UpdateRecord is read as seven float4
 
 // Replaces objects in place: the object-order geometry (packed as create_impl's geom_of packs it), the shading normal and
 // the object's box.  One thread per record; the host has checked that every index is < n_objs and appears once.
-__global__ void scatter_prims(const UpdateRecord* recs, uint32_t n, uint32_t n_objs, float4* ogeom, float4* normals, float4* boxes) {
+// rest: the scene's rest geometry once p3d_scene_transform_prims has made it (else null): a replaced object rests where it is put
+__global__ void scatter_prims(const UpdateRecord* recs, uint32_t n, uint32_t n_objs, float4* ogeom, float4* normals, float4* boxes, float4* rest) {
   const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   const float4* r = reinterpret_cast<const float4*>(recs + i);
@@ -202,6 +203,11 @@ __global__ void scatter_prims(const UpdateRecord* recs, uint32_t n, uint32_t n_o
   ogeom[3 * obj] = a;
   ogeom[3 * obj + 1] = b;
   ogeom[3 * obj + 2] = make_float4(c.x, __uint_as_float(tm), __uint_as_float(obj), 0.f);
+  if (rest) {
+    rest[3 * obj] = a;
+    rest[3 * obj + 1] = b;
+    rest[3 * obj + 2] = make_float4(c.x, __uint_as_float(tm), __uint_as_float(obj), 0.f);
+  }
   normals[obj] = make_float4(d.x, d.y, d.z, 0.f);
   boxes[2 * obj] = make_float4(e.x, e.y, e.z, 0.f);
   boxes[2 * obj + 1] = make_float4(f.x, f.y, f.z, 0.f);

@@ -19,11 +19,7 @@
 namespace p3d {
 
 namespace {
-constexpr float kEpsilon = 0.0001f;                 // scene.h:31 EPSILON
 constexpr float kPi = 3.141592653589793238462f;     // camera.h:13 (float literal)
-
-inline float lo3(float a, float b, float c) { return std::min(std::min(a, b), c); }
-inline float hi3(float a, float b, float c) { return std::max(std::max(a, b), c); }
 }  // namespace
 
 // ---- shapes -----------------------------------------------------------------
@@ -36,12 +32,12 @@ void Sphere::pack(float v[9], float n[3]) const {
 // scene.cpp:12-35: unit normal of (P1-P0)x(P2-P0); bbox grown by EPSILON on every side
 Triangle::Triangle(const Vector& P0, const Vector& P1, const Vector& P2) {
   points[0] = P0; points[1] = P1; points[2] = P2;
-  normal = (P1 - P0) % (P2 - P0);
-  normal.normalize();
-  Min = Vector(lo3(P0.x, P1.x, P2.x) - kEpsilon, lo3(P0.y, P1.y, P2.y) - kEpsilon,
-               lo3(P0.z, P1.z, P2.z) - kEpsilon);
-  Max = Vector(hi3(P0.x, P1.x, P2.x) + kEpsilon, hi3(P0.y, P1.y, P2.y) + kEpsilon,
-               hi3(P0.z, P1.z, P2.z) + kEpsilon);
+  const float v[9] = {P0.x, P0.y, P0.z, P1.x, P1.y, P1.z, P2.x, P2.y, P2.z};
+  float n[3], lo[3], hi[3];
+  triangle_normal_box(v, n, lo, hi);  // (prim_rule.hpp: shared with the device transform)
+  normal = Vector(n[0], n[1], n[2]);
+  Min = Vector(lo[0], lo[1], lo[2]);
+  Max = Vector(hi[0], hi[1], hi[2]);
 }
 void Triangle::pack(float v[9], float n[3]) const {
   for (int k = 0; k < 3; ++k) {

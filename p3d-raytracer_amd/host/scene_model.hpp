@@ -21,6 +21,8 @@
 #include <string>
 #include <vector>
 
+#include "prim_rule.hpp"
+
 struct p3d_scene;  // include/p3d.h: the device-resident scene
 
 namespace p3d {
@@ -162,9 +164,11 @@ class Sphere final : public Object {
  public:
   Sphere(const Vector& c, float r) : center(c), radius(r) {}
   Kind kind() const override { return Kind::Sphere; }
-  AABB GetBoundingBox() const override {  // scene.cpp:194-198
-    const Vector rr(radius, radius, radius);
-    return {center - rr, center + rr};
+  AABB GetBoundingBox() const override {  // scene.cpp:194-198 (prim_rule.hpp: shared with the device transform)
+    const float c[3] = {center.x, center.y, center.z};
+    float lo[3], hi[3];
+    sphere_box(c, radius, lo, hi);
+    return {Vector(lo[0], lo[1], lo[2]), Vector(hi[0], hi[1], hi[2])};
   }
   Vector getCentroid() const override { return center; }
   Vector GetCenter() const { return center; }
