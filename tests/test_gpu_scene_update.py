@@ -13,6 +13,7 @@ import pytest
 
 import p3d_amd as p3d
 from conftest import ROOT, scene_path
+from lbvh_reference import check_boxes
 from oracle import binding as ob
 from scene_update_helpers import PLANE, SPHERE, random_moves, write_moved_p3f
 
@@ -126,27 +127,6 @@ def test_rebuild_is_a_fresh_create(name, paths):
     assert dev.update_prims([], p3d.UPDATE_REBUILD) > 0
     assert_same_tree(dev.export_bvh(), tree, "rebuild of nothing")
     assert_same_frames(frames(dev, name), last, "rebuild of nothing")
-
-
-def check_boxes(tree, a, what):
-    """Every leaf box is the union of its objects' boxes, every inner box the union of its two children: float32 equality"""
-    leaf = (tree["bvh_count_leaf"] & 0x80000000) != 0
-    count = tree["bvh_count_leaf"] & 0x7fffffff
-    index = tree["bvh_index"]
-    seen = np.zeros(len(tree["bvh_order"]), np.int32)
-    for i in range(len(index)):
-        if leaf[i]:
-            objs = tree["bvh_order"][index[i]:index[i] + count[i]]
-            assert len(objs) == count[i] and count[i] >= 1
-            seen[index[i]:index[i] + count[i]] += 1
-            lo, hi = a["prim_bmin"][objs].min(0), a["prim_bmax"][objs].max(0)
-        else:
-            assert index[i] > i and index[i] + 1 < len(index)
-            lo = np.minimum(tree["bvh_bmin"][index[i]], tree["bvh_bmin"][index[i] + 1])
-            hi = np.maximum(tree["bvh_bmax"][index[i]], tree["bvh_bmax"][index[i] + 1])
-        assert np.array_equal(tree["bvh_bmin"][i], lo) and np.array_equal(tree["bvh_bmax"][i], hi), "%s: box of node %d" % (what, i)
-    assert (seen == 1).all(), "%s: the leaves do not partition the leaf order" % what
-    assert sorted(tree["bvh_order"].tolist()) == list(range(a["n_prims"]))
 
 
 @pytest.mark.parametrize("name", WHITTED_SCENES + ["cornell"])
