@@ -457,6 +457,51 @@ int p3d_scene_export_bvh(p3d_scene* scene, p3d_bvh_node* nodes, uint32_t* n_node
                          uint32_t* n_prim_index, uint32_t* max_depth);
 
 /*
+ * The QUALITY of a device-built tree, and a refit that rebuilds by itself.  Detected by the symbols (P3D_ABI_VERSION and
+ * p3d_update_mode are unchanged).  The same scenes as p3d_scene_update_prims.
+ *
+ * The cost is the surface-area estimate with traversal and intersection cost both 1, stated on the tree
+ * p3d_scene_export_bvh returns (float32 boxes):
+ *   A(node) = (dx dy + dy dz) + dz dx,  dx = (double)bmax[0] - (double)bmin[0], dy, dz alike: float64, left to right, no
+ *             contraction
+ *   sah     = (sum over inner nodes A(node) + sum over leaves count(leaf) A(leaf)) / A(root)
+ * The root counts like any node.  A(root) == 0 (or not above 0), or no objects: sah = 0.  One object is one leaf: sah = 1.
+ * The sum is taken on the device in an order that depends on the number of objects alone (no floating-point atomics): the
+ * same tree gives the same bits, on every call and on every scene that holds it.  Against another summation order of the
+ * same terms it differs by rounding only (relative n 2^-53).
+ *
+ * p3d_scene_bvh_cost measures the scene's current tree.  Like p3d_scene_export_bvh it is a host call that WAITS (tail stream,
+ * then the whole device, then for its two short launches and 32 bytes read back).  It allocates the builder's state if the
+ * scene has none; on a scene that was never updated it recovers the topology and runs the fit over the boxes the tree was
+ * built from, which rewrites the node array with the same bits.  It changes no frame, schedule or generation counter.
+ *
+ * p3d_scene_set_auto_rebuild(ratio): 0 = off, the default: every call behaves, and launches, as without it.  With a ratio >= 1
+ * (+inf allowed: measure, never rebuild) an update called with P3D_UPDATE_REFIT, through p3d_scene_update_prims or
+ * p3d_scene_transform_prims, refits, measures the refitted tree, and if sah > ratio * sah_baseline (strict, float64) runs the
+ * builder in the same call.  The result of such a promoted update is, bit for bit, that of the same update called with
+ * P3D_UPDATE_REBUILD; the result of one that is not promoted is that of a plain REFIT.  A device-built grid is rebuilt once,
+ * after the final tree, and *update_ms covers all of it.  P3D_UPDATE_REBUILD is unchanged except that, with the policy on, it
+ * measures the new tree as the new baseline.
+ * sah_baseline is the cost of the tree at the latest of: create, as long as no update has run since (recorded by the first
+ * p3d_scene_bvh_cost; the same holds for any tree that no refit has touched since it was built); an update that ran the
+ * builder with the policy on; the moment the policy was switched on (off -> a ratio; changing the ratio keeps it).  With the
+ * policy off an update voids it (0 = none recorded), and so does switching the policy off.
+ * p3d_scene_auto_rebuild returns the ratio.
+ * Refused with P3D_ERR_INVALID, nothing changed: null arguments; a scene of p3d_scene_create; a ratio that is NaN, negative or
+ * inside (0, 1).
+ */
+typedef struct p3d_bvh_cost {   /* 32 bytes */
+  double sah;                   /* the scene's current tree */
+  double sah_baseline;          /* the tree the policy compares against; 0 = none recorded */
+  uint32_t n_inner, n_leaves;   /* of the exported tree */
+  uint32_t refits_since_build;  /* updates that kept the topology since it was last built */
+  uint32_t last_update_rebuilt; /* 1: the last update ran the builder (REBUILD, or a REFIT the policy promoted) */
+} p3d_bvh_cost;
+int p3d_scene_bvh_cost(p3d_scene* scene, p3d_bvh_cost* out);
+int p3d_scene_set_auto_rebuild(p3d_scene* scene, float ratio);
+int p3d_scene_auto_rebuild(p3d_scene* scene, float* ratio);
+
+/*
  * Moving objects by TRANSFORMS, applied on the device.  Detected by the symbol (P3D_ABI_VERSION is unchanged).  The same
  * scenes as p3d_scene_update_prims, and the same call from the BVH work onwards; what differs is where the new geometry comes
  * from: the caller sends 64 bytes per transform and 16 bytes per range of objects, and a kernel moves the objects and does

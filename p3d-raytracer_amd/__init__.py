@@ -48,6 +48,7 @@ EXPORTS = [
     "p3d_temporal_accumulate", "p3d_temporal_accumulate_device",
     "p3d_scene_update_prims", "p3d_scene_export_bvh", "p3d_host_scene_set_geometry",
     "p3d_scene_build_grid", "p3d_scene_export_grid", "p3d_scene_transform_prims",
+    "p3d_scene_bvh_cost", "p3d_scene_set_auto_rebuild", "p3d_scene_auto_rebuild",
 ]
 
 
@@ -69,6 +70,11 @@ class Xform(C.Structure):
 
 class XformRange(C.Structure):
     _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("xform", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BvhCost(C.Structure):
+    _fields_ = [("sah", C.c_double), ("sah_baseline", C.c_double), ("n_inner", C.c_uint32), ("n_leaves", C.c_uint32),
+                ("refits_since_build", C.c_uint32), ("last_update_rebuilt", C.c_uint32)]
 
 
 class Material(C.Structure):
@@ -294,6 +300,9 @@ def lib():
                                             C.POINTER(C.c_uint32)]
         L.p3d_scene_transform_prims.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                 C.POINTER(C.c_float)]
+        L.p3d_scene_bvh_cost.argtypes = [C.c_void_p, C.POINTER(BvhCost)]
+        L.p3d_scene_set_auto_rebuild.argtypes = [C.c_void_p, C.c_float]
+        L.p3d_scene_auto_rebuild.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -535,6 +544,20 @@ class HostScene:
         return out
 
 
+def tree_cost(tree):
+    """The SAH cost p3d_scene_bvh_cost reports (include/p3d.h), evaluated in float64 on a tree with the bvh_* keys of
+    DeviceScene.export_bvh() or HostScene.arrays(bvh=True): A = (dx dy + dy dz) + dz dx per node, inner nodes count once, a
+    leaf once per object, over A(root).  No nodes or a root without area: 0."""
+    lo, hi = np.asarray(tree["bvh_bmin"], np.float32).reshape(-1, 3), np.asarray(tree["bvh_bmax"], np.float32).reshape(-1, 3)
+    if len(lo) == 0:
+        return 0.0
+    d = hi.astype(np.float64) - lo.astype(np.float64)
+    area = (d[:, 0] * d[:, 1] + d[:, 1] * d[:, 2]) + d[:, 2] * d[:, 0]
+    count_leaf = np.asarray(tree["bvh_count_leaf"], np.uint32)
+    weight = np.where(count_leaf & np.uint32(0x80000000), (count_leaf & np.uint32(0x7fffffff)).astype(np.float64), 1.0)
+    return float((weight * area).sum() / area[0]) if area[0] > 0 else 0.0
+
+
 class DeviceScene:
     """p3d_scene_create: the flattened scene resident in HBM of one MI355X."""
 
@@ -676,6 +699,24 @@ class DeviceScene:
         _check(self._L.p3d_scene_export_bvh(self._h, buf.ctypes.data, C.byref(n), order.ctypes.data, C.byref(m), C.byref(depth)))
         return dict(bvh_bmin=buf[:, 0:3].view(np.float32), bvh_index=buf[:, 3].copy(), bvh_bmax=buf[:, 4:7].view(np.float32),
                     bvh_count_leaf=buf[:, 7].copy(), bvh_order=order, bvh_max_depth=depth.value)
+
+    def bvh_cost(self):
+        """p3d_scene_bvh_cost: the SAH cost of the current device-built tree (tree_cost of export_bvh(), summed on the GPU)
+        -> dict(sah, sah_baseline, n_inner, n_leaves, refits_since_build, last_update_rebuilt).  Waits for the device."""
+        c = BvhCost()
+        _check(self._L.p3d_scene_bvh_cost(self._h, C.byref(c)))
+        return {n: getattr(c, n) for n, _ in c._fields_}
+
+    def set_auto_rebuild(self, ratio):
+        """p3d_scene_set_auto_rebuild: 0 = off (the default); with a ratio >= 1 (inf: never) an UPDATE_REFIT whose refitted tree
+        costs more than ratio x sah_baseline runs the builder in the same call, with the result of UPDATE_REBUILD."""
+        _check(self._L.p3d_scene_set_auto_rebuild(self._h, float(ratio)))
+
+    def auto_rebuild(self):
+        """p3d_scene_auto_rebuild: the ratio, 0 = off."""
+        r = C.c_float(0)
+        _check(self._L.p3d_scene_auto_rebuild(self._h, C.byref(r)))
+        return r.value
 
     def build_grid(self):
         """p3d_scene_build_grid: builds (or builds again) the uniform grid on the GPU from the scene's current object boxes - the

@@ -133,6 +133,12 @@ struct p3d_scene {
   std::vector<float4> create_boxes;    // the object boxes the tree was built from, until the first update moves them to the device
   lbvh::Workspace lbvh_ws;             // allocated by the first update: object boxes and the topology of the tree in d_blob
   bool lbvh_topology = false;          // lbvh_ws.sorted / children / parent describe the tree in d_blob
+  bool lbvh_fitted = false;            // ... and lbvh_ws.node_box holds its boxes: lbvh::enqueue_cost may run
+  // p3d_scene_bvh_cost, p3d_scene_set_auto_rebuild (the same scenes)
+  float auto_rebuild = 0.0f;           // 0: off; otherwise a REFIT whose tree costs more than this x sah_baseline rebuilds
+  double sah_baseline = 0.0;           // 0: none recorded
+  uint32_t refits_since_build = 0;
+  bool last_update_rebuilt = false;
   Scratch upd_stage;                   // lbvh::UpdateRecord[n] of the update in progress
   std::vector<lbvh::UpdateRecord> upd_host;
   // p3d_scene_transform_prims (the same scenes)

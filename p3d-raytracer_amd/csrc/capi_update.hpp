@@ -23,16 +23,56 @@ int begin_update(p3d_scene* s, uint32_t mode, const char* who) {
   return P3D_OK;
 }
 
+// sah of include/p3d.h from what the cost kernels left
+double sah_of(const lbvh::CostResult& c) { return c.root_area > 0.0 ? c.sum / c.root_area : 0.0; }
+
+// The cost of the tree lbvh_ws describes, behind whatever is enqueued on the null stream; waits for it
+hipError_t read_cost(lbvh::Workspace& w, lbvh::CostResult* out) {
+  if (hipError_t e = lbvh::enqueue_cost(w); e != hipSuccess) return e;
+  return hipMemcpy(out, w.cost_result, sizeof(*out), hipMemcpyDeviceToHost);
+}
+
+// The builder's state describes the tree in d_blob, boxes included.  A scene that was never updated recovers the topology and
+// runs the fit over the boxes the tree was built from: the node array is rewritten with the same bits.  The device is idle.
+int ensure_fitted_workspace(p3d_scene* s, const char* who) {
+  if (int rc = ensure_box_workspace(s, who)) return rc;
+  lbvh::Workspace& w = s->lbvh_ws;
+  if (s->lbvh_topology && s->lbvh_fitted) return P3D_OK;
+  hipError_t e = hipSuccess;
+  if (!s->lbvh_topology) e = lbvh::enqueue_topology(w, w.boxes);
+  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, s->d_blob + s->off_ogeom, s->d_blob + s->off_nodes, s->d_blob + s->off_bgeom);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": fit: " + hipGetErrorString(e));
+  s->lbvh_topology = s->lbvh_fitted = true;
+  return P3D_OK;
+}
+
 // What every geometry update does behind the kernel that wrote the new object-order geometry, normals and boxes (`e`: what
-// enqueueing that gave; ev0 is recorded): the BVH, the device-built grid, the waits and the scene's bookkeeping
+// enqueueing that gave; ev0 is recorded): the BVH, the device-built grid, the waits and the scene's bookkeeping.
+// With p3d_scene_set_auto_rebuild on, a REFIT reads the cost of the refitted tree back and runs the builder in the same
+// call if it has grown past the ratio; the grid is built once, over the final tree's boxes.
 int finish_update(p3d_scene* s, uint32_t mode, hipError_t e, const char* who, float* update_ms) {
   lbvh::Workspace& w = s->lbvh_ws;
   float4* blob = s->d_blob;
-  if (e == hipSuccess && mode == P3D_UPDATE_REBUILD) {
+  const bool policy = s->auto_rebuild > 0.0f;
+  bool rebuilt = mode == P3D_UPDATE_REBUILD;
+  auto build = [&]() {
     s->lbvh_topology = false;
     e = lbvh::enqueue_topology(w, w.boxes);
+  };
+  auto fit = [&]() { e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom); };
+  if (e == hipSuccess && rebuilt) build();
+  if (e == hipSuccess) fit();
+  lbvh::CostResult cost{};
+  if (e == hipSuccess && policy && !rebuilt) {
+    e = read_cost(w, &cost);
+    if (e == hipSuccess && sah_of(cost) > (double)s->auto_rebuild * s->sah_baseline) {  // (+inf x 0 is NaN: never)
+      rebuilt = true;
+      build();
+      if (e == hipSuccess) fit();
+    }
   }
-  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom);
+  if (e == hipSuccess && policy && rebuilt) e = read_cost(w, &cost);  // the new baseline
   // a device-built grid follows in full, in both modes; if that fails the grid is dropped and the rest of the update stands
   int grid_rc = P3D_OK;
   if (e == hipSuccess && s->has_grid) grid_rc = rebuild_grid(s, who);
@@ -49,15 +89,31 @@ int finish_update(p3d_scene* s, uint32_t mode, hipError_t e, const char* who, fl
   ++s->geom_gen;
   drop_schedules(s);
   s->ho_chain_key.clear();
+  s->lbvh_fitted = e == hipSuccess;
   if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": update: " + hipGetErrorString(e));
-  if (mode == P3D_UPDATE_REBUILD) {
+  if (rebuilt) {
     s->lbvh_topology = true;
     s->bvh_max_depth = depth;
   }
+  s->last_update_rebuilt = rebuilt;
+  s->refits_since_build = rebuilt ? 0u : s->refits_since_build + 1u;
+  // with the policy off nothing was measured: what was recorded for the old boxes is void
+  s->sah_baseline = !policy ? 0.0 : rebuilt ? sah_of(cost) : s->sah_baseline;
   s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
   s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
   if (update_ms) *update_ms = ms;
   return grid_rc;  // (rebuild_grid has recorded its message)
+}
+
+// What p3d_scene_bvh_cost and p3d_scene_set_auto_rebuild share: the waits, the builder's state, the two launches, 32 bytes back
+int measure_cost(p3d_scene* s, const char* who, lbvh::CostResult* out) {
+  P3D_HIP(hipSetDevice(s->device));
+  if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
+  P3D_HIP(hipDeviceSynchronize());
+  if (int rc = ensure_fitted_workspace(s, who)) return rc;
+  if (hipError_t e = read_cost(s->lbvh_ws, out); e != hipSuccess)
+    return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": cost: " + hipGetErrorString(e));
+  return P3D_OK;
 }
 
 }  // namespace
@@ -291,6 +347,51 @@ int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, u
     return fail(P3D_ERR_CAPACITY, "p3d_scene_export_bvh: the arrays are too small (call with nodes = NULL for the sizes)");
   std::memcpy(nodes, out.data(), out.size() * sizeof(p3d_bvh_node));
   for (uint32_t i = 0; i < n; ++i) std::memcpy(&prim_index[i], &geom[3 * (size_t)i + 2].z, 4);  // geom_of: the object index
+  return P3D_OK;
+}
+
+int p3d_scene_bvh_cost(p3d_scene* s, p3d_bvh_cost* out) {
+  if (!s || !out) return fail(P3D_ERR_INVALID, "p3d_scene_bvh_cost: null argument");
+  if (!s->device_bvh) return fail(P3D_ERR_INVALID, "p3d_scene_bvh_cost: the scene was not created by p3d_scene_create_device_bvh");
+  p3d_bvh_cost c{};
+  if (s->dev.n_objs) {
+    lbvh::CostResult r{};
+    if (int rc = measure_cost(s, "p3d_scene_bvh_cost", &r)) return rc;
+    c.sah = sah_of(r);
+    c.n_inner = r.n_inner;
+    c.n_leaves = r.n_leaves;
+    // a tree that no refit has touched since it was built is its own baseline
+    if (s->sah_baseline == 0.0 && s->refits_since_build == 0) s->sah_baseline = c.sah;
+  }
+  c.sah_baseline = s->sah_baseline;
+  c.refits_since_build = s->refits_since_build;
+  c.last_update_rebuilt = s->last_update_rebuilt ? 1u : 0u;
+  *out = c;
+  return P3D_OK;
+}
+
+int p3d_scene_set_auto_rebuild(p3d_scene* s, float ratio) {
+  if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_set_auto_rebuild: null scene");
+  if (!s->device_bvh) return fail(P3D_ERR_INVALID, "p3d_scene_set_auto_rebuild: the scene was not created by p3d_scene_create_device_bvh");
+  if (!(ratio == 0.0f || ratio >= 1.0f)) return fail(P3D_ERR_INVALID, "p3d_scene_set_auto_rebuild: the ratio must be 0 (off) or >= 1");
+  if (ratio == 0.0f) {
+    s->auto_rebuild = 0.0f;
+    s->sah_baseline = 0.0;
+    return P3D_OK;
+  }
+  if (s->auto_rebuild == 0.0f && s->dev.n_objs) {  // switched on: the tree of this moment is what later refits are compared with
+    lbvh::CostResult r{};
+    if (int rc = measure_cost(s, "p3d_scene_set_auto_rebuild", &r)) return rc;
+    s->sah_baseline = sah_of(r);
+  }
+  s->auto_rebuild = ratio;
+  return P3D_OK;
+}
+
+int p3d_scene_auto_rebuild(p3d_scene* s, float* ratio) {
+  if (!s || !ratio) return fail(P3D_ERR_INVALID, "p3d_scene_auto_rebuild: null argument");
+  if (!s->device_bvh) return fail(P3D_ERR_INVALID, "p3d_scene_auto_rebuild: the scene was not created by p3d_scene_create_device_bvh");
+  *ratio = s->auto_rebuild;
   return P3D_OK;
 }
 

@@ -180,6 +180,87 @@ __global__ void emit(const unsigned long long* keys, uint32_t n, const uint2* ch
   }
 }
 
+// ---- SAH cost of the emitted tree -------------------------------------------------------------------------------------------
+// sah = (sum over inner nodes A(node) + sum over leaves count(leaf) * A(leaf)) / A(root), stated on the tree
+// p3d_scene_export_bvh returns (include/p3d.h).  The sum decides whether a refitted tree is rebuilt, and the tree's shape is
+// observable in frames, so it must be a function of the workspace arrays alone: no floating-point atomics, every addition in
+// an order the launch geometry fixes.
+
+// (dx dy + dy dz) + dz dx of a box, float64, left to right, no fused multiply-add
+__device__ __forceinline__ double half_area(const float4 lo, const float4 hi) {
+#pragma clang fp contract(off)
+  const double dx = (double)hi.x - (double)lo.x, dy = (double)hi.y - (double)lo.y, dz = (double)hi.z - (double)lo.z;
+  const double xy = dx * dy, yz = dy * dz, zx = dz * dx;
+  return (xy + yz) + zx;
+}
+
+// Sum of one value per thread of a kThreads block, in a fixed order: inside each wave lane l takes lane l + 32, + 16, ... + 1,
+// then thread 0 adds the four wave sums from LDS in wave order.  The result is valid in thread 0.  Every thread of the
+// block must call it.
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T* wave_sums) {
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63u) == 0) wave_sums[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T total = wave_sums[0];
+  for (int w = 1; w < kThreads / 64; ++w) total += wave_sums[w];
+  __syncthreads();  // (wave_sums may be written again)
+  return total;
+}
+
+// {sum, A(root), n_inner, n_leaves} of the emitted tree, and the pairs counter the first launch adds into (integers: exact)
+struct CostResult {
+  double sum, root_area;
+  uint32_t n_inner, n_leaves, pairs, pad;
+};
+static_assert(sizeof(CostResult) == 32, "read back as 32 bytes");
+
+// One thread per Karras internal node, as emit sees it: a node with two leaf children is ONE leaf of two objects (2 A(node),
+// its children nothing), any other is an inner node (A(node)) plus A(child) for each child that is a single-object leaf.
+// partials[block] = the block's terms summed by block_sum; result->pairs += its nodes of the first kind (zeroed before)
+__global__ void cost_partials(uint32_t n, const uint2* children, const float4* node_box, double* partials, CostResult* result) {
+  __shared__ double wave_sums[kThreads / 64];
+  __shared__ uint32_t wave_pairs[kThreads / 64];
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  double term = 0.0;
+  uint32_t pair = 0;
+  if (n == 1) {
+    if (i == 0) term = half_area(node_box[2], node_box[3]);  // the root is the only leaf (reference value 1)
+  } else if (i < n - 1) {
+    const uint2 ch = children[i];
+    const double a = half_area(node_box[4 * (size_t)i], node_box[4 * (size_t)i + 1]);
+    if (ch.x & ch.y & 1u) {
+      pair = 1;
+      term = 2.0 * a;
+    } else {
+      term = a;
+      if (ch.x & 1u) term += half_area(node_box[2 * (size_t)ch.x], node_box[2 * (size_t)ch.x + 1]);
+      if (ch.y & 1u) term += half_area(node_box[2 * (size_t)ch.y], node_box[2 * (size_t)ch.y + 1]);
+    }
+  }
+  const double s = block_sum(term, wave_sums);
+  const uint32_t p = block_sum(pair, wave_pairs);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = s;
+    if (p) atomicAdd(&result->pairs, p);
+  }
+}
+
+// One block: thread t adds partials[t], [t + kThreads], ... in index order, block_sum adds the threads
+__global__ void cost_final(uint32_t n, uint32_t n_partials, const double* partials, const float4* node_box, CostResult* result) {
+  __shared__ double wave_sums[kThreads / 64];
+  double v = 0.0;
+  for (uint32_t k = threadIdx.x; k < n_partials; k += kThreads) v += partials[k];
+  const double s = block_sum(v, wave_sums);
+  if (threadIdx.x == 0) {
+    const uint32_t root = n == 1 ? 1u : 0u;
+    result->sum = s;
+    result->root_area = half_area(node_box[2 * root], node_box[2 * root + 1]);
+    result->n_leaves = n - result->pairs;
+    result->n_inner = n - 1 - result->pairs;
+  }
+}
+
 // One object of p3d_scene_update_prims as it is staged for scatter_prims: the caller's record and the object it replaces
 struct UpdateRecord {
   p3d_prim prim;
@@ -235,9 +316,12 @@ struct Workspace {
   uint2* children = nullptr;
   uint32_t *parent = nullptr, *visits = nullptr, *depth = nullptr;
   float4* node_box = nullptr;
+  double* cost_partials = nullptr;  // one per block of enqueue_cost's first launch
+  CostResult* cost_result = nullptr;
   void* temp = nullptr;
   size_t temp_bytes = 0;
 
+  static uint32_t cost_blocks(uint32_t n_objs) { return n_objs > 1 ? (n_objs - 1 + kThreads - 1) / kThreads : 1; }
   hipError_t alloc(uint32_t n_objs, bool with_boxes) {
     n = n_objs;
     if (with_boxes) P3D_LBVH_HIP(hipMalloc((void**)&boxes, (size_t)2 * n * sizeof(float4)));
@@ -249,13 +333,15 @@ struct Workspace {
     P3D_LBVH_HIP(hipMalloc((void**)&visits, (size_t)n * sizeof(uint32_t)));
     P3D_LBVH_HIP(hipMalloc((void**)&depth, sizeof(uint32_t)));
     P3D_LBVH_HIP(hipMalloc((void**)&node_box, (size_t)4 * n * sizeof(float4)));
+    P3D_LBVH_HIP(hipMalloc((void**)&cost_partials, (size_t)cost_blocks(n) * sizeof(double)));
+    P3D_LBVH_HIP(hipMalloc((void**)&cost_result, sizeof(CostResult)));
     P3D_LBVH_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, temp_bytes, keys, sorted, (int)n));
     P3D_LBVH_HIP(hipMalloc(&temp, temp_bytes ? temp_bytes : 16));
     return hipSuccess;
   }
   void release() {
     for (void* p : {(void*)boxes, (void*)bounds, (void*)keys, (void*)sorted, (void*)children, (void*)parent, (void*)visits,
-                    (void*)depth, (void*)node_box, temp})
+                    (void*)depth, (void*)node_box, (void*)cost_partials, (void*)cost_result, temp})
       if (p) (void)hipFree(p);
     *this = Workspace{};
   }
@@ -280,6 +366,15 @@ inline hipError_t enqueue_fit(Workspace& w, const float4* d_boxes, const float4*
   P3D_LBVH_HIP(hipMemsetAsync(w.depth, 0, sizeof(uint32_t), 0));
   hipLaunchKernelGGL(refit, dim3(blocks), dim3(kThreads), 0, 0, w.sorted, d_boxes, n, w.children, w.parent, w.visits, w.node_box, w.depth);
   hipLaunchKernelGGL(emit, dim3(blocks), dim3(kThreads), 0, 0, w.sorted, n, w.children, w.node_box, d_ogeom, d_nodes, d_bgeom);
+  return hipGetLastError();
+}
+
+// The cost of the tree enqueue_fit has just emitted from w (children, node_box) -> w.cost_result, behind it on the null stream
+inline hipError_t enqueue_cost(Workspace& w) {
+  const uint32_t n = w.n, blocks = Workspace::cost_blocks(n);
+  P3D_LBVH_HIP(hipMemsetAsync(w.cost_result, 0, sizeof(CostResult), 0));
+  hipLaunchKernelGGL(cost_partials, dim3(blocks), dim3(kThreads), 0, 0, n, w.children, w.node_box, w.cost_partials, w.cost_result);
+  hipLaunchKernelGGL(cost_final, dim3(1), dim3(kThreads), 0, 0, n, blocks, w.cost_partials, w.node_box, w.cost_result);
   return hipGetLastError();
 }
 
