@@ -546,6 +546,57 @@ int p3d_scene_transform_prims(p3d_scene* scene, uint32_t n_ranges, const p3d_xfo
                               const p3d_xform* xforms, uint32_t mode, float* update_ms);
 
 /*
+ * New geometry for triangles and spheres FROM DEVICE MEMORY: a deforming mesh or a particle set that a GPU program keeps
+ * (positions [V, 3] and indices [F, 3], or centres and radii [N, 4]) goes into the scene with one kernel and no host round
+ * trip.  Detected by the symbol (P3D_ABI_VERSION and p3d_update_mode are unchanged).  The same scenes as
+ * p3d_scene_update_prims, and the same call from the BVH work onwards.
+ *
+ * Every object of sources[i] = [first, first + count) gets its nine geometry floats from the buffers: triangle k of a source
+ * takes the positions d_index[3k], d_index[3k + 1], d_index[3k + 2] of d_data (without d_index: 3k, 3k + 1, 3k + 2), sphere k
+ * takes d_data[4k .. 4k + 3].  The kernel computes the triangle normal and box, or the sphere box, with the arithmetic of the
+ * host's constructors (host/prim_rule.hpp) and writes what p3d_scene_update_prims writes - geometry, shading normal, box,
+ * and the rest copy of p3d_scene_transform_prims if the scene has one (a deformed object rests where it is put).  Type,
+ * material and index of an object stay.  The result is, bit for bit, what p3d_host_scene_set_geometry +
+ * p3d_scene_update_prims give for the same numbers, with one exception: the normal of a zero-area triangle is NaN on both
+ * routes and its bit pattern (sign, payload) is unspecified.  The bound host scene is not touched.
+ *
+ * Ordering.  Like every update the call WAITS before its kernel: for the scene's tail stream, then for the whole device.
+ * Whatever any stream of this device had enqueued to fill the buffers before the call has therefore finished; that is why
+ * there is no stream argument (a stream could only promise less).  The buffers are only read, and they may be freed or
+ * overwritten once the call returns.  Modes, the auto-rebuild policy, the device-grid rebuild inside *update_ms, the
+ * forgotten schedules and row chains, the root box and accumulators refusing passes until reset are those of
+ * p3d_scene_update_prims; p3d_temporal knows nothing of it.  n_sources = 0 is allowed and behaves like
+ * p3d_scene_update_prims with n = 0; a scene without objects returns P3D_OK.  The staging for the source table grows when
+ * needed and is kept: a second call of the same size allocates nothing.
+ *
+ * Per-object failures, found by the kernel: a triangle with an index >= n_elems (checked before anything is read through
+ * it: nothing outside [0, n_elems) of d_data or [0, 3 count) of d_index is ever read), and an object whose new box is
+ * non-finite or inverted (a NaN or infinite position, a negative or NaN radius).  Such an object is NOT written and keeps its
+ * current geometry; the others are updated, the BVH and grid work runs, and the call returns P3D_ERR_INVALID with the two
+ * counts, separately, in p3d_last_error.
+ * Refused with P3D_ERR_INVALID, nothing changed, before any launch: a null scene; a scene of p3d_scene_create; a scene with an
+ * uploaded grid; an unknown mode; NULL sources with n_sources > 0; a source with count = 0, with first + count > the object
+ * count, with a kind other than P3D_PRIM_TRIANGLE / P3D_PRIM_SPHERE, or that covers an object of another type; NULL d_data;
+ * d_data or d_index not 4-byte aligned; d_index given for spheres; n_elems = 0; a soup with n_elems != 3 count; spheres with
+ * n_elems != count; reserved != 0; sources that overlap (their order is free).  A d_data or d_index that the HIP runtime
+ * identifies as host memory (registered or not), or as memory of another device, is refused too, and so is a buffer that
+ * ends behind the allocation the runtime reports for it.  A pointer the runtime cannot answer for is let through.
+ */
+typedef struct p3d_geom_source {  /* 48 bytes */
+  uint32_t first, count;     /* objects [first, first + count), all of type `kind` */
+  uint32_t kind;             /* P3D_PRIM_TRIANGLE or P3D_PRIM_SPHERE */
+  uint32_t n_elems;          /* triangles: number of positions in d_data; spheres: must equal count */
+  const void* d_data;        /* DEVICE memory, float32, 4-byte aligned.  triangles: n_elems x 3 (x y z);
+                                spheres: count x 4 (centre x y z, radius) */
+  const uint32_t* d_index;   /* triangles only, DEVICE memory, count x 3: triangle k has positions d_index[3k..3k+2].
+                                NULL = soup: triangle k has positions 3k, 3k+1, 3k+2, and n_elems must equal 3 * count.
+                                Must be NULL for spheres. */
+  uint64_t reserved[2];      /* must be 0 */
+} p3d_geom_source;
+int p3d_scene_update_geometry_device(p3d_scene* scene, uint32_t n_sources, const p3d_geom_source* sources,
+                                     uint32_t mode, float* update_ms);
+
+/*
  * The uniform grid of a live scene, built on the device.  Detected by the symbols (P3D_ABI_VERSION is unchanged).  Only for
  * scenes of p3d_scene_create_device_bvh, which keep their objects' boxes on the device and accept updates.
  *

@@ -49,6 +49,7 @@ EXPORTS = [
     "p3d_scene_update_prims", "p3d_scene_export_bvh", "p3d_host_scene_set_geometry",
     "p3d_scene_build_grid", "p3d_scene_export_grid", "p3d_scene_transform_prims",
     "p3d_scene_bvh_cost", "p3d_scene_set_auto_rebuild", "p3d_scene_auto_rebuild",
+    "p3d_scene_update_geometry_device",
 ]
 
 
@@ -70,6 +71,11 @@ class Xform(C.Structure):
 
 class XformRange(C.Structure):
     _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("xform", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GeomSource(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("kind", C.c_uint32), ("n_elems", C.c_uint32),
+                ("d_data", C.c_void_p), ("d_index", C.c_void_p), ("reserved", C.c_uint64 * 2)]
 
 
 class BvhCost(C.Structure):
@@ -303,6 +309,7 @@ def lib():
         L.p3d_scene_bvh_cost.argtypes = [C.c_void_p, C.POINTER(BvhCost)]
         L.p3d_scene_set_auto_rebuild.argtypes = [C.c_void_p, C.c_float]
         L.p3d_scene_auto_rebuild.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.p3d_scene_update_geometry_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -432,6 +439,67 @@ def transformed(prim_type, prim_v, ranges, xforms, sphere_scale=None):
     if not objects:
         return np.zeros(0, np.uint32), np.zeros((0, 9), np.float32)
     return np.concatenate(objects).astype(np.uint32), np.concatenate(rows).astype(np.float32)
+
+
+def deformed(prim_v, first, positions, indices=None):
+    """The host route of DeviceScene.update_triangles, a plain gather in numpy: triangle first + k takes the positions
+    indices[k] of `positions` ((V, 3) float32), or 3k, 3k + 1, 3k + 2 without indices -> (objects, rows), the arguments of
+    HostScene.set_geometry that bring a host scene along.  prim_v (the scene's (n, 9) geometry) bounds the range."""
+    pos = np.ascontiguousarray(positions, np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError("deformed: positions must be (V, 3), got shape %r" % (pos.shape,))
+    if indices is None:
+        if len(pos) % 3:
+            raise ValueError("deformed: a soup needs 3 positions per triangle, got %d" % len(pos))
+        idx = np.arange(len(pos), dtype=np.int64).reshape(-1, 3)
+    else:
+        idx = np.asarray(indices)
+        if idx.ndim != 2 or idx.shape[1] != 3 or idx.dtype.kind not in "iu":
+            raise ValueError("deformed: indices must be an integer (F, 3) array")
+        idx = idx.astype(np.uint32).astype(np.int64) if idx.dtype.itemsize == 4 else idx.astype(np.int64)
+        if len(idx) and (idx.min() < 0 or idx.max() >= len(pos)):
+            raise ValueError("deformed: an index is outside the %d positions" % len(pos))
+    n = len(np.asarray(prim_v).reshape(-1, 9))
+    if first < 0 or len(idx) == 0 or first + len(idx) > n:
+        raise ValueError("deformed: objects [%d, %d) of %d" % (first, first + len(idx), n))
+    return np.arange(first, first + len(idx), dtype=np.uint32), np.ascontiguousarray(pos[idx].reshape(-1, 9))
+
+
+def deformed_spheres(prim_v, first, centre_radius):
+    """The host route of DeviceScene.update_spheres: sphere first + k takes centre and radius centre_radius[k] ((N, 4)
+    float32), the other five floats of its row stay -> (objects, rows) for HostScene.set_geometry."""
+    cr = np.ascontiguousarray(centre_radius, np.float32)
+    if cr.ndim != 2 or cr.shape[1] != 4:
+        raise ValueError("deformed_spheres: centre_radius must be (N, 4), got shape %r" % (cr.shape,))
+    v = np.ascontiguousarray(prim_v, np.float32).reshape(-1, 9)
+    if first < 0 or len(cr) == 0 or first + len(cr) > len(v):
+        raise ValueError("deformed_spheres: objects [%d, %d) of %d" % (first, first + len(cr), len(v)))
+    rows = v[first:first + len(cr)].copy()
+    rows[:, :4] = cr
+    return np.arange(first, first + len(cr), dtype=np.uint32), rows
+
+
+def _device_rows(x, what, cols, dtypes, device):
+    """(address, rows) of a contiguous (rows, cols) CUDA/HIP torch.Tensor of one of `dtypes` on `device`, or of a raw
+    (address, rows) pair, which is taken at its word.  Anything else: P3DError, and the library is not called."""
+    if isinstance(x, tuple) and len(x) == 2 and not hasattr(x[0], "data_ptr"):
+        ptr, rows = int(x[0]), int(x[1])
+        if ptr <= 0 or rows <= 0:
+            raise P3DError(-1, "%s: a raw pair needs an address and a row count > 0" % what)
+        return ptr, rows
+    if not (hasattr(x, "data_ptr") and hasattr(x, "is_cuda")):
+        raise P3DError(-1, "%s: a CUDA/HIP torch.Tensor or an (address, rows) pair is needed, got %s" % (what, type(x).__name__))
+    if str(x.dtype).replace("torch.", "") not in dtypes:
+        raise P3DError(-1, "%s: dtype %s, needed: %s" % (what, x.dtype, " or ".join(dtypes)))
+    if x.dim() != 2 or x.shape[1] != cols or x.shape[0] == 0:
+        raise P3DError(-1, "%s: shape %r, needed: (n, %d) with n > 0" % (what, tuple(x.shape), cols))
+    if not x.is_contiguous():
+        raise P3DError(-1, "%s: the tensor is not contiguous" % what)
+    if not x.is_cuda:
+        raise P3DError(-1, "%s: the tensor is in host memory (device %s)" % (what, x.device))
+    if x.device.index is not None and x.device.index != device:
+        raise P3DError(-1, "%s: the tensor is on device %d, the scene on device %d" % (what, x.device.index, device))
+    return int(x.data_ptr()), int(x.shape[0])
 
 
 class HostScene:
@@ -688,6 +756,51 @@ class DeviceScene:
         _check(self._L.p3d_scene_transform_prims(self._h, len(r), C.cast(rg, C.c_void_p) if len(r) else None, len(m),
                                                  C.cast(xf, C.c_void_p) if len(m) else None, int(mode), C.byref(ms)))
         return ms.value
+
+    def triangle_source(self, first, positions, indices=None):
+        """A GeomSource for update_geometry_device: triangles first, first + 1, ... from `positions` (float32 (V, 3)) and
+        `indices` (int32 or uint32 (F, 3); None = a soup of V / 3 triangles), each a contiguous CUDA/HIP torch.Tensor on the
+        scene's device or a raw (address, rows) pair.  Keep the tensors alive until the update has returned."""
+        d_pos, n_pos = _device_rows(positions, "positions", 3, ("float32",), self.device)
+        if indices is None:
+            if n_pos % 3:
+                raise P3DError(-1, "positions: a soup needs 3 positions per triangle, got %d" % n_pos)
+            return GeomSource(int(first), n_pos // 3, 1, n_pos, d_pos, None)
+        d_idx, n_tri = _device_rows(indices, "indices", 3, ("int32", "uint32"), self.device)
+        return GeomSource(int(first), n_tri, 1, n_pos, d_pos, d_idx)
+
+    def sphere_source(self, first, centre_radius):
+        """A GeomSource for update_geometry_device: spheres first, first + 1, ... from a float32 (N, 4) tensor of centres and
+        radii (or a raw (address, rows) pair)."""
+        d_cr, n = _device_rows(centre_radius, "centre_radius", 4, ("float32",), self.device)
+        return GeomSource(int(first), n, 0, n, d_cr, None)
+
+    def update_geometry_device(self, sources, mode=UPDATE_REFIT):
+        """p3d_scene_update_geometry_device: the objects of every GeomSource in `sources` (raw device addresses; see
+        triangle_source / sphere_source) take their nine geometry floats from device memory, normals and boxes are computed on
+        the device as the host's constructors compute them, and the device BVH is refitted or rebuilt.  Waits for the device -
+        work that any stream had enqueued to fill the buffers has finished before they are read; returns update_ms.  The bound
+        host scene is not touched: HostScene.set_geometry(*deformed(...)) brings it along.  Accumulators of this scene refuse
+        passes until they are reset."""
+        src = list(sources)
+        arr = (GeomSource * max(len(src), 1))(*src)
+        ms = C.c_float(0)
+        _check(self._L.p3d_scene_update_geometry_device(self._h, len(src), C.cast(arr, C.c_void_p) if src else None, int(mode), C.byref(ms)))
+        return ms.value
+
+    def update_triangles(self, first, positions=None, indices=None, mode=UPDATE_REFIT):
+        """Triangles first, first + 1, ... from a float32 (V, 3) position tensor and an int32 / uint32 (F, 3) index tensor on
+        the scene's device (F objects), or from positions alone (V / 3 objects); raw (address, rows) pairs are taken too.
+        Several meshes in one call: update_triangles([(first, positions), (first, positions, indices), ...], mode=...).
+        A tensor on the host, of another dtype or shape, or not contiguous raises P3DError before the library is called."""
+        meshes = first if isinstance(first, list) else [(first, positions, indices)]
+        return self.update_geometry_device([self.triangle_source(*m) for m in meshes], mode)
+
+    def update_spheres(self, first, centre_radius=None, mode=UPDATE_REFIT):
+        """Spheres first, first + 1, ... from a float32 (N, 4) tensor of centres and radii on the scene's device; or a list
+        of (first, centre_radius) for several sets in one call."""
+        sets = first if isinstance(first, list) else [(first, centre_radius)]
+        return self.update_geometry_device([self.sphere_source(*m) for m in sets], mode)
 
     def export_bvh(self):
         """p3d_scene_export_bvh: the current device-built tree as numpy arrays, with the bvh_* keys of HostScene.arrays(bvh=True)

@@ -1,4 +1,5 @@
-// capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims, p3d_scene_transform_prims), and the export of a device-built tree
+// capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims, p3d_scene_transform_prims,
+// p3d_scene_update_geometry_device), and the export of a device-built tree
 #pragma once
 #include "capi_grid.hpp"
 
@@ -103,6 +104,30 @@ int finish_update(p3d_scene* s, uint32_t mode, hipError_t e, const char* who, fl
   s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
   if (update_ms) *update_ms = ms;
   return grid_rc;  // (rebuild_grid has recorded its message)
+}
+
+// A caller's buffer that a kernel of scene `s` is about to read: refused if the runtime says it is host memory (pinned, or
+// memory it has never seen) or memory of another device, or if it reports the allocation and the buffer ends behind it.  A
+// pointer the runtime cannot answer for is let through: an allocator may hand out memory the queries do not know.
+int device_buffer_usable(const p3d_scene* s, const void* p, size_t bytes, const std::string& what) {
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return P3D_OK;
+  }
+  if (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeUnregistered) return fail(P3D_ERR_INVALID, what + " is host memory");
+  if (attr.type == hipMemoryTypeDevice && attr.device != s->device)
+    return fail(P3D_ERR_INVALID, what + " is memory of device " + std::to_string(attr.device) + ", the scene is on device " + std::to_string(s->device));
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return P3D_OK;
+  }
+  const uintptr_t end = (uintptr_t)base + size, at = (uintptr_t)p;
+  if (at < (uintptr_t)base || at > end || bytes > end - at)
+    return fail(P3D_ERR_INVALID, what + " ends behind its allocation (" + std::to_string(bytes) + " bytes needed, " + std::to_string(at <= end ? end - at : 0) + " there)");
+  return P3D_OK;
 }
 
 // What p3d_scene_bvh_cost and p3d_scene_set_auto_rebuild share: the waits, the builder's state, the two launches, 32 bytes back
@@ -289,6 +314,80 @@ int p3d_scene_transform_prims(p3d_scene* s, uint32_t n_ranges, const p3d_xform_r
   P3D_HIP(hipMemcpy(&skipped, s->xf_stage.p, sizeof(skipped), hipMemcpyDeviceToHost));
   if (rc || !skipped) return rc;  // (a failed grid rebuild has recorded its message)
   return fail(P3D_ERR_INVALID, pre + std::to_string(skipped) + " object(s) would have a non-finite or inverted box and keep their geometry; the others are updated");
+}
+
+int p3d_scene_update_geometry_device(p3d_scene* s, uint32_t n_sources, const p3d_geom_source* sources, uint32_t mode, float* update_ms) {
+  const char* who = "p3d_scene_update_geometry_device";
+  const std::string pre = std::string(who) + ": ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (n_sources && !sources) return fail(P3D_ERR_INVALID, pre + "null sources with n_sources > 0");
+  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, pre + "unknown mode");
+  if (!s->device_bvh)
+    return fail(P3D_ERR_INVALID, pre + "the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
+  if (s->uploaded_grid) return fail(P3D_ERR_INVALID, pre + "the scene carries the host's grid, which would go stale");
+  const uint32_t n_objs = s->dev.n_objs;
+  if (n_sources > n_objs) return fail(P3D_ERR_INVALID, pre + "more sources than objects (sources overlap or are empty)");
+  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
+  // sorted by `first`, with the objects covered in front of each: what the kernel searches
+  std::vector<geomsrc::StagedSource> sorted(n_sources);
+  for (uint32_t r = 0; r < n_sources; ++r) {
+    const p3d_geom_source& g = sources[r];
+    const std::string at = pre + "source " + std::to_string(r);
+    if (g.count == 0) return fail(P3D_ERR_INVALID, at + " is empty");
+    if ((uint64_t)g.first + g.count > n_objs) return fail(P3D_ERR_INVALID, at + " ends behind the last object");
+    if (g.kind != P3D_PRIM_TRIANGLE && g.kind != P3D_PRIM_SPHERE) return fail(P3D_ERR_INVALID, at + ": kind must be P3D_PRIM_TRIANGLE or P3D_PRIM_SPHERE");
+    if (g.reserved[0] | g.reserved[1]) return fail(P3D_ERR_INVALID, at + ": reserved must be 0");
+    if (!g.d_data) return fail(P3D_ERR_INVALID, at + ": null d_data");
+    if (((uintptr_t)g.d_data | (uintptr_t)g.d_index) & 3u) return fail(P3D_ERR_INVALID, at + ": d_data and d_index must be 4-byte aligned");
+    if (g.n_elems == 0) return fail(P3D_ERR_INVALID, at + ": n_elems is 0");
+    if (g.kind == P3D_PRIM_SPHERE) {
+      if (g.d_index) return fail(P3D_ERR_INVALID, at + ": d_index given for spheres");
+      if (g.n_elems != g.count) return fail(P3D_ERR_INVALID, at + ": spheres need n_elems == count");
+    } else if (!g.d_index && (uint64_t)g.n_elems != 3 * (uint64_t)g.count) {
+      return fail(P3D_ERR_INVALID, at + ": a soup (d_index NULL) needs n_elems == 3 * count");
+    }
+    for (uint32_t o = g.first; o < g.first + g.count; ++o)
+      if ((s->obj_tm[o] & 0xffu) != g.kind) return fail(P3D_ERR_INVALID, at + ": object " + std::to_string(o) + " is of another type");
+    const size_t data_bytes = g.kind == P3D_PRIM_SPHERE ? (size_t)16 * g.count : (size_t)12 * g.n_elems;
+    if (int rc = device_buffer_usable(s, g.d_data, data_bytes, at + ": d_data")) return rc;
+    if (g.d_index)
+      if (int rc = device_buffer_usable(s, g.d_index, (size_t)12 * g.count, at + ": d_index")) return rc;
+    sorted[r] = geomsrc::StagedSource{g.first, g.count, g.kind, g.n_elems, (const float*)g.d_data, g.d_index, 0u, {0u, 0u, 0u}};
+  }
+  std::sort(sorted.begin(), sorted.end(), [](const geomsrc::StagedSource& a, const geomsrc::StagedSource& b) { return a.first < b.first; });
+  uint32_t total = 0;
+  for (uint32_t r = 0; r < n_sources; ++r) {
+    geomsrc::StagedSource& g = sorted[r];
+    if (r && sorted[r - 1].first + sorted[r - 1].count > g.first)
+      return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(g.first) + " is in two sources");
+    g.before = total;
+    total += g.count;  // (disjoint sources inside n_objs: no overflow)
+  }
+  if (update_ms) *update_ms = 0.0f;
+  if (n_objs == 0) return P3D_OK;
+  // one upload: the two counters (zero), the sources
+  const size_t words = 1 + 3 * (size_t)n_sources;
+  s->gs_host.assign(words, make_uint4(0, 0, 0, 0));
+  if (n_sources) std::memcpy(s->gs_host.data() + 1, sorted.data(), (size_t)n_sources * sizeof(geomsrc::StagedSource));
+  if (int rc = begin_update(s, mode, who)) return rc;
+  if (int rc = s->gs_stage.ensure(words * sizeof(uint4))) return rc;
+  // from here on the scene changes
+  float4* blob = s->d_blob;
+  hipError_t e = hipEventRecord(s->ev0, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(s->gs_stage.p, s->gs_host.data(), words * sizeof(uint4), hipMemcpyHostToDevice, 0);
+  if (e == hipSuccess && total) {
+    hipLaunchKernelGGL(geomsrc::gather_geometry, dim3((total + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
+                       (const geomsrc::StagedSource*)((const uint4*)s->gs_stage.p + 1), n_sources, total, n_objs, blob + s->off_ogeom,
+                       blob + s->off_normals, s->lbvh_ws.boxes, (float4*)s->rest.p, (uint32_t*)s->gs_stage.p);
+    e = hipGetLastError();
+  }
+  const int rc = finish_update(s, mode, e, who, update_ms);
+  if (rc == P3D_ERR_NO_DEVICE) return rc;
+  uint32_t bad[2] = {0, 0};
+  P3D_HIP(hipMemcpy(bad, s->gs_stage.p, sizeof(bad), hipMemcpyDeviceToHost));
+  if (rc || !(bad[0] | bad[1])) return rc;  // (a failed grid rebuild has recorded its message)
+  return fail(P3D_ERR_INVALID, pre + std::to_string(bad[0]) + " triangle(s) with an index >= n_elems, " + std::to_string(bad[1]) +
+                                   " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated");
 }
 
 int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {
