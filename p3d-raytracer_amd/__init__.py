@@ -962,13 +962,16 @@ class DeviceScene:
                                          t.ctypes.data if want_t else None, hp.ctypes.data))
         return (hit, hp, t) if want_t else (hit, hp)
 
-    def object_intercepts(self, obj, origin, direction):
-        """Object::intercepts for n rays: -> (hit, t, direction as the test left it)."""
+    def object_intercepts(self, obj, origin, direction, t_init=None):
+        """Object::intercepts for n rays: -> (hit, t, direction as the test left it).  t starts as t_init (a scalar or n values;
+        default zeros) and keeps that value where the test fails."""
         o = np.ascontiguousarray(origin, np.float32)
         d = np.array(direction, np.float32, order="C")
         n = o.shape[0]
         hit = np.zeros(n, np.uint8)
         t = np.zeros(n, np.float32)
+        if t_init is not None:
+            t[:] = t_init
         _check(self._L.p3d_object_intercepts(self._h, int(obj), n, C.c_void_p(o.ctypes.data), C.c_void_p(d.ctypes.data),
                                              C.c_void_p(hit.ctypes.data), C.c_void_p(t.ctypes.data)))
         return hit.astype(bool), t, d

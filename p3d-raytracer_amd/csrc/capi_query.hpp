@@ -65,6 +65,7 @@ static int object_query(p3d_scene* s, int what, uint32_t object, uint32_t n, con
   if (what == 2 && !s->has_sky) return fail(P3D_ERR_INVALID, "p3d_skybox_color: no cubemap was supplied (p3d_scene_set_skybox)");
   if (n == 0) return P3D_OK;
   P3D_HIP(hipSetDevice(s->device));
+  // (no p3d_scene_join as in trace_common: only q_in / q_out are written here, which no frame launch touches, and a frame does not write the geometry)
   const size_t vec = (size_t)n * 3 * sizeof(float);
   if (int rc = s->q_in.ensure(vec)) return rc;
   if (int rc = s->q_out.ensure(vec + (size_t)n * (sizeof(float) + 1) + 64)) return rc;
