@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -16,8 +17,7 @@
 #include "kernels.hpp"
 #include "lbvh.hpp"
 #include "grid_build.hpp"
-#include "xform_prims.hpp"
-#include "geom_source.hpp"
+#include "update_kernels.hpp"
 #include "p3d.h"
 #include "p3d_debug.h"
 #include "wavefront.hpp"
@@ -140,15 +140,10 @@ struct p3d_scene {
   double sah_baseline = 0.0;           // 0: none recorded
   uint32_t refits_since_build = 0;
   bool last_update_rebuilt = false;
-  Scratch upd_stage;                   // lbvh::UpdateRecord[n] of the update in progress
-  std::vector<lbvh::UpdateRecord> upd_host;
-  // p3d_scene_transform_prims (the same scenes)
+  // the geometry updates: p3d_scene_update_prims, p3d_scene_transform_prims, p3d_scene_update_geometry_device (the same scenes)
+  Scratch stage;                       // the call in progress: a 16-byte counter block | the route's payload (capi_update.hpp)
+  std::vector<uint4> stage_host;       // what is uploaded there
   Scratch rest;                        // object-order geometry of the rest pose, 3 float4 per object; made by the first transform
-  Scratch xf_stage;                    // the call in progress: skipped-object counter (16 bytes) | xform::StagedRange[] | p3d_xform[]
-  std::vector<uint4> xf_host;          // what is uploaded there
-  // p3d_scene_update_geometry_device (the same scenes)
-  Scratch gs_stage;                    // the call in progress: the two failure counters (16 bytes) | geomsrc::StagedSource[]
-  std::vector<uint4> gs_host;          // what is uploaded there
   // p3d_scene_build_grid (the same scenes): d_cell_start / d_cell_items above are then the device-built grid
   bool uploaded_grid = false;          // the descriptor carried the host's grid: it cannot follow updates and is never rebuilt
   uint64_t cell_start_cap = 0, cell_items_cap = 0;  // words allocated; they grow when a build needs more and are kept otherwise

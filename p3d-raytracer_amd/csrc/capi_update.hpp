@@ -141,6 +141,68 @@ int measure_cost(p3d_scene* s, const char* who, lbvh::CostResult* out) {
   return P3D_OK;
 }
 
+// What every geometry update refuses first, in this order; `null_arrays`: the route's own text if a counted array is null
+int update_refused(const p3d_scene* s, uint32_t mode, const std::string& pre, const char* null_arrays) {
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (null_arrays) return fail(P3D_ERR_INVALID, pre + null_arrays);
+  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, pre + "unknown mode");
+  if (!s->device_bvh)
+    return fail(P3D_ERR_INVALID, pre + "the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
+  if (s->uploaded_grid) return fail(P3D_ERR_INVALID, pre + "the scene carries the host's grid, which would go stale");
+  return P3D_OK;
+}
+
+// Staged spans (upd::StagedRange, upd::StagedSource; each non-empty and inside the scene) as upd::find_span searches them:
+// sorted by `first`, refused if two overlap (`noun`: "ranges", "sources"), `before` filled; `each` checks a span once it is
+// known to be disjoint from those in front of it.  *total: the objects covered
+template <class Span, class Each>
+int sort_spans(std::vector<Span>& spans, const std::string& pre, const char* noun, uint32_t* total, Each&& each) {
+  std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.first < b.first; });
+  *total = 0;
+  for (size_t r = 0; r < spans.size(); ++r) {
+    Span& g = spans[r];
+    if (r && spans[r - 1].first + spans[r - 1].count > g.first)
+      return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(g.first) + " is in two " + noun);
+    g.before = *total;
+    *total += g.count;  // (disjoint spans inside n_objs: no overflow)
+    if (int rc = each(g)) return rc;
+  }
+  return P3D_OK;
+}
+
+// A geometry update from "validated, and s->stage_host holds a zeroed counter block and the payload" (or nothing: no upload)
+// to the return code.  `launch(grid, block, payload, counters)` enqueues the route's kernel over `total` objects, if there
+// are any.  make_rest: the route reads the rest pose, which until its first call IS the object-order geometry.  `failed`
+// (null: the route counts nothing) words what the kernel left in the counter block, if anything.
+template <class Launch>
+int run_update(p3d_scene* s, uint32_t mode, const char* who, float* update_ms, uint32_t total, bool make_rest, Launch&& launch,
+               const std::function<std::string(const uint32_t*)>& failed) {
+  const size_t bytes = s->stage_host.size() * sizeof(uint4);
+  if (int rc = begin_update(s, mode, who)) return rc;
+  if (int rc = s->stage.ensure(bytes)) return rc;
+  if (make_rest && !s->rest.p) {
+    const size_t rest_bytes = (size_t)3 * s->dev.n_objs * sizeof(float4);
+    if (int rc = s->rest.ensure(rest_bytes)) return rc;
+    if (hipError_t e = hipMemcpy(s->rest.p, s->d_blob + s->off_ogeom, rest_bytes, hipMemcpyDeviceToDevice); e != hipSuccess) {
+      s->rest.release();
+      return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": rest copy: " + hipGetErrorString(e));
+    }
+  }
+  // from here on the scene changes
+  hipError_t e = hipEventRecord(s->ev0, 0);
+  if (e == hipSuccess && bytes) e = hipMemcpyAsync(s->stage.p, s->stage_host.data(), bytes, hipMemcpyHostToDevice, 0);
+  if (e == hipSuccess && total) {
+    launch(dim3((total + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), (const uint4*)s->stage.p + 1, (uint32_t*)s->stage.p);
+    e = hipGetLastError();
+  }
+  const int rc = finish_update(s, mode, e, who, update_ms);
+  if (rc == P3D_ERR_NO_DEVICE || !failed) return rc;
+  uint32_t bad[2] = {0, 0};
+  P3D_HIP(hipMemcpy(bad, s->stage.p, sizeof(bad), hipMemcpyDeviceToHost));
+  if (rc || !(bad[0] | bad[1])) return rc;  // (a failed grid rebuild has recorded its message)
+  return fail(P3D_ERR_INVALID, std::string(who) + ": " + failed(bad));
+}
+
 }  // namespace
 
 extern "C" {
@@ -183,63 +245,45 @@ int p3d_scene_set_camera(p3d_scene* s, const p3d_camera* cam) {
 
 int p3d_scene_update_prims(p3d_scene* s, uint32_t n, const uint32_t* object, const p3d_prim* prims, uint32_t mode, float* update_ms) {
   const char* who = "p3d_scene_update_prims";
-  if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null scene");
-  if (n && (!object || !prims)) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: null array with n > 0");
-  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: unknown mode");
-  if (!s->device_bvh)
-    return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
-  if (s->uploaded_grid) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: the scene carries the host's grid, which would go stale");
+  const std::string pre = std::string(who) + ": ";
+  if (int rc = update_refused(s, mode, pre, n && (!object || !prims) ? "null array with n > 0" : nullptr)) return rc;
   const uint32_t n_objs = s->dev.n_objs;
-  if (n > n_objs) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: more records than objects (an index is repeated)");
+  if (n > n_objs) return fail(P3D_ERR_INVALID, pre + "more records than objects (an index is repeated)");
   {
     std::vector<uint8_t> seen(n_objs, 0);
     for (uint32_t i = 0; i < n; ++i) {
       const p3d_prim& p = prims[i];
-      if (object[i] >= n_objs) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object index out of range");
-      if (seen[object[i]]) return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " appears twice");
+      if (object[i] >= n_objs) return fail(P3D_ERR_INVALID, pre + "object index out of range");
+      if (seen[object[i]]) return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(object[i]) + " appears twice");
       seen[object[i]] = 1;
       if (p.type > 0xffu || p.material > 0xffffffu || (p.type | (p.material << 8)) != s->obj_tm[object[i]])
-        return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " changes its type or material");
+        return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(object[i]) + " changes its type or material");
       for (int k = 0; k < 3; ++k)
         if (!std::isfinite(p.bmin[k]) || !std::isfinite(p.bmax[k]) || !(p.bmin[k] <= p.bmax[k]))
-          return fail(P3D_ERR_INVALID, "p3d_scene_update_prims: object " + std::to_string(object[i]) + " has a non-finite or inverted box");
+          return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(object[i]) + " has a non-finite or inverted box");
     }
   }
   if (update_ms) *update_ms = 0.0f;
   if (n_objs == 0) return P3D_OK;
-  if (n) s->upd_host.assign(n, lbvh::UpdateRecord{});
+  // one upload, or none: the counter block (unused), the records
+  static_assert(sizeof(upd::UpdateRecord) == 7 * sizeof(uint4), "the records are staged as uint4");
+  s->stage_host.assign(n ? 1 + 7 * (size_t)n : 0, make_uint4(0, 0, 0, 0));
   for (uint32_t i = 0; i < n; ++i) {
-    s->upd_host[i].prim = prims[i];
-    s->upd_host[i].object = object[i];
+    const upd::UpdateRecord rec{prims[i], object[i], {0u, 0u, 0u}};
+    std::memcpy(s->stage_host.data() + 1 + 7 * (size_t)i, &rec, sizeof(rec));
   }
-  if (int rc = begin_update(s, mode, who)) return rc;
-  if (n)
-    if (int rc = s->upd_stage.ensure((size_t)n * sizeof(lbvh::UpdateRecord))) return rc;
-  // from here on the scene changes
-  float4* blob = s->d_blob;
-  hipError_t e = hipEventRecord(s->ev0, 0);
-  if (e == hipSuccess && n) {
-    e = hipMemcpyAsync(s->upd_stage.p, s->upd_host.data(), (size_t)n * sizeof(lbvh::UpdateRecord), hipMemcpyHostToDevice, 0);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(lbvh::scatter_prims, dim3((n + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
-                         (const lbvh::UpdateRecord*)s->upd_stage.p, n, n_objs, blob + s->off_ogeom, blob + s->off_normals, s->lbvh_ws.boxes,
-                         (float4*)s->rest.p);
-      e = hipGetLastError();
-    }
-  }
-  return finish_update(s, mode, e, who, update_ms);
+  auto launch = [&](dim3 grid, dim3 block, const uint4* payload, uint32_t*) {
+    hipLaunchKernelGGL(upd::scatter_prims, grid, block, 0, 0, (const upd::UpdateRecord*)payload, n, n_objs, s->d_blob + s->off_ogeom,
+                       s->d_blob + s->off_normals, s->lbvh_ws.boxes, (float4*)s->rest.p);
+  };
+  return run_update(s, mode, who, update_ms, n, false, launch, nullptr);
 }
 
 int p3d_scene_transform_prims(p3d_scene* s, uint32_t n_ranges, const p3d_xform_range* ranges, uint32_t n_xforms, const p3d_xform* xforms,
                               uint32_t mode, float* update_ms) {
   const char* who = "p3d_scene_transform_prims";
   const std::string pre = std::string(who) + ": ";
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if ((n_ranges && !ranges) || (n_xforms && !xforms)) return fail(P3D_ERR_INVALID, pre + "null array with a non-zero count");
-  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, pre + "unknown mode");
-  if (!s->device_bvh)
-    return fail(P3D_ERR_INVALID, pre + "the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
-  if (s->uploaded_grid) return fail(P3D_ERR_INVALID, pre + "the scene carries the host's grid, which would go stale");
+  if (int rc = update_refused(s, mode, pre, (n_ranges && !ranges) || (n_xforms && !xforms) ? "null array with a non-zero count" : nullptr)) return rc;
   const uint32_t n_objs = s->dev.n_objs;
   if (n_ranges > n_objs) return fail(P3D_ERR_INVALID, pre + "more ranges than objects (ranges overlap or are empty)");
   std::vector<uint8_t> diagonal(n_xforms, 0);  // the transform may move a box
@@ -252,8 +296,7 @@ int p3d_scene_transform_prims(p3d_scene* s, uint32_t n_ranges, const p3d_xform_r
     if (t.reserved[0] | t.reserved[1] | t.reserved[2]) return fail(P3D_ERR_INVALID, pre + "transform " + std::to_string(x) + ": reserved must be 0");
     diagonal[x] = xform_is_positive_diagonal(t.m) ? 1 : 0;
   }
-  // sorted by `first`, with the objects covered in front of each: what the kernel searches
-  std::vector<xform::StagedRange> sorted(n_ranges);
+  std::vector<upd::StagedRange> sorted(n_ranges);
   for (uint32_t r = 0; r < n_ranges; ++r) {
     const p3d_xform_range& g = ranges[r];
     const std::string at = pre + "range " + std::to_string(r);
@@ -261,16 +304,10 @@ int p3d_scene_transform_prims(p3d_scene* s, uint32_t n_ranges, const p3d_xform_r
     if ((uint64_t)g.first + g.count > n_objs) return fail(P3D_ERR_INVALID, at + " ends behind the last object");
     if (g.xform >= n_xforms) return fail(P3D_ERR_INVALID, at + " names a transform that is not there");
     if (g.reserved) return fail(P3D_ERR_INVALID, at + ": reserved must be 0");
-    sorted[r] = xform::StagedRange{g.first, g.count, g.xform, 0u};
+    sorted[r] = upd::StagedRange{g.first, g.count, g.xform, 0u};
   }
-  std::sort(sorted.begin(), sorted.end(), [](const xform::StagedRange& a, const xform::StagedRange& b) { return a.first < b.first; });
   uint32_t total = 0;
-  for (uint32_t r = 0; r < n_ranges; ++r) {
-    xform::StagedRange& g = sorted[r];
-    if (r && sorted[r - 1].first + sorted[r - 1].count > g.first)
-      return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(g.first) + " is in two ranges");
-    g.before = total;
-    total += g.count;  // (disjoint ranges inside n_objs: no overflow)
+  auto movable = [&](const upd::StagedRange& g) {
     for (uint32_t o = g.first; o < g.first + g.count; ++o) {
       const uint32_t type = s->obj_tm[o] & 0xffu;
       if (type == P3D_PRIM_PLANE) return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(o) + " is a plane");
@@ -278,58 +315,33 @@ int p3d_scene_transform_prims(p3d_scene* s, uint32_t n_ranges, const p3d_xform_r
         return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(o) + " is a box, and transform " + std::to_string(g.xform) +
                                          " is not a positive scale per axis and a translation");
     }
-  }
+    return (int)P3D_OK;
+  };
+  if (int rc = sort_spans(sorted, pre, "ranges", &total, movable)) return rc;
   if (update_ms) *update_ms = 0.0f;
   if (n_objs == 0) return P3D_OK;
   // one upload: the counter (zero), the ranges, the transforms
   static_assert(sizeof(p3d_xform) == 64 && sizeof(p3d_xform_range) == 16, "p3d_xform is read as four float4, a range as one uint4");
-  const size_t words = 1 + (size_t)n_ranges + 4 * (size_t)n_xforms;
-  s->xf_host.assign(words, make_uint4(0, 0, 0, 0));
-  if (n_ranges) std::memcpy(s->xf_host.data() + 1, sorted.data(), (size_t)n_ranges * sizeof(uint4));
-  if (n_xforms) std::memcpy(s->xf_host.data() + 1 + n_ranges, xforms, (size_t)n_xforms * sizeof(p3d_xform));
-  if (int rc = begin_update(s, mode, who)) return rc;
-  if (int rc = s->xf_stage.ensure(words * sizeof(uint4))) return rc;
-  if (!s->rest.p) {  // no transform has run: the object-order geometry IS the rest pose
-    const size_t bytes = (size_t)3 * n_objs * sizeof(float4);
-    if (int rc = s->rest.ensure(bytes)) return rc;
-    if (hipError_t e = hipMemcpy(s->rest.p, s->d_blob + s->off_ogeom, bytes, hipMemcpyDeviceToDevice); e != hipSuccess) {
-      s->rest.release();
-      return fail(P3D_ERR_NO_DEVICE, pre + "rest copy: " + hipGetErrorString(e));
-    }
-  }
-  // from here on the scene changes
-  float4* blob = s->d_blob;
-  const uint4* stage = (const uint4*)s->xf_stage.p;
-  hipError_t e = hipEventRecord(s->ev0, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->xf_stage.p, s->xf_host.data(), words * sizeof(uint4), hipMemcpyHostToDevice, 0);
-  if (e == hipSuccess && total) {
-    hipLaunchKernelGGL(xform::transform_prims, dim3((total + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
-                       (const float4*)s->rest.p, stage + 1, n_ranges, (const float4*)(stage + 1 + n_ranges), n_xforms, total, n_objs,
-                       blob + s->off_ogeom, blob + s->off_normals, s->lbvh_ws.boxes, (uint32_t*)s->xf_stage.p);
-    e = hipGetLastError();
-  }
-  const int rc = finish_update(s, mode, e, who, update_ms);
-  if (rc == P3D_ERR_NO_DEVICE) return rc;
-  uint32_t skipped = 0;
-  P3D_HIP(hipMemcpy(&skipped, s->xf_stage.p, sizeof(skipped), hipMemcpyDeviceToHost));
-  if (rc || !skipped) return rc;  // (a failed grid rebuild has recorded its message)
-  return fail(P3D_ERR_INVALID, pre + std::to_string(skipped) + " object(s) would have a non-finite or inverted box and keep their geometry; the others are updated");
+  s->stage_host.assign(1 + (size_t)n_ranges + 4 * (size_t)n_xforms, make_uint4(0, 0, 0, 0));
+  if (n_ranges) std::memcpy(s->stage_host.data() + 1, sorted.data(), (size_t)n_ranges * sizeof(uint4));
+  if (n_xforms) std::memcpy(s->stage_host.data() + 1 + n_ranges, xforms, (size_t)n_xforms * sizeof(p3d_xform));
+  auto launch = [&](dim3 grid, dim3 block, const uint4* payload, uint32_t* skipped) {
+    hipLaunchKernelGGL(upd::transform_prims, grid, block, 0, 0, (const float4*)s->rest.p, payload, n_ranges, (const float4*)(payload + n_ranges),
+                       n_xforms, total, n_objs, s->d_blob + s->off_ogeom, s->d_blob + s->off_normals, s->lbvh_ws.boxes, skipped);
+  };
+  return run_update(s, mode, who, update_ms, total, true, launch, [](const uint32_t* bad) {
+    return std::to_string(bad[0]) + " object(s) would have a non-finite or inverted box and keep their geometry; the others are updated";
+  });
 }
 
 int p3d_scene_update_geometry_device(p3d_scene* s, uint32_t n_sources, const p3d_geom_source* sources, uint32_t mode, float* update_ms) {
   const char* who = "p3d_scene_update_geometry_device";
   const std::string pre = std::string(who) + ": ";
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (n_sources && !sources) return fail(P3D_ERR_INVALID, pre + "null sources with n_sources > 0");
-  if (mode != P3D_UPDATE_REFIT && mode != P3D_UPDATE_REBUILD) return fail(P3D_ERR_INVALID, pre + "unknown mode");
-  if (!s->device_bvh)
-    return fail(P3D_ERR_INVALID, pre + "the scene was not created by p3d_scene_create_device_bvh (an uploaded tree cannot follow its objects)");
-  if (s->uploaded_grid) return fail(P3D_ERR_INVALID, pre + "the scene carries the host's grid, which would go stale");
+  if (int rc = update_refused(s, mode, pre, n_sources && !sources ? "null sources with n_sources > 0" : nullptr)) return rc;
   const uint32_t n_objs = s->dev.n_objs;
   if (n_sources > n_objs) return fail(P3D_ERR_INVALID, pre + "more sources than objects (sources overlap or are empty)");
   P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
-  // sorted by `first`, with the objects covered in front of each: what the kernel searches
-  std::vector<geomsrc::StagedSource> sorted(n_sources);
+  std::vector<upd::StagedSource> sorted(n_sources);
   for (uint32_t r = 0; r < n_sources; ++r) {
     const p3d_geom_source& g = sources[r];
     const std::string at = pre + "source " + std::to_string(r);
@@ -352,42 +364,23 @@ int p3d_scene_update_geometry_device(p3d_scene* s, uint32_t n_sources, const p3d
     if (int rc = device_buffer_usable(s, g.d_data, data_bytes, at + ": d_data")) return rc;
     if (g.d_index)
       if (int rc = device_buffer_usable(s, g.d_index, (size_t)12 * g.count, at + ": d_index")) return rc;
-    sorted[r] = geomsrc::StagedSource{g.first, g.count, g.kind, g.n_elems, (const float*)g.d_data, g.d_index, 0u, {0u, 0u, 0u}};
+    sorted[r] = upd::StagedSource{g.first, g.count, g.kind, 0u, (const float*)g.d_data, g.d_index, g.n_elems, {0u, 0u, 0u}};
   }
-  std::sort(sorted.begin(), sorted.end(), [](const geomsrc::StagedSource& a, const geomsrc::StagedSource& b) { return a.first < b.first; });
   uint32_t total = 0;
-  for (uint32_t r = 0; r < n_sources; ++r) {
-    geomsrc::StagedSource& g = sorted[r];
-    if (r && sorted[r - 1].first + sorted[r - 1].count > g.first)
-      return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(g.first) + " is in two sources");
-    g.before = total;
-    total += g.count;  // (disjoint sources inside n_objs: no overflow)
-  }
+  if (int rc = sort_spans(sorted, pre, "sources", &total, [](const upd::StagedSource&) { return (int)P3D_OK; })) return rc;
   if (update_ms) *update_ms = 0.0f;
   if (n_objs == 0) return P3D_OK;
   // one upload: the two counters (zero), the sources
-  const size_t words = 1 + 3 * (size_t)n_sources;
-  s->gs_host.assign(words, make_uint4(0, 0, 0, 0));
-  if (n_sources) std::memcpy(s->gs_host.data() + 1, sorted.data(), (size_t)n_sources * sizeof(geomsrc::StagedSource));
-  if (int rc = begin_update(s, mode, who)) return rc;
-  if (int rc = s->gs_stage.ensure(words * sizeof(uint4))) return rc;
-  // from here on the scene changes
-  float4* blob = s->d_blob;
-  hipError_t e = hipEventRecord(s->ev0, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->gs_stage.p, s->gs_host.data(), words * sizeof(uint4), hipMemcpyHostToDevice, 0);
-  if (e == hipSuccess && total) {
-    hipLaunchKernelGGL(geomsrc::gather_geometry, dim3((total + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, 0,
-                       (const geomsrc::StagedSource*)((const uint4*)s->gs_stage.p + 1), n_sources, total, n_objs, blob + s->off_ogeom,
-                       blob + s->off_normals, s->lbvh_ws.boxes, (float4*)s->rest.p, (uint32_t*)s->gs_stage.p);
-    e = hipGetLastError();
-  }
-  const int rc = finish_update(s, mode, e, who, update_ms);
-  if (rc == P3D_ERR_NO_DEVICE) return rc;
-  uint32_t bad[2] = {0, 0};
-  P3D_HIP(hipMemcpy(bad, s->gs_stage.p, sizeof(bad), hipMemcpyDeviceToHost));
-  if (rc || !(bad[0] | bad[1])) return rc;  // (a failed grid rebuild has recorded its message)
-  return fail(P3D_ERR_INVALID, pre + std::to_string(bad[0]) + " triangle(s) with an index >= n_elems, " + std::to_string(bad[1]) +
-                                   " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated");
+  s->stage_host.assign(1 + 3 * (size_t)n_sources, make_uint4(0, 0, 0, 0));
+  if (n_sources) std::memcpy(s->stage_host.data() + 1, sorted.data(), (size_t)n_sources * sizeof(upd::StagedSource));
+  auto launch = [&](dim3 grid, dim3 block, const uint4* payload, uint32_t* counters) {
+    hipLaunchKernelGGL(upd::gather_geometry, grid, block, 0, 0, (const upd::StagedSource*)payload, n_sources, total, n_objs,
+                       s->d_blob + s->off_ogeom, s->d_blob + s->off_normals, s->lbvh_ws.boxes, (float4*)s->rest.p, counters);
+  };
+  return run_update(s, mode, who, update_ms, total, false, launch, [](const uint32_t* bad) {
+    return std::to_string(bad[0]) + " triangle(s) with an index >= n_elems, " + std::to_string(bad[1]) +
+           " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated";
+  });
 }
 
 int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {

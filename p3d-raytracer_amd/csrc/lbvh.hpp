@@ -261,39 +261,6 @@ __global__ void cost_final(uint32_t n, uint32_t n_partials, const double* partia
   }
 }
 
-// One object of p3d_scene_update_prims as it is staged for scatter_prims: the caller's record and the object it replaces
-struct UpdateRecord {
-  p3d_prim prim;
-  uint32_t object;
-  uint32_t pad[3];
-};
-static_assert(sizeof(UpdateRecord) == 112, "UpdateRecord is read as seven float4");
-
-// Replaces objects in place: the object-order geometry (packed as create_impl's geom_of packs it), the shading normal and
-// the object's box.  One thread per record; the host has checked that every index is < n_objs and appears once.
-// rest: the scene's rest geometry once p3d_scene_transform_prims has made it (else null): a replaced object rests where it is put
-__global__ void scatter_prims(const UpdateRecord* recs, uint32_t n, uint32_t n_objs, float4* ogeom, float4* normals, float4* boxes, float4* rest) {
-  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const float4* r = reinterpret_cast<const float4*>(recs + i);
-  const float4 a = r[0], b = r[1], c = r[2], d = r[3], e = r[4], f = r[5], g = r[6];
-  // p3d_prim: v[0..8] = a.xyzw b.xyzw c.x, type = c.y, material = c.z, n = d.xyz, bmin = e.xyz, bmax = f.xyz
-  const uint32_t obj = __float_as_uint(g.x);
-  if (obj >= n_objs) return;
-  const uint32_t tm = __float_as_uint(c.y) | (__float_as_uint(c.z) << 8);
-  ogeom[3 * obj] = a;
-  ogeom[3 * obj + 1] = b;
-  ogeom[3 * obj + 2] = make_float4(c.x, __uint_as_float(tm), __uint_as_float(obj), 0.f);
-  if (rest) {
-    rest[3 * obj] = a;
-    rest[3 * obj + 1] = b;
-    rest[3 * obj + 2] = make_float4(c.x, __uint_as_float(tm), __uint_as_float(obj), 0.f);
-  }
-  normals[obj] = make_float4(d.x, d.y, d.z, 0.f);
-  boxes[2 * obj] = make_float4(e.x, e.y, e.z, 0.f);
-  boxes[2 * obj + 1] = make_float4(f.x, f.y, f.z, 0.f);
-}
-
 struct Result {
   uint32_t n_nodes = 0, max_depth = 0;
   float build_ms = 0;

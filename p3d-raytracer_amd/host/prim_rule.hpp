@@ -1,7 +1,7 @@
 // prim_rule.hpp — the arithmetic that turns nine geometry floats into an object, in ONE place for its users: the shape
 // constructors of the host scene (scene_model.cpp: Triangle::Triangle, Sphere::GetBoundingBox) and the device kernels of
-// p3d_scene_transform_prims (csrc/xform_prims.hpp), which moves an object and then does what the constructors do, and of
-// p3d_scene_update_geometry_device (csrc/geom_source.hpp), which gathers an object from device buffers first.  The device
+// p3d_scene_transform_prims, which moves an object and then does what the constructors do, and of
+// p3d_scene_update_geometry_device, which gathers an object from device buffers first (both csrc/update_kernels.hpp).  The device
 // routes must give the host route's bits, so neither side spells these expressions out for itself.  float32 throughout,
 // evaluated left to right; both translation units are compiled without contraction (-ffp-contract=off) and with correctly
 // rounded square root and division.

@@ -15,7 +15,7 @@ import torch
 import p3d_amd as p3d
 import test_gpu_scene_transform as T
 from device_geometry_helpers import deformed_mesh, diagonal, moved_spheres
-from scene_update_helpers import SPHERE, TRIANGLE
+from scene_update_helpers import SPHERE, TRIANGLE, translated
 
 pytestmark = pytest.mark.gpu
 
@@ -424,3 +424,57 @@ def test_no_sources_is_update_prims_of_nothing(paths):
     assert _raw(dev_b, [], mode=p3d.UPDATE_REFIT) == 0 and _raw(dev_b, [], mode=p3d.UPDATE_REFIT, null=True) == 0
     assert dev_b.update_triangles(0, d_soup, mode=p3d.UPDATE_REFIT) > 0  # the same size again: the staging is kept
     T.assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "the same geometry once more")
+
+
+# 11. the three routes in turn, through the one staging buffer they share
+def test_the_three_routes_share_one_stage(paths):
+    """transform_prims (the largest payload, and it leaves a non-zero counter block behind), update_spheres (a much smaller
+    one: its own upload zeroes the counters again), update_prims, update_triangles: after each, scene B is scene A, which
+    took the host route.  The identity at the end reads the rest copy the last three calls wrote."""
+    hs, a, dev_a, dev_b = twins(paths["cornell"], "cornell")
+    kinds, n = a["prim_type"], a["n_prims"]
+    tri, sph = np.nonzero(kinds == TRIANGLE)[0], np.nonzero(kinds == SPHERE)[0]
+    t0, s0 = int(tri[0]), int(sph[0])
+    assert len(tri) + len(sph) == n and len(sph) >= 3
+    assert np.array_equal(tri, np.arange(t0, t0 + len(tri))) and np.array_equal(sph, np.arange(s0, s0 + len(sph)))
+    # 1. one range per object, every range with a matrix of its own; the largest sphere overflows (a radius below 1 times a
+    # finite sphere_scale stays finite, so it is also moved by 3e38, as in test_an_object_that_overflows_keeps_its_geometry)
+    victim = int(sph[np.argmax(a["prim_v"][sph, 3])])
+    with np.errstate(over="ignore"):
+        assert np.isinf(np.float32(3e38) + a["prim_v"][victim, 3] * np.float32(3e38))
+    rng = np.random.default_rng(81)
+    xforms = np.stack([T.rigid(a, rng, reach=0.02 + 0.002 * i) for i in range(n)])
+    xforms[victim] = T.IDENTITY
+    xforms[victim][:, 3] = 3e38
+    scale = np.full(n, 1.25, np.float32)
+    scale[victim] = 3e38
+    ranges = [(i, 1, i) for i in range(n)]
+    T.host_route(hs, dev_a, a, [r for r in ranges if r[0] != victim], xforms, scale, p3d.UPDATE_REFIT)  # A: the victim is left out
+    with pytest.raises(p3d.P3DError) as e:
+        dev_b.transform_prims(ranges, xforms, p3d.UPDATE_REFIT, sphere_scale=scale)
+    assert e.value.code == -1 and "1 object" in str(e.value), e.value
+    moved = assert_same(dev_a, dev_b, "cornell", "step 1: a transform per object, one sphere overflows")
+    # 2. two spheres with valid radii: returns normally
+    cr = moved_spheres(a, s0, 2, seed=82)
+    host_spheres(hs, dev_a, a, s0, cr, p3d.UPDATE_REFIT)
+    assert dev_b.update_spheres(s0, gpu(cr), mode=p3d.UPDATE_REFIT) > 0
+    now = assert_same(dev_a, dev_b, "cornell", "step 2: two spheres from device memory")
+    assert T.frames_differ(now, moved)
+    # 3. three objects from the host scene, which both scenes are bound to
+    objs = np.array([t0, t0 + len(tri) // 2, s0 + 1], np.uint32)
+    offsets = np.random.default_rng(83).uniform(-0.05, 0.05, (3, 3)).astype(np.float32)
+    hs.set_geometry(objs, translated(kinds, hs.arrays()["prim_v"], objs, offsets))
+    for dev in (dev_a, dev_b):
+        assert dev.update_prims(objs, p3d.UPDATE_REBUILD) > 0
+    assert_same(dev_a, dev_b, "cornell", "step 3: three records from the host")
+    # 4. the whole triangle soup
+    soup = a["prim_v"][tri].reshape(-1, 3).astype(np.float64)
+    soup = (soup + np.random.default_rng(84).uniform(-1, 1, soup.shape) * 0.01 * diagonal(a, tri)).astype(np.float32)
+    assert not (soup == 0).any()  # (1 * -0 + 0 is +0: the one value the identity below would change)
+    host_triangles(hs, dev_a, a, t0, soup, None, p3d.UPDATE_REFIT)
+    assert dev_b.update_triangles(t0, gpu(soup), mode=p3d.UPDATE_REFIT) > 0
+    last = assert_same(dev_a, dev_b, "cornell", "step 4: the triangle soup")
+    # the triangles rest where step 4 put them (not where step 3, step 1 or the scene's file had them)
+    dev_b.transform_prims([(t0, len(tri), 0)], T.IDENTITY[None], p3d.UPDATE_REFIT)
+    T.assert_same_frames(assert_same(dev_a, dev_b, "cornell", "the identity on the triangles"), last, "the identity moved a triangle")
+    assert dev_b.status() == 0
