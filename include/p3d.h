@@ -881,6 +881,61 @@ int p3d_trace_closest(p3d_scene* scene, uint32_t accel, uint32_t n, const float*
 int p3d_trace_any(p3d_scene* scene, uint32_t accel, uint32_t n, const float* origin,
                   const float* direction, uint8_t* occluded);
 /*
+ * The same queries over DEVICE buffers on the caller's stream, and an any-hit with a distance limit.  Detected by the symbols
+ * (P3D_ABI_VERSION is unchanged).  For programs that keep their rays where they keep the positions they hand to
+ * p3d_scene_update_geometry_device: no copy, and no wait.
+ *
+ * Buffers.  Every pointer is an address on the scene's device; the float and int32 buffers must be 4-byte aligned.
+ *   d_origin, d_direction : n*3 float32 (direction used as given, not normalised, as in the host forms)
+ *   d_t_max               : n float32, or NULL = no limit
+ *   d_hit_id : n int32, required ; d_t : n float32 ; d_hit_point, d_normal : n*3 float32 - these three may be NULL
+ *   d_occluded : n uint8, required
+ * t and t_max are DISTANCES only for unit directions: a sphere test measures t along the normalised direction, the other kinds
+ * in units of the direction as given (Q8), and the limit is compared with whatever the test reports.
+ *
+ * Stream.  The kernel is enqueued on `hip_stream` (a hipStream_t, NULL = the default stream) under the scene's stream rules
+ * (p3d_render_tile_device: the launches on one scene share its stack spill area).  The call does not wait, neither before nor
+ * after the launch: what the stream had enqueued to produce the rays runs first, and the outputs are complete when the
+ * stream has passed the call.  Over a tree deeper than the 16-entry LDS window the call may have to grow the scene's spill
+ * area; freeing the old one waits for the device, as it does in a render call; a second call of the same n allocates nothing.
+ * With a tail stream set (p3d_scene_set_tail_stream) the launch first joins the previous frame's tail, as the next render
+ * call on the scene does.
+ *
+ * p3d_trace_closest_device is the traversal of p3d_trace_closest.  With d_t_max = NULL every output equals the host form's, bit
+ * for bit: d_t is FLT_MAX and d_hit_point zero on a miss.  With d_t_max a hit is kept only if t < t_max[i] (strict; a NaN limit
+ * keeps nothing); otherwise the ray reports a miss.  The limit filters the traversal's nearest hit, it does not shorten the
+ * traversal.  d_normal is Object::getNormal of the hit object at d_hit_point - what p3d_object_normal(hit_id, hit_point)
+ * returns, bit for bit; it is NOT turned against the ray, and zero on a miss.
+ *
+ * p3d_trace_any_device with d_t_max = NULL is p3d_trace_any, bit for bit, for every accel: the reference's shadow feeler, which
+ * has no distance limit (main.cpp:192-217) - an object BEHIND the point the feeler was sent to shadows it.
+ * With d_t_max it is the SEGMENT query, which no traversal of the reference answers ("can A see B"):
+ *   occluded[i] = 1 iff some object j has Object::intercepts(object j, a fresh copy of ray i, t) true and t < t_max[i].
+ * Every primitive is tested on a copy of the caller's ray, so a sphere test's normalisation cannot change what a later test
+ * sees, and the answer does not depend on the order of the visits.  A NaN t_max, and t_max <= 0, leave every ray free.
+ *   P3D_ACCEL_NONE : a loop over all objects.
+ *   P3D_ACCEL_BVH  : a stack traversal that skips a child whose box the ray misses or enters behind t_max, takes the nearer
+ *                    child first and, at a dead end, pops the next entry - not the feeler's restart from the bottom of the stack
+ *                    (bvh.cpp:329-338), which can miss an occluder.  Boxes are culled with the ray as given, as the closest-hit
+ *                    traversal prunes; for unit directions it answers as P3D_ACCEL_NONE does wherever the decision is not a
+ *                    matter of the last bits.  Planes are lost by the BVH as everywhere (Q12).
+ *   P3D_ACCEL_GRID : P3D_ERR_UNSUPPORTED.  The reference's grid feeler runs the brute-force loop as well (Q6), so
+ *                    P3D_ACCEL_NONE gives the answer a grid segment query would.
+ *
+ * Refused with P3D_ERR_INVALID, nothing enqueued: a null scene; an unknown accel, or one the scene was created without (and
+ * P3D_ERR_UNSUPPORTED for a grid over an empty scene, as in the host forms); with n > 0, a null d_origin, d_direction,
+ * d_hit_id or d_occluded; a misaligned pointer; a pointer that the HIP runtime identifies as host memory (registered or not)
+ * or as memory of another device, or whose buffer ends behind the allocation the runtime reports for it (a pointer the
+ * runtime cannot answer for is let through).  n = 0 returns P3D_OK.  P3D_ERR_CAPACITY: n x the tree's depth does not fit the
+ * 32-bit offsets of the spill area (split the batch), as in the host forms.
+ */
+int p3d_trace_closest_device(p3d_scene* scene, uint32_t accel, uint32_t n,
+                             const float* d_origin, const float* d_direction, const float* d_t_max /* may be NULL */,
+                             int32_t* d_hit_id, float* d_t, float* d_hit_point, float* d_normal, void* hip_stream);
+int p3d_trace_any_device(p3d_scene* scene, uint32_t accel, uint32_t n,
+                         const float* d_origin, const float* d_direction, const float* d_t_max /* may be NULL */,
+                         uint8_t* d_occluded, void* hip_stream);
+/*
  * Per-object queries — device counterparts of the virtual Object::intercepts(Ray&, float&)
  * (scene.cpp:47-94,116-137,149-186,215-227) and Object::getNormal(Vector) (scene.cpp:41-44,
  * 139-142,188-192,229-267) for object `object` (index in Scene::objects) and n rays / points.

@@ -50,6 +50,7 @@ EXPORTS = [
     "p3d_scene_build_grid", "p3d_scene_export_grid", "p3d_scene_transform_prims",
     "p3d_scene_bvh_cost", "p3d_scene_set_auto_rebuild", "p3d_scene_auto_rebuild",
     "p3d_scene_update_geometry_device",
+    "p3d_trace_closest_device", "p3d_trace_any_device",
 ]
 
 
@@ -310,6 +311,9 @@ def lib():
         L.p3d_scene_set_auto_rebuild.argtypes = [C.c_void_p, C.c_float]
         L.p3d_scene_auto_rebuild.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.p3d_scene_update_geometry_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        L.p3d_trace_closest_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_trace_any_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -500,6 +504,18 @@ def _device_rows(x, what, cols, dtypes, device):
     if x.device.index is not None and x.device.index != device:
         raise P3DError(-1, "%s: the tensor is on device %d, the scene on device %d" % (what, x.device.index, device))
     return int(x.data_ptr()), int(x.shape[0])
+
+
+def _device_vector(x, what, dtypes, device):
+    """_device_rows for one value per row: a contiguous (rows,) tensor, or a raw (address, rows) pair"""
+    if hasattr(x, "data_ptr") and hasattr(x, "dim"):
+        if x.dim() != 1:
+            raise P3DError(-1, "%s: shape %r, needed: (n,) with n > 0" % (what, tuple(x.shape)))
+        x = x.unsqueeze(1)  # (a strided vector stays non-contiguous)
+    return _device_rows(x, what, 1, dtypes, device)
+
+
+_TRACE_OUTPUTS = {"hit_id": ("int32", None), "t": ("float32", None), "hit_point": ("float32", 3), "normal": ("float32", 3)}
 
 
 class HostScene:
@@ -995,6 +1011,68 @@ class DeviceScene:
         occ = np.zeros(n, np.uint8)
         _check(self._L.p3d_trace_any(self._h, int(accel), n, o.ctypes.data, d.ctypes.data, occ.ctypes.data))
         return occ
+
+    def _device_rays(self, who, origin, direction, t_max):
+        """(address of origin, of direction, of t_max or None, n) of the rays of a device query, or P3DError"""
+        d_o, n = _device_rows(origin, who + ": origin", 3, ("float32",), self.device)
+        d_d, n_d = _device_rows(direction, who + ": direction", 3, ("float32",), self.device)
+        d_tm, n_tm = _device_vector(t_max, who + ": t_max", ("float32",), self.device) if t_max is not None else (None, n)
+        if n_d != n or n_tm != n:
+            raise P3DError(-1, "%s: %d origins, %d directions%s" % (who, n, n_d, "" if t_max is None else ", %d limits" % n_tm))
+        return d_o, d_d, d_tm, n
+
+    def _device_outputs(self, who, names, n, out, like):
+        """name -> (tensor or None, address) for the outputs `names`: taken from the dict `out` (tensors or raw (address, rows)
+        pairs, checked like the inputs), or allocated on the scene's device when `out` is None"""
+        res = {}
+        for name in names:
+            dtype, cols = _TRACE_OUTPUTS.get(name, ("uint8", None))
+            if out is None:
+                import torch
+                dev = like.device if hasattr(like, "device") else torch.device("cuda", self.device)
+                tensor = torch.empty((n,) if cols is None else (n, cols), dtype=getattr(torch, dtype), device=dev)
+            else:
+                if name not in out:
+                    raise P3DError(-1, "%s: out has no %r" % (who, name))
+                tensor = out[name]
+            what = "%s: out[%r]" % (who, name)
+            ptr, rows = _device_vector(tensor, what, (dtype,), self.device) if cols is None else _device_rows(tensor, what, cols, (dtype,), self.device)
+            if rows != n:
+                raise P3DError(-1, "%s: %d rows for %d rays" % (what, rows, n))
+            res[name] = (tensor, ptr)
+        return res
+
+    def trace_closest_device(self, accel, origin, direction, t_max=None, want=("hit_id", "t"), stream=0, out=None):
+        """p3d_trace_closest_device: the closest hits of n rays held in device memory, enqueued on `stream` (a torch.cuda.Stream
+        or a raw hipStream_t; 0 = the default stream) without a wait -> {name: tensor} for the names in `want` ("hit_id", always
+        there, "t", "hit_point", "normal").  origin, direction: contiguous float32 (n, 3) CUDA/HIP tensors on the scene's device,
+        or raw (address, rows) pairs; t_max: float32 (n,), a hit is kept only if t < t_max.  `out`: a dict of tensors (or raw
+        pairs) to write into instead of new ones.  A tensor on the host, of another dtype or shape, not contiguous, or row
+        counts that differ raise P3DError before the library is called.  Read the results once the stream has passed the call."""
+        who = "trace_closest_device"
+        names = ["hit_id"] + [w for w in ("t", "hit_point", "normal") if w in want]
+        unknown = [w for w in want if w not in _TRACE_OUTPUTS]
+        if unknown:
+            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+        d_o, d_d, d_tm, n = self._device_rays(who, origin, direction, t_max)
+        res = self._device_outputs(who, names, n, out, origin)
+        ptr = {k: C.c_void_p(v[1]) for k, v in res.items()}
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_trace_closest_device(self._h, int(accel), n, C.c_void_p(d_o), C.c_void_p(d_d), C.c_void_p(d_tm), ptr["hit_id"],
+                                                ptr.get("t"), ptr.get("hit_point"), ptr.get("normal"), C.c_void_p(raw or None)))
+        return {k: v[0] for k, v in res.items()}
+
+    def trace_any_device(self, accel, origin, direction, t_max=None, stream=0, out=None):
+        """p3d_trace_any_device -> {"occluded": uint8 (n,) tensor}.  Without t_max the reference's shadow feeler (trace_any: no
+        distance limit); with t_max (float32 (n,)) the segment query: 1 iff some object is hit at t < t_max, for ACCEL_NONE and
+        ACCEL_BVH (the grid is refused).  Arguments and stream as trace_closest_device."""
+        who = "trace_any_device"
+        d_o, d_d, d_tm, n = self._device_rays(who, origin, direction, t_max)
+        res = self._device_outputs(who, ["occluded"], n, out, origin)
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_trace_any_device(self._h, int(accel), n, C.c_void_p(d_o), C.c_void_p(d_d), C.c_void_p(d_tm),
+                                            C.c_void_p(res["occluded"][1]), C.c_void_p(raw or None)))
+        return {k: v[0] for k, v in res.items()}
 
 
 class Accumulator:

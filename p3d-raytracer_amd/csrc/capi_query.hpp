@@ -1,6 +1,60 @@
 // capi_query.hpp — batched single-ray and per-object queries (p3d_trace_*, p3d_object_*, p3d_skybox_color)
 #pragma once
-#include "capi_common.hpp"
+#include "capi_update.hpp"  // device_buffer_usable
+#include "ray_query.hpp"
+
+namespace {
+
+// p3d_trace_closest_device / p3d_trace_any_device: the refusals, the spill scratch and one launch on the caller's stream.
+// No wait anywhere but in a hipFree of a spill area that has to grow.
+int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
+                 int32_t* d_hit_id, float* d_t, float* d_hit_point, float* d_normal, uint8_t* d_occluded, void* hip_stream, bool any) {
+  const std::string pre = any ? "p3d_trace_any_device: " : "p3d_trace_closest_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (accel == P3D_ACCEL_GRID && s->dev.n_objs == 0) return fail(P3D_ERR_UNSUPPORTED, "grid over an empty scene");
+  if (any && d_t_max && accel == P3D_ACCEL_GRID)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "no segment query through the grid (P3D_ACCEL_NONE gives the answer the grid's feeler would: it runs the brute-force loop as well)");
+  if (n == 0) return P3D_OK;
+  if (!d_origin || !d_direction || (any ? !d_occluded : !d_hit_id)) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (((uintptr_t)d_origin | (uintptr_t)d_direction | (uintptr_t)d_t_max | (uintptr_t)d_hit_id | (uintptr_t)d_t | (uintptr_t)d_hit_point |
+       (uintptr_t)d_normal) & 3u)
+    return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
+  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
+      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"}, {d_hit_id, one, "d_hit_id"},
+      {d_t, one, "d_t"}, {d_hit_point, vec, "d_hit_point"}, {d_normal, vec, "d_normal"}, {d_occluded, (size_t)n, "d_occluded"}};
+  for (const auto& b : bufs)
+    if (b.p)
+      if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
+  // the stack as trace_common binds it: a 16-entry LDS window, the rest of a deep tree's worst case in the spill area
+  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
+  const uint32_t cap = 16;
+  const uint32_t blocks = (n + kBlock - 1) / kBlock;
+  if ((uint64_t)(bound > cap ? bound : 0) * blocks * kBlock > 0xffffffffull)  // entries are addressed with 32-bit offsets (device_core.hpp Stack)
+    return fail(P3D_ERR_CAPACITY, pre + "too many rays for one call over a tree this deep (split the batch)");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (s->tail_pending) {  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
+    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
+    s->tail_pending = false;
+  }
+  if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)(bound > cap ? bound : 0) * blocks * kBlock * sizeof(uint2)))) return rc;
+  RayQueryParams P{};
+  P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
+  P.hit_id = d_hit_id; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.occluded = d_occluded;
+  P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
+  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
+  (void)with_accel(accel, [&](auto A) {
+    if (any) hipLaunchKernelGGL((trace_device_kernel<decltype(A)::value, true>), dim3(blocks), dim3(kBlock), lds, st, P);
+    else hipLaunchKernelGGL((trace_device_kernel<decltype(A)::value, false>), dim3(blocks), dim3(kBlock), lds, st, P);
+    return hipSuccess;
+  });
+  P3D_HIP(hipGetLastError());
+  return P3D_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -57,6 +111,15 @@ int p3d_trace_closest(p3d_scene* s, uint32_t accel, uint32_t n, const float* ori
 }
 int p3d_trace_any(p3d_scene* s, uint32_t accel, uint32_t n, const float* origin, const float* direction, uint8_t* occluded) {
   return trace_common(s, accel, n, origin, direction, nullptr, nullptr, nullptr, occluded, true);
+}
+
+int p3d_trace_closest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
+                             int32_t* d_hit_id, float* d_t, float* d_hit_point, float* d_normal, void* hip_stream) {
+  return trace_device(s, accel, n, d_origin, d_direction, d_t_max, d_hit_id, d_t, d_hit_point, d_normal, nullptr, hip_stream, false);
+}
+int p3d_trace_any_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
+                         uint8_t* d_occluded, void* hip_stream) {
+  return trace_device(s, accel, n, d_origin, d_direction, d_t_max, nullptr, nullptr, nullptr, nullptr, d_occluded, hip_stream, true);
 }
 
 static int object_query(p3d_scene* s, int what, uint32_t object, uint32_t n, const float* a, float* b, uint8_t* hit, float* t) {
