@@ -597,6 +597,54 @@ int p3d_scene_update_geometry_device(p3d_scene* scene, uint32_t n_sources, const
                                      uint32_t mode, float* update_ms);
 
 /*
+ * The REFIT of p3d_scene_update_geometry_device ENQUEUED ON THE CALLER'S STREAM, without a wait: a simulation step that
+ * produces positions on a stream hands them to the scene and asks rays of it (p3d_trace_*_device) or renders it, and the host
+ * is never in the loop.  Detected by the symbol (P3D_ABI_VERSION and p3d_update_mode are unchanged).  `sources` are the
+ * records of p3d_scene_update_geometry_device, with the same meaning.
+ *
+ * What it writes: object-order geometry, shading normal, box, and the rest copy if the scene has one; then the REFIT of the
+ * kept topology - node records and leaf-order geometry.  All of it is, bit for bit, what
+ * p3d_scene_update_geometry_device(..., P3D_UPDATE_REFIT, ...) leaves for the same buffers (boxes are exact min / max and
+ * the keys are unique), with that call's one exception: the NaN normal of a zero-area triangle.  The tree's depth stands: a
+ * refit keeps the topology.
+ *
+ * Stream.  Everything is enqueued on hip_stream (NULL = the default stream) under the scene's stream rules
+ * (p3d_render_tile_device): keep one scene's work on one stream, or order the streams with events.  What the stream had
+ * enqueued to produce the buffers runs first; frames and queries enqueued on that stream after the call see the new
+ * geometry; the buffers may be reused once the stream has passed the call.  With a tail stream set, the launch first joins a
+ * pending tail with hipStreamWaitEvent, as p3d_trace_*_device does.  The sources travel as kernel arguments - nothing of the
+ * call has to outlive it - so there are at most 16 per call: more is P3D_ERR_CAPACITY (the waiting form stages any number).
+ * Capturing the call into a graph is not supported.
+ *
+ * Which calls may wait.  The FIRST p3d_scene_refit_device of a scene allocates the two failure counters and, unless an
+ * earlier update, grid build or cost query has made them, the builder's state and the tree's topology, as the waiting forms
+ * do: it waits for the tail stream and the device.  So does the first call after a geometry update that failed with
+ * P3D_ERR_NO_DEVICE (which voids the topology).  Every other call neither allocates, nor frees, nor waits for the device, nor
+ * copies anything back.  There is no update_ms: time the stream.
+ *
+ * Per-object failures (an index >= n_elems; a new box that is non-finite or inverted) are found by the kernel as in the
+ * waiting form: the object keeps its geometry, the others are updated, and THE CALL RETURNS P3D_OK.  The kernel counts the two
+ * kinds in a block the scene owns and raises a flag: p3d_scene_status then returns P3D_ERR_INVALID with the two counts since
+ * the last check in p3d_last_error, and clears both (with capacity flags pending too it returns P3D_ERR_CAPACITY and the
+ * message carries both).  Render calls never report them: the check behind a call with `stats` leaves this flag pending.
+ *
+ * On return, without a wait: accumulators and adaptive frames refuse passes until reset, the hit_stack row chains are
+ * forgotten, p3d_bvh_cost.refits_since_build is one more, last_update_rebuilt is 0 and sah_baseline is void, as after
+ * a waiting REFIT with the policy off.  The memoised tile schedules are not freed (that would wait): each is recorded
+ * again, in the memory it holds, by the next frame with its key.  The cached root box - it only cuts the ray bins of
+ * P3D_CHAIN_PER_LEVEL, and never changes a result - goes stale; the next call on the scene that waits for the device anyway
+ * (a waiting update, p3d_scene_status, p3d_scene_export_bvh, p3d_scene_bvh_cost, p3d_scene_set_auto_rebuild switching on,
+ * p3d_scene_set_camera) brings it up to date, and a P3D_CHAIN_PER_LEVEL frame that still finds it stale first waits for
+ * its stream and reads it back: THAT FRAME MAY WAIT.
+ *
+ * Refused, nothing enqueued and nothing changed: everything p3d_scene_update_geometry_device refuses before its launch, in
+ * the same words (mode apart); P3D_ERR_UNSUPPORTED for a scene with a device-built grid (its rebuild reads sizes back) and
+ * for a scene whose auto-rebuild ratio is not 0 (the policy needs the cost on the host): both take the waiting form.
+ * n_sources = 0 returns P3D_OK and enqueues nothing.
+ */
+int p3d_scene_refit_device(p3d_scene* scene, uint32_t n_sources, const p3d_geom_source* sources, void* hip_stream);
+
+/*
  * The uniform grid of a live scene, built on the device.  Detected by the symbols (P3D_ABI_VERSION is unchanged).  Only for
  * scenes of p3d_scene_create_device_bvh, which keep their objects' boxes on the device and accept updates.
  *
@@ -862,7 +910,8 @@ int p3d_temporal_accumulate_device(p3d_temporal* tp, const p3d_temporal_params* 
  * incoming hit_stack could not be established, a sample hand-out loop that reached its trip bound and would write pixels
  * with samples missing) raise a flag on the device.  The host-buffer
  * call and every call with `stats` turn it into P3D_ERR_CAPACITY themselves; after device-buffer calls without
- * `stats` ask here: waits for the scene's device, returns P3D_OK or P3D_ERR_CAPACITY and clears the flag.
+ * `stats` ask here: waits for the scene's device, returns P3D_OK or P3D_ERR_CAPACITY and clears the flag.  Once
+ * p3d_scene_refit_device has been used on the scene, the objects its kernel skipped show here too, as P3D_ERR_INVALID (see there).
  */
 int p3d_scene_status(p3d_scene* scene);
 /*

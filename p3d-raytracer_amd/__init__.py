@@ -51,6 +51,7 @@ EXPORTS = [
     "p3d_scene_bvh_cost", "p3d_scene_set_auto_rebuild", "p3d_scene_auto_rebuild",
     "p3d_scene_update_geometry_device",
     "p3d_trace_closest_device", "p3d_trace_any_device",
+    "p3d_scene_refit_device",
 ]
 
 
@@ -314,6 +315,7 @@ def lib():
         L.p3d_trace_closest_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.p3d_trace_any_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_scene_refit_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -817,6 +819,28 @@ class DeviceScene:
         of (first, centre_radius) for several sets in one call."""
         sets = first if isinstance(first, list) else [(first, centre_radius)]
         return self.update_geometry_device([self.sphere_source(*m) for m in sets], mode)
+
+    def refit_device(self, sources, stream=0):
+        """p3d_scene_refit_device: the REFIT of update_geometry_device enqueued on `stream` (a torch.cuda.Stream or a raw
+        hipStream_t; 0 = the default stream) without a wait: what the stream had enqueued to fill the buffers runs first,
+        frames and queries enqueued on it afterwards see the new geometry.  At most 16 GeomSources.  Only the first call on a
+        scene may wait.  Keep the tensors alive until the stream has passed the call.  Objects the kernel skips (a bad
+        index, an unusable box) show in status(), not here.  Accumulators of this scene refuse passes until they are reset."""
+        src = list(sources)
+        arr = (GeomSource * max(len(src), 1))(*src)
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_scene_refit_device(self._h, len(src), C.cast(arr, C.c_void_p) if src else None, C.c_void_p(raw or None)))
+
+    def refit_triangles(self, first, positions=None, indices=None, stream=0):
+        """update_triangles(..., UPDATE_REFIT) on `stream` without a wait (refit_device): the same arguments, tensors or raw
+        (address, rows) pairs, or a list of meshes; refused before the library is called like there."""
+        meshes = first if isinstance(first, list) else [(first, positions, indices)]
+        self.refit_device([self.triangle_source(*m) for m in meshes], stream)
+
+    def refit_spheres(self, first, centre_radius=None, stream=0):
+        """update_spheres(..., UPDATE_REFIT) on `stream` without a wait (refit_device)."""
+        sets = first if isinstance(first, list) else [(first, centre_radius)]
+        self.refit_device([self.sphere_source(*m) for m in sets], stream)
 
     def export_bvh(self):
         """p3d_scene_export_bvh: the current device-built tree as numpy arrays, with the bvh_* keys of HostScene.arrays(bvh=True)

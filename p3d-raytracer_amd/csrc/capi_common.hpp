@@ -144,6 +144,10 @@ struct p3d_scene {
   Scratch stage;                       // the call in progress: a 16-byte counter block | the route's payload (capi_update.hpp)
   std::vector<uint4> stage_host;       // what is uploaded there
   Scratch rest;                        // object-order geometry of the rest pose, 3 float4 per object; made by the first transform
+  // p3d_scene_refit_device (the same scenes)
+  uint32_t* d_refit_skipped = nullptr; // {triangles with an index >= n_elems, objects with an unusable box} since the last check_status();
+                                       // allocated by the first call, added to by its kernel together with upd::kStatusRefitSkipped in d_status
+  bool root_stale = false;             // root_min / root_max are those of an older fit: refresh_root_box() before they are used
   // p3d_scene_build_grid (the same scenes): d_cell_start / d_cell_items above are then the device-built grid
   bool uploaded_grid = false;          // the descriptor carried the host's grid: it cannot follow updates and is never rebuilt
   uint64_t cell_start_cap = 0, cell_items_cap = 0;  // words allocated; they grow when a build needs more and are kept otherwise
@@ -158,6 +162,24 @@ void drop_schedules(p3d_scene* s) {
   for (SchedEntry& e : s->sched)
     if (e.ready) (void)hipEventDestroy(e.ready);
   s->sched.clear();
+}
+
+// The same without freeing anything (a hipFree waits for the device): every schedule is recorded again by the next frame with
+// its key, in the memory it holds (schedule_lookup)
+void void_schedules(p3d_scene* s) {
+  for (SchedEntry& e : s->sched) e.built = false;
+}
+
+// root_min / root_max from the node array, if a fit has been enqueued since they were read.  The caller has waited for the
+// stream(s) that fit ran on
+int refresh_root_box(p3d_scene* s) {
+  if (!s->root_stale) return P3D_OK;
+  float4 root[2];
+  P3D_HIP(hipMemcpy(root, s->d_blob + s->off_nodes, sizeof(root), hipMemcpyDeviceToHost));
+  s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
+  s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
+  s->root_stale = false;
+  return P3D_OK;
 }
 
 // Every float field of a camera is finite, and the view window and plane distance are positive
@@ -197,13 +219,33 @@ hipError_t with_accel(uint32_t accel, F&& f) {
 
 // Device-detected errors (sample hand-out loop hit its trip bound, a leftover outgrew its slot, the hand-off found no
 // fixed point): read and clear the status word.  Call only where the stream has been synchronised.
-int check_status(p3d_scene* s) {
+// render_call: the check behind a render call with `stats` - the objects p3d_scene_refit_device skipped are not the frame's
+// fault: their bit stays pending for p3d_scene_status.
+int check_status(p3d_scene* s, bool render_call = false) {
   uint32_t h = 0;
   P3D_HIP(hipMemcpy(&h, s->d_status, sizeof(h), hipMemcpyDeviceToHost));
-  s->last_status = h;
-  if (!h) return P3D_OK;
-  P3D_HIP(hipMemset(s->d_status, 0, sizeof(uint32_t)));
-  std::string what;
+  if (render_call) {
+    const uint32_t pending = h & upd::kStatusRefitSkipped;
+    h &= ~upd::kStatusRefitSkipped;
+    s->last_status = h;
+    if (!h) return P3D_OK;
+    P3D_HIP(hipMemcpy(s->d_status, &pending, sizeof(pending), hipMemcpyHostToDevice));
+  } else {
+    s->last_status = h;
+    if (!h) return P3D_OK;
+    P3D_HIP(hipMemset(s->d_status, 0, sizeof(uint32_t)));
+  }
+  static_assert((upd::kStatusRefitSkipped & (kHoErrLeftoverCap | kHoErrNoFixedPoint | kHoErrTrips | kHoErrList | kHoErrHalo)) == 0, "one word, distinct bits");
+  std::string skipped;  // p3d_scene_refit_device: objects its kernel did not write
+  if ((h & upd::kStatusRefitSkipped) && s->d_refit_skipped) {
+    uint32_t bad[2] = {0, 0};
+    P3D_HIP(hipMemcpy(bad, s->d_refit_skipped, sizeof(bad), hipMemcpyDeviceToHost));
+    P3D_HIP(hipMemset(s->d_refit_skipped, 0, sizeof(bad)));
+    skipped = " p3d_scene_refit_device: " + std::to_string(bad[0]) + " triangle(s) with an index >= n_elems, " + std::to_string(bad[1]) +
+              " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated;";
+    if (!(h & ~upd::kStatusRefitSkipped)) return fail(P3D_ERR_INVALID, "device-detected error:" + skipped);
+  }
+  std::string what = skipped;
   if (h & kHoErrTrips) what += " sample hand-out loop reached its trip bound (pixels would miss samples);";
   if (h & kHoErrLeftoverCap) what += " the hit_stack leftovers of this frame do not fit their records (p3d_config.handoff_records = P3D_HANDOFF_DENSE has room for the worst case);";
   if (h & kHoErrNoFixedPoint) what += " hit_stack hand-off did not reach a fixed point;";

@@ -177,7 +177,10 @@ int schedule_lookup(p3d_scene* s, const p3d_config* cfg, bool pt, RenderParams& 
       return P3D_OK;
     }
   SchedEntry* e = nullptr;
-  if (s->sched.size() < kSchedCacheEntries) {
+  for (SchedEntry& c : s->sched)
+    if (!e && !c.built && c.same_key(key)) e = &c;
+  if (e) {  // voided by p3d_scene_refit_device (void_schedules): recorded again in the memory it holds, nothing freed
+  } else if (s->sched.size() < kSchedCacheEntries) {
     s->sched.emplace_back();
     e = &s->sched.back();
   } else {  // recycle the least recently used entry once the work queued with it has drained
@@ -238,7 +241,7 @@ int finish_stats(p3d_scene* s, hipStream_t st, p3d_stats* stats, bool literal) {
     if (print_handoff) std::fprintf(stderr, "handoff: checked %u redone %u rounds %u pool %u lists A %u B %u C %u D %u check_n %u round0 %u round1 %u\n", c[kHoChecked], c[kHoRedone], c[kHoRounds], c[kHoPoolTop], c[kHoListA], c[kHoListB], c[kHoListC], c[kHoListD], c[kHoCheckN], c[kHoRound0], c[kHoRound1]);
     stats->handoff_checked = c[kHoChecked]; stats->handoff_redone = c[kHoRedone]; stats->handoff_rounds = c[kHoRounds] + (c[kHoRound0] ? 1 : 0) + (c[kHoRound1] ? 1 : 0);
   }
-  return check_status(s);
+  return check_status(s, true);
 }
 
 // What every render call checks before it touches the device: the tile lies in the image, the options are known.
@@ -305,6 +308,10 @@ struct FrameLaunch {
       s->tail_pending = false;
     }
     if (int rc = plan_frame(scene_facts(s), cfg, tile, sample_begin, sample_end, mode, resident, plan)) return rc;
+    if (plan.per_level && s->root_stale) {  // the ray queue's bins are cut from the root box, which p3d_scene_refit_device left on the device
+      P3D_HIP(hipStreamSynchronize(st));    // (the scene's stream rules put that refit in front of this frame on `st`)
+      if (int rc = refresh_root_box(s)) return rc;
+    }
     want_counts = stats && cfg->collect_stats;
     fill_params(sample_begin, sample_end);
     if (int rc = ensure_scratch()) return rc;
@@ -823,6 +830,7 @@ int p3d_scene_status(p3d_scene* s) {
   if (!s) return fail(P3D_ERR_INVALID, "p3d_scene_status: null argument");
   P3D_HIP(hipSetDevice(s->device));
   P3D_HIP(hipDeviceSynchronize());
+  if (int rc = refresh_root_box(s)) return rc;
   return check_status(s);
 }
 

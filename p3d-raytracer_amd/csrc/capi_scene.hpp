@@ -14,7 +14,7 @@ int p3d_device_count(void) {
 void p3d_scene_destroy(p3d_scene* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  for (void* p : {(void*)s->d_blob, (void*)s->d_cell_start, (void*)s->d_cell_items, (void*)s->d_emitters, (void*)s->d_stats, (void*)s->d_status,
+  for (void* p : {(void*)s->d_blob, (void*)s->d_cell_start, (void*)s->d_cell_items, (void*)s->d_emitters, (void*)s->d_stats, (void*)s->d_status, (void*)s->d_refit_skipped,
                   (void*)s->d_halo_verdict, (void*)s->d_sky[0], (void*)s->d_sky[1], (void*)s->d_sky[2], (void*)s->d_sky[3], (void*)s->d_sky[4], (void*)s->d_sky[5]})
     if (p) (void)hipFree(p);
   drop_schedules(s);

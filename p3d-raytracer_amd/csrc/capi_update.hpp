@@ -1,5 +1,5 @@
 // capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims, p3d_scene_transform_prims,
-// p3d_scene_update_geometry_device), and the export of a device-built tree
+// p3d_scene_update_geometry_device, and p3d_scene_refit_device on the caller's stream), and the export of a device-built tree
 #pragma once
 #include "capi_grid.hpp"
 
@@ -102,6 +102,7 @@ int finish_update(p3d_scene* s, uint32_t mode, hipError_t e, const char* who, fl
   s->sah_baseline = !policy ? 0.0 : rebuilt ? sah_of(cost) : s->sah_baseline;
   s->root_min[0] = root[0].x; s->root_min[1] = root[0].y; s->root_min[2] = root[0].z;
   s->root_max[0] = root[1].x; s->root_max[1] = root[1].y; s->root_max[2] = root[1].z;
+  s->root_stale = false;
   if (update_ms) *update_ms = ms;
   return grid_rc;  // (rebuild_grid has recorded its message)
 }
@@ -135,6 +136,7 @@ int measure_cost(p3d_scene* s, const char* who, lbvh::CostResult* out) {
   P3D_HIP(hipSetDevice(s->device));
   if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
   P3D_HIP(hipDeviceSynchronize());
+  if (int rc = refresh_root_box(s)) return rc;
   if (int rc = ensure_fitted_workspace(s, who)) return rc;
   if (hipError_t e = read_cost(s->lbvh_ws, out); e != hipSuccess)
     return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": cost: " + hipGetErrorString(e));
@@ -203,6 +205,41 @@ int run_update(p3d_scene* s, uint32_t mode, const char* who, float* update_ms, u
   return fail(P3D_ERR_INVALID, std::string(who) + ": " + failed(bad));
 }
 
+// The sources of p3d_scene_update_geometry_device / p3d_scene_refit_device, each checked against the scene and its buffers
+// against what the runtime knows of them, then sorted as find_span wants them; *total: the objects covered.  Makes the
+// scene's device current (the pointer queries answer for the current device's context)
+int stage_sources(const p3d_scene* s, const std::string& pre, uint32_t n_sources, const p3d_geom_source* sources,
+                  std::vector<upd::StagedSource>& sorted, uint32_t* total) {
+  const uint32_t n_objs = s->dev.n_objs;
+  P3D_HIP(hipSetDevice(s->device));
+  sorted.resize(n_sources);
+  for (uint32_t r = 0; r < n_sources; ++r) {
+    const p3d_geom_source& g = sources[r];
+    const std::string at = pre + "source " + std::to_string(r);
+    if (g.count == 0) return fail(P3D_ERR_INVALID, at + " is empty");
+    if ((uint64_t)g.first + g.count > n_objs) return fail(P3D_ERR_INVALID, at + " ends behind the last object");
+    if (g.kind != P3D_PRIM_TRIANGLE && g.kind != P3D_PRIM_SPHERE) return fail(P3D_ERR_INVALID, at + ": kind must be P3D_PRIM_TRIANGLE or P3D_PRIM_SPHERE");
+    if (g.reserved[0] | g.reserved[1]) return fail(P3D_ERR_INVALID, at + ": reserved must be 0");
+    if (!g.d_data) return fail(P3D_ERR_INVALID, at + ": null d_data");
+    if (((uintptr_t)g.d_data | (uintptr_t)g.d_index) & 3u) return fail(P3D_ERR_INVALID, at + ": d_data and d_index must be 4-byte aligned");
+    if (g.n_elems == 0) return fail(P3D_ERR_INVALID, at + ": n_elems is 0");
+    if (g.kind == P3D_PRIM_SPHERE) {
+      if (g.d_index) return fail(P3D_ERR_INVALID, at + ": d_index given for spheres");
+      if (g.n_elems != g.count) return fail(P3D_ERR_INVALID, at + ": spheres need n_elems == count");
+    } else if (!g.d_index && (uint64_t)g.n_elems != 3 * (uint64_t)g.count) {
+      return fail(P3D_ERR_INVALID, at + ": a soup (d_index NULL) needs n_elems == 3 * count");
+    }
+    for (uint32_t o = g.first; o < g.first + g.count; ++o)
+      if ((s->obj_tm[o] & 0xffu) != g.kind) return fail(P3D_ERR_INVALID, at + ": object " + std::to_string(o) + " is of another type");
+    const size_t data_bytes = g.kind == P3D_PRIM_SPHERE ? (size_t)16 * g.count : (size_t)12 * g.n_elems;
+    if (int rc = device_buffer_usable(s, g.d_data, data_bytes, at + ": d_data")) return rc;
+    if (g.d_index)
+      if (int rc = device_buffer_usable(s, g.d_index, (size_t)12 * g.count, at + ": d_index")) return rc;
+    sorted[r] = upd::StagedSource{g.first, g.count, g.kind, 0u, (const float*)g.d_data, g.d_index, g.n_elems, {0u, 0u, 0u}};
+  }
+  return sort_spans(sorted, pre, "sources", total, [](const upd::StagedSource&) { return (int)P3D_OK; });
+}
+
 }  // namespace
 
 extern "C" {
@@ -233,6 +270,7 @@ int p3d_scene_set_camera(p3d_scene* s, const p3d_camera* cam) {
   // The scene's scratch and memos may still be in use by enqueued work: its tail stream and the caller's streams
   if (int rc = p3d_scene_join(s, nullptr, 1)) return rc;
   P3D_HIP(hipDeviceSynchronize());
+  if (int rc = refresh_root_box(s)) return rc;
   const DevCamera n = dev_camera(*cam);
   if (std::memcmp(&n, &c, sizeof(DevCamera)) == 0) return P3D_OK;  // the same view: nothing to forget
   c = n;
@@ -340,34 +378,9 @@ int p3d_scene_update_geometry_device(p3d_scene* s, uint32_t n_sources, const p3d
   if (int rc = update_refused(s, mode, pre, n_sources && !sources ? "null sources with n_sources > 0" : nullptr)) return rc;
   const uint32_t n_objs = s->dev.n_objs;
   if (n_sources > n_objs) return fail(P3D_ERR_INVALID, pre + "more sources than objects (sources overlap or are empty)");
-  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
-  std::vector<upd::StagedSource> sorted(n_sources);
-  for (uint32_t r = 0; r < n_sources; ++r) {
-    const p3d_geom_source& g = sources[r];
-    const std::string at = pre + "source " + std::to_string(r);
-    if (g.count == 0) return fail(P3D_ERR_INVALID, at + " is empty");
-    if ((uint64_t)g.first + g.count > n_objs) return fail(P3D_ERR_INVALID, at + " ends behind the last object");
-    if (g.kind != P3D_PRIM_TRIANGLE && g.kind != P3D_PRIM_SPHERE) return fail(P3D_ERR_INVALID, at + ": kind must be P3D_PRIM_TRIANGLE or P3D_PRIM_SPHERE");
-    if (g.reserved[0] | g.reserved[1]) return fail(P3D_ERR_INVALID, at + ": reserved must be 0");
-    if (!g.d_data) return fail(P3D_ERR_INVALID, at + ": null d_data");
-    if (((uintptr_t)g.d_data | (uintptr_t)g.d_index) & 3u) return fail(P3D_ERR_INVALID, at + ": d_data and d_index must be 4-byte aligned");
-    if (g.n_elems == 0) return fail(P3D_ERR_INVALID, at + ": n_elems is 0");
-    if (g.kind == P3D_PRIM_SPHERE) {
-      if (g.d_index) return fail(P3D_ERR_INVALID, at + ": d_index given for spheres");
-      if (g.n_elems != g.count) return fail(P3D_ERR_INVALID, at + ": spheres need n_elems == count");
-    } else if (!g.d_index && (uint64_t)g.n_elems != 3 * (uint64_t)g.count) {
-      return fail(P3D_ERR_INVALID, at + ": a soup (d_index NULL) needs n_elems == 3 * count");
-    }
-    for (uint32_t o = g.first; o < g.first + g.count; ++o)
-      if ((s->obj_tm[o] & 0xffu) != g.kind) return fail(P3D_ERR_INVALID, at + ": object " + std::to_string(o) + " is of another type");
-    const size_t data_bytes = g.kind == P3D_PRIM_SPHERE ? (size_t)16 * g.count : (size_t)12 * g.n_elems;
-    if (int rc = device_buffer_usable(s, g.d_data, data_bytes, at + ": d_data")) return rc;
-    if (g.d_index)
-      if (int rc = device_buffer_usable(s, g.d_index, (size_t)12 * g.count, at + ": d_index")) return rc;
-    sorted[r] = upd::StagedSource{g.first, g.count, g.kind, 0u, (const float*)g.d_data, g.d_index, g.n_elems, {0u, 0u, 0u}};
-  }
+  std::vector<upd::StagedSource> sorted;
   uint32_t total = 0;
-  if (int rc = sort_spans(sorted, pre, "sources", &total, [](const upd::StagedSource&) { return (int)P3D_OK; })) return rc;
+  if (int rc = stage_sources(s, pre, n_sources, sources, sorted, &total)) return rc;
   if (update_ms) *update_ms = 0.0f;
   if (n_objs == 0) return P3D_OK;
   // one upload: the two counters (zero), the sources
@@ -381,6 +394,60 @@ int p3d_scene_update_geometry_device(p3d_scene* s, uint32_t n_sources, const p3d
     return std::to_string(bad[0]) + " triangle(s) with an index >= n_elems, " + std::to_string(bad[1]) +
            " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated";
   });
+}
+
+int p3d_scene_refit_device(p3d_scene* s, uint32_t n_sources, const p3d_geom_source* sources, void* hip_stream) {
+  const char* who = "p3d_scene_refit_device";
+  const std::string pre = std::string(who) + ": ";
+  if (int rc = update_refused(s, P3D_UPDATE_REFIT, pre, n_sources && !sources ? "null sources with n_sources > 0" : nullptr)) return rc;
+  const uint32_t n_objs = s->dev.n_objs;
+  if (n_sources > n_objs) return fail(P3D_ERR_INVALID, pre + "more sources than objects (sources overlap or are empty)");
+  if (s->has_grid)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene has a device-built grid, whose rebuild reads sizes back (p3d_scene_update_geometry_device follows it)");
+  if (s->auto_rebuild != 0.0f)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the auto-rebuild policy is on and needs the cost on the host (p3d_scene_update_geometry_device applies it, p3d_scene_set_auto_rebuild(0) switches it off)");
+  if (n_sources > upd::kMaxArgSources)
+    return fail(P3D_ERR_CAPACITY, pre + std::to_string(n_sources) + " sources, at most " + std::to_string(upd::kMaxArgSources) +
+                                      " travel with one call (p3d_scene_update_geometry_device stages any number)");
+  std::vector<upd::StagedSource> sorted;
+  uint32_t total = 0;
+  if (int rc = stage_sources(s, pre, n_sources, sources, sorted, &total)) return rc;
+  if (n_objs == 0 || n_sources == 0) return P3D_OK;
+  lbvh::Workspace& w = s->lbvh_ws;
+  if (!w.n || !s->lbvh_topology || !s->d_refit_skipped) {
+    // the setup, as the waiting forms do it: the builder's state and the topology of the tree in d_blob, behind everything
+    // enqueued; and the counter block
+    if (int rc = begin_update(s, P3D_UPDATE_REFIT, who)) return rc;
+    if (!s->d_refit_skipped) {
+      P3D_HIP(hipMalloc((void**)&s->d_refit_skipped, 2 * sizeof(uint32_t)));
+      P3D_HIP(hipMemset(s->d_refit_skipped, 0, 2 * sizeof(uint32_t)));
+    }
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (s->tail_pending) {  // the previous frame's tail reads the geometry (p3d_scene_set_tail_stream)
+    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
+    s->tail_pending = false;
+  }
+  // from here on the scene changes
+  upd::ArgSources table{};
+  std::copy(sorted.begin(), sorted.end(), table.s);
+  float4* blob = s->d_blob;
+  // (total <= n_objs = w.n: the grid that gathers also clears the fit's n_objs arrival counters)
+  hipLaunchKernelGGL(upd::gather_geometry_args, dim3((n_objs + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, st, table, n_sources,
+                     total, n_objs, blob + s->off_ogeom, blob + s->off_normals, w.boxes, (float4*)s->rest.p, s->d_refit_skipped, s->d_status, w.visits);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom, st, true, true);
+  // the old geometry's memos are void, as after every update; nothing here frees or reads back
+  ++s->geom_gen;
+  void_schedules(s);
+  s->ho_chain_key.clear();
+  s->root_stale = true;
+  s->lbvh_fitted = e == hipSuccess;
+  if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, pre + "update: " + hipGetErrorString(e));
+  s->last_update_rebuilt = false;
+  ++s->refits_since_build;
+  s->sah_baseline = 0.0;  // (the policy is off: nothing was measured)
+  return P3D_OK;
 }
 
 int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {
@@ -401,6 +468,7 @@ int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, u
   std::vector<float4> rec((size_t)2 * n_rec), geom((size_t)3 * n);
   P3D_HIP(hipMemcpy(rec.data(), s->d_blob + s->off_nodes, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
   P3D_HIP(hipMemcpy(geom.data(), s->d_blob + s->off_bgeom, geom.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  if (int rc = refresh_root_box(s)) return rc;  // (a call that waits anyway brings the cached root box up to date)
   // The device numbering (children of Karras node i at 1 + 2 i, 2 + 2 i) does not put children behind their parent, and a
   // pair of leaves emitted as one leaf leaves its child records unused: relabel by a depth-first walk, left child first
   std::vector<p3d_bvh_node> out;

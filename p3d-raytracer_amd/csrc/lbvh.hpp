@@ -114,9 +114,11 @@ __device__ __forceinline__ float4 fresh(const float4* p) {
                      __hip_atomic_load(f + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0.f);
 }
 
-// node_box: [2 * ref] / [2 * ref + 1] = min / max of the node with that reference value
-__global__ void refit(const unsigned long long* keys, const float4* boxes, uint32_t n, const uint2* children,
-                      const uint32_t* parent, uint32_t* visits, float4* node_box, uint32_t* leaf_depth_max) {
+// node_box: [2 * ref] / [2 * ref + 1] = min / max of the node with that reference value.  DEPTH: every leaf then walks to the
+// root once more and leaves the tree's depth in *leaf_depth_max; without it that word is neither read nor written
+template <bool DEPTH>
+__device__ __forceinline__ void refit_leaf(const unsigned long long* keys, const float4* boxes, uint32_t n, const uint2* children,
+                                           const uint32_t* parent, uint32_t* visits, float4* node_box, uint32_t* leaf_depth_max) {
   const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
   if (k >= n) return;
   const uint32_t obj = (uint32_t)(keys[k] & 0xffffffffull);
@@ -124,7 +126,10 @@ __global__ void refit(const unsigned long long* keys, const float4* boxes, uint3
   node_box[2 * ref] = boxes[2 * obj];
   node_box[2 * ref + 1] = boxes[2 * obj + 1];
   uint32_t depth = 1;
-  if (n == 1) { atomicMax(leaf_depth_max, depth); return; }
+  if (n == 1) {
+    if (DEPTH) atomicMax(leaf_depth_max, depth);
+    return;
+  }
   uint32_t p = parent[ref];
   while (true) {
     __threadfence();  // this thread's box is visible before it announces itself
@@ -139,9 +144,19 @@ __global__ void refit(const unsigned long long* keys, const float4* boxes, uint3
     if (p == 0) break;
     p = parent[ref];
   }
+  if (!DEPTH) return;
   // depth of this leaf = number of nodes on its path from the root (bvh_max_depth convention)
   for (uint32_t r = (k << 1) | 1u; parent[r] != 0xffffffffu; r = parent[r] << 1) ++depth;
   atomicMax(leaf_depth_max, depth + 0u);
+}
+__global__ void refit(const unsigned long long* keys, const float4* boxes, uint32_t n, const uint2* children,
+                      const uint32_t* parent, uint32_t* visits, float4* node_box, uint32_t* leaf_depth_max) {
+  refit_leaf<true>(keys, boxes, n, children, parent, visits, node_box, leaf_depth_max);
+}
+// The fit of a kept topology: the depth cannot have changed (p3d_scene_refit_device)
+__global__ void refit_kept_depth(const unsigned long long* keys, const float4* boxes, uint32_t n, const uint2* children,
+                                 const uint32_t* parent, uint32_t* visits, float4* node_box) {
+  refit_leaf<false>(keys, boxes, n, children, parent, visits, node_box, nullptr);
 }
 
 // An internal node whose two children are both leaves is emitted as ONE leaf of two objects (their
@@ -326,13 +341,22 @@ inline hipError_t enqueue_topology(Workspace& w, const float4* d_boxes) {
   return hipGetLastError();
 }
 
-// Steps 4 and 5 over the topology in w: node boxes bottom-up from d_boxes, then the node records and the leaf-order geometry
-inline hipError_t enqueue_fit(Workspace& w, const float4* d_boxes, const float4* d_ogeom, float4* d_nodes, float4* d_bgeom) {
+// Steps 4 and 5 over the topology in w, on `st`: node boxes bottom-up from d_boxes, then the node records and the leaf-order
+// geometry.  keep_depth: the topology is the one w.depth was worked out for - no depth walk, w.depth untouched.
+// visits_clear: a kernel in front of this call on `st` has zeroed w.visits[0 .. n) - no memset launch.  The one kernel that
+// does is upd::gather_geometry_args (p3d_scene_refit_device); a caller that passes true without it makes the fit count
+// wrong arrivals, silently
+inline hipError_t enqueue_fit(Workspace& w, const float4* d_boxes, const float4* d_ogeom, float4* d_nodes, float4* d_bgeom,
+                              hipStream_t st = 0, bool keep_depth = false, bool visits_clear = false) {
   const uint32_t n = w.n, blocks = (n + kThreads - 1) / kThreads;
-  P3D_LBVH_HIP(hipMemsetAsync(w.visits, 0, (size_t)n * sizeof(uint32_t), 0));
-  P3D_LBVH_HIP(hipMemsetAsync(w.depth, 0, sizeof(uint32_t), 0));
-  hipLaunchKernelGGL(refit, dim3(blocks), dim3(kThreads), 0, 0, w.sorted, d_boxes, n, w.children, w.parent, w.visits, w.node_box, w.depth);
-  hipLaunchKernelGGL(emit, dim3(blocks), dim3(kThreads), 0, 0, w.sorted, n, w.children, w.node_box, d_ogeom, d_nodes, d_bgeom);
+  if (!visits_clear) P3D_LBVH_HIP(hipMemsetAsync(w.visits, 0, (size_t)n * sizeof(uint32_t), st));
+  if (keep_depth) {
+    hipLaunchKernelGGL(refit_kept_depth, dim3(blocks), dim3(kThreads), 0, st, w.sorted, d_boxes, n, w.children, w.parent, w.visits, w.node_box);
+  } else {
+    P3D_LBVH_HIP(hipMemsetAsync(w.depth, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(refit, dim3(blocks), dim3(kThreads), 0, st, w.sorted, d_boxes, n, w.children, w.parent, w.visits, w.node_box, w.depth);
+  }
+  hipLaunchKernelGGL(emit, dim3(blocks), dim3(kThreads), 0, st, w.sorted, n, w.children, w.node_box, d_ogeom, d_nodes, d_bgeom);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // update_kernels.hpp — the device half of the three geometry updates of a live scene: host records (p3d_scene_update_prims),
-// transforms of the rest pose (p3d_scene_transform_prims) and positions in device memory (p3d_scene_update_geometry_device).
+// transforms of the rest pose (p3d_scene_transform_prims) and positions in device memory (p3d_scene_update_geometry_device,
+// and p3d_scene_refit_device, which hands its sources over as a kernel argument).
 //
 // One thread per covered object, blocks of lbvh::kThreads.  Each kernel works out an object's nine geometry floats, shading
 // normal and box its own way - the arithmetic is host/prim_rule.hpp's, so the result is what the host constructors give for
@@ -40,6 +41,10 @@ struct StagedSource {
   uint32_t n_elems, pad[3];
 };
 static_assert(sizeof(StagedRange) == 16 && sizeof(StagedSource) == 48, "a span is staged as one or three uint4, its head read as one");
+
+// The bit p3d_scene_refit_device's kernel raises in the scene's status word when it skips an object (the kHoErr* bits of
+// handoff.hpp are below it); the counts are in the scene's counter block
+constexpr uint32_t kStatusRefitSkipped = 32u;
 
 __device__ __forceinline__ bool box_usable(const float lo[3], const float hi[3]) {
   bool ok = true;
@@ -145,14 +150,9 @@ __global__ void transform_prims(const float4* rest, const uint4* ranges, uint32_
 // positions gathered, as scalar floats (the caller's memory is 4-byte aligned, no more).
 // counters[0]: triangles with an index >= n_elems, counters[1]: objects whose new box is non-finite or inverted.  Neither kind
 // of object is written.  No read of a source's `data` outside [0, n_elems) elements, none of `index` outside [0, 3 count).
-__global__ void gather_geometry(const StagedSource* sources, uint32_t n_sources, uint32_t total, uint32_t n_objs, float4* ogeom,
-                                float4* normals, float4* boxes, float4* rest, uint32_t* counters) {
-  const uint32_t i = blockIdx.x * lbvh::kThreads + threadIdx.x;
-  if (i >= total) return;
-  uint32_t at, k, obj;
-  uint4 head;
-  if (!find_span<3>(reinterpret_cast<const uint4*>(sources), n_sources, i, n_objs, at, head, k, obj)) return;
-  const StagedSource sg = sources[at];
+// `skipped` (null: nothing more) takes kStatusRefitSkipped when an object fails: p3d_scene_refit_device, whose caller asks later.
+__device__ __forceinline__ void gather_object(const StagedSource& sg, uint32_t k, uint32_t obj, float4* ogeom, float4* normals, float4* boxes,
+                                              float4* rest, uint32_t* counters, uint32_t* skipped) {
   const float4 c = ogeom[3 * obj + 2];
   const uint32_t type = __float_as_uint(c.y) & 0xffu;
   if (type != sg.kind) return;
@@ -164,6 +164,7 @@ __global__ void gather_geometry(const StagedSource* sources, uint32_t n_sources,
       for (int q = 0; q < 3; ++q) idx[q] = sg.index[3 * (size_t)k + q];
     if (idx[0] >= sg.n_elems || idx[1] >= sg.n_elems || idx[2] >= sg.n_elems) {  // before the gather
       atomicAdd(&counters[0], 1u);
+      if (skipped) atomicOr(skipped, kStatusRefitSkipped);
       return;
     }
     for (int q = 0; q < 3; ++q) {
@@ -181,10 +182,46 @@ __global__ void gather_geometry(const StagedSource* sources, uint32_t n_sources,
   }
   if (!box_usable(lo, hi)) {
     atomicAdd(&counters[1], 1u);
+    if (skipped) atomicOr(skipped, kStatusRefitSkipped);
     return;
   }
   store_object(obj, make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), v[8], __float_as_uint(c.y), n, lo, hi, ogeom,
                rest, normals, boxes);
+}
+
+__global__ void gather_geometry(const StagedSource* sources, uint32_t n_sources, uint32_t total, uint32_t n_objs, float4* ogeom,
+                                float4* normals, float4* boxes, float4* rest, uint32_t* counters) {
+  const uint32_t i = blockIdx.x * lbvh::kThreads + threadIdx.x;
+  if (i >= total) return;
+  uint32_t at, k, obj;
+  uint4 head;
+  if (!find_span<3>(reinterpret_cast<const uint4*>(sources), n_sources, i, n_objs, at, head, k, obj)) return;
+  const StagedSource sg = sources[at];
+  gather_object(sg, k, obj, ogeom, normals, boxes, rest, counters, nullptr);
+}
+
+// gather_geometry with the sources as a kernel argument (p3d_scene_refit_device: no staging buffer, nothing to outlive the
+// call): at most kMaxArgSources, sorted and with `before` filled like the staged ones.  The thread's source is picked by a
+// chain of selects over constant indices - a search through the argument by a run-time index would first copy the table to
+// scratch.  counters: the scene's own block, added to and never cleared here; *status takes kStatusRefitSkipped with them.
+// The launch covers n_objs threads (total <= n_objs): thread i also zeroes visits[i], the fit's arrival counters, which
+// spares the stream a memset launch between this kernel and the fit (lbvh::enqueue_fit, visits_clear).
+constexpr uint32_t kMaxArgSources = 16;
+struct ArgSources {
+  StagedSource s[kMaxArgSources];
+};
+__global__ void gather_geometry_args(const ArgSources table, uint32_t n_sources, uint32_t total, uint32_t n_objs, float4* ogeom,
+                                     float4* normals, float4* boxes, float4* rest, uint32_t* counters, uint32_t* status, uint32_t* visits) {
+  const uint32_t i = blockIdx.x * lbvh::kThreads + threadIdx.x;
+  if (i < n_objs) visits[i] = 0u;
+  if (i >= total) return;
+  StagedSource sg = table.s[0];
+#pragma unroll
+  for (uint32_t r = 1; r < kMaxArgSources; ++r)
+    if (r < n_sources && table.s[r].before <= i) sg = table.s[r];  // (sorted: the last one with before <= i stays)
+  const uint32_t k = i - sg.before, obj = sg.first + k;
+  if (k >= sg.count || obj >= n_objs) return;
+  gather_object(sg, k, obj, ogeom, normals, boxes, rest, counters, status);
 }
 
 }  // namespace upd
