@@ -645,6 +645,67 @@ int p3d_scene_update_geometry_device(p3d_scene* scene, uint32_t n_sources, const
 int p3d_scene_refit_device(p3d_scene* scene, uint32_t n_sources, const p3d_geom_source* sources, void* hip_stream);
 
 /*
+ * The REFIT of p3d_scene_transform_prims ENQUEUED ON THE CALLER'S STREAM, without a wait: a rigid-body or robot simulation
+ * that produces one 3x4 pose per body per step in device memory hands the poses to the scene and asks rays of it or renders
+ * it, and the host is never in the loop.  Detected by the symbols (P3D_ABI_VERSION and p3d_update_mode are unchanged).  The
+ * same scenes as p3d_scene_transform_prims.  Which objects follow which body does not change from step to step, only the
+ * matrices do: the ranges are given once, as a RIG, by a call that may wait; the pose call takes the matrices and a stream.
+ *
+ * p3d_scene_set_rig: objects [first, first + count) of ranges[i] follow transform slot ranges[i].xform of later poses, with
+ * the meaning the records have in p3d_scene_transform_prims; objects that no range names are never touched.  n_xforms is the
+ * number of slots every later pose must bring.  The call waits for the tail stream and the device, as every update does, and
+ * makes what a pose needs and may not wait for: the rest copy, from the scene's geometry of this moment if the scene has none
+ * (the rule of the first p3d_scene_transform_prims); the builder's state and the tree's topology; two failure counters; and
+ * the rig on the device, one word per object (4 bytes per object, whatever the number of ranges).  A second call replaces the
+ * rig; n_ranges = 0 removes it and frees the table.  The rig survives every geometry update, REBUILD included (objects keep
+ * their types and indices).  Refused with P3D_ERR_INVALID, nothing changed: a null scene; a scene of p3d_scene_create; a
+ * scene with an uploaded grid; NULL ranges with n_ranges > 0; n_ranges > 0 with n_xforms = 0; a range with count = 0, first +
+ * count > the object count, xform >= n_xforms or reserved != 0; ranges that overlap (their order is free); a range that
+ * covers a plane.  A box IS accepted: whether a matrix suits it is only known on the device (see below).
+ * p3d_scene_rig: the ranges and slots of the current rig and the objects it covers; three zeros without one.
+ *
+ * p3d_scene_pose_device: every rigged object becomes d_xforms[its slot](rest), with radius' = radius * d_sphere_scale[its
+ * slot] for a sphere, by the arithmetic of p3d_scene_transform_prims; then the REFIT of the kept topology.  What the call
+ * leaves - object-order geometry, shading normals, boxes, node records, leaf-order geometry - is, bit for bit, what
+ * p3d_scene_transform_prims(the rig's ranges, the same numbers, P3D_UPDATE_REFIT) leaves.  The rest copy is not written.
+ * d_xforms: n_xforms x 12 float32 in DEVICE memory, row-major 3x4, one matrix per slot (a contiguous [K, 3, 4] tensor);
+ * d_sphere_scale: n_xforms float32 in DEVICE memory, or NULL = 1 for every slot.  4-byte alignment is enough.
+ *
+ * Stream, and which calls may wait: as p3d_scene_refit_device.  Everything is enqueued on hip_stream (NULL = the default
+ * stream); what the stream had enqueued to produce the matrices runs first, frames and queries enqueued on it afterwards see
+ * the new pose, and the buffers may be reused once the stream has passed the call.  A pending tail stream is joined with
+ * hipStreamWaitEvent.  On a rigged scene the call neither allocates, nor frees, nor waits for the device, nor copies anything
+ * back, and returns while the stream may still be busy (the one exception: the first call after a geometry update that
+ * failed with P3D_ERR_NO_DEVICE, which makes the topology again).  What it leaves on the host - accumulators refusing
+ * passes, forgotten row chains, refits_since_build, the tile schedules recorded again in place, the stale root box and the
+ * P3D_CHAIN_PER_LEVEL frame that may wait for it - is what p3d_scene_refit_device leaves.  Capturing the call into a graph is
+ * not supported.
+ *
+ * Per-object skips, found by the kernel (the host cannot see the numbers: these are the checks the waiting form makes on the
+ * host, made per object).  An object keeps its current geometry, and is counted in the first of two counters, if its
+ * transform has a non-finite entry among the 12, if its sphere_scale is not finite and > 0 (whatever the object's type, as
+ * the waiting form refuses such a transform whatever it moves), or if it is a box and the matrix is not positive-diagonal
+ * (m[0], m[5], m[10] > 0 and the six off-diagonal entries exactly 0).  It keeps its geometry and is counted in the second
+ * if its new box is non-finite or inverted (finite inputs can overflow).  The other objects are updated and THE CALL RETURNS
+ * P3D_OK; p3d_scene_status then returns P3D_ERR_INVALID with the two counts since the last check in p3d_last_error and
+ * clears both, exactly as for the skips of p3d_scene_refit_device (with capacity flags pending too it returns
+ * P3D_ERR_CAPACITY and the message carries both; render calls never report them).
+ *
+ * Refused, nothing enqueued and nothing changed: P3D_ERR_INVALID for a null scene, a scene of p3d_scene_create, a scene with
+ * an uploaded grid, a scene without a rig, n_xforms other than the rig's, NULL d_xforms, a pointer that is not 4-byte
+ * aligned, and a buffer that the HIP runtime identifies as host memory or memory of another device or that ends behind its
+ * allocation (48 n_xforms bytes, 4 n_xforms for the scales; a pointer the runtime cannot answer for is let through);
+ * P3D_ERR_UNSUPPORTED for a scene with a device-built grid and for a scene whose auto-rebuild ratio is not 0: both take
+ * p3d_scene_transform_prims.  A scene without objects returns P3D_OK.
+ */
+int p3d_scene_set_rig(p3d_scene* scene, uint32_t n_ranges, const p3d_xform_range* ranges /* HOST */, uint32_t n_xforms);
+int p3d_scene_rig(p3d_scene* scene, uint32_t* n_ranges, uint32_t* n_xforms, uint32_t* n_posed_objects);
+int p3d_scene_pose_device(p3d_scene* scene, uint32_t n_xforms,
+                          const void* d_xforms,        /* DEVICE, float32, n_xforms x 12, row-major 3x4, 4-byte aligned */
+                          const void* d_sphere_scale,  /* DEVICE, float32, n_xforms; NULL = 1 for every transform */
+                          void* hip_stream);
+
+/*
  * The uniform grid of a live scene, built on the device.  Detected by the symbols (P3D_ABI_VERSION is unchanged).  Only for
  * scenes of p3d_scene_create_device_bvh, which keep their objects' boxes on the device and accept updates.
  *
@@ -911,7 +972,8 @@ int p3d_temporal_accumulate_device(p3d_temporal* tp, const p3d_temporal_params* 
  * with samples missing) raise a flag on the device.  The host-buffer
  * call and every call with `stats` turn it into P3D_ERR_CAPACITY themselves; after device-buffer calls without
  * `stats` ask here: waits for the scene's device, returns P3D_OK or P3D_ERR_CAPACITY and clears the flag.  Once
- * p3d_scene_refit_device has been used on the scene, the objects its kernel skipped show here too, as P3D_ERR_INVALID (see there).
+ * p3d_scene_refit_device or p3d_scene_pose_device has been used on the scene, the objects their kernels skipped show here
+ * too, as P3D_ERR_INVALID (see there).
  */
 int p3d_scene_status(p3d_scene* scene);
 /*

@@ -52,6 +52,7 @@ EXPORTS = [
     "p3d_scene_update_geometry_device",
     "p3d_trace_closest_device", "p3d_trace_any_device",
     "p3d_scene_refit_device",
+    "p3d_scene_set_rig", "p3d_scene_rig", "p3d_scene_pose_device",
 ]
 
 
@@ -316,6 +317,9 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.p3d_trace_any_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.p3d_scene_refit_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.p3d_scene_set_rig.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.p3d_scene_rig.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.p3d_scene_pose_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -841,6 +845,46 @@ class DeviceScene:
         """update_spheres(..., UPDATE_REFIT) on `stream` without a wait (refit_device)."""
         sets = first if isinstance(first, list) else [(first, centre_radius)]
         self.refit_device([self.sphere_source(*m) for m in sets], stream)
+
+    def set_rig(self, ranges, n_xforms):
+        """p3d_scene_set_rig: the objects of every (first, count, xform) in `ranges` (as for transform_prims) follow slot
+        `xform` of the `n_xforms` matrices every later pose_device brings.  A setup call: it waits for the device and makes
+        the rest copy, the builder's state and the rig's table.  No ranges remove the rig."""
+        r = np.asarray(list(ranges), np.int64).reshape(-1, 3)
+        if len(r) and (r.min() < 0 or r.max() > 0xffffffff):
+            raise P3DError(-1, "set_rig: a range does not fit uint32")
+        rg = (XformRange * max(len(r), 1))()
+        for i, (first, count, x) in enumerate(r):
+            rg[i] = XformRange(int(first), int(count), int(x), 0)
+        _check(self._L.p3d_scene_set_rig(self._h, len(r), C.cast(rg, C.c_void_p) if len(r) else None, int(n_xforms)))
+
+    def rig(self):
+        """p3d_scene_rig: {"n_ranges", "n_xforms", "n_posed_objects"} of the current rig, three zeros without one"""
+        n = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)]
+        _check(self._L.p3d_scene_rig(self._h, C.byref(n[0]), C.byref(n[1]), C.byref(n[2])))
+        return dict(n_ranges=n[0].value, n_xforms=n[1].value, n_posed_objects=n[2].value)
+
+    def pose_device(self, xforms, sphere_scale=None, stream=0):
+        """p3d_scene_pose_device: transform_prims(the rig's ranges, xforms, UPDATE_REFIT, sphere_scale) enqueued on `stream`
+        (a torch.cuda.Stream or a raw hipStream_t; 0 = the default stream) without a wait.  `xforms`: a contiguous float32
+        CUDA/HIP torch.Tensor of shape [K, 3, 4] or [K, 12] on the scene's device, K the rig's n_xforms, or a raw
+        (address, K) pair; `sphere_scale`: a [K] tensor, a raw pair, or None = 1.  What the stream had enqueued to fill them
+        runs first; keep them alive until the stream has passed the call.  Objects the kernel skips (an unusable transform
+        or box) show in status(), not here.  Accumulators of this scene refuse passes until they are reset."""
+        if hasattr(xforms, "data_ptr") and hasattr(xforms, "dim") and xforms.dim() == 3:
+            if tuple(xforms.shape[1:]) != (3, 4):
+                raise P3DError(-1, "xforms: shape %r, needed: (n, 3, 4) or (n, 12) with n > 0" % (tuple(xforms.shape),))
+            if not xforms.is_contiguous():
+                raise P3DError(-1, "xforms: the tensor is not contiguous")
+            xforms = xforms.view(xforms.shape[0], 12)
+        d_x, k = _device_rows(xforms, "xforms", 12, ("float32",), self.device)
+        d_s = None
+        if sphere_scale is not None:
+            d_s, n = _device_vector(sphere_scale, "sphere_scale", ("float32",), self.device)
+            if n != k:
+                raise P3DError(-1, "sphere_scale: %d values for %d transforms" % (n, k))
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_scene_pose_device(self._h, k, C.c_void_p(d_x), C.c_void_p(d_s) if d_s else None, C.c_void_p(raw or None)))
 
     def export_bvh(self):
         """p3d_scene_export_bvh: the current device-built tree as numpy arrays, with the bvh_* keys of HostScene.arrays(bvh=True)

@@ -148,6 +148,11 @@ struct p3d_scene {
   uint32_t* d_refit_skipped = nullptr; // {triangles with an index >= n_elems, objects with an unusable box} since the last check_status();
                                        // allocated by the first call, added to by its kernel together with upd::kStatusRefitSkipped in d_status
   bool root_stale = false;             // root_min / root_max are those of an older fit: refresh_root_box() before they are used
+  // p3d_scene_set_rig, p3d_scene_pose_device (the same scenes)
+  Scratch rig;                         // one uint32 per object: its transform slot or upd::kRigNotPosed; null: no rig
+  uint32_t rig_ranges = 0, rig_xforms = 0, rig_posed = 0;  // what p3d_scene_rig answers
+  Scratch pose_skipped;                // {objects with an unusable transform, objects with an unusable box} since the last check_status();
+                                       // made by p3d_scene_set_rig, added to by upd::pose_rig together with upd::kStatusPoseSkipped in d_status
   // p3d_scene_build_grid (the same scenes): d_cell_start / d_cell_items above are then the device-built grid
   bool uploaded_grid = false;          // the descriptor carried the host's grid: it cannot follow updates and is never rebuilt
   uint64_t cell_start_cap = 0, cell_items_cap = 0;  // words allocated; they grow when a build needs more and are kept otherwise
@@ -219,14 +224,15 @@ hipError_t with_accel(uint32_t accel, F&& f) {
 
 // Device-detected errors (sample hand-out loop hit its trip bound, a leftover outgrew its slot, the hand-off found no
 // fixed point): read and clear the status word.  Call only where the stream has been synchronised.
-// render_call: the check behind a render call with `stats` - the objects p3d_scene_refit_device skipped are not the frame's
-// fault: their bit stays pending for p3d_scene_status.
+// render_call: the check behind a render call with `stats` - the objects p3d_scene_refit_device or p3d_scene_pose_device
+// skipped are not the frame's fault: their bits stay pending for p3d_scene_status.
 int check_status(p3d_scene* s, bool render_call = false) {
+  constexpr uint32_t kSkipped = upd::kStatusRefitSkipped | upd::kStatusPoseSkipped;
   uint32_t h = 0;
   P3D_HIP(hipMemcpy(&h, s->d_status, sizeof(h), hipMemcpyDeviceToHost));
   if (render_call) {
-    const uint32_t pending = h & upd::kStatusRefitSkipped;
-    h &= ~upd::kStatusRefitSkipped;
+    const uint32_t pending = h & kSkipped;
+    h &= ~kSkipped;
     s->last_status = h;
     if (!h) return P3D_OK;
     P3D_HIP(hipMemcpy(s->d_status, &pending, sizeof(pending), hipMemcpyHostToDevice));
@@ -235,16 +241,26 @@ int check_status(p3d_scene* s, bool render_call = false) {
     if (!h) return P3D_OK;
     P3D_HIP(hipMemset(s->d_status, 0, sizeof(uint32_t)));
   }
-  static_assert((upd::kStatusRefitSkipped & (kHoErrLeftoverCap | kHoErrNoFixedPoint | kHoErrTrips | kHoErrList | kHoErrHalo)) == 0, "one word, distinct bits");
-  std::string skipped;  // p3d_scene_refit_device: objects its kernel did not write
+  static_assert((upd::kStatusRefitSkipped & (kHoErrLeftoverCap | kHoErrNoFixedPoint | kHoErrTrips | kHoErrList | kHoErrHalo)) == 0 &&
+                    (upd::kStatusPoseSkipped & (upd::kStatusRefitSkipped | kHoErrLeftoverCap | kHoErrNoFixedPoint | kHoErrTrips | kHoErrList | kHoErrHalo)) == 0,
+                "one word, distinct bits");
+  std::string skipped;  // p3d_scene_refit_device, p3d_scene_pose_device: objects their kernels did not write
   if ((h & upd::kStatusRefitSkipped) && s->d_refit_skipped) {
     uint32_t bad[2] = {0, 0};
     P3D_HIP(hipMemcpy(bad, s->d_refit_skipped, sizeof(bad), hipMemcpyDeviceToHost));
     P3D_HIP(hipMemset(s->d_refit_skipped, 0, sizeof(bad)));
     skipped = " p3d_scene_refit_device: " + std::to_string(bad[0]) + " triangle(s) with an index >= n_elems, " + std::to_string(bad[1]) +
               " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated;";
-    if (!(h & ~upd::kStatusRefitSkipped)) return fail(P3D_ERR_INVALID, "device-detected error:" + skipped);
   }
+  if ((h & upd::kStatusPoseSkipped) && s->pose_skipped.p) {
+    uint32_t bad[2] = {0, 0};
+    P3D_HIP(hipMemcpy(bad, s->pose_skipped.p, sizeof(bad), hipMemcpyDeviceToHost));
+    P3D_HIP(hipMemset(s->pose_skipped.p, 0, sizeof(bad)));
+    skipped += " p3d_scene_pose_device: " + std::to_string(bad[0]) +
+               " object(s) with an unusable transform (a non-finite entry, a sphere_scale that is not finite and > 0, or a box under a matrix that is not positive-diagonal), " +
+               std::to_string(bad[1]) + " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated;";
+  }
+  if (!skipped.empty() && !(h & ~kSkipped)) return fail(P3D_ERR_INVALID, "device-detected error:" + skipped);
   std::string what = skipped;
   if (h & kHoErrTrips) what += " sample hand-out loop reached its trip bound (pixels would miss samples);";
   if (h & kHoErrLeftoverCap) what += " the hit_stack leftovers of this frame do not fit their records (p3d_config.handoff_records = P3D_HANDOFF_DENSE has room for the worst case);";

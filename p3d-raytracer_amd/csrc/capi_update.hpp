@@ -1,5 +1,6 @@
 // capi_update.hpp — a live scene changes: camera, geometry (p3d_scene_update_prims, p3d_scene_transform_prims,
-// p3d_scene_update_geometry_device, and p3d_scene_refit_device on the caller's stream), and the export of a device-built tree
+// p3d_scene_update_geometry_device, and p3d_scene_refit_device and p3d_scene_set_rig / p3d_scene_pose_device on the caller's
+// stream), and the export of a device-built tree
 #pragma once
 #include "capi_grid.hpp"
 
@@ -172,6 +173,18 @@ int sort_spans(std::vector<Span>& spans, const std::string& pre, const char* nou
   return P3D_OK;
 }
 
+// The rest copy of the transform routes, from the geometry of this moment if the scene has none.  The device is idle
+int ensure_rest(p3d_scene* s, const char* who) {
+  if (s->rest.p) return P3D_OK;
+  const size_t rest_bytes = (size_t)3 * s->dev.n_objs * sizeof(float4);
+  if (int rc = s->rest.ensure(rest_bytes)) return rc;
+  if (hipError_t e = hipMemcpy(s->rest.p, s->d_blob + s->off_ogeom, rest_bytes, hipMemcpyDeviceToDevice); e != hipSuccess) {
+    s->rest.release();
+    return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": rest copy: " + hipGetErrorString(e));
+  }
+  return P3D_OK;
+}
+
 // A geometry update from "validated, and s->stage_host holds a zeroed counter block and the payload" (or nothing: no upload)
 // to the return code.  `launch(grid, block, payload, counters)` enqueues the route's kernel over `total` objects, if there
 // are any.  make_rest: the route reads the rest pose, which until its first call IS the object-order geometry.  `failed`
@@ -182,14 +195,8 @@ int run_update(p3d_scene* s, uint32_t mode, const char* who, float* update_ms, u
   const size_t bytes = s->stage_host.size() * sizeof(uint4);
   if (int rc = begin_update(s, mode, who)) return rc;
   if (int rc = s->stage.ensure(bytes)) return rc;
-  if (make_rest && !s->rest.p) {
-    const size_t rest_bytes = (size_t)3 * s->dev.n_objs * sizeof(float4);
-    if (int rc = s->rest.ensure(rest_bytes)) return rc;
-    if (hipError_t e = hipMemcpy(s->rest.p, s->d_blob + s->off_ogeom, rest_bytes, hipMemcpyDeviceToDevice); e != hipSuccess) {
-      s->rest.release();
-      return fail(P3D_ERR_NO_DEVICE, std::string(who) + ": rest copy: " + hipGetErrorString(e));
-    }
-  }
+  if (make_rest)
+    if (int rc = ensure_rest(s, who)) return rc;
   // from here on the scene changes
   hipError_t e = hipEventRecord(s->ev0, 0);
   if (e == hipSuccess && bytes) e = hipMemcpyAsync(s->stage.p, s->stage_host.data(), bytes, hipMemcpyHostToDevice, 0);
@@ -238,6 +245,37 @@ int stage_sources(const p3d_scene* s, const std::string& pre, uint32_t n_sources
     sorted[r] = upd::StagedSource{g.first, g.count, g.kind, 0u, (const float*)g.d_data, g.d_index, g.n_elems, {0u, 0u, 0u}};
   }
   return sort_spans(sorted, pre, "sources", total, [](const upd::StagedSource&) { return (int)P3D_OK; });
+}
+
+// What the stream forms (p3d_scene_refit_device, p3d_scene_pose_device) do behind their kernel on `st`, which wrote the
+// object-order geometry, normals and boxes and zeroed the fit's arrival counters (`e`: what enqueueing it gave): the fit of
+// the kept topology, and the scene's bookkeeping as after a waiting REFIT with the policy off.  Nothing here allocates,
+// frees, waits or reads back
+int finish_stream_refit(p3d_scene* s, hipStream_t st, hipError_t e, const std::string& pre) {
+  lbvh::Workspace& w = s->lbvh_ws;
+  float4* blob = s->d_blob;
+  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom, st, true, true);
+  // the old geometry's memos are void, as after every update
+  ++s->geom_gen;
+  void_schedules(s);
+  s->ho_chain_key.clear();
+  s->root_stale = true;
+  s->lbvh_fitted = e == hipSuccess;
+  if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, pre + "update: " + hipGetErrorString(e));
+  s->last_update_rebuilt = false;
+  ++s->refits_since_build;
+  s->sah_baseline = 0.0;  // (the policy is off: nothing was measured)
+  return P3D_OK;
+}
+
+// What the stream forms refuse behind their arguments, in the same words
+int stream_form_unsupported(const p3d_scene* s, const std::string& pre, const char* waiting_form) {
+  if (s->has_grid)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene has a device-built grid, whose rebuild reads sizes back (" + waiting_form + " follows it)");
+  if (s->auto_rebuild != 0.0f)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the auto-rebuild policy is on and needs the cost on the host (" + waiting_form +
+                                         " applies it, p3d_scene_set_auto_rebuild(0) switches it off)");
+  return P3D_OK;
 }
 
 }  // namespace
@@ -402,10 +440,7 @@ int p3d_scene_refit_device(p3d_scene* s, uint32_t n_sources, const p3d_geom_sour
   if (int rc = update_refused(s, P3D_UPDATE_REFIT, pre, n_sources && !sources ? "null sources with n_sources > 0" : nullptr)) return rc;
   const uint32_t n_objs = s->dev.n_objs;
   if (n_sources > n_objs) return fail(P3D_ERR_INVALID, pre + "more sources than objects (sources overlap or are empty)");
-  if (s->has_grid)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene has a device-built grid, whose rebuild reads sizes back (p3d_scene_update_geometry_device follows it)");
-  if (s->auto_rebuild != 0.0f)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "the auto-rebuild policy is on and needs the cost on the host (p3d_scene_update_geometry_device applies it, p3d_scene_set_auto_rebuild(0) switches it off)");
+  if (int rc = stream_form_unsupported(s, pre, "p3d_scene_update_geometry_device")) return rc;
   if (n_sources > upd::kMaxArgSources)
     return fail(P3D_ERR_CAPACITY, pre + std::to_string(n_sources) + " sources, at most " + std::to_string(upd::kMaxArgSources) +
                                       " travel with one call (p3d_scene_update_geometry_device stages any number)");
@@ -435,19 +470,101 @@ int p3d_scene_refit_device(p3d_scene* s, uint32_t n_sources, const p3d_geom_sour
   // (total <= n_objs = w.n: the grid that gathers also clears the fit's n_objs arrival counters)
   hipLaunchKernelGGL(upd::gather_geometry_args, dim3((n_objs + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, st, table, n_sources,
                      total, n_objs, blob + s->off_ogeom, blob + s->off_normals, w.boxes, (float4*)s->rest.p, s->d_refit_skipped, s->d_status, w.visits);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = lbvh::enqueue_fit(w, w.boxes, blob + s->off_ogeom, blob + s->off_nodes, blob + s->off_bgeom, st, true, true);
-  // the old geometry's memos are void, as after every update; nothing here frees or reads back
-  ++s->geom_gen;
-  void_schedules(s);
-  s->ho_chain_key.clear();
-  s->root_stale = true;
-  s->lbvh_fitted = e == hipSuccess;
-  if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, pre + "update: " + hipGetErrorString(e));
-  s->last_update_rebuilt = false;
-  ++s->refits_since_build;
-  s->sah_baseline = 0.0;  // (the policy is off: nothing was measured)
+  return finish_stream_refit(s, st, hipGetLastError(), pre);
+}
+
+int p3d_scene_set_rig(p3d_scene* s, uint32_t n_ranges, const p3d_xform_range* ranges, uint32_t n_xforms) {
+  const char* who = "p3d_scene_set_rig";
+  const std::string pre = std::string(who) + ": ";
+  if (int rc = update_refused(s, P3D_UPDATE_REFIT, pre, n_ranges && !ranges ? "null ranges with n_ranges > 0" : nullptr)) return rc;
+  if (n_ranges == 0) {  // no rig: the table goes (a hipFree waits for what may still read it)
+    P3D_HIP(hipSetDevice(s->device));
+    s->rig.release();
+    s->rig_ranges = s->rig_xforms = s->rig_posed = 0;
+    return P3D_OK;
+  }
+  const uint32_t n_objs = s->dev.n_objs;
+  if (n_xforms == 0) return fail(P3D_ERR_INVALID, pre + "ranges without transforms (n_xforms is 0)");
+  if (n_ranges > n_objs) return fail(P3D_ERR_INVALID, pre + "more ranges than objects (ranges overlap or are empty)");
+  std::vector<upd::StagedRange> sorted(n_ranges);
+  for (uint32_t r = 0; r < n_ranges; ++r) {
+    const p3d_xform_range& g = ranges[r];
+    const std::string at = pre + "range " + std::to_string(r);
+    if (g.count == 0) return fail(P3D_ERR_INVALID, at + " is empty");
+    if ((uint64_t)g.first + g.count > n_objs) return fail(P3D_ERR_INVALID, at + " ends behind the last object");
+    if (g.xform >= n_xforms) return fail(P3D_ERR_INVALID, at + " names a transform that is not there");
+    if (g.reserved) return fail(P3D_ERR_INVALID, at + ": reserved must be 0");
+    sorted[r] = upd::StagedRange{g.first, g.count, g.xform, 0u};
+  }
+  // one word per object, on the host; a box is accepted here: whether its matrix suits it is only known on the device
+  std::vector<uint32_t> table(n_objs, upd::kRigNotPosed);
+  uint32_t total = 0;
+  auto place = [&](const upd::StagedRange& g) {
+    for (uint32_t o = g.first; o < g.first + g.count; ++o) {
+      if ((s->obj_tm[o] & 0xffu) == P3D_PRIM_PLANE) return fail(P3D_ERR_INVALID, pre + "object " + std::to_string(o) + " is a plane");
+      table[o] = g.xform;
+    }
+    return (int)P3D_OK;
+  };
+  if (int rc = sort_spans(sorted, pre, "ranges", &total, place)) return rc;
+  // what a later pose needs and may not wait for: the builder's state and the topology behind everything enqueued (the
+  // device is idle from here on: nothing reads the old table), the rest copy, the counter block, the table on the device
+  if (int rc = begin_update(s, P3D_UPDATE_REFIT, who)) return rc;
+  if (int rc = ensure_rest(s, who)) return rc;
+  if (!s->pose_skipped.p) {
+    if (int rc = s->pose_skipped.ensure(2 * sizeof(uint32_t))) return rc;
+    P3D_HIP(hipMemset(s->pose_skipped.p, 0, 2 * sizeof(uint32_t)));
+  }
+  Scratch fresh;
+  if (int rc = fresh.ensure((size_t)n_objs * sizeof(uint32_t))) return rc;
+  P3D_HIP(hipMemcpy(fresh.p, table.data(), (size_t)n_objs * sizeof(uint32_t), hipMemcpyHostToDevice));
+  s->rig = std::move(fresh);
+  s->rig_ranges = n_ranges;
+  s->rig_xforms = n_xforms;
+  s->rig_posed = total;
   return P3D_OK;
+}
+
+int p3d_scene_rig(p3d_scene* s, uint32_t* n_ranges, uint32_t* n_xforms, uint32_t* n_posed_objects) {
+  if (!s || !n_ranges || !n_xforms || !n_posed_objects) return fail(P3D_ERR_INVALID, "p3d_scene_rig: null argument");
+  *n_ranges = s->rig_ranges;
+  *n_xforms = s->rig_xforms;
+  *n_posed_objects = s->rig_posed;
+  return P3D_OK;
+}
+
+int p3d_scene_pose_device(p3d_scene* s, uint32_t n_xforms, const void* d_xforms, const void* d_sphere_scale, void* hip_stream) {
+  const char* who = "p3d_scene_pose_device";
+  const std::string pre = std::string(who) + ": ";
+  if (int rc = update_refused(s, P3D_UPDATE_REFIT, pre, nullptr)) return rc;
+  const uint32_t n_objs = s->dev.n_objs;
+  if (n_objs == 0) return P3D_OK;
+  if (!s->rig.p) return fail(P3D_ERR_INVALID, pre + "the scene has no rig (p3d_scene_set_rig)");
+  if (n_xforms != s->rig_xforms)
+    return fail(P3D_ERR_INVALID, pre + std::to_string(n_xforms) + " transforms, the rig was set for " + std::to_string(s->rig_xforms));
+  if (!d_xforms) return fail(P3D_ERR_INVALID, pre + "null d_xforms");
+  if (((uintptr_t)d_xforms | (uintptr_t)d_sphere_scale) & 3u) return fail(P3D_ERR_INVALID, pre + "d_xforms and d_sphere_scale must be 4-byte aligned");
+  P3D_HIP(hipSetDevice(s->device));
+  if (int rc = device_buffer_usable(s, d_xforms, (size_t)48 * n_xforms, pre + "d_xforms")) return rc;
+  if (d_sphere_scale)
+    if (int rc = device_buffer_usable(s, d_sphere_scale, (size_t)4 * n_xforms, pre + "d_sphere_scale")) return rc;
+  if (int rc = stream_form_unsupported(s, pre, "p3d_scene_transform_prims")) return rc;
+  lbvh::Workspace& w = s->lbvh_ws;
+  if (!w.n || !s->lbvh_topology) {
+    // a geometry update has failed with P3D_ERR_NO_DEVICE since the rig was set and voided the topology: the setup again
+    if (int rc = begin_update(s, P3D_UPDATE_REFIT, who)) return rc;
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (s->tail_pending) {  // the previous frame's tail reads the geometry (p3d_scene_set_tail_stream)
+    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
+    s->tail_pending = false;
+  }
+  // from here on the scene changes
+  float4* blob = s->d_blob;
+  hipLaunchKernelGGL(upd::pose_rig, dim3((n_objs + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, st, (const float4*)s->rest.p,
+                     (const uint32_t*)s->rig.p, (const float*)d_xforms, (const float*)d_sphere_scale, n_xforms, n_objs, blob + s->off_ogeom,
+                     blob + s->off_normals, w.boxes, (uint32_t*)s->pose_skipped.p, s->d_status, w.visits);
+  return finish_stream_refit(s, st, hipGetLastError(), pre);
 }
 
 int p3d_scene_export_bvh(p3d_scene* s, p3d_bvh_node* nodes, uint32_t* n_nodes, uint32_t* prim_index, uint32_t* n_prim_index, uint32_t* max_depth) {

@@ -1,6 +1,7 @@
 // update_kernels.hpp — the device half of the three geometry updates of a live scene: host records (p3d_scene_update_prims),
-// transforms of the rest pose (p3d_scene_transform_prims) and positions in device memory (p3d_scene_update_geometry_device,
-// and p3d_scene_refit_device, which hands its sources over as a kernel argument).
+// transforms of the rest pose (p3d_scene_transform_prims, and p3d_scene_pose_device, which reads its matrices from device
+// memory and its ranges from the scene's rig) and positions in device memory (p3d_scene_update_geometry_device, and
+// p3d_scene_refit_device, which hands its sources over as a kernel argument).
 //
 // One thread per covered object, blocks of lbvh::kThreads.  Each kernel works out an object's nine geometry floats, shading
 // normal and box its own way - the arithmetic is host/prim_rule.hpp's, so the result is what the host constructors give for
@@ -45,6 +46,10 @@ static_assert(sizeof(StagedRange) == 16 && sizeof(StagedSource) == 48, "a span i
 // The bit p3d_scene_refit_device's kernel raises in the scene's status word when it skips an object (the kHoErr* bits of
 // handoff.hpp are below it); the counts are in the scene's counter block
 constexpr uint32_t kStatusRefitSkipped = 32u;
+// The same for p3d_scene_pose_device's kernel, with a counter block of its own
+constexpr uint32_t kStatusPoseSkipped = 64u;
+// A rig (p3d_scene_set_rig) is one word per object: its transform slot, or this for an object no range names
+constexpr uint32_t kRigNotPosed = 0xffffffffu;
 
 __device__ __forceinline__ bool box_usable(const float lo[3], const float hi[3]) {
   bool ok = true;
@@ -104,6 +109,37 @@ __global__ void scatter_prims(const UpdateRecord* recs, uint32_t n, uint32_t n_o
   store_object(obj, a, b, c.x, __float_as_uint(c.y) | (__float_as_uint(c.z) << 8), nr, lo, hi, ogeom, rest, normals, boxes);
 }
 
+// Object `obj` set to T(rest), the work of both transform kernels: a, b, c are its three float4 of the rest copy, m the
+// row-major 3x4 matrix.  A triangle's vertices, a sphere's centre and a box's min and max go through xform_point; the
+// triangle gets the loader's normal and box, the sphere radius * sphere_scale and its box.  -> false if the new box is
+// non-finite or inverted: the object is not written.  A plane is left alone (the host refuses a range that covers one).
+__device__ __forceinline__ bool transform_object(uint32_t obj, float4 a, float4 b, float4 c, const float m[12], float sphere_scale,
+                                                 float4* ogeom, float4* normals, float4* boxes) {
+  float v[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
+  float n[3] = {0.f, 0.f, 0.f}, lo[3], hi[3];
+  const uint32_t type = __float_as_uint(c.y) & 0xffu;
+  if (type == P3D_PRIM_TRIANGLE) {
+    xform_point(m, v, v);
+    xform_point(m, v + 3, v + 3);
+    xform_point(m, v + 6, v + 6);
+    triangle_normal_box(v, n, lo, hi);
+  } else if (type == P3D_PRIM_SPHERE) {
+    xform_point(m, v, v);
+    v[3] = v[3] * sphere_scale;
+    sphere_box(v, v[3], lo, hi);
+  } else if (type == P3D_PRIM_BOX) {
+    xform_point(m, v, v);
+    xform_point(m, v + 3, v + 3);
+    for (int q = 0; q < 3; ++q) { lo[q] = v[q]; hi[q] = v[3 + q]; }
+  } else {
+    return true;
+  }
+  if (!box_usable(lo, hi)) return false;
+  store_object(obj, make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), v[8], __float_as_uint(c.y), n, lo, hi, ogeom,
+               nullptr, normals, boxes);
+  return true;
+}
+
 // Sets objects to T(rest) in place.  rest: 3 float4 per object, the object-order geometry it was created with or last given
 // by another route; xforms: 4 float4 per p3d_xform (m rows 0-2, then sphere_scale), one address for a whole wave inside a
 // range.  An object whose new box is non-finite or inverted is not written and counted in *skipped.  The rest pose stays.
@@ -117,31 +153,41 @@ __global__ void transform_prims(const float4* rest, const uint4* ranges, uint32_
   const float4 a = rest[3 * obj], b = rest[3 * obj + 1], c = rest[3 * obj + 2];
   const float4 m0 = xforms[4 * rg.z], m1 = xforms[4 * rg.z + 1], m2 = xforms[4 * rg.z + 2], m3 = xforms[4 * rg.z + 3];
   const float m[12] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w};
-  float v[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
-  float n[3] = {0.f, 0.f, 0.f}, lo[3], hi[3];
-  const uint32_t type = __float_as_uint(c.y) & 0xffu;
-  if (type == P3D_PRIM_TRIANGLE) {
-    xform_point(m, v, v);
-    xform_point(m, v + 3, v + 3);
-    xform_point(m, v + 6, v + 6);
-    triangle_normal_box(v, n, lo, hi);
-  } else if (type == P3D_PRIM_SPHERE) {
-    xform_point(m, v, v);
-    v[3] = v[3] * m3.x;
-    sphere_box(v, v[3], lo, hi);
-  } else if (type == P3D_PRIM_BOX) {
-    xform_point(m, v, v);
-    xform_point(m, v + 3, v + 3);
-    for (int q = 0; q < 3; ++q) { lo[q] = v[q]; hi[q] = v[3 + q]; }
-  } else {
-    return;  // a plane: refused on the host
+  if (!transform_object(obj, a, b, c, m, m3.x, ogeom, normals, boxes)) atomicAdd(skipped, 1u);
+}
+
+// transform_prims with the ranges as the scene's rig and the matrices in the CALLER's device memory (p3d_scene_pose_device).
+// rig: one word per object, its transform slot or kRigNotPosed - a thread is an object: no search, coalesced reads, any
+// number of ranges.  xforms: 12 floats per slot, sphere_scale: one (null: 1 for every slot), read as scalar floats: the
+// caller's memory is 4-byte aligned and no more.  What the host checks in the waiting form is checked here, per object, and
+// a failing object keeps its geometry: counters[0] counts objects whose transform has a non-finite entry, whose
+// sphere_scale is not finite and > 0 (whatever the object's type, as there), or that are boxes under a matrix that is not
+// positive-diagonal; counters[1] objects whose new box is non-finite or inverted.  counters: the scene's own block, added to
+// and never cleared here; *status takes kStatusPoseSkipped with them.  Thread i also zeroes visits[i], the fit's arrival
+// counters, as gather_geometry_args does (lbvh::enqueue_fit, visits_clear).  No read of xforms outside [0, 12 n_xforms).
+__global__ void pose_rig(const float4* rest, const uint32_t* rig, const float* xforms, const float* sphere_scale, uint32_t n_xforms,
+                         uint32_t n_objs, float4* ogeom, float4* normals, float4* boxes, uint32_t* counters, uint32_t* status,
+                         uint32_t* visits) {
+  const uint32_t i = blockIdx.x * lbvh::kThreads + threadIdx.x;
+  if (i >= n_objs) return;
+  visits[i] = 0u;
+  const uint32_t slot = rig[i];
+  if (slot >= n_xforms) return;  // kRigNotPosed (the host has checked every other slot against n_xforms)
+  const float* t = xforms + 12 * (size_t)slot;
+  float m[12];
+  bool ok = true;
+  for (int q = 0; q < 12; ++q) {
+    m[q] = t[q];
+    ok = ok && fabsf(m[q]) < INFINITY;  // (NaN fails)
   }
-  if (!box_usable(lo, hi)) {
-    atomicAdd(skipped, 1u);
-    return;
+  const float scale = sphere_scale ? sphere_scale[slot] : 1.0f;
+  ok = ok && fabsf(scale) < INFINITY && scale > 0.0f;
+  const float4 a = rest[3 * i], b = rest[3 * i + 1], c = rest[3 * i + 2];
+  if ((__float_as_uint(c.y) & 0xffu) == P3D_PRIM_BOX) ok = ok && xform_is_positive_diagonal(m);
+  if (!ok || !transform_object(i, a, b, c, m, scale, ogeom, normals, boxes)) {
+    atomicAdd(&counters[ok ? 1 : 0], 1u);
+    atomicOr(status, kStatusPoseSkipped);
   }
-  store_object(obj, make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), v[8], __float_as_uint(c.y), n, lo, hi, ogeom,
-               nullptr, normals, boxes);
 }
 
 // Triangles and spheres take their nine geometry floats from buffers in DEVICE memory: a [V, 3] position array, gathered

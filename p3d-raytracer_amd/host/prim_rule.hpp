@@ -53,7 +53,8 @@ P3D_PRIM_HD inline void sphere_box(const float c[3], float radius, float lo[3], 
 }
 
 // What p3d_scene_transform_prims accepts for an axis-aligned box: a positive scale per axis and a translation
-inline bool xform_is_positive_diagonal(const float m[12]) {
+// (p3d_scene_pose_device asks on the device, where its matrices are)
+P3D_PRIM_HD inline bool xform_is_positive_diagonal(const float m[12]) {
   return m[0] > 0 && m[5] > 0 && m[10] > 0 && m[1] == 0 && m[2] == 0 && m[4] == 0 && m[6] == 0 && m[8] == 0 && m[9] == 0;
 }
 
