@@ -1047,6 +1047,47 @@ int p3d_trace_any_device(p3d_scene* scene, uint32_t accel, uint32_t n,
                          const float* d_origin, const float* d_direction, const float* d_t_max /* may be NULL */,
                          uint8_t* d_occluded, void* hip_stream);
 /*
+ * NEAREST-SURFACE queries: which object's surface is nearest to a point, how far away it is, and where on it - the contact
+ * and proximity query of a particle or cloth step, and a distance field around a deforming mesh.  Detected by the symbols
+ * (P3D_ABI_VERSION is unchanged).
+ *
+ * The per-object rule (host/nearest_rule.hpp, float32, one spelling for the host and the device): the closest point q on the
+ * object's SURFACE and d2 = |p - q|^2 taken from q as stored.
+ *   triangle : the closest point of the closed triangle - the face, an edge or a vertex
+ *   sphere   : q = c + (p - c) * (r / |p - c|), inside and outside alike (the surface, not the solid); p == c: q = c + (r, 0, 0)
+ *   box      : outside, the clamp of p to the box; inside or on it, p moved onto the nearest face (ties: the lowest axis, then
+ *              the min face)
+ *   plane    : q = p - ((p - A).N) N
+ * The answer is the object with the smallest d2, equal d2 going to the smallest object index.  With a limit an object counts
+ * only if max_dist > 0 and d2 < max_dist * max_dist (the float32 product): a zero, negative or NaN limit finds nothing.
+ *   object : n int32, -1 = nothing ; dist : n float32, sqrtf(d2), FLT_MAX for nothing ; closest : n*3 float32, q, zero for nothing
+ * p3d_host_scene_nearest (host side, below) is the statement of these semantics, on the CPU.
+ *
+ * p3d_nearest_device answers the question for n points in DEVICE memory with one kernel on the caller's stream, under
+ * the buffer and stream rules of p3d_trace_closest_device: no copy, no wait, no allocation once the spill area is large
+ * enough, and with a tail stream set the launch first joins the previous frame's tail.  Behind p3d_scene_refit_device or
+ * p3d_scene_pose_device on the same stream it sees the moved geometry.
+ *   d_point    : n*3 float32 ; d_max_dist : n float32, or NULL = no limit
+ *   d_object   : n int32, required ; d_dist : n float32 ; d_closest, d_normal : n*3 float32 - these three may be NULL
+ * d_object, d_dist and d_closest equal p3d_host_scene_nearest's for the same geometry, bit for bit, for both accels.
+ * d_normal is Object::getNormal of the found object at d_closest - what p3d_object_normal(object, closest) returns, bit for
+ * bit; it is not turned towards the point, and zero where nothing was found.
+ *   P3D_ACCEL_NONE : a loop over all objects, planes included.
+ *   P3D_ACCEL_BVH  : a stack traversal, uploaded and device-built trees alike, that visits the child whose box is nearer
+ *                    first and drops a node only if its box lies farther than the shrinking search radius, with a slack of
+ *                    2^-10 on the squared distance (the box distance and an object's d2 are rounded along different paths).
+ *                    A scene that holds a plane is refused with P3D_ERR_UNSUPPORTED: a plane's box is the [-1,1]^3 default
+ *                    (Q12), so the tree cannot find it.
+ *   P3D_ACCEL_GRID : P3D_ERR_UNSUPPORTED.
+ * Refused with P3D_ERR_INVALID, nothing enqueued, as p3d_trace_closest_device refuses: a null scene; an unknown accel, or
+ * P3D_ACCEL_BVH on a scene created without one; with n > 0, a null d_point or d_object; a misaligned pointer; host memory,
+ * memory of another device, or a buffer that ends behind its allocation.  n = 0 returns P3D_OK; an empty scene answers -1
+ * everywhere.  P3D_ERR_CAPACITY: n x the tree's depth does not fit the 32-bit offsets of the spill area (split the batch).
+ */
+int p3d_nearest_device(p3d_scene* scene, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist /* may be NULL */,
+                       int32_t* d_object /* int32, required */, float* d_dist, float* d_closest, float* d_normal /* optional */,
+                       void* hip_stream);
+/*
  * Per-object queries — device counterparts of the virtual Object::intercepts(Ray&, float&)
  * (scene.cpp:47-94,116-137,149-186,215-227) and Object::getNormal(Vector) (scene.cpp:41-44,
  * 139-142,188-192,229-267) for object `object` (index in Scene::objects) and n rays / points.
@@ -1088,6 +1129,14 @@ int p3d_host_scene_set_lens(p3d_host_scene* hs, float aperture_ratio, float foca
  * p3d_host_scene_desc builds them again - and invalidates the flattened arrays.  Host only, no device needed.
  */
 int p3d_host_scene_set_geometry(p3d_host_scene* hs, uint32_t n, const uint32_t* object, const float* v /* n x 9 */);
+/*
+ * The nearest-surface query of p3d_nearest_device (see there for the rule, the tie and the limit), stated as a brute force
+ * over the host scene's objects: the yardstick the device forms are held to bit for bit.  points : n*3 float32; max_dist :
+ * n float32 or NULL; object : n int32, required; dist : n float32 and closest : n*3 float32 may be NULL.  Host only, no
+ * device needed.
+ */
+int p3d_host_scene_nearest(p3d_host_scene* hs, uint32_t n, const float* points, const float* max_dist /* may be NULL */,
+                           int32_t* object, float* dist, float* closest);
 /* Replaces every light by SPP x SPP jittered copies (main.cpp:725-745); used for
  * SOFT_SHADOWS without ANTIALIASING. */
 int p3d_host_scene_replicate_lights(p3d_host_scene* hs, uint32_t spp_sqrt, float light_side);

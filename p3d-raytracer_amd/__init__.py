@@ -53,6 +53,7 @@ EXPORTS = [
     "p3d_trace_closest_device", "p3d_trace_any_device",
     "p3d_scene_refit_device",
     "p3d_scene_set_rig", "p3d_scene_rig", "p3d_scene_pose_device",
+    "p3d_host_scene_nearest", "p3d_nearest_device",
 ]
 
 
@@ -320,6 +321,9 @@ def lib():
         L.p3d_scene_set_rig.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.p3d_scene_rig.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.p3d_scene_pose_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_host_scene_nearest.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_nearest_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -522,6 +526,7 @@ def _device_vector(x, what, dtypes, device):
 
 
 _TRACE_OUTPUTS = {"hit_id": ("int32", None), "t": ("float32", None), "hit_point": ("float32", 3), "normal": ("float32", 3)}
+_NEAREST_OUTPUTS = {"object": ("int32", None), "dist": ("float32", None), "closest": ("float32", 3), "normal": ("float32", 3)}
 
 
 class HostScene:
@@ -562,6 +567,22 @@ class HostScene:
         if len(g) != len(obj):
             raise ValueError("set_geometry: %d objects, %d rows of nine floats" % (len(obj), len(g)))
         _check(self._L.p3d_host_scene_set_geometry(self._h, len(obj), obj.ctypes.data, g.ctypes.data))
+
+    def nearest(self, points, max_dist=None):
+        """p3d_host_scene_nearest: for every point the object whose surface is nearest, by brute force on the CPU ->
+        (object int32 (n,), dist float32 (n,), closest float32 (n, 3)); -1, FLT_MAX and zeros where nothing lies within
+        max_dist (float32 (n,), or None: no limit)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(p)
+        m = None
+        if max_dist is not None:
+            m = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
+            if len(m) != n:
+                raise ValueError("nearest: %d points, %d limits" % (n, len(m)))
+        obj, dist, closest = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        _check(self._L.p3d_host_scene_nearest(self._h, n, p.ctypes.data, m.ctypes.data if m is not None else None, obj.ctypes.data,
+                                              dist.ctypes.data, closest.ctypes.data))
+        return obj, dist, closest
 
     def has_skybox(self):
         """A cubemap is loaded: the folder of the scene's `env` line was found, or load_skybox was called (p3d_host_scene_has_skybox)."""
@@ -1089,12 +1110,12 @@ class DeviceScene:
             raise P3DError(-1, "%s: %d origins, %d directions%s" % (who, n, n_d, "" if t_max is None else ", %d limits" % n_tm))
         return d_o, d_d, d_tm, n
 
-    def _device_outputs(self, who, names, n, out, like):
+    def _device_outputs(self, who, names, n, out, like, table=_TRACE_OUTPUTS, rows_of="rays"):
         """name -> (tensor or None, address) for the outputs `names`: taken from the dict `out` (tensors or raw (address, rows)
         pairs, checked like the inputs), or allocated on the scene's device when `out` is None"""
         res = {}
         for name in names:
-            dtype, cols = _TRACE_OUTPUTS.get(name, ("uint8", None))
+            dtype, cols = table.get(name, ("uint8", None))
             if out is None:
                 import torch
                 dev = like.device if hasattr(like, "device") else torch.device("cuda", self.device)
@@ -1106,7 +1127,7 @@ class DeviceScene:
             what = "%s: out[%r]" % (who, name)
             ptr, rows = _device_vector(tensor, what, (dtype,), self.device) if cols is None else _device_rows(tensor, what, cols, (dtype,), self.device)
             if rows != n:
-                raise P3DError(-1, "%s: %d rows for %d rays" % (what, rows, n))
+                raise P3DError(-1, "%s: %d rows for %d %s" % (what, rows, n, rows_of))
             res[name] = (tensor, ptr)
         return res
 
@@ -1140,6 +1161,28 @@ class DeviceScene:
         raw = getattr(stream, "cuda_stream", stream)
         _check(self._L.p3d_trace_any_device(self._h, int(accel), n, C.c_void_p(d_o), C.c_void_p(d_d), C.c_void_p(d_tm),
                                             C.c_void_p(res["occluded"][1]), C.c_void_p(raw or None)))
+        return {k: v[0] for k, v in res.items()}
+
+    def nearest_device(self, accel, points, max_dist=None, want=("object", "dist"), stream=0, out=None):
+        """p3d_nearest_device: for n points held in device memory the object whose surface is nearest, enqueued on `stream`
+        without a wait -> {name: tensor} for the names in `want` ("object", always there, "dist", "closest", "normal").  points:
+        a contiguous float32 (n, 3) CUDA/HIP tensor on the scene's device, or a raw (address, rows) pair; max_dist: float32 (n,),
+        an object counts only nearer than it.  ACCEL_NONE and ACCEL_BVH (not over a scene with planes); the answers are
+        HostScene.nearest's, bit for bit.  `out`, `stream` and the refusals as trace_closest_device."""
+        who = "nearest_device"
+        names = ["object"] + [w for w in ("dist", "closest", "normal") if w in want]
+        unknown = [w for w in want if w not in _NEAREST_OUTPUTS]
+        if unknown:
+            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+        d_p, n = _device_rows(points, who + ": points", 3, ("float32",), self.device)
+        d_m, n_m = _device_vector(max_dist, who + ": max_dist", ("float32",), self.device) if max_dist is not None else (None, n)
+        if n_m != n:
+            raise P3DError(-1, "%s: %d points, %d limits" % (who, n, n_m))
+        res = self._device_outputs(who, names, n, out, points, _NEAREST_OUTPUTS, "points")
+        ptr = {k: C.c_void_p(v[1]) for k, v in res.items()}
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_nearest_device(self._h, int(accel), n, C.c_void_p(d_p), C.c_void_p(d_m), ptr["object"], ptr.get("dist"),
+                                          ptr.get("closest"), ptr.get("normal"), C.c_void_p(raw or None)))
         return {k: v[0] for k, v in res.items()}
 
 

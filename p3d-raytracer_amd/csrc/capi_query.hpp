@@ -1,6 +1,7 @@
-// capi_query.hpp — batched single-ray and per-object queries (p3d_trace_*, p3d_object_*, p3d_skybox_color)
+// capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_nearest_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_update.hpp"  // device_buffer_usable
+#include "nearest_query.hpp"
 #include "ray_query.hpp"
 
 namespace {
@@ -50,6 +51,50 @@ int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin
     else hipLaunchKernelGGL((trace_device_kernel<decltype(A)::value, false>), dim3(blocks), dim3(kBlock), lds, st, P);
     return hipSuccess;
   });
+  P3D_HIP(hipGetLastError());
+  return P3D_OK;
+}
+
+// p3d_nearest_device: trace_device's refusals, stack binding and tail wait, and one launch on the caller's stream
+int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist, int32_t* d_object,
+                   float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
+  const std::string pre = "p3d_nearest_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no nearest-surface query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (accel == P3D_ACCEL_BVH && s->has_planes)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
+  if (n == 0) return P3D_OK;
+  if (!d_point || !d_object) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (((uintptr_t)d_point | (uintptr_t)d_max_dist | (uintptr_t)d_object | (uintptr_t)d_dist | (uintptr_t)d_closest | (uintptr_t)d_normal) & 3u)
+    return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
+  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
+      {d_point, vec, "d_point"}, {d_max_dist, one, "d_max_dist"}, {d_object, one, "d_object"},
+      {d_dist, one, "d_dist"}, {d_closest, vec, "d_closest"}, {d_normal, vec, "d_normal"}};
+  for (const auto& b : bufs)
+    if (b.p)
+      if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
+  // the stack as trace_device binds it: a 16-entry LDS window, the rest of a deep tree's worst case in the spill area
+  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
+  const uint32_t cap = 16;
+  const uint32_t blocks = (n + kBlock - 1) / kBlock;
+  if ((uint64_t)(bound > cap ? bound : 0) * blocks * kBlock > 0xffffffffull)  // entries are addressed with 32-bit offsets (device_core.hpp Stack)
+    return fail(P3D_ERR_CAPACITY, pre + "too many points for one call over a tree this deep (split the batch)");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (s->tail_pending) {  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
+    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
+    s->tail_pending = false;
+  }
+  if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)(bound > cap ? bound : 0) * blocks * kBlock * sizeof(uint2)))) return rc;
+  NearestParams P{};
+  P.sc = s->dev; P.n = n; P.point = d_point; P.max_dist = d_max_dist;
+  P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal;
+  P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
+  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
+  if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((nearest_device_kernel<P3D_ACCEL_BVH>), dim3(blocks), dim3(kBlock), lds, st, P);
+  else hipLaunchKernelGGL((nearest_device_kernel<P3D_ACCEL_NONE>), dim3(blocks), dim3(kBlock), lds, st, P);
   P3D_HIP(hipGetLastError());
   return P3D_OK;
 }
@@ -120,6 +165,11 @@ int p3d_trace_closest_device(p3d_scene* s, uint32_t accel, uint32_t n, const flo
 int p3d_trace_any_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
                          uint8_t* d_occluded, void* hip_stream) {
   return trace_device(s, accel, n, d_origin, d_direction, d_t_max, nullptr, nullptr, nullptr, nullptr, d_occluded, hip_stream, true);
+}
+
+int p3d_nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist, int32_t* d_object,
+                       float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
+  return nearest_device(s, accel, n, d_point, d_max_dist, d_object, d_dist, d_closest, d_normal, hip_stream);
 }
 
 static int object_query(p3d_scene* s, int what, uint32_t object, uint32_t n, const float* a, float* b, uint8_t* hit, float* t) {

@@ -1,11 +1,14 @@
 // host_capi.cpp — the p3d_host_* half of include/p3d.h: .p3f -> Scene -> accel builds ->
 // flat p3d_scene_desc.  Pure host code (no HIP).
+#include <cfloat>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "accel_build.hpp"
+#include "nearest_rule.hpp"
 #include "p3d.h"
 #include "p3d_error.hpp"
 #include "scene_model.hpp"
@@ -244,6 +247,43 @@ int p3d_host_scene_skybox_face(p3d_host_scene* hs, int face, const uint8_t** img
   if (!hs || !img) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_skybox_face: null argument");
   *img = hs->scene.SkyboxFace(face, res_x, res_y);
   return *img ? P3D_OK : p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_skybox_face: no cubemap loaded, or face not in 0..5");
+}
+
+// The statement of the nearest-surface query: nearest_rule.hpp on every object, the smallest (d2, object index) wins
+int p3d_host_scene_nearest(p3d_host_scene* hs, uint32_t n, const float* points, const float* max_dist, int32_t* object, float* dist,
+                           float* closest) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest: null scene");
+  if (n && (!points || !object)) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest: null array with n > 0");
+  using namespace p3d;
+  const int n_objs = hs->scene.getNumObjects();
+  std::vector<float> v(9 * static_cast<size_t>(n_objs));
+  std::vector<uint32_t> kind(n_objs);
+  for (int j = 0; j < n_objs; ++j) {
+    float normal[3];
+    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
+    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* p = points + 3 * static_cast<size_t>(i);
+    float best, best_q[3] = {0.0f, 0.0f, 0.0f};
+    int32_t best_object = -1;
+    if (nearest_radius(max_dist != nullptr, max_dist ? max_dist[i] : 0.0f, best)) {
+      for (int j = 0; j < n_objs; ++j) {
+        float q[3];
+        const float d2 = nearest_point(kind[j], &v[9 * static_cast<size_t>(j)], p, q);
+        if (nearest_wins(d2, j, best, best_object)) {
+          best = d2; best_object = j;
+          best_q[0] = q[0]; best_q[1] = q[1]; best_q[2] = q[2];
+        }
+      }
+    }
+    const bool found = best_object >= 0;
+    object[i] = best_object;
+    if (dist) dist[i] = found ? sqrtf(best) : FLT_MAX;
+    if (closest)
+      for (int k = 0; k < 3; ++k) closest[3 * static_cast<size_t>(i) + k] = found ? best_q[k] : 0.0f;
+  }
+  return P3D_OK;
 }
 
 int p3d_host_scene_bind_device(p3d_host_scene* hs, p3d_scene* scene) {
