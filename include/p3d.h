@@ -1088,6 +1088,50 @@ int p3d_nearest_device(p3d_scene* scene, uint32_t accel, uint32_t n, const float
                        int32_t* d_object /* int32, required */, float* d_dist, float* d_closest, float* d_normal /* optional */,
                        void* hip_stream);
 /*
+ * THE K NEAREST SURFACES within a radius: for every point the (at most) k objects nearest to it, in order, each with its
+ * distance, closest point and normal - what a contact solver needs where a point touches several surfaces at once (a cloth
+ * vertex in a corner, a particle in a crease).  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ *
+ * The per-object rule and the limit are those of p3d_nearest_device.  Let radius2 be +inf without a limit and the float32
+ * product max_dist * max_dist with one (a zero, negative or NaN limit finds nothing), and S(i) the objects with d2 < radius2
+ * for point i, ordered by (d2, object index): the smaller d2 first, equal d2 to the smaller index.  Then
+ *   count[i] = min(|S(i)|, k), and row i*k + j holds for j < count[i] the j-th object of S(i):
+ *     object : its index ; dist : sqrtf(d2) ; closest : the rule's q ; normal (device form) : Object::getNormal of that object
+ *     at q - the bits of p3d_object_normal(object, closest), not turned towards the point
+ *   and for j >= count[i]: -1, FLT_MAX, zeros and zeros.
+ * count[i] == k means "there may be more": ask with a larger k or a smaller radius.  The size of S(i) is deliberately not
+ * reported: counting it would forbid the search to cull against its k-th entry.  With k = 1 object, dist, closest and normal
+ * equal p3d_nearest_device's / p3d_host_scene_nearest's bit for bit, and count is object >= 0.  The first k' rows of a point's
+ * answer are its answer for k' < k.
+ * p3d_host_scene_nearest_k (host side, below) is the statement of these semantics, on the CPU.
+ *
+ * p3d_nearest_k_device answers for n points in DEVICE memory with one kernel on the caller's stream, under the buffer, stream,
+ * tail-join and spill-area rules of p3d_nearest_device: no copy, no wait, no allocation once the spill area is large enough.
+ * Behind p3d_scene_refit_device or p3d_scene_pose_device on the same stream it sees the moved geometry.
+ *   d_point  : n*3 float32 ; d_max_dist : n float32, or NULL = no limit
+ *   d_count  : n int32, required ; d_object : n*k int32, required
+ *   d_dist   : n*k float32 ; d_closest, d_normal : n*k*3 float32 - these three may be NULL
+ * d_count, d_object, d_dist and d_closest equal p3d_host_scene_nearest_k's for the same geometry, bit for bit, for both accels.
+ *   P3D_ACCEL_NONE : a loop over all objects, planes included.
+ *   P3D_ACCEL_BVH  : the traversal of p3d_nearest_device, uploaded and device-built trees alike, with a sorted candidate list
+ *                    per point (in LDS, sized for the k of the call).  A node is dropped only if its box lies farther than the
+ *                    search bound - radius2 while fewer than k candidates are listed, the k-th candidate's d2 afterwards -
+ *                    with the same slack of 2^-10.  A scene that holds a plane is refused with P3D_ERR_UNSUPPORTED.
+ *   P3D_ACCEL_GRID : P3D_ERR_UNSUPPORTED.
+ * Refused with P3D_ERR_INVALID, nothing enqueued and nothing written, as p3d_nearest_device refuses: a null scene; an unknown
+ * accel, or P3D_ACCEL_BVH on a scene created without one; k == 0 or k > P3D_NEAREST_K_MAX; with n > 0, a null d_point, d_count
+ * or d_object; a misaligned pointer; host memory, memory of another device, or a buffer that ends behind its allocation (n, n*k
+ * and n*k*3 elements, computed in 64 bits).  n = 0 returns P3D_OK, whatever the pointers, once k is valid; an empty scene
+ * answers count 0 everywhere.  P3D_ERR_CAPACITY: n x the tree's depth does not fit the 32-bit offsets of the spill area (split
+ * the batch).
+ */
+#define P3D_NEAREST_K_MAX 16u
+int p3d_nearest_k_device(p3d_scene* scene, uint32_t accel, uint32_t n, uint32_t k,
+                         const float* d_point, const float* d_max_dist /* may be NULL */,
+                         int32_t* d_count /* n, required */, int32_t* d_object /* n*k, required */,
+                         float* d_dist /* n*k */, float* d_closest /* n*k*3 */, float* d_normal /* n*k*3 */, /* may be NULL */
+                         void* hip_stream);
+/*
  * Per-object queries — device counterparts of the virtual Object::intercepts(Ray&, float&)
  * (scene.cpp:47-94,116-137,149-186,215-227) and Object::getNormal(Vector) (scene.cpp:41-44,
  * 139-142,188-192,229-267) for object `object` (index in Scene::objects) and n rays / points.
@@ -1137,6 +1181,17 @@ int p3d_host_scene_set_geometry(p3d_host_scene* hs, uint32_t n, const uint32_t* 
  */
 int p3d_host_scene_nearest(p3d_host_scene* hs, uint32_t n, const float* points, const float* max_dist /* may be NULL */,
                            int32_t* object, float* dist, float* closest);
+/*
+ * The k-nearest query of p3d_nearest_k_device (see there for the order, the limit and the rows), stated as a brute force over
+ * the host scene's objects with the candidate list of host/nearest_rule.hpp: the yardstick the device form is held to bit for
+ * bit.  points : n*3 float32; max_dist : n float32 or NULL; count : n int32 and object : n*k int32, required; dist : n*k
+ * float32 and closest : n*k*3 float32 may be NULL.  P3D_ERR_INVALID: a null scene, k == 0 or k > P3D_NEAREST_K_MAX, a null
+ * required array with n > 0.  Host only, no device needed.
+ */
+int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points,
+                             const float* max_dist /* may be NULL */,
+                             int32_t* count /* n, required */, int32_t* object /* n*k, required */,
+                             float* dist /* n*k */, float* closest /* n*k*3 */);   /* the last two may be NULL */
 /* Replaces every light by SPP x SPP jittered copies (main.cpp:725-745); used for
  * SOFT_SHADOWS without ANTIALIASING. */
 int p3d_host_scene_replicate_lights(p3d_host_scene* hs, uint32_t spp_sqrt, float light_side);

@@ -54,6 +54,7 @@ EXPORTS = [
     "p3d_scene_refit_device",
     "p3d_scene_set_rig", "p3d_scene_rig", "p3d_scene_pose_device",
     "p3d_host_scene_nearest", "p3d_nearest_device",
+    "p3d_host_scene_nearest_k", "p3d_nearest_k_device",
 ]
 
 
@@ -324,6 +325,10 @@ def lib():
         L.p3d_host_scene_nearest.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.p3d_nearest_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
+        L.p3d_host_scene_nearest_k.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        L.p3d_nearest_k_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -525,8 +530,26 @@ def _device_vector(x, what, dtypes, device):
     return _device_rows(x, what, 1, dtypes, device)
 
 
+def _device_blocks(x, what, tail, dtypes, device):
+    """_device_rows for a block of values per row: a contiguous (rows,) + tail tensor (tail: two sizes), or a raw (address, rows) pair"""
+    if hasattr(x, "data_ptr") and hasattr(x, "dim"):
+        if x.dim() != 3 or tuple(x.shape[1:]) != tuple(tail):
+            raise P3DError(-1, "%s: shape %r, needed: (n, %d, %d) with n > 0" % (what, tuple(x.shape), tail[0], tail[1]))
+        if x.is_contiguous():
+            x = x.view(x.shape[0], tail[0] * tail[1])
+        else:
+            raise P3DError(-1, "%s: the tensor is not contiguous" % what)
+    return _device_rows(x, what, tail[0] * tail[1], dtypes, device)
+
+
 _TRACE_OUTPUTS = {"hit_id": ("int32", None), "t": ("float32", None), "hit_point": ("float32", 3), "normal": ("float32", 3)}
 _NEAREST_OUTPUTS = {"object": ("int32", None), "dist": ("float32", None), "closest": ("float32", 3), "normal": ("float32", 3)}
+NEAREST_K_MAX = 16  # P3D_NEAREST_K_MAX
+
+
+def _nearest_k_outputs(k):
+    """name -> (dtype, columns) of p3d_nearest_k_device's outputs for this k: k rows per point"""
+    return {"count": ("int32", None), "object": ("int32", k), "dist": ("float32", k), "closest": ("float32", (k, 3)), "normal": ("float32", (k, 3))}
 
 
 class HostScene:
@@ -583,6 +606,25 @@ class HostScene:
         _check(self._L.p3d_host_scene_nearest(self._h, n, p.ctypes.data, m.ctypes.data if m is not None else None, obj.ctypes.data,
                                               dist.ctypes.data, closest.ctypes.data))
         return obj, dist, closest
+
+    def nearest_k(self, points, k, max_dist=None):
+        """p3d_host_scene_nearest_k: for every point the (at most) k objects whose surfaces are nearest, nearer than max_dist
+        (float32 (n,), or None: no limit), ordered by (distance, object index), by brute force on the CPU -> (count int32 (n,),
+        object int32 (n, k), dist float32 (n, k), closest float32 (n, k, 3)); rows from count on hold -1, FLT_MAX and zeros.
+        count == k: there may be more.  1 <= k <= NEAREST_K_MAX."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n, k = len(p), int(k)
+        m = None
+        if max_dist is not None:
+            m = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
+            if len(m) != n:
+                raise ValueError("nearest_k: %d points, %d limits" % (n, len(m)))
+        rows = max(k, 0)
+        count, obj = np.zeros(n, np.int32), np.zeros((n, rows), np.int32)
+        dist, closest = np.zeros((n, rows), np.float32), np.zeros((n, rows, 3), np.float32)
+        _check(self._L.p3d_host_scene_nearest_k(self._h, n, k & 0xffffffff, p.ctypes.data, m.ctypes.data if m is not None else None,
+                                                count.ctypes.data, obj.ctypes.data, dist.ctypes.data, closest.ctypes.data))
+        return count, obj, dist, closest
 
     def has_skybox(self):
         """A cubemap is loaded: the folder of the scene's `env` line was found, or load_skybox was called (p3d_host_scene_has_skybox)."""
@@ -1119,13 +1161,19 @@ class DeviceScene:
             if out is None:
                 import torch
                 dev = like.device if hasattr(like, "device") else torch.device("cuda", self.device)
-                tensor = torch.empty((n,) if cols is None else (n, cols), dtype=getattr(torch, dtype), device=dev)
+                tail = () if cols is None else tuple(cols) if isinstance(cols, tuple) else (cols,)
+                tensor = torch.empty((n,) + tail, dtype=getattr(torch, dtype), device=dev)
             else:
                 if name not in out:
                     raise P3DError(-1, "%s: out has no %r" % (who, name))
                 tensor = out[name]
             what = "%s: out[%r]" % (who, name)
-            ptr, rows = _device_vector(tensor, what, (dtype,), self.device) if cols is None else _device_rows(tensor, what, cols, (dtype,), self.device)
+            if cols is None:
+                ptr, rows = _device_vector(tensor, what, (dtype,), self.device)
+            elif isinstance(cols, tuple):
+                ptr, rows = _device_blocks(tensor, what, cols, (dtype,), self.device)
+            else:
+                ptr, rows = _device_rows(tensor, what, cols, (dtype,), self.device)
             if rows != n:
                 raise P3DError(-1, "%s: %d rows for %d %s" % (what, rows, n, rows_of))
             res[name] = (tensor, ptr)
@@ -1184,6 +1232,32 @@ class DeviceScene:
         _check(self._L.p3d_nearest_device(self._h, int(accel), n, C.c_void_p(d_p), C.c_void_p(d_m), ptr["object"], ptr.get("dist"),
                                           ptr.get("closest"), ptr.get("normal"), C.c_void_p(raw or None)))
         return {k: v[0] for k, v in res.items()}
+
+    def nearest_k_device(self, accel, points, k, max_dist=None, want=("count", "object", "dist"), stream=0, out=None):
+        """p3d_nearest_k_device: for n points held in device memory the (at most) k objects whose surfaces are nearest, nearer
+        than max_dist, ordered by (distance, object index), enqueued on `stream` without a wait -> {name: tensor} for the names
+        in `want` ("count" (n,) and "object" (n, k), always there, "dist" (n, k), "closest" and "normal" (n, k, 3)); rows from
+        count on hold -1, FLT_MAX and zeros, and count == k says that there may be more.  1 <= k <= NEAREST_K_MAX.  points,
+        max_dist, `out`, `stream` and the refusals as nearest_device; the answers are HostScene.nearest_k's, bit for bit."""
+        who = "nearest_k_device"
+        k = int(k)
+        table = _nearest_k_outputs(max(k, 0))
+        names = ["count", "object"] + [w for w in ("dist", "closest", "normal") if w in want]
+        unknown = [w for w in want if w not in table]
+        if unknown:
+            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+        d_p, n = _device_rows(points, who + ": points", 3, ("float32",), self.device)
+        d_m, n_m = _device_vector(max_dist, who + ": max_dist", ("float32",), self.device) if max_dist is not None else (None, n)
+        if n_m != n:
+            raise P3DError(-1, "%s: %d points, %d limits" % (who, n, n_m))
+        if out is None and not 1 <= k <= NEAREST_K_MAX:  # (with the caller's outputs the library says it)
+            raise P3DError(-1, "%s: k must be 1 .. %d, got %d" % (who, NEAREST_K_MAX, k))
+        res = self._device_outputs(who, names, n, out, points, table, "points")
+        ptr = {name: C.c_void_p(v[1]) for name, v in res.items()}
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_nearest_k_device(self._h, int(accel), n, k & 0xffffffff, C.c_void_p(d_p), C.c_void_p(d_m), ptr["count"],
+                                            ptr["object"], ptr.get("dist"), ptr.get("closest"), ptr.get("normal"), C.c_void_p(raw or None)))
+        return {name: v[0] for name, v in res.items()}
 
 
 class Accumulator:

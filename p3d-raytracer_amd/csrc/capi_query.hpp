@@ -1,6 +1,8 @@
-// capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_nearest_device, p3d_object_*, p3d_skybox_color)
+// capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_nearest_device, p3d_nearest_k_device,
+// p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_update.hpp"  // device_buffer_usable
+#include "nearest_k_query.hpp"
 #include "nearest_query.hpp"
 #include "ray_query.hpp"
 
@@ -55,24 +57,27 @@ int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin
   return P3D_OK;
 }
 
-// p3d_nearest_device: trace_device's refusals, stack binding and tail wait, and one launch on the caller's stream
-int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist, int32_t* d_object,
-                   float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
-  const std::string pre = "p3d_nearest_device: ";
+// p3d_nearest_device (k_form false: k = 1, no d_count) and p3d_nearest_k_device: trace_device's refusals, stack binding and
+// tail wait, and one launch on the caller's stream.  One set of checks for both; the outputs hold k rows per point
+int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_form, const float* d_point, const float* d_max_dist,
+                   int32_t* d_count, int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
+  const std::string pre = k_form ? "p3d_nearest_k_device: " : "p3d_nearest_device: ";
   if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
   if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no nearest-surface query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
   if (int rc = check_accel(s, accel)) return rc;
   if (accel == P3D_ACCEL_BVH && s->has_planes)
     return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
+  if (k == 0 || k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
   if (n == 0) return P3D_OK;
-  if (!d_point || !d_object) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (((uintptr_t)d_point | (uintptr_t)d_max_dist | (uintptr_t)d_object | (uintptr_t)d_dist | (uintptr_t)d_closest | (uintptr_t)d_normal) & 3u)
+  if (!d_point || !d_object || (k_form && !d_count)) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (((uintptr_t)d_point | (uintptr_t)d_max_dist | (uintptr_t)d_count | (uintptr_t)d_object | (uintptr_t)d_dist | (uintptr_t)d_closest |
+       (uintptr_t)d_normal) & 3u)
     return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
   P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
   const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
-      {d_point, vec, "d_point"}, {d_max_dist, one, "d_max_dist"}, {d_object, one, "d_object"},
-      {d_dist, one, "d_dist"}, {d_closest, vec, "d_closest"}, {d_normal, vec, "d_normal"}};
+      {d_point, vec, "d_point"}, {d_max_dist, one, "d_max_dist"}, {d_count, one, "d_count"}, {d_object, one * k, "d_object"},
+      {d_dist, one * k, "d_dist"}, {d_closest, vec * k, "d_closest"}, {d_normal, vec * k, "d_normal"}};
   for (const auto& b : bufs)
     if (b.p)
       if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
@@ -88,11 +93,22 @@ int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_poin
     s->tail_pending = false;
   }
   if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)(bound > cap ? bound : 0) * blocks * kBlock * sizeof(uint2)))) return rc;
+  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
+  if (k_form) {  // the lists of this call's k behind the stack window
+    NearestKParams P{};
+    P.sc = s->dev; P.n = n; P.k = k; P.point = d_point; P.max_dist = d_max_dist;
+    P.count = d_count; P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal;
+    P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
+    const size_t lds_k = lds + nearest_k_lds_bytes(k);
+    if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_BVH>), dim3(blocks), dim3(kBlock), lds_k, st, P);
+    else hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_NONE>), dim3(blocks), dim3(kBlock), lds_k, st, P);
+    P3D_HIP(hipGetLastError());
+    return P3D_OK;
+  }
   NearestParams P{};
   P.sc = s->dev; P.n = n; P.point = d_point; P.max_dist = d_max_dist;
   P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal;
   P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
-  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
   if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((nearest_device_kernel<P3D_ACCEL_BVH>), dim3(blocks), dim3(kBlock), lds, st, P);
   else hipLaunchKernelGGL((nearest_device_kernel<P3D_ACCEL_NONE>), dim3(blocks), dim3(kBlock), lds, st, P);
   P3D_HIP(hipGetLastError());
@@ -169,7 +185,11 @@ int p3d_trace_any_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* 
 
 int p3d_nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist, int32_t* d_object,
                        float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
-  return nearest_device(s, accel, n, d_point, d_max_dist, d_object, d_dist, d_closest, d_normal, hip_stream);
+  return nearest_device(s, accel, n, 1, false, d_point, d_max_dist, nullptr, d_object, d_dist, d_closest, d_normal, hip_stream);
+}
+int p3d_nearest_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_point, const float* d_max_dist, int32_t* d_count,
+                         int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
+  return nearest_device(s, accel, n, k, true, d_point, d_max_dist, d_count, d_object, d_dist, d_closest, d_normal, hip_stream);
 }
 
 static int object_query(p3d_scene* s, int what, uint32_t object, uint32_t n, const float* a, float* b, uint8_t* hit, float* t) {

@@ -103,6 +103,16 @@ std::vector<p3d::Object*> object_list(const p3d::Scene& S) {
   return v;
 }
 
+// the candidate list of nearest_rule.hpp as the host keeps it: k entries in an array
+struct HostNearestList {
+  struct Entry { float d2; int32_t object; };
+  Entry e_[P3D_NEAREST_K_MAX];
+  float d2(uint32_t e) const { return e_[e].d2; }
+  int32_t object(uint32_t e) const { return e_[e].object; }
+  void move(uint32_t to, uint32_t from) { e_[to] = e_[from]; }
+  void set(uint32_t e, float d2, int32_t object, uint32_t) { e_[e] = Entry{d2, object}; }
+};
+
 }  // namespace
 
 extern "C" {
@@ -282,6 +292,49 @@ int p3d_host_scene_nearest(p3d_host_scene* hs, uint32_t n, const float* points, 
     if (dist) dist[i] = found ? sqrtf(best) : FLT_MAX;
     if (closest)
       for (int k = 0; k < 3; ++k) closest[3 * static_cast<size_t>(i) + k] = found ? best_q[k] : 0.0f;
+  }
+  return P3D_OK;
+}
+
+// The statement of the k-nearest query: nearest_rule.hpp on every object, the k smallest (d2, object index) under the limit
+// in that order.  q is not kept in the list: the rule is run once more on each listed object, which gives the same bits
+int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist, int32_t* count,
+                             int32_t* object, float* dist, float* closest) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest_k: null scene");
+  if (k == 0 || k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest_k: k must be 1 .. P3D_NEAREST_K_MAX (16)");
+  if (n && (!points || !count || !object)) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest_k: null array with n > 0");
+  using namespace p3d;
+  const int n_objs = hs->scene.getNumObjects();
+  std::vector<float> v(9 * static_cast<size_t>(n_objs));
+  std::vector<uint32_t> kind(n_objs);
+  for (int j = 0; j < n_objs; ++j) {
+    float normal[3];
+    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
+    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* p = points + 3 * static_cast<size_t>(i);
+    HostNearestList list;
+    NearestKGate gate;
+    uint32_t found = 0;
+    if (nearest_k_open(max_dist != nullptr, max_dist ? max_dist[i] : 0.0f, gate)) {
+      for (int j = 0; j < n_objs; ++j) {
+        float q[3];
+        const float d2 = nearest_point(kind[j], &v[9 * static_cast<size_t>(j)], p, q);
+        if (nearest_k_admits(d2, j, gate)) nearest_k_insert(list, found, k, gate, d2, j, static_cast<uint32_t>(j));
+      }
+    }
+    count[i] = static_cast<int32_t>(found);
+    for (uint32_t e = 0; e < k; ++e) {
+      const size_t row = static_cast<size_t>(i) * k + e;
+      float q[3] = {0.0f, 0.0f, 0.0f};
+      const int32_t j = e < found ? list.object(e) : -1;
+      if (j >= 0) nearest_point(kind[j], &v[9 * static_cast<size_t>(j)], p, q);
+      object[row] = j;
+      if (dist) dist[row] = j >= 0 ? sqrtf(list.d2(e)) : FLT_MAX;
+      if (closest)
+        for (int c = 0; c < 3; ++c) closest[3 * row + c] = q[c];
+    }
   }
   return P3D_OK;
 }

@@ -1,6 +1,6 @@
-// nearest_rule.hpp — the arithmetic of a nearest-surface query, in ONE place for its users: p3d_host_scene_nearest
-// (host_capi.cpp), which states the semantics by brute force, and nearest_device_kernel (csrc/nearest_query.hpp), whose
-// answers must be the host form's bits.  For a point p and an object's nine geometry floats (what p3d_prim.v holds for its
+// nearest_rule.hpp — the arithmetic of a nearest-surface query, in ONE place for its users: p3d_host_scene_nearest and
+// p3d_host_scene_nearest_k (host_capi.cpp), which state the semantics by brute force, and nearest_device_kernel /
+// nearest_k_device_kernel (csrc/nearest_query.hpp, csrc/nearest_k_query.hpp), whose answers must be the host forms' bits.  For a point p and an object's nine geometry floats (what p3d_prim.v holds for its
 // kind) nearest_point gives the closest point q on the object's SURFACE and d2 = |p - q|^2, taken from q as stored.  Also
 // here: the squared distance from p to a BVH node's box, and the two comparisons of a search - which candidate wins, and
 // when a node may be dropped.  float32 throughout, evaluated as written; both translation units are compiled without
@@ -147,6 +147,43 @@ P3D_PRIM_HD inline bool nearest_wins(float d2, int32_t object, float best, int32
 P3D_PRIM_HD inline bool nearest_radius(bool limited, float max_dist, float& best) {
   best = limited ? max_dist * max_dist : INFINITY;
   return !limited || max_dist > 0.0f;
+}
+
+// ---- the k nearest objects within a radius (p3d_host_scene_nearest_k, nearest_k_device_kernel) -----------------------------------
+// A candidate list of at most k entries, sorted ascending by (d2, object): the order of nearest_wins.  The list itself lives
+// where its user keeps it (an array on the host, LDS on the device) and is reached through four members:
+//   float d2(uint32_t e) ; int32_t object(uint32_t e) ; void move(uint32_t to, uint32_t from) ; void set(uint32_t e, float d2,
+//   int32_t object, uint32_t slot)          (slot: where the object's geometry lives, for the user's own use)
+// Every object lies in exactly one leaf of both kinds of tree (and is visited once by a brute force), so a search offers it
+// once: no de-duplication is needed, and none is done.
+
+// What a candidate must beat to enter, and what a node is culled against.  While the list holds fewer than k entries it is
+// (radius^2, -1), the start of a k = 1 search: d2 < radius^2 gets in.  Once the list is full it is the last entry, which an
+// admitted candidate drops out.  One comparison for both states: nearest_wins(d2, object, gate.d2, gate.object); the cull is
+// nearest_culls(box_d2, gate.d2), with the slack of the k = 1 search.  A NaN d2 wins against nothing and never enters.
+struct NearestKGate {
+  float d2;
+  int32_t object;
+};
+
+// The gate of an empty list; false: the limit keeps nothing (nearest_radius)
+P3D_PRIM_HD inline bool nearest_k_open(bool limited, float max_dist, NearestKGate& gate) {
+  gate.object = -1;
+  return nearest_radius(limited, max_dist, gate.d2);
+}
+
+P3D_PRIM_HD inline bool nearest_k_admits(float d2, int32_t object, const NearestKGate& gate) {
+  return nearest_wins(d2, object, gate.d2, gate.object);
+}
+
+// Puts an ADMITTED candidate where it belongs: the entries it wins against move one place down, the last one of a full list
+// out.  Updates count and the gate
+template <class List>
+P3D_PRIM_HD inline void nearest_k_insert(List& list, uint32_t& count, uint32_t k, NearestKGate& gate, float d2, int32_t object, uint32_t slot) {
+  uint32_t e = count < k ? count++ : k - 1;
+  for (; e > 0 && nearest_wins(d2, object, list.d2(e - 1), list.object(e - 1)); --e) list.move(e, e - 1);
+  list.set(e, d2, object, slot);
+  if (count == k) { gate.d2 = list.d2(k - 1); gate.object = list.object(k - 1); }
 }
 
 }  // namespace p3d
