@@ -176,6 +176,15 @@ void void_schedules(p3d_scene* s) {
   for (SchedEntry& e : s->sched) e.built = false;
 }
 
+// Puts `st` behind the previous frame's tail (p3d_scene_set_tail_stream), if one is still pending.  Enqueues a wait only
+int wait_for_tail(p3d_scene* s, hipStream_t st) {
+  if (s->tail_pending) {
+    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
+    s->tail_pending = false;
+  }
+  return P3D_OK;
+}
+
 // root_min / root_max from the node array, if a fit has been enqueued since they were read.  The caller has waited for the
 // stream(s) that fit ran on
 int refresh_root_box(p3d_scene* s) {

@@ -303,10 +303,7 @@ struct FrameLaunch {
   int begin(FrameMode mode, uint32_t sample_begin, uint32_t sample_end, uint32_t resident) {
     P3D_HIP(hipSetDevice(s->device));
     s->last_status = 0;
-    if (s->tail_pending) {  // the scene's scratch is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
-      P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
-      s->tail_pending = false;
-    }
+    if (int rc = wait_for_tail(s, st)) return rc;  // the scene's scratch is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
     if (int rc = plan_frame(scene_facts(s), cfg, tile, sample_begin, sample_end, mode, resident, plan)) return rc;
     if (plan.per_level && s->root_stale) {  // the ray queue's bins are cut from the root box, which p3d_scene_refit_device left on the device
       P3D_HIP(hipStreamSynchronize(st));    // (the scene's stream rules put that refit in front of this frame on `st`)

@@ -2,11 +2,43 @@
 // p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_update.hpp"  // device_buffer_usable
-#include "nearest_k_query.hpp"
 #include "nearest_query.hpp"
 #include "ray_query.hpp"
 
 namespace {
+
+// What a launcher needs to start a traversing query kernel over n rays or points
+struct QueryLaunch {
+  QueryStack stack;  // for the kernel's parameters
+  uint32_t blocks;
+  size_t lds;        // bytes of the stack's LDS window
+};
+
+// The stack of one query launch: a 16-entry LDS window (a power of two) and, for a tree deeper than that, its worst case in
+// the scene's spill area, which grows here if it has to (the one place a query may wait: in the hipFree of the old area).
+// Refuses a batch whose spill entries 32-bit offsets cannot address (device_core.hpp Stack); `what` names its elements
+int bind_query_stack(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& pre, const char* what, QueryLaunch& out) {
+  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
+  const uint32_t cap = 16;
+  out.blocks = (n + kBlock - 1) / kBlock;
+  const uint64_t spill_entries = (uint64_t)(bound > cap ? bound : 0) * out.blocks * kBlock;
+  if (spill_entries > 0xffffffffull)
+    return fail(P3D_ERR_CAPACITY, pre + "too many " + what + " for one call over a tree this deep (split the batch)");
+  if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)spill_entries * sizeof(uint2)))) return rc;
+  out.stack.spill = (uint2*)s->spill.p; out.stack.spill_stride = out.blocks * kBlock; out.stack.stack_cap = (int32_t)cap;
+  out.lds = (size_t)cap * kBlock * sizeof(uint2);
+  return P3D_OK;
+}
+
+// ray_query_kernel<accel, any, EXTRAS> on `st`
+template <bool EXTRAS>
+void launch_ray_query(uint32_t accel, bool any, const QueryLaunch& q, hipStream_t st, const RayQueryParams& P) {
+  (void)with_accel(accel, [&](auto A) {
+    if (any) hipLaunchKernelGGL((ray_query_kernel<decltype(A)::value, true, EXTRAS>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+    else hipLaunchKernelGGL((ray_query_kernel<decltype(A)::value, false, EXTRAS>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+    return hipSuccess;
+  });
+}
 
 // p3d_trace_closest_device / p3d_trace_any_device: the refusals, the spill scratch and one launch on the caller's stream.
 // No wait anywhere but in a hipFree of a spill area that has to grow.
@@ -31,28 +63,14 @@ int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin
   for (const auto& b : bufs)
     if (b.p)
       if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
-  // the stack as trace_common binds it: a 16-entry LDS window, the rest of a deep tree's worst case in the spill area
-  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
-  const uint32_t cap = 16;
-  const uint32_t blocks = (n + kBlock - 1) / kBlock;
-  if ((uint64_t)(bound > cap ? bound : 0) * blocks * kBlock > 0xffffffffull)  // entries are addressed with 32-bit offsets (device_core.hpp Stack)
-    return fail(P3D_ERR_CAPACITY, pre + "too many rays for one call over a tree this deep (split the batch)");
+  QueryLaunch q;
+  if (int rc = bind_query_stack(s, accel, n, pre, "rays", q)) return rc;
   hipStream_t st = (hipStream_t)hip_stream;
-  if (s->tail_pending) {  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
-    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
-    s->tail_pending = false;
-  }
-  if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)(bound > cap ? bound : 0) * blocks * kBlock * sizeof(uint2)))) return rc;
+  if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
   RayQueryParams P{};
   P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
-  P.hit_id = d_hit_id; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.occluded = d_occluded;
-  P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
-  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
-  (void)with_accel(accel, [&](auto A) {
-    if (any) hipLaunchKernelGGL((trace_device_kernel<decltype(A)::value, true>), dim3(blocks), dim3(kBlock), lds, st, P);
-    else hipLaunchKernelGGL((trace_device_kernel<decltype(A)::value, false>), dim3(blocks), dim3(kBlock), lds, st, P);
-    return hipSuccess;
-  });
+  P.hit_id = d_hit_id; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.occluded = d_occluded; P.stack = q.stack;
+  launch_ray_query<true>(accel, any, q, st, P);
   P3D_HIP(hipGetLastError());
   return P3D_OK;
 }
@@ -81,36 +99,16 @@ int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_
   for (const auto& b : bufs)
     if (b.p)
       if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
-  // the stack as trace_device binds it: a 16-entry LDS window, the rest of a deep tree's worst case in the spill area
-  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
-  const uint32_t cap = 16;
-  const uint32_t blocks = (n + kBlock - 1) / kBlock;
-  if ((uint64_t)(bound > cap ? bound : 0) * blocks * kBlock > 0xffffffffull)  // entries are addressed with 32-bit offsets (device_core.hpp Stack)
-    return fail(P3D_ERR_CAPACITY, pre + "too many points for one call over a tree this deep (split the batch)");
+  QueryLaunch q;
+  if (int rc = bind_query_stack(s, accel, n, pre, "points", q)) return rc;
   hipStream_t st = (hipStream_t)hip_stream;
-  if (s->tail_pending) {  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
-    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
-    s->tail_pending = false;
-  }
-  if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)(bound > cap ? bound : 0) * blocks * kBlock * sizeof(uint2)))) return rc;
-  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
-  if (k_form) {  // the lists of this call's k behind the stack window
-    NearestKParams P{};
-    P.sc = s->dev; P.n = n; P.k = k; P.point = d_point; P.max_dist = d_max_dist;
-    P.count = d_count; P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal;
-    P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
-    const size_t lds_k = lds + nearest_k_lds_bytes(k);
-    if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_BVH>), dim3(blocks), dim3(kBlock), lds_k, st, P);
-    else hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_NONE>), dim3(blocks), dim3(kBlock), lds_k, st, P);
-    P3D_HIP(hipGetLastError());
-    return P3D_OK;
-  }
-  NearestParams P{};
-  P.sc = s->dev; P.n = n; P.point = d_point; P.max_dist = d_max_dist;
-  P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal;
-  P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
-  if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((nearest_device_kernel<P3D_ACCEL_BVH>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else hipLaunchKernelGGL((nearest_device_kernel<P3D_ACCEL_NONE>), dim3(blocks), dim3(kBlock), lds, st, P);
+  if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
+  NearestKParams P{};
+  P.sc = s->dev; P.n = n; P.k = k; P.point = d_point; P.max_dist = d_max_dist;
+  P.count = d_count; P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal; P.stack = q.stack;
+  const size_t lds = q.lds + nearest_k_lds_bytes(k);  // the lists of this call's k behind the stack window
+  if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_BVH>), dim3(q.blocks), dim3(kBlock), lds, st, P);
+  else hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), lds, st, P);
   P3D_HIP(hipGetLastError());
   return P3D_OK;
 }
@@ -139,21 +137,12 @@ static int trace_common(p3d_scene* s, uint32_t accel, uint32_t n, const float* o
   uint8_t* d_occ = (uint8_t*)(d_t + n);
   P3D_HIP(hipMemcpy(d_o, origin, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
   P3D_HIP(hipMemcpy(d_d, direction, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
-  const uint32_t cap = 16;  // LDS window of the spilling stack (a power of two), the rest in the backing array
-  const uint32_t blocks = (n + kBlock - 1) / kBlock;
-  if ((uint64_t)(bound > cap ? bound : 0) * blocks * kBlock > 0xffffffffull)  // entries are addressed with 32-bit offsets (device_core.hpp Stack)
-    return fail(P3D_ERR_CAPACITY, "p3d_trace: too many rays for one call over a tree this deep (split the batch)");
-  if (int rc = s->spill.ensure(std::max<size_t>(16, (size_t)(bound > cap ? bound : 0) * blocks * kBlock * sizeof(uint2)))) return rc;
-  TraceParams P{};
+  QueryLaunch q;
+  if (int rc = bind_query_stack(s, accel, n, "p3d_trace: ", "rays", q)) return rc;
+  RayQueryParams P{};  // the host form: no t_max, no normal
   P.sc = s->dev; P.n = n; P.origin = d_o; P.direction = d_d; P.hit_id = d_hit; P.hit_point = d_hp; P.occluded = d_occ;
-  P.t = t_host ? d_t : nullptr; P.spill = (uint2*)s->spill.p; P.spill_stride = blocks * kBlock; P.stack_cap = (int32_t)cap;
-  const size_t lds = (size_t)cap * kBlock * sizeof(uint2);
-  (void)with_accel(accel, [&](auto A) {
-    if (any) hipLaunchKernelGGL((trace_kernel<decltype(A)::value, true>), dim3(blocks), dim3(kBlock), lds, 0, P);
-    else hipLaunchKernelGGL((trace_kernel<decltype(A)::value, false>), dim3(blocks), dim3(kBlock), lds, 0, P);
-    return hipSuccess;
-  });
+  P.t = t_host ? d_t : nullptr; P.stack = q.stack;
+  launch_ray_query<false>(accel, any, q, nullptr, P);
   P3D_HIP(hipGetLastError());
   P3D_HIP(hipDeviceSynchronize());
   if (any) {

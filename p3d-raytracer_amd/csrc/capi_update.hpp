@@ -459,10 +459,7 @@ int p3d_scene_refit_device(p3d_scene* s, uint32_t n_sources, const p3d_geom_sour
     }
   }
   hipStream_t st = (hipStream_t)hip_stream;
-  if (s->tail_pending) {  // the previous frame's tail reads the geometry (p3d_scene_set_tail_stream)
-    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
-    s->tail_pending = false;
-  }
+  if (int rc = wait_for_tail(s, st)) return rc;  // the previous frame's tail reads the geometry (p3d_scene_set_tail_stream)
   // from here on the scene changes
   upd::ArgSources table{};
   std::copy(sorted.begin(), sorted.end(), table.s);
@@ -555,10 +552,7 @@ int p3d_scene_pose_device(p3d_scene* s, uint32_t n_xforms, const void* d_xforms,
     if (int rc = begin_update(s, P3D_UPDATE_REFIT, who)) return rc;
   }
   hipStream_t st = (hipStream_t)hip_stream;
-  if (s->tail_pending) {  // the previous frame's tail reads the geometry (p3d_scene_set_tail_stream)
-    P3D_HIP(hipStreamWaitEvent(st, s->ev_tail_done, 0));
-    s->tail_pending = false;
-  }
+  if (int rc = wait_for_tail(s, st)) return rc;  // the previous frame's tail reads the geometry (p3d_scene_set_tail_stream)
   // from here on the scene changes
   float4* blob = s->d_blob;
   hipLaunchKernelGGL(upd::pose_rig, dim3((n_objs + lbvh::kThreads - 1) / lbvh::kThreads), dim3(lbvh::kThreads), 0, st, (const float4*)s->rest.p,

@@ -1,70 +1,94 @@
-// nearest_query.hpp — nearest-surface queries over device buffers (p3d_nearest_device): nearest_device_kernel.  Which object's
-// surface is nearest to a point, how far, and where on it: the arithmetic is host/nearest_rule.hpp's, shared with
-// p3d_host_scene_nearest, whose bits the kernel must give.  Not a ray traversal: children are ordered by the distance of their
-// boxes from the point, and the search radius shrinks with every candidate found.  Nothing of device_core.hpp is changed: the
-// node and geometry records, the stack and its push / pop are used as they are.
+// nearest_query.hpp — nearest-surface queries over device buffers (p3d_nearest_device, p3d_nearest_k_device): one kernel,
+// nearest_k_device_kernel, and one traversal, bvh_nearest_k.  For every point the (at most) k objects with the smallest
+// (d2, object) under the limit, in that order, how far each is and where on it; p3d_nearest_device is k = 1 without a count.
+// The arithmetic, the candidate list, its admission and the bound a node is culled against are host/nearest_rule.hpp's,
+// shared with p3d_host_scene_nearest and p3d_host_scene_nearest_k, whose bits the kernel must give.  Not a ray traversal:
+// children are ordered by the distance of their boxes from the point, and the search radius shrinks as candidates are found.
+// Of device_core.hpp the node and geometry records, the stack and its push / pop are used.
 #pragma once
 
-#include "device_core.hpp"
 #include "nearest_rule.hpp"
+#include "queries.hpp"  // QueryStack
 
 namespace p3d {
 
-// The state of one point's search: the best candidate so far.  `slot` is where its geometry lives (an object index under
-// P3D_ACCEL_NONE, a leaf slot under P3D_ACCEL_BVH): it is fetched again for the normal instead of being carried in twelve
-// registers through the traversal.
-struct NearestBest {
-  float d2;
-  int32_t object;
-  uint32_t slot;
-  float q[3];
-};
-
-__device__ __forceinline__ void nearest_try(const Geom& g, uint32_t slot, const float p[3], NearestBest& b) {
-  const float v[9] = {g.a.x, g.a.y, g.a.z, g.a.w, g.b.x, g.b.y, g.b.z, g.b.w, g.c.x};
-  float q[3];
-  const float d2 = nearest_point(geom_type(g), v, p, q);
-  const int32_t object = (int32_t)geom_object(g);
-  if (nearest_wins(d2, object, b.d2, b.object)) {
-    b.d2 = d2; b.object = object; b.slot = slot;
-    b.q[0] = q[0]; b.q[1] = q[1]; b.q[2] = q[2];
+// The candidate list of one lane.  A list indexed by a runtime position cannot live in registers (it would go to scratch
+// memory), so it lives in LDS behind the stack window, strided by lane like the stack: dword f of entry e of a lane at
+// [(3 e + f) * kBlock + lane] - a wave's access to one entry's field touches 64 consecutive dwords, no bank conflicts.  An
+// entry is d2, the object and the slot of its geometry (an object index under P3D_ACCEL_NONE, a leaf slot under
+// P3D_ACCEL_BVH): 12 bytes, 768 k bytes per wave.  The closest point is not kept: it is computed again from the slot at the
+// end (nearest_point is evaluated as written in both translation units, so these are the bits the host has).
+struct LdsNearestList {
+  lds_u32* base;  // &list[lane]
+  __device__ __forceinline__ float d2(uint32_t e) const { return __uint_as_float(base[(3 * e) * kBlock]); }
+  __device__ __forceinline__ int32_t object(uint32_t e) const { return (int32_t)base[(3 * e + 1) * kBlock]; }
+  __device__ __forceinline__ uint32_t slot(uint32_t e) const { return base[(3 * e + 2) * kBlock]; }
+  __device__ __forceinline__ void move(uint32_t to, uint32_t from) {
+    for (uint32_t f = 0; f < 3; ++f) base[(3 * to + f) * kBlock] = base[(3 * from + f) * kBlock];
   }
-}
+  __device__ __forceinline__ void set(uint32_t e, float d2, int32_t object, uint32_t slot) {
+    base[(3 * e) * kBlock] = __float_as_uint(d2);
+    base[(3 * e + 1) * kBlock] = (uint32_t)object;
+    base[(3 * e + 2) * kBlock] = slot;
+  }
+};
+// LDS of one workgroup's lists, in bytes
+__host__ __device__ constexpr uint32_t nearest_k_lds_bytes(uint32_t k) { return k * kBlock * 12u; }
+
+// The state of one point's search.  The gate (what a candidate must beat, what a node is culled against) stays in registers:
+// LDS is touched only when a candidate is admitted.
+struct NearestKSearch {
+  LdsNearestList list;
+  NearestKGate gate;
+  uint32_t count, k;
+};
 
 __device__ __forceinline__ float nearest_node_d2(const NodeRec& n, const float p[3]) {
   const float lo[3] = {n.lo.x, n.lo.y, n.lo.z}, hi[3] = {n.hi.x, n.hi.y, n.hi.z};
   return nearest_box_d2(p, lo, hi);
 }
 
-// P3D_ACCEL_NONE: every object, planes included - the loop of p3d_host_scene_nearest
-__device__ void brute_nearest(const DevScene& sc, const float p[3], NearestBest& b) {
-  for (uint32_t i = 0; i < sc.n_objs; ++i) nearest_try(load_geom(sc.ogeom, i), i, p, b);
+__device__ __forceinline__ void nearest_k_offer(const Geom& g, uint32_t slot, const float p[3], NearestKSearch& s) {
+  const float v[9] = {g.a.x, g.a.y, g.a.z, g.a.w, g.b.x, g.b.y, g.b.z, g.b.w, g.c.x};
+  float q[3];
+  const float d2 = nearest_point(geom_type(g), v, p, q);
+  const int32_t object = (int32_t)geom_object(g);
+  if (nearest_k_admits(d2, object, s.gate)) nearest_k_insert(s.list, s.count, s.k, s.gate, d2, object, slot);
+}
+
+// P3D_ACCEL_NONE: every object, planes included - the loop of p3d_host_scene_nearest_k
+__device__ void brute_nearest_k(const DevScene& sc, const float p[3], NearestKSearch& s) {
+  for (uint32_t i = 0; i < sc.n_objs; ++i) nearest_k_offer(load_geom(sc.ogeom, i), i, p, s);
 }
 
 // P3D_ACCEL_BVH: a stack traversal over sc.nodes / sc.bgeom.  The float of a stack entry is the child's box d2.
 //   - an inner node fetches both children (64 contiguous bytes), visits the nearer one first and pushes the farther one if
 //     the cull lets it live;
 //   - a popped entry meets the cull again: the radius has shrunk since it was pushed;
-//   - a leaf runs the rule on its objects; (d2, object) is a total order, so the order of the visits does not show in the answer;
-//   - the cull is nearest_culls, a positive test with slack: a NaN box drops nothing (odd_boxes scenes stay correct).
+//   - a leaf offers each of its objects to the list; (d2, object) is a total order and every object sits in one leaf, so the
+//     order of the visits does not show in the list;
+//   - the cull is nearest_culls, a positive test with slack: a NaN box drops nothing (odd_boxes scenes stay correct).  It is
+//     taken against s.gate.d2: the squared radius while the list is not full, the k-th entry's d2 once it is.  Until k
+//     candidates are in, nothing inside the radius is dropped, so a search is wider than a k = 1 search by what it takes to
+//     fill the list.
 // A lane pushes at most one entry per step down, so the stack is never deeper than the tree: the bound the host sizes the
 // spill area with.  The stack is empty on entry and on exit.
 // The steps are taken by wave vote as in bvh_segment_any, not as nested loops: neighbouring lanes hold unrelated points here
 // (no pixel coherence), so descents differ in length from lane to lane and the nested form would let the longest hold up every
 // lane that stands on a leaf; these scenes are traversed from global memory, where bvh_closest measured the vote ahead.
 // UNMEASURED for this traversal; the nested-loop form is the alternative.
-__device__ void bvh_nearest(const DevScene& sc, Stack& st, const float p[3], NearestBest& b) {
+__device__ void bvh_nearest_k(const DevScene& sc, Stack& st, const float p[3], NearestKSearch& s) {
   constexpr int SPILL = kStackWindow;
   Counters<false> ct;
   const NodeRec root = load_node(sc.nodes, 0);
-  if (nearest_culls(nearest_node_d2(root, p), b.d2)) return;
+  if (nearest_culls(nearest_node_d2(root, p), s.gate.d2)) return;
   uint32_t desc = __float_as_uint(root.lo.w);  // a descriptor, or kDescDone
   auto next_entry = [&]() {
     desc = kDescDone;
     bool more = st.sp > 0;
     while (more) {
       const uint2 e = pop<SPILL>(st);
-      const bool take = !nearest_culls(__uint_as_float(e.y), b.d2);
+      const bool take = !nearest_culls(__uint_as_float(e.y), s.gate.d2);
       if (take) desc = e.x;
       more = !take && st.sp > 0;
     }
@@ -78,7 +102,7 @@ __device__ void bvh_nearest(const DevScene& sc, Stack& st, const float p[3], Nea
       const uint32_t index = desc_index(desc);
       const NodeRec l = load_node(sc.nodes, index), r = load_node(sc.nodes, index + 1);
       const float l_d2 = nearest_node_d2(l, p), r_d2 = nearest_node_d2(r, p);
-      const bool l_in = !nearest_culls(l_d2, b.d2), r_in = !nearest_culls(r_d2, b.d2);
+      const bool l_in = !nearest_culls(l_d2, s.gate.d2), r_in = !nearest_culls(r_d2, s.gate.d2);
       const uint32_t ld = __float_as_uint(l.lo.w), rd = __float_as_uint(r.lo.w);
       if (l_in && r_in) {
         if (r_d2 < l_d2) { desc = rd; push<SPILL>(st, ld, l_d2, ct); }
@@ -89,56 +113,78 @@ __device__ void bvh_nearest(const DevScene& sc, Stack& st, const float p[3], Nea
     }
     if (!descend && on_leaf) {
       const uint32_t first = desc_index(desc), end = first + desc_count(desc);
-      for (uint32_t s = first; s < end; ++s) nearest_try(load_geom(sc.bgeom, s), s, p, b);
+      for (uint32_t g = first; g < end; ++g) nearest_k_offer(load_geom(sc.bgeom, g), g, p, s);
       next_entry();
     }
   }
 }
 
-struct NearestParams {
+struct NearestKParams {
   DevScene sc;
-  uint32_t n;
+  uint32_t n, k;          // 1 <= k <= P3D_NEAREST_K_MAX
   const float* point;     // n x 3
   const float* max_dist;  // n, or null: no limit
-  int32_t* object;        // required
-  float* dist;            // optional, like closest and normal
+  int32_t* count;         // n, or null: not written (p3d_nearest_device)
+  int32_t* object;        // n x k, required
+  float* dist;            // n x k; optional, like closest and normal (n x k x 3)
   float* closest;
   float* normal;
-  uint2* spill;
-  uint32_t spill_stride;
-  int32_t stack_cap;
+  QueryStack stack;
 };
 
-// One point per lane on an empty stack bound as in trace_device_kernel.  object = -1, dist = FLT_MAX, closest = normal = 0
-// where nothing lies within the limit.  normal: get_normal of the found object at the closest point, not turned.
-// A lane reads its point with three dword loads 12 bytes apart from its neighbours' (trace_device_kernel: whole 128-byte
-// lines either way, in front of dozens of dependent node fetches).  UNMEASURED, like the staged form.
+// One point per lane on an empty stack; the dynamic LDS holds the stack window and, behind it, the lists of
+// the call's k (not of P3D_NEAREST_K_MAX: LDS per workgroup decides how many waves a CU holds).  Row i k + j, j < count: the
+// j-th listed object, sqrtf(d2), the closest point (the rule once more at the listed slot) and get_normal of the object
+// there, not turned.  Rows j >= count: -1, FLT_MAX, zeros.
+// k is a runtime argument.  k as a template parameter over a few sizes would unroll the insertion and fix the LDS offsets; it
+// was not tried: UNMEASURED.
+// A lane writes its k rows itself: neighbouring lanes are k rows apart, so the stores of one row index are 4 k (object, dist)
+// or 12 k (closest, normal) bytes apart and not coalesced.  UNMEASURED; the alternatives are to write row-major through LDS
+// (the lists are already there) or to give the outputs the layout (k, n).
+// A lane reads its point with three dword loads 12 bytes apart from its neighbours' (ray_query_kernel: whole 128-byte lines
+// either way, in front of dozens of dependent node fetches).  UNMEASURED, like the staged form.
 template <int ACCEL>
-__global__ void __launch_bounds__(kBlock) nearest_device_kernel(const NearestParams P) {
+__global__ void __launch_bounds__(kBlock) nearest_k_device_kernel(const NearestKParams P) {
   extern __shared__ float4 smem[];
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   Stack st;
-  stack_bind(st, smem, 0, threadIdx.x, P.stack_cap, P.spill, P.spill_stride, i);
+  query_stack_bind(st, smem, P.stack, i);
+  NearestKSearch s;
+  s.list.base = (lds_u32*)(reinterpret_cast<uint32_t*>(smem + stack_lds_f4(kStackWindow, (uint32_t)P.stack.stack_cap))) + threadIdx.x;
+  s.count = 0; s.k = P.k;
   if (i >= P.n) return;
   const float p[3] = {P.point[3 * i], P.point[3 * i + 1], P.point[3 * i + 2]};
-  NearestBest b;
-  b.object = -1; b.slot = 0; b.q[0] = b.q[1] = b.q[2] = 0.0f;
-  const bool open = nearest_radius(P.max_dist != nullptr, P.max_dist ? P.max_dist[i] : 0.0f, b.d2);
+  const bool open = nearest_k_open(P.max_dist != nullptr, P.max_dist ? P.max_dist[i] : 0.0f, s.gate);
   if (open && P.sc.n_objs > 0) {
-    if (ACCEL == P3D_ACCEL_BVH) bvh_nearest(P.sc, st, p, b);
-    else brute_nearest(P.sc, p, b);
+    if (ACCEL == P3D_ACCEL_BVH) bvh_nearest_k(P.sc, st, p, s);
+    else brute_nearest_k(P.sc, p, s);
   }
-  const bool found = b.object >= 0;
-  P.object[i] = b.object;
-  if (P.dist) P.dist[i] = found ? sqrtf(b.d2) : FLT_MAX;
-  const F3 q = found ? f3(b.q[0], b.q[1], b.q[2]) : f3(0, 0, 0);
-  if (P.closest) {
-    P.closest[3 * i] = q.x; P.closest[3 * i + 1] = q.y; P.closest[3 * i + 2] = q.z;
-  }
-  if (P.normal) {
-    F3 nrm = f3(0, 0, 0);
-    if (found) nrm = get_normal(load_geom(ACCEL == P3D_ACCEL_BVH ? P.sc.bgeom : P.sc.ogeom, b.slot), P.sc.normals, q);
-    P.normal[3 * i] = nrm.x; P.normal[3 * i + 1] = nrm.y; P.normal[3 * i + 2] = nrm.z;
+  if (P.count) P.count[i] = (int32_t)s.count;
+  const float4* geom = ACCEL == P3D_ACCEL_BVH ? P.sc.bgeom : P.sc.ogeom;
+  for (uint32_t e = 0; e < P.k; ++e) {
+    const size_t row = (size_t)i * P.k + e;
+    const bool found = e < s.count;
+    int32_t object = -1;
+    float dist = FLT_MAX;
+    F3 q = f3(0, 0, 0), nrm = f3(0, 0, 0);
+    if (found) {
+      const Geom g = load_geom(geom, s.list.slot(e));
+      const float v[9] = {g.a.x, g.a.y, g.a.z, g.a.w, g.b.x, g.b.y, g.b.z, g.b.w, g.c.x};
+      float c[3];
+      nearest_point(geom_type(g), v, p, c);
+      object = s.list.object(e);
+      dist = sqrtf(s.list.d2(e));
+      q = f3(c[0], c[1], c[2]);
+      if (P.normal) nrm = get_normal(g, P.sc.normals, q);
+    }
+    P.object[row] = object;
+    if (P.dist) P.dist[row] = dist;
+    if (P.closest) {
+      P.closest[3 * row] = q.x; P.closest[3 * row + 1] = q.y; P.closest[3 * row + 2] = q.z;
+    }
+    if (P.normal) {
+      P.normal[3 * row] = nrm.x; P.normal[3 * row + 1] = nrm.y; P.normal[3 * row + 2] = nrm.z;
+    }
   }
 }
 

@@ -12,6 +12,6 @@
 #include "capi_adaptive.hpp"      // p3d_adaptive
 #include "capi_denoise.hpp"       // feature buffers, a-trous filter, variance
 #include "capi_temporal.hpp"      // p3d_temporal
-#include "ray_query.hpp"          // trace_device_kernel, bvh_segment_any (kernels of the device-buffer ray queries)
+#include "ray_query.hpp"          // ray_query_kernel, bvh_segment_any (kernels of the batched ray queries)
 #include "capi_query.hpp"         // p3d_trace_*, p3d_object_*, p3d_skybox_color
 #include "capi_debug.hpp"         // test hooks, instrumented builds

@@ -1,5 +1,5 @@
-// queries.hpp — batched queries against a scene, for the unit-level parity of the traversal back ends and of the host
-// classes: trace_kernel (bvh.cpp:198-340, grid.cpp:71-208, main.cpp:116-124,208-216) and object_query_kernel.
+// queries.hpp — batched per-object queries against a scene, for the unit-level parity of the host classes
+// (object_query_kernel), and QueryStack, the stack every traversing query kernel's parameters embed.
 #pragma once
 
 #include "device_core.hpp"
@@ -39,45 +39,17 @@ __global__ void __launch_bounds__(kBlock) object_query_kernel(const ObjectQueryP
   }
 }
 
-struct TraceParams {
-  DevScene sc;
-  uint32_t n;
-  const float* origin;
-  const float* direction;
-  int32_t* hit_id;
-  float* t;
-  float* hit_point;
-  uint8_t* occluded;
+// The spilling stack of a query kernel that traverses the tree (ray_query.hpp, nearest_query.hpp), one lane per query: a
+// stack_cap-entry LDS window per lane at the start of the dynamic LDS and, for a tree deeper than the window, the lane's
+// column of the scene's spill area.  The host fills it in one place (capi_query.hpp bind_query_stack).
+struct QueryStack {
   uint2* spill;
   uint32_t spill_stride;
   int32_t stack_cap;
 };
-
-template <int ACCEL, bool ANY>
-__global__ void __launch_bounds__(kBlock) trace_kernel(const TraceParams P) {
-  extern __shared__ float4 smem[];
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  Stack st;
-  stack_bind(st, smem, 0, threadIdx.x, P.stack_cap, P.spill, P.spill_stride, i);
-  if (i >= P.n) return;
-  Counters<false> ct;
-  RayS ray;
-  ray_set(ray, f3(P.origin[3 * i], P.origin[3 * i + 1], P.origin[3 * i + 2]),
-          f3(P.direction[3 * i], P.direction[3 * i + 1], P.direction[3 * i + 2]));
-  if (ANY) {
-    P.occluded[i] = any_hit<ACCEL, true, true>(P.sc, st, ray, ct) ? 1 : 0;
-  } else {
-    F3 hp = f3(0, 0, 0);
-    Geom g;
-    float t = FLT_MAX;
-    const int obj = closest_hit<ACCEL, true, true>(P.sc, st, ray, hp, g, ct, nullptr, &t);
-    P.hit_id[i] = obj;
-    if (P.t) P.t[i] = obj < 0 ? FLT_MAX : t;
-    if (obj < 0) hp = f3(0, 0, 0);
-    if (P.hit_point) {
-      P.hit_point[3 * i] = hp.x; P.hit_point[3 * i + 1] = hp.y; P.hit_point[3 * i + 2] = hp.z;
-    }
-  }
+// Lane threadIdx.x's empty stack for query i
+__device__ __forceinline__ void query_stack_bind(Stack& st, float4* smem, const QueryStack& q, uint32_t i) {
+  stack_bind(st, smem, 0, threadIdx.x, q.stack_cap, q.spill, q.spill_stride, i);
 }
 
 }  // namespace p3d

@@ -1,9 +1,10 @@
-// ray_query.hpp — ray queries over device buffers (p3d_trace_closest_device, p3d_trace_any_device): trace_device_kernel, and
-// bvh_segment_any, the any-hit with a distance limit.  Nothing of device_core.hpp's traversals is changed: the unlimited paths
-// call closest_hit / any_hit as queries.hpp's trace_kernel does, the segment query has a traversal of its own.
+// ray_query.hpp — the batched ray queries, from host arrays (p3d_trace_closest, p3d_trace_any) and over device buffers
+// (p3d_trace_closest_device, p3d_trace_any_device): ray_query_kernel, one body for both, and bvh_segment_any, the any-hit
+// with a distance limit.  The unlimited paths call device_core.hpp's closest_hit / any_hit (bvh.cpp:198-340,
+// grid.cpp:71-208, main.cpp:116-124,208-216), the segment query has a traversal of its own.
 #pragma once
 
-#include "device_core.hpp"
+#include "queries.hpp"  // QueryStack
 
 namespace p3d {
 
@@ -93,54 +94,55 @@ struct RayQueryParams {
   uint32_t n;
   const float* origin;     // n x 3
   const float* direction;  // n x 3, used as given
-  const float* t_max;      // n, or null: no limit
+  const float* t_max;      // n, or null: no limit (EXTRAS only)
   int32_t* hit_id;         // closest: required
   float* t;                // closest: optional, like hit_point and normal
   float* hit_point;
-  float* normal;
+  float* normal;           // (EXTRAS only)
   uint8_t* occluded;       // any: required
-  uint2* spill;
-  uint32_t spill_stride;
-  int32_t stack_cap;
+  QueryStack stack;
 };
 
-// One ray per lane on an empty stack bound as in trace_kernel.  Without t_max: the closest-hit and any-hit paths of trace_kernel,
-// bit for bit.  With it: a closest hit is kept only if t < t_max (strict; a NaN limit keeps nothing), and the any-hit is the
-// segment query above (the host refuses it for the grid).  normal: get_normal of the hit object at the reported hit point,
-// not turned against the ray, zero on a miss.
+// One ray per lane on an empty stack: closest_hit / any_hit as the frame kernels call them.  EXTRAS = false is the form of
+// the host-array calls: t_max and normal are not read.  EXTRAS = true, the device-buffer calls, gives the same bits where
+// they are null, and otherwise: with t_max a closest hit is kept only if t < t_max (strict; a NaN limit keeps nothing), and
+// the any-hit is the segment query above (the host refuses it for the grid); normal is get_normal of the hit object at the
+// reported hit point, not turned against the ray, zero on a miss.  A compile-time switch, not two null pointers: the normal
+// keeps the hit's geometry live through the traversal (grid closest hit: 88 VGPRs and 5 waves against 72 and 7).
 // A lane reads its ray with six dword loads 12 bytes apart from its neighbours': a wave's 768 bytes per array are six whole
 // 128-byte lines either way, fetched once per ray in front of a traversal of dozens of dependent node fetches, so the rays
 // are not staged through LDS with wide loads.  UNMEASURED, like the staged form.
-template <int ACCEL, bool ANY>
-__global__ void __launch_bounds__(kBlock) trace_device_kernel(const RayQueryParams P) {
+template <int ACCEL, bool ANY, bool EXTRAS>
+__global__ void __launch_bounds__(kBlock) ray_query_kernel(const RayQueryParams P) {
   extern __shared__ float4 smem[];
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   Stack st;
-  stack_bind(st, smem, 0, threadIdx.x, P.stack_cap, P.spill, P.spill_stride, i);
+  query_stack_bind(st, smem, P.stack, i);
   if (i >= P.n) return;
   Counters<false> ct;
   RayS ray;
   ray_set(ray, f3(P.origin[3 * i], P.origin[3 * i + 1], P.origin[3 * i + 2]),
           f3(P.direction[3 * i], P.direction[3 * i + 1], P.direction[3 * i + 2]));
+  const float* t_max = EXTRAS ? P.t_max : nullptr;
   if (ANY) {
     bool occluded;
-    if (!P.t_max) occluded = any_hit<ACCEL, true, true>(P.sc, st, ray, ct);
-    else if (ACCEL == P3D_ACCEL_BVH) occluded = bvh_segment_any(P.sc, st, ray, P.t_max[i], ct);
-    else occluded = brute_segment_any(P.sc, ray, P.t_max[i], ct);
+    if (!t_max) occluded = any_hit<ACCEL, true, true>(P.sc, st, ray, ct);
+    else if (ACCEL == P3D_ACCEL_BVH) occluded = bvh_segment_any(P.sc, st, ray, t_max[i], ct);
+    else occluded = brute_segment_any(P.sc, ray, t_max[i], ct);
     P.occluded[i] = occluded ? 1 : 0;
   } else {
     F3 hp = f3(0, 0, 0);
     Geom g;
     float t = FLT_MAX;
     int obj = closest_hit<ACCEL, true, true>(P.sc, st, ray, hp, g, ct, nullptr, &t);
-    if (P.t_max && obj >= 0 && !(t < P.t_max[i])) obj = -1;
+    if (t_max && obj >= 0 && !(t < t_max[i])) obj = -1;
     P.hit_id[i] = obj;
     if (P.t) P.t[i] = obj < 0 ? FLT_MAX : t;
     if (obj < 0) hp = f3(0, 0, 0);
     if (P.hit_point) {
       P.hit_point[3 * i] = hp.x; P.hit_point[3 * i + 1] = hp.y; P.hit_point[3 * i + 2] = hp.z;
     }
-    if (P.normal) {
+    if (EXTRAS && P.normal) {
       const F3 nrm = obj < 0 ? f3(0, 0, 0) : get_normal(g, P.sc.normals, hp);
       P.normal[3 * i] = nrm.x; P.normal[3 * i + 1] = nrm.y; P.normal[3 * i + 2] = nrm.z;
     }

@@ -1,6 +1,6 @@
 // nearest_rule.hpp — the arithmetic of a nearest-surface query, in ONE place for its users: p3d_host_scene_nearest and
-// p3d_host_scene_nearest_k (host_capi.cpp), which state the semantics by brute force, and nearest_device_kernel /
-// nearest_k_device_kernel (csrc/nearest_query.hpp, csrc/nearest_k_query.hpp), whose answers must be the host forms' bits.  For a point p and an object's nine geometry floats (what p3d_prim.v holds for its
+// p3d_host_scene_nearest_k (host_capi.cpp), which state the semantics by brute force, and nearest_k_device_kernel
+// (csrc/nearest_query.hpp), whose answers must be the host forms' bits.  For a point p and an object's nine geometry floats (what p3d_prim.v holds for its
 // kind) nearest_point gives the closest point q on the object's SURFACE and d2 = |p - q|^2, taken from q as stored.  Also
 // here: the squared distance from p to a BVH node's box, and the two comparisons of a search - which candidate wins, and
 // when a node may be dropped.  float32 throughout, evaluated as written; both translation units are compiled without

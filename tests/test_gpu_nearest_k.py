@@ -143,6 +143,7 @@ def test_k_1_is_nearest_device(worlds):
     dev = w.devs["device"]
     n = max(BATCHES)
     lim, d_lim = w.limits(1)
+    host = {False: w.hs.nearest(w.p), True: w.hs.nearest(w.p, max_dist=lim)}
     for accel in w.accels("device"):
         for d_m in (None, d_lim):
             one = {name: v.cpu().numpy() for name, v in dev.nearest_device(accel, w.d_p, max_dist=d_m, want=("object", "dist", "closest", "normal")).items()}
@@ -151,6 +152,10 @@ def test_k_1_is_nearest_device(worlds):
                 assert bits(got[name]) == bits(one[name]), "accel %d, %s: %s" % (accel, "no limit" if d_m is None else "limits", name)
             assert (got["count"] == (one["object"] >= 0)).all()
             assert d_m is None or 0 < got["count"].sum() < n
+            # (nearest_device is the k = 1 launch of the same kernel: the independent statement is the host's k = 1 brute force)
+            h_object, h_dist, h_closest = host[d_m is not None]
+            assert (got["object"][:, 0] == h_object).all(), "accel %d: HostScene.nearest's object" % accel
+            assert bits(got["dist"][:, 0]) == bits(h_dist) and bits(got["closest"][:, 0]) == bits(h_closest), "accel %d: HostScene.nearest's bits" % accel
     assert dev.status() == 0
 
 
