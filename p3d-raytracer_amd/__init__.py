@@ -1075,6 +1075,14 @@ class DeviceScene:
         lim = (C.c_uint32 * 4)(trip_bound, max_rounds, halo_chain, leftover_pool)
         _check(self._L.p3d_debug_scene_limits(self._h, C.cast(lim, C.c_void_p)))
 
+    def staged_f4(self, cfg, tile=None):
+        """csrc/p3d_debug.h, read-only: the float4s a frame of `cfg` over `tile` copies into LDS (0: the scene is not
+        staged, the kernels traverse it from global memory)."""
+        n = C.c_uint32(0)
+        self._L.p3d_debug_staged_f4.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        _check(self._L.p3d_debug_staged_f4(self._h, C.byref(cfg), C.byref(tile or self.full_tile()), C.byref(n)))
+        return n.value
+
     def render_features(self, cfg, samples=0, tile=None):
         """p3d_render_features: the feature buffers of the primary rays of samples [0, K) (0: min(16, SPP*SPP)) ->
         (normal_depth, albedo_cov), two (h, w, 4) float32 arrays: (n, t) and (diff_color, coverage), means over the samples

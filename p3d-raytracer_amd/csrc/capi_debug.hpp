@@ -13,10 +13,29 @@ int p3d_debug_scene_limits(p3d_scene* s, const p3d_debug_limits* limits) {
   return P3D_OK;
 }
 
+// What a frame of `cfg` over `tile` copies into LDS: the float4s of the staged range, 0 when the scene is traversed from
+// global memory (plan_frame's decision; read-only, no device call, no test-hook switch needed)
+int p3d_debug_staged_f4(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, uint32_t* staged_f4) {
+  if (!s || !cfg || !tile || !staged_f4) return fail(P3D_ERR_INVALID, "p3d_debug_staged_f4: null argument");
+  if (int rc = check_frame(s, cfg, tile)) return rc;
+  FramePlan plan{};
+  const uint32_t samples = cfg->antialiasing ? cfg->spp_sqrt * cfg->spp_sqrt : 1u;
+  if (int rc = plan_frame(scene_facts(s), cfg, tile, 0, samples, kFrame, 0, plan)) return rc;
+  *staged_f4 = plan.lds_scene ? plan.stage_hi - plan.stage_lo : 0u;
+  return P3D_OK;
+}
+
 #ifdef P3D_PT_PROFILE
 int p3d_debug_set_pt_prof(void* device_ptr) {
   unsigned long long* p = static_cast<unsigned long long*>(device_ptr);
   return hipMemcpyToSymbol(HIP_SYMBOL(p3d::g_pt_prof), &p, sizeof(p)) == hipSuccess ? P3D_OK : P3D_ERR_NO_DEVICE;
+}
+#endif
+#ifdef P3D_ENTRY_CLOCK
+int p3d_debug_set_entry_clock(void* device_ptr, uint32_t half) {
+  unsigned long long* p = static_cast<unsigned long long*>(device_ptr);
+  if (hipMemcpyToSymbol(HIP_SYMBOL(p3d::g_entry_clock), &p, sizeof(p)) != hipSuccess) return P3D_ERR_NO_DEVICE;
+  return hipMemcpyToSymbol(HIP_SYMBOL(p3d::g_entry_half), &half, sizeof(half)) == hipSuccess ? P3D_OK : P3D_ERR_NO_DEVICE;
 }
 #endif
 #ifdef P3D_TIMELINE

@@ -46,6 +46,27 @@ __device__ unsigned long long* g_timeline = nullptr;
 #define P3D_TL_END()
 #endif
 
+#ifdef P3D_ENTRY_CLOCK  // debug builds only (profiles/tools/entry_clock.py): per-workgroup ticks from the first instruction of
+// whitted_kernel to the end of scene staging (kind 2) or to the LIT == 3 exit (kind 1), and to the end of the workgroup.
+// Round 0 (LIT == 3) records behind g_entry_half workgroups, so that one frame keeps pass 1 and round 0 apart; the work-list
+// launches (LIT == 2) record nothing.
+__device__ unsigned long long* g_entry_clock = nullptr;
+__device__ unsigned int g_entry_half = 0;
+#define P3D_EC_SLOT(LIT) (3 * ((size_t)((LIT) == 3 ? g_entry_half : 0u) + blockIdx.x))
+#define P3D_EC_BEGIN() const unsigned long long ec_t0 = wall_clock64();
+#define P3D_EC_MARK(LIT, kind)                                          \
+  if ((LIT) != 2 && g_entry_clock && threadIdx.x == 0) {                \
+    g_entry_clock[P3D_EC_SLOT(LIT)] = wall_clock64() - ec_t0;           \
+    g_entry_clock[P3D_EC_SLOT(LIT) + 2] = (kind);                       \
+  }
+#define P3D_EC_END(LIT) \
+  if ((LIT) != 2 && g_entry_clock && threadIdx.x == 0) g_entry_clock[P3D_EC_SLOT(LIT) + 1] = wall_clock64() - ec_t0;
+#else
+#define P3D_EC_BEGIN()
+#define P3D_EC_MARK(LIT, kind)
+#define P3D_EC_END(LIT)
+#endif
+
 #ifdef P3D_PT_PROFILE  // debug builds only: wave-time, entries and active lanes per region of a kernel's loop
 __device__ unsigned long long* g_pt_prof = nullptr;
 constexpr int kProfRegions = 12;
@@ -153,17 +174,80 @@ struct RenderParams {
 
 // LDS map of one workgroup:  [ staged scene (lds_scene_f4 float4) | node stack (cap * 64 * 8 B) | per-pixel sample ring (PT, 4 lanes per pixel) ]
 // OBJECTS: the launch stages the object-order geometry too (every kernel but Whitted over the BVH; the host's stage range)
+// The copy comes in two halves, so that a kernel can have its first loads on their way while it waits for something that
+// does not depend on them (whitted_kernel: its schedule entry): stage_issue() starts the loads of the lane's first
+// kStageBatch float4s, stage_scene() stores them and copies what is left, kStageBatch loads of a lane in flight at a time (a
+// plain loop of load + store waits for every load on its own).  A load past the staged range reads the range's last float4
+// instead and is not stored.  16 registers, at a point where a kernel holds little else.  What it buys is small - every
+// wave of a CU reads the same few KB, the round trips are short - and measured in profiles/entry/README.md.
+constexpr int kStageBatch = 4;
+static_assert(kStageBatch == 4, "StageRegs holds a batch in named members (an indexed array in a struct that lives across the kernel's early exits went to scratch)");
+struct StageBatch { float4 a, b, c, d; };
+template <bool LDS> struct StageRegs { StageBatch v; };
+template <> struct StageRegs<false> {};
+
+__device__ __forceinline__ StageBatch stage_load_batch(const RenderParams& P, uint32_t base) {
+  StageBatch v;
+  const float4* src = P.blob + P.stage_lo;
+  const uint32_t last = P.blob_f4 - 1;  // (callers: blob_f4 != 0)
+  const uint32_t i = base + threadIdx.x;
+  v.a = src[i < last ? i : last];
+  v.b = src[i + kBlock < last ? i + kBlock : last];
+  v.c = src[i + 2 * kBlock < last ? i + 2 * kBlock : last];
+  v.d = src[i + 3 * kBlock < last ? i + 3 * kBlock : last];
+  return v;
+}
+__device__ __forceinline__ void stage_store_batch(const RenderParams& P, uint32_t base, const StageBatch& v, float4* smem) {
+  const uint32_t i = base + threadIdx.x;
+  if (i < P.blob_f4) smem[i] = v.a;
+  if (i + kBlock < P.blob_f4) smem[i + kBlock] = v.b;
+  if (i + 2 * kBlock < P.blob_f4) smem[i + 2 * kBlock] = v.c;
+  if (i + 3 * kBlock < P.blob_f4) smem[i + 3 * kBlock] = v.d;
+}
+
+template <bool LDS>
+__device__ __forceinline__ void stage_issue(const RenderParams& P, StageRegs<LDS>& first) {
+  if constexpr (LDS) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    first.v = P.blob_f4 ? stage_load_batch(P, 0) : StageBatch{zero, zero, zero, zero};
+  }
+}
+
+// the copy is complete: wait for every lane's stores, then the kernel's scene arrays are the staged ones
+template <bool OBJECTS>
+__device__ __forceinline__ void stage_bind(DevScene& sc, const RenderParams& P, float4* smem) {
+  __syncthreads();
+  sc.nodes = smem + (P.off_nodes - P.stage_lo);
+  sc.bgeom = smem + (P.off_bgeom - P.stage_lo);
+  sc.normals = smem + (P.off_normals - P.stage_lo);
+  sc.mats = smem + (P.off_mats - P.stage_lo);
+  sc.lights = smem + (P.off_lights - P.stage_lo);
+  if (OBJECTS) sc.ogeom = smem + (P.off_ogeom - P.stage_lo);  // (otherwise: stays in global memory)
+}
+
+template <bool LDS, bool OBJECTS>
+__device__ __forceinline__ void stage_scene(DevScene& sc, const RenderParams& P, float4* smem, const StageRegs<LDS>& first) {
+  if constexpr (LDS) {
+    if (P.blob_f4) stage_store_batch(P, 0, first.v, smem);
+    for (uint32_t base = kStageBatch * kBlock; base < P.blob_f4; base += kStageBatch * kBlock)
+      stage_store_batch(P, base, stage_load_batch(P, base), smem);
+    stage_bind<OBJECTS>(sc, P, smem);
+  }
+}
 template <bool LDS, bool OBJECTS>
 __device__ __forceinline__ void stage_scene(DevScene& sc, const RenderParams& P, float4* smem) {
-  if (LDS) {
+  StageRegs<LDS> first;
+  stage_issue<LDS>(P, first);
+  stage_scene<LDS, OBJECTS>(sc, P, smem, first);
+}
+// One float4 at a time, every load waited for on its own: the work-list launches of the hit_stack hand-off only (a few
+// waves behind a frame's round 0, nothing to gain; with the batched copy two of their anti-aliased instantiations, which
+// the allocator holds to 128 registers, spilled 12 and 16 bytes more).
+template <bool LDS, bool OBJECTS>
+__device__ __forceinline__ void stage_scene_plain(DevScene& sc, const RenderParams& P, float4* smem) {
+  if constexpr (LDS) {
     for (uint32_t i = threadIdx.x; i < P.blob_f4; i += kBlock) smem[i] = P.blob[P.stage_lo + i];
-    __syncthreads();
-    sc.nodes = smem + (P.off_nodes - P.stage_lo);
-    sc.bgeom = smem + (P.off_bgeom - P.stage_lo);
-    sc.normals = smem + (P.off_normals - P.stage_lo);
-    sc.mats = smem + (P.off_mats - P.stage_lo);
-    sc.lights = smem + (P.off_lights - P.stage_lo);
-    if (OBJECTS) sc.ogeom = smem + (P.off_ogeom - P.stage_lo);  // (otherwise: stays in global memory)
+    stage_bind<OBJECTS>(sc, P, smem);
   }
 }
 
@@ -390,6 +474,12 @@ __global__ void __launch_bounds__(kBlock, whitted_waves(AA, LDS, LIT, GHOSTS)) w
   constexpr bool REDO = LIT >= 2;               // launches that render units again, seeded with their predecessor's leftover
   constexpr bool GHOST = LIT != 0 && GHOSTS;    // zero-weight reflection rays are put aside and traced (whitted_sample.inc)
   extern __shared__ float4 smem[];
+  P3D_EC_BEGIN()
+  // The staged bytes depend on neither the tile nor the schedule entry: the launches whose waves all stage (LIT < 2) start the
+  // copy's first loads before anything else, the others behind the exit most of their waves take.
+  constexpr bool STAGE_FIRST = LIT < 2, STAGE_PLAIN = LIT == 2;
+  StageRegs<LDS && !STAGE_PLAIN> staged;
+  if (STAGE_FIRST) stage_issue<LDS && !STAGE_PLAIN>(P, staged);
   uint32_t tx = 0, ty = 0;
   const bool halo_block = (LIT == 1 || LIT == 3) && blockIdx.x >= P.tile_blocks;
   if (LIT != 2 && !halo_block && !tile_of_block(P, tx, ty)) return;
@@ -413,12 +503,22 @@ __global__ void __launch_bounds__(kBlock, whitted_waves(AA, LDS, LIT, GHOSTS)) w
         t_slot_count = pm & 0x1ffffu;
       }
     }
-    if (__ballot(t_need) == 0) return;
+    if (__ballot(t_need) == 0) {
+      P3D_EC_MARK(LIT, 1)
+      P3D_EC_END(LIT)
+      return;
+    }
   }
   P3D_TL_BEGIN()
   const unsigned long long t_begin = (LIT < 2 && P.tile_cost) ? wall_clock64() : 0;
   DevScene sc = P.sc;
-  stage_scene<LDS, ACCEL != P3D_ACCEL_BVH>(sc, P, smem);
+  if constexpr (STAGE_PLAIN) {
+    stage_scene_plain<LDS, ACCEL != P3D_ACCEL_BVH>(sc, P, smem);
+  } else {
+    if (!STAGE_FIRST) stage_issue<LDS>(P, staged);
+    stage_scene<LDS, ACCEL != P3D_ACCEL_BVH>(sc, P, smem, staged);
+  }
+  P3D_EC_MARK(LIT, 2)
 
   const uint32_t px = SUB == 4 ? lane >> 2 : lane;  // pixel of the tile this lane works for
   const uint32_t sub = SUB == 4 ? lane & 3u : 0u;
@@ -694,6 +794,7 @@ __global__ void __launch_bounds__(kBlock, whitted_waves(AA, LDS, LIT, GHOSTS)) w
   if (STATS && LIT == 0) flush_stats<STATS>(ct, P.stats);  // LITERAL: ucount_reduce_kernel
   if (LIT < 2 && !halo_block) record_tile_cost(P, tx, ty, t_begin);
   P3D_TL_END()
+  P3D_EC_END(LIT)
 }
 
 }  // namespace p3d

@@ -16,6 +16,8 @@ typedef struct p3d_debug_limits {
 } p3d_debug_limits;
 /* NULL limits = all real again. */
 int p3d_debug_scene_limits(p3d_scene* scene, const p3d_debug_limits* limits);
+/* Read-only, works without P3D_TEST_HOOKS: the float4s a frame of `cfg` over `tile` stages in LDS (0: the scene is not staged). */
+int p3d_debug_staged_f4(p3d_scene* scene, const p3d_config* cfg, const p3d_tile* tile, uint32_t* staged_f4);
 #ifdef __cplusplus
 }
 #endif
