@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -214,6 +215,14 @@ DevCamera dev_camera(const p3d_camera& c) {
   return d;
 }
 
+// An integer read from the environment: `def` when the variable is unset or its value lies outside [lo, hi].  Callers
+// keep the result in a function-local static: one read per process.
+inline int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX) {
+  const char* e = getenv(name);
+  const int n = e ? atoi(e) : def;
+  return n >= lo && n <= hi ? n : def;
+}
+
 int check_accel(const p3d_scene* s, uint32_t accel) {
   if (accel == P3D_ACCEL_BVH && !s->has_bvh) return fail(P3D_ERR_INVALID, "accel = Bvh but the scene was created without BVH arrays");
   if (accel == P3D_ACCEL_GRID && !s->has_grid) return fail(P3D_ERR_INVALID, "accel = UGrid but the scene was created without a grid");
@@ -224,7 +233,7 @@ int check_accel(const p3d_scene* s, uint32_t accel) {
 // The one place where a run-time p3d_config.accel picks the ACCEL template argument of a launch: f is called with a
 // std::integral_constant of P3D_ACCEL_BVH, _GRID or _NONE.
 template <class F>
-hipError_t with_accel(uint32_t accel, F&& f) {
+auto with_accel(uint32_t accel, F&& f) {
   switch (accel) {
     case P3D_ACCEL_BVH: return f(std::integral_constant<int, P3D_ACCEL_BVH>{});
     case P3D_ACCEL_GRID: return f(std::integral_constant<int, P3D_ACCEL_GRID>{});

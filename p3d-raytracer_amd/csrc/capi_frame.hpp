@@ -1,7 +1,8 @@
-// capi_frame.hpp — the frame launcher: kernel dispatch, the tile-schedule cache, and FrameLaunch, whose steps enqueue what a
-// FramePlan (capi_frame_plan.hpp) says; the frame, adaptive-pass and feature entry points each compose the steps they need
+// capi_frame.hpp — the frame launcher: the tile-schedule cache and FrameLaunch, whose steps enqueue what a FramePlan
+// (capi_frame_plan.hpp) says with the kernels capi_dispatch.hpp chooses; the frame, adaptive-pass and feature entry points
+// each compose the steps they need
 #pragma once
-#include "capi_frame_plan.hpp"
+#include "capi_dispatch.hpp"
 
 namespace {
 
@@ -17,35 +18,14 @@ constexpr uint32_t kWfHistWords = kWfBins + 32;  // bin counts of one level + th
 //    8 per wave  24.7 k / 23.8 k Mrays/s, 0.333 ms      32 per wave  36.9 k / 31.6 k, 0.337 ms
 //   16 per wave  32.0 k / 29.5 k,         0.332 ms      64 per wave  38.9 k / 34.0 k, 0.348 ms
 // P3D_REDO_LANES in the environment overrides it.
-inline uint32_t redo_lanes() {
-  static const uint32_t v = [] {
-    const char* e = getenv("P3D_REDO_LANES");
-    const int n = e ? atoi(e) : P3D_REDO_LANES;
-    return (uint32_t)(n >= 1 && n <= 64 ? n : P3D_REDO_LANES);
-  }();
-  return v;
-}
-inline uint32_t round1_lanes() {  // list entries per wave of the round-1 launch (successors to re-check; P3D_ROUND1_LANES overrides)
-  static const uint32_t v = [] {
-    const char* e = getenv("P3D_ROUND1_LANES");
-    const int n = e ? atoi(e) : 64;
-    return (uint32_t)(n >= 1 && n <= 64 ? n : 64);
-  }();
-  return v;
-}
-inline uint32_t list_blocks() {  // workgroups of the round-1 work-list launch (P3D_LIST_BLOCKS overrides)
-  static const uint32_t v = [] {
-    const char* e = getenv("P3D_LIST_BLOCKS");
-    const int n = e ? atoi(e) : 256;
-    return (uint32_t)(n >= 1 ? n : 256);
-  }();
-  return v;
-}
+inline uint32_t redo_lanes() { static const uint32_t v = (uint32_t)env_int("P3D_REDO_LANES", P3D_REDO_LANES, 1, 64); return v; }
+// list entries per wave of the round-1 launch (successors to re-check; P3D_ROUND1_LANES overrides)
+inline uint32_t round1_lanes() { static const uint32_t v = (uint32_t)env_int("P3D_ROUND1_LANES", 64, 1, 64); return v; }
+// workgroups of the round-1 work-list launch (P3D_LIST_BLOCKS overrides)
+inline uint32_t list_blocks() { static const uint32_t v = (uint32_t)env_int("P3D_LIST_BLOCKS", 256, 1); return v; }
 #ifdef P3D_ABLATION  // timing experiments only (profiles/r04/experiments): stages of the literal frame left out, frames WRONG
-inline uint32_t abl_skip() {  // P3D_ABL_SKIP: 1 = no check launch, 2 = no redo launch (round 0), 4 = no round 1 launch, 8 = round 1 launched on an empty list
-  static const uint32_t v = [] { const char* e = getenv("P3D_ABL_SKIP"); return e ? (uint32_t)atoi(e) : 0u; }();
-  return v;
-}
+// P3D_ABL_SKIP: 1 = no check launch, 2 = no redo launch (round 0), 4 = no round 1 launch, 8 = round 1 launched on an empty list
+inline uint32_t abl_skip() { static const uint32_t v = (uint32_t)env_int("P3D_ABL_SKIP", 0); return v; }
 #else
 constexpr uint32_t abl_skip() { return 0; }
 #endif
@@ -54,45 +34,6 @@ constexpr size_t kSchedCacheEntries = 16;
 constexpr uint32_t kSchedMinTiles = 8192;  // LDS-staged scenes: with fewer tiles than ~2 per wave slot nearly all start at once anyway
 constexpr uint32_t kSchedMinTilesL2 = 256;  // scenes traversed from L2: a wave lives a millisecond, the order matters from a few hundred tiles
 
-// ---------------------------------------------------------------------------
-// dispatch
-// ---------------------------------------------------------------------------
-template <int ACCEL, bool LDS, bool STATS>
-hipError_t launch_one(bool pt, bool aa, bool sub4, const RenderParams& P, uint32_t blocks, size_t lds, hipStream_t st) {
-  if (pt && sub4) hipLaunchKernelGGL((pt_kernel<ACCEL, LDS, STATS, 4>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else if (pt) hipLaunchKernelGGL((pt_kernel<ACCEL, LDS, STATS, 1>), dim3(blocks), dim3(kBlock), lds, st, P);
-  // anti-aliased, four or more samples per pixel, scene traversed from L2: four lanes per pixel (4x4-pixel
-  // tiles).  Only there: 100k triangles 512x512 2x2 AA 11.17 -> 6.84 ms, but a staged scene pays for one LDS
-  // copy per 16 pixels instead of per 64 (balls_medium 3x3 AA 3.48 -> 5.17 ms, balls_low 2x2 0.60 -> 0.65 ms).
-  else if (aa && sub4 && !LDS) {
-    if constexpr (!LDS) hipLaunchKernelGGL((whitted_kernel<ACCEL, false, STATS, true, true, 4>), dim3(blocks), dim3(kBlock), lds, st, P);
-  }
-  // LDS-staged scene whose worst-case stack does not fit LDS: staged scene + spilling stack
-  else if (LDS && P.stack_spills && aa) hipLaunchKernelGGL((whitted_kernel<ACCEL, LDS, STATS, true, true>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else if (LDS && P.stack_spills) hipLaunchKernelGGL((whitted_kernel<ACCEL, LDS, STATS, false, true>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else if (aa) hipLaunchKernelGGL((whitted_kernel<ACCEL, LDS, STATS, true>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else hipLaunchKernelGGL((whitted_kernel<ACCEL, LDS, STATS, false>), dim3(blocks), dim3(kBlock), lds, st, P);
-  return hipGetLastError();
-}
-template <int ACCEL>
-hipError_t launch_accel(bool pt, bool aa, bool sub4, bool lds_scene, bool stats, const RenderParams& P, uint32_t blocks, size_t lds, hipStream_t st) {
-  if (lds_scene) return stats ? launch_one<ACCEL, true, true>(pt, aa, sub4, P, blocks, lds, st) : launch_one<ACCEL, true, false>(pt, aa, sub4, P, blocks, lds, st);
-  return stats ? launch_one<ACCEL, false, true>(pt, aa, sub4, P, blocks, lds, st) : launch_one<ACCEL, false, false>(pt, aa, sub4, P, blocks, lds, st);
-}
-
-// Adaptive passes (pt_adaptive_kernel): the grid is sized to the resident waves, not to the frame
-template <int ACCEL, bool LDS, bool STATS>
-hipError_t launch_adapt_one(bool sub4, const RenderParams& P, const PtAdaptParams& A, uint32_t blocks, size_t lds, hipStream_t st) {
-  if (sub4) hipLaunchKernelGGL((pt_adaptive_kernel<ACCEL, LDS, STATS, 4>), dim3(blocks), dim3(kBlock), lds, st, P, A);
-  else hipLaunchKernelGGL((pt_adaptive_kernel<ACCEL, LDS, STATS, 1>), dim3(blocks), dim3(kBlock), lds, st, P, A);
-  return hipGetLastError();
-}
-template <int ACCEL>
-hipError_t launch_adapt_accel(bool sub4, bool lds_scene, bool stats, const RenderParams& P, const PtAdaptParams& A, uint32_t blocks, size_t lds, hipStream_t st) {
-  if (lds_scene) return stats ? launch_adapt_one<ACCEL, true, true>(sub4, P, A, blocks, lds, st) : launch_adapt_one<ACCEL, true, false>(sub4, P, A, blocks, lds, st);
-  return stats ? launch_adapt_one<ACCEL, false, true>(sub4, P, A, blocks, lds, st) : launch_adapt_one<ACCEL, false, false>(sub4, P, A, blocks, lds, st);
-}
-
 // What one pass of an adaptive frame (p3d_adaptive) needs besides the plan: the list the pass renders and the resolve /
 // decide / compact launch behind it.
 struct AdaptPass {
@@ -100,65 +41,6 @@ struct AdaptPass {
   AdaptResolveParams r;
   uint32_t resident;  // workgroups the device holds at once (the grid of pt_adaptive_kernel at most)
 };
-
-// Feature buffers (p3d_render_features, features.hpp): one launch over the tile's 8x8 tiles with the frame's staging and stack
-template <int ACCEL>
-hipError_t launch_features(bool lds_scene, int stack_mode, const RenderParams& P, const FeatureParams& F, uint32_t blocks, size_t lds, hipStream_t st) {
-  if (!lds_scene) hipLaunchKernelGGL((feature_kernel<ACCEL, false, kStackWindow>), dim3(blocks), dim3(kBlock), lds, st, P, F);
-  else if (stack_mode == kStackLds8) hipLaunchKernelGGL((feature_kernel<ACCEL, true, kStackLds8>), dim3(blocks), dim3(kBlock), lds, st, P, F);
-  else if (stack_mode == kStackLds6) hipLaunchKernelGGL((feature_kernel<ACCEL, true, kStackLds6>), dim3(blocks), dim3(kBlock), lds, st, P, F);
-  else hipLaunchKernelGGL((feature_kernel<ACCEL, true, kStackWindow>), dim3(blocks), dim3(kBlock), lds, st, P, F);
-  return hipGetLastError();
-}
-
-// P3D_STACK_LITERAL launches (BVH only).  lit 1: pass 1; lit 2: work-list launch; lit 0: the check launch over the tiles; lit 3:
-// the check launch over pass 1's list; lit 4: check + repair over the tiles in one launch (whitted_kernel LIT = 3).
-// ghosts: the scene has zero-weight reflection rays to trace (a transmissive AND reflective material).
-template <bool LDS, bool SPILL, int LIT, bool GHOSTS>
-hipError_t launch_whitted_literal(bool aa, bool stats, const RenderParams& P, uint32_t blocks, size_t lds, hipStream_t st) {
-  constexpr int A = P3D_ACCEL_BVH;
-  if (aa && stats) hipLaunchKernelGGL((whitted_kernel<A, LDS, true, true, SPILL, 1, LIT, GHOSTS>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else if (aa) hipLaunchKernelGGL((whitted_kernel<A, LDS, false, true, SPILL, 1, LIT, GHOSTS>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else if (stats) hipLaunchKernelGGL((whitted_kernel<A, LDS, true, false, SPILL, 1, LIT, GHOSTS>), dim3(blocks), dim3(kBlock), lds, st, P);
-  else hipLaunchKernelGGL((whitted_kernel<A, LDS, false, false, SPILL, 1, LIT, GHOSTS>), dim3(blocks), dim3(kBlock), lds, st, P);
-  return hipGetLastError();
-}
-template <bool LDS, bool SPILL>
-hipError_t launch_literal_variant(int lit, bool ghosts, bool aa, bool stats, const RenderParams& P, uint32_t blocks, size_t lds, hipStream_t st) {
-  if (lit == 1) return ghosts ? launch_whitted_literal<LDS, SPILL, 1, true>(aa, stats, P, blocks, lds, st) : launch_whitted_literal<LDS, SPILL, 1, false>(aa, stats, P, blocks, lds, st);
-  if (lit == 2) return ghosts ? launch_whitted_literal<LDS, SPILL, 2, true>(aa, stats, P, blocks, lds, st) : launch_whitted_literal<LDS, SPILL, 2, false>(aa, stats, P, blocks, lds, st);
-  if (lit == 4) {
-    if constexpr (LDS) {  // (only LDS-staged scenes repair over the tiles: FramePlan::repair_tiles)
-      return ghosts ? launch_whitted_literal<LDS, SPILL, 3, true>(aa, stats, P, blocks, lds, st) : launch_whitted_literal<LDS, SPILL, 3, false>(aa, stats, P, blocks, lds, st);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  }
-  if (lit == 5) {  // round 1 as a light launch: check the entries of list B, pass the few that change on to list C
-    if (stats) hipLaunchKernelGGL((handoff_check_entries_kernel<LDS, SPILL, true>), dim3(blocks), dim3(kBlock), lds, st, P);
-    else hipLaunchKernelGGL((handoff_check_entries_kernel<LDS, SPILL, false>), dim3(blocks), dim3(kBlock), lds, st, P);
-    return hipGetLastError();
-  }
-  if (lit == 3) {
-    if constexpr (!LDS) {  // (only scenes traversed from global memory announce: FrameLaunch::setup_handoff)
-      if (stats) hipLaunchKernelGGL((handoff_check_list_kernel<LDS, SPILL, true>), dim3(blocks), dim3(kBlock), lds, st, P);
-      else hipLaunchKernelGGL((handoff_check_list_kernel<LDS, SPILL, false>), dim3(blocks), dim3(kBlock), lds, st, P);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  } else if (stats) {
-    hipLaunchKernelGGL((handoff_check_kernel<LDS, SPILL, true>), dim3(blocks), dim3(kBlock), lds, st, P);
-  } else {
-    hipLaunchKernelGGL((handoff_check_kernel<LDS, SPILL, false>), dim3(blocks), dim3(kBlock), lds, st, P);
-  }
-  return hipGetLastError();
-}
-// lit 0 here = the check kernel
-hipError_t launch_literal(int lit, bool ghosts, bool aa, bool lds_scene, bool stats, const RenderParams& P, uint32_t blocks, size_t lds, hipStream_t st) {
-  if (lds_scene && P.stack_spills) return launch_literal_variant<true, true>(lit, ghosts, aa, stats, P, blocks, lds, st);
-  if (lds_scene) return launch_literal_variant<true, false>(lit, ghosts, aa, stats, P, blocks, lds, st);
-  return launch_literal_variant<false, true>(lit, ghosts, aa, stats, P, blocks, lds, st);
-}
 
 // Looks up the schedule for the launch described by (cfg, P).  Known key: P.sched is set.  New
 // key: P.tile_cost is set so that this launch (in frame order) records the costs, and *fresh
@@ -510,9 +392,7 @@ struct FrameLaunch {
     whole_tile(plan.adapt_blocks);
     P.rgb = nullptr; P.hit_id = nullptr; P.rgb8 = nullptr;
     P.accum_sum = accum_sum; P.accum_hit = accum_hit;
-    hipError_t e = with_accel(cfg->accel, [&](auto A) {
-      return launch_adapt_accel<decltype(A)::value>(plan.sub4, plan.lds_scene, want_counts, P, ap.k, plan.adapt_blocks, plan.lds_bytes, st);
-    });
+    hipError_t e = enqueue(adaptive_kernel(cfg->accel, plan, want_counts), plan.adapt_blocks, kBlock, plan.lds_bytes, st, P, ap.k);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(adapt_resolve_kernel, dim3((ap.r.slots + kAdaptResolveThreads - 1) / kAdaptResolveThreads), dim3(kAdaptResolveThreads), 0, st, ap.r);
       e = hipGetLastError();
@@ -525,9 +405,7 @@ struct FrameLaunch {
   int feature_launch(const FeatureParams& F) {
     whole_tile(plan.feat_blocks);
     const size_t feat_lds = (size_t)P.lds_scene_f4 * sizeof(float4) + (size_t)stack_lds_f4(plan.stack_mode, plan.cap) * sizeof(float4);
-    const hipError_t e = with_accel(cfg->accel, [&](auto A) {
-      return launch_features<decltype(A)::value>(plan.lds_scene, plan.stack_mode, P, F, plan.feat_blocks, feat_lds, st);
-    });
+    const hipError_t e = enqueue(feature_kernel_of(cfg->accel, plan), plan.feat_blocks, kBlock, feat_lds, st, P, F);
     if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("feature launch: ") + hipGetErrorString(e));
     return P3D_OK;
   }
@@ -536,7 +414,6 @@ struct FrameLaunch {
   // above wrote, then the fold.  The grid of a queue launch is fixed (the queue length is only known on the device): 24
   // waves per CU, each taking every (grid / 8)-th chunk of 64 entries of its segment.
   hipError_t level_chain(uint32_t blocks) {
-    const bool literal = plan.literal;
     hipError_t e = hipSuccess;
     P.wf_seg_cap = wf_seg_cap;
     P.wf_final = (float4*)s->wf_final.p;
@@ -559,11 +436,7 @@ struct FrameLaunch {
       P.level_stride = g * kBlock;
       // (wf_level_kernel keeps its shading state in registers: no cold area behind its stack window)
       const size_t wf_lds = plan.lds_bytes - (plan.cold_lds ? (size_t)kColdDwords * kBlock * sizeof(float) : 0);
-      if (want_counts && literal) hipLaunchKernelGGL((wf_level_kernel<true, 1>), dim3(g), dim3(kBlock), wf_lds, st, P);
-      else if (want_counts) hipLaunchKernelGGL((wf_level_kernel<true, 0>), dim3(g), dim3(kBlock), wf_lds, st, P);
-      else if (literal) hipLaunchKernelGGL((wf_level_kernel<false, 1>), dim3(g), dim3(kBlock), wf_lds, st, P);
-      else hipLaunchKernelGGL((wf_level_kernel<false, 0>), dim3(g), dim3(kBlock), wf_lds, st, P);
-      e = hipGetLastError();
+      e = enqueue(level_kernel(want_counts, plan.literal), g, kBlock, wf_lds, st, P);
       if (e == hipSuccess && level < cfg->max_depth) {  // put the child rays in bin order for the next level
         hipLaunchKernelGGL(wf_scan_kernel, dim3(1), dim3(1024), 0, st, P.wf_hist);
         P.wf_n_in = P.wf_n_out;
@@ -577,6 +450,12 @@ struct FrameLaunch {
     }
     P.level_stride = blocks * kBlock;
     return e;
+  }
+
+  // One launch of a LITERAL frame with the frame's staging, stack and LDS
+  hipError_t literal_launch(LiteralStep step, uint32_t blocks) {
+    return enqueue(literal_kernel(step, plan.lds_scene, plan.lds_spill, s->zero_weight_reflections, cfg->antialiasing != 0, want_counts),
+                   blocks, kBlock, plan.lds_bytes, st, P);
   }
 
   // The tile in launches of bands_per_launch tile bands.  pass 0 = the render launches (LITERAL: pass 1 of the hand-off,
@@ -625,11 +504,9 @@ struct FrameLaunch {
         e = level_chain(blocks);
       } else if (literal) {
         if (pass == 1) { H.list_out = ho_list[plan.repair_tiles ? 1 : 0]; H.n_out = ho_counters + kHoListA + (plan.repair_tiles ? 1 : 0); }
-        e = launch_literal(pass == 0 ? 1 : (plan.repair_tiles ? 4 : 0), s->zero_weight_reflections, cfg->antialiasing != 0, lds_scene, want_counts, P, blocks, plan.lds_bytes, st);
+        e = literal_launch(pass == 0 ? LiteralStep::Pass1 : (plan.repair_tiles ? LiteralStep::RepairTiles : LiteralStep::CheckTiles), blocks);
       } else {
-        e = with_accel(cfg->accel, [&](auto A) {
-          return launch_accel<decltype(A)::value>(plan.pt, cfg->antialiasing != 0, plan.sub4, lds_scene, want_counts, P, blocks, plan.lds_bytes, st);
-        });
+        e = enqueue(frame_kernel(cfg->accel, plan, cfg->antialiasing != 0, want_counts), blocks, kBlock, plan.lds_bytes, st, P);
       }
       if (e != hipSuccess) {
         if (fresh) fresh->built = false;
@@ -649,9 +526,7 @@ struct FrameLaunch {
   // whatever is left after that - almost never anything - to the fixed point (C -> D -> C ...).
   int handoff_rounds() {
     Handoff& H = P.hand;
-    const bool ghosts = s->zero_weight_reflections, lds_scene = plan.lds_scene;
     const uint32_t max_threads = plan.max_threads;
-    const size_t lds_bytes = plan.lds_bytes;
     P.x0 = tile->x0; P.w = tile->w; P.h = tile->h; P.row0 = 0; P.y0 = tile->y0;
     P.rgb = d_rgb; P.hit_id = d_hit; P.rgb8 = d_rgb8;
     P.sched = nullptr; P.tile_cost = nullptr;
@@ -663,7 +538,7 @@ struct FrameLaunch {
       H.list_out = ho_list[0]; H.n_out = ho_counters + kHoListA;
       P.level_stride = wide * kBlock;
       P.tile_blocks = wide;
-      const hipError_t e = launch_literal(3, ghosts, cfg->antialiasing != 0, lds_scene, want_counts, P, wide, lds_bytes, st);
+      const hipError_t e = literal_launch(LiteralStep::CheckList, wide);
       if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("hand-off check launch: ") + hipGetErrorString(e));
     }
     for (int round = 0; round < 3; ++round) {
@@ -685,7 +560,7 @@ struct FrameLaunch {
       P.tile_blocks = blocks;
       const uint32_t real_cap = H.list_cap;
       if (abl_skip() & 8u) H.list_cap = 0;  // (ablation: the launch happens, every workgroup finds an empty list)
-      const hipError_t e = launch_literal(round == 1 ? 5 : 2, ghosts, cfg->antialiasing != 0, lds_scene, want_counts, P, blocks, lds_bytes, st);
+      const hipError_t e = literal_launch(round == 1 ? LiteralStep::CheckEntries : LiteralStep::RepairList, blocks);
       H.list_cap = real_cap;
       if (e != hipSuccess) return fail(P3D_ERR_NO_DEVICE, std::string("hand-off kernel launch: ") + hipGetErrorString(e));
     }

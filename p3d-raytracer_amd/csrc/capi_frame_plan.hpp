@@ -25,7 +25,7 @@ constexpr uint32_t kMaxLaunchThreads = 1u << 24;
 // Tile of a wave of the one-lane-per-pixel Whitted kernels over a scene traversed from L2 (see plan_frame).
 // P3D_TILE_SHAPE = 88 | 84 | 44 in the environment overrides the rule (experiments).
 void tile_shape(uint64_t pixels, uint32_t& w, uint32_t& h) {
-  static const int forced = [] { const char* e = getenv("P3D_TILE_SHAPE"); return e ? atoi(e) : 0; }();
+  static const int forced = env_int("P3D_TILE_SHAPE", 0);
   int shape = forced;
   if (shape != 88 && shape != 84 && shape != 44) shape = 88;
   w = shape == 44 ? 4 : 8;

@@ -1,6 +1,7 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_nearest_device, p3d_nearest_k_device,
 // p3d_object_*, p3d_skybox_color)
 #pragma once
+#include "capi_dispatch.hpp"  // with_flags
 #include "capi_update.hpp"  // device_buffer_usable
 #include "nearest_query.hpp"
 #include "ray_query.hpp"
@@ -33,10 +34,8 @@ int bind_query_stack(p3d_scene* s, uint32_t accel, uint32_t n, const std::string
 // ray_query_kernel<accel, any, EXTRAS> on `st`
 template <bool EXTRAS>
 void launch_ray_query(uint32_t accel, bool any, const QueryLaunch& q, hipStream_t st, const RayQueryParams& P) {
-  (void)with_accel(accel, [&](auto A) {
-    if (any) hipLaunchKernelGGL((ray_query_kernel<decltype(A)::value, true, EXTRAS>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-    else hipLaunchKernelGGL((ray_query_kernel<decltype(A)::value, false, EXTRAS>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-    return hipSuccess;
+  with_accel(accel, [&](auto A) {
+    with_flags([&](auto ANY) { hipLaunchKernelGGL((ray_query_kernel<decltype(A)::value, ANY, EXTRAS>), dim3(q.blocks), dim3(kBlock), q.lds, st, P); }, any);
   });
 }
 
@@ -181,10 +180,13 @@ int p3d_nearest_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, c
   return nearest_device(s, accel, n, k, true, d_point, d_max_dist, d_count, d_object, d_dist, d_closest, d_normal, hip_stream);
 }
 
-static int object_query(p3d_scene* s, int what, uint32_t object, uint32_t n, const float* a, float* b, uint8_t* hit, float* t) {
-  if (!s || !a || !b || (what == 0 && (!hit || !t))) return fail(P3D_ERR_INVALID, "p3d object query: null argument");
-  if (what != 2 && object >= s->dev.n_objs) return fail(P3D_ERR_INVALID, "p3d object query: no such object");
-  if (what == 2 && !s->has_sky) return fail(P3D_ERR_INVALID, "p3d_skybox_color: no cubemap was supplied (p3d_scene_set_skybox)");
+enum class ObjectQuery { Intercepts = 0, Normal = 1, SkyboxColour = 2 };  // the values are object_query_kernel's WHAT
+
+static int object_query(p3d_scene* s, ObjectQuery what, uint32_t object, uint32_t n, const float* a, float* b, uint8_t* hit, float* t) {
+  const bool intercepts = what == ObjectQuery::Intercepts, sky = what == ObjectQuery::SkyboxColour;
+  if (!s || !a || !b || (intercepts && (!hit || !t))) return fail(P3D_ERR_INVALID, "p3d object query: null argument");
+  if (!sky && object >= s->dev.n_objs) return fail(P3D_ERR_INVALID, "p3d object query: no such object");
+  if (sky && !s->has_sky) return fail(P3D_ERR_INVALID, "p3d_skybox_color: no cubemap was supplied (p3d_scene_set_skybox)");
   if (n == 0) return P3D_OK;
   P3D_HIP(hipSetDevice(s->device));
   // (no p3d_scene_join as in trace_common: only q_in / q_out are written here, which no frame launch touches, and a frame does not write the geometry)
@@ -196,33 +198,34 @@ static int object_query(p3d_scene* s, int what, uint32_t object, uint32_t n, con
   float* d_t = d_b + (size_t)n * 3;
   uint8_t* d_hit = (uint8_t*)(d_t + n);
   P3D_HIP(hipMemcpy(d_a, a, vec, hipMemcpyHostToDevice));
-  if (what == 0) {
+  if (intercepts) {
     P3D_HIP(hipMemcpy(d_b, b, vec, hipMemcpyHostToDevice));
     P3D_HIP(hipMemcpy(d_t, t, (size_t)n * sizeof(float), hipMemcpyHostToDevice));  // untouched where the test fails
   }
   ObjectQueryParams Q{};
   Q.sc = s->dev; Q.object = object; Q.n = n; Q.a = d_a; Q.b = d_b; Q.hit = d_hit; Q.t = d_t;
   const uint32_t blocks = (n + kBlock - 1) / kBlock;
-  if (what == 0) hipLaunchKernelGGL((object_query_kernel<0>), dim3(blocks), dim3(kBlock), 0, 0, Q);
-  else if (what == 1) hipLaunchKernelGGL((object_query_kernel<1>), dim3(blocks), dim3(kBlock), 0, 0, Q);
-  else hipLaunchKernelGGL((object_query_kernel<2>), dim3(blocks), dim3(kBlock), 0, 0, Q);
+  with_flags([&](auto INTERCEPTS, auto NORMAL) {
+    constexpr ObjectQuery WHAT = INTERCEPTS ? ObjectQuery::Intercepts : (NORMAL ? ObjectQuery::Normal : ObjectQuery::SkyboxColour);
+    hipLaunchKernelGGL((object_query_kernel<(int)WHAT>), dim3(blocks), dim3(kBlock), 0, 0, Q);
+  }, intercepts, what == ObjectQuery::Normal);
   P3D_HIP(hipGetLastError());
   P3D_HIP(hipDeviceSynchronize());
   P3D_HIP(hipMemcpy(b, d_b, vec, hipMemcpyDeviceToHost));
-  if (what == 0) {
+  if (intercepts) {
     P3D_HIP(hipMemcpy(hit, d_hit, n, hipMemcpyDeviceToHost));
     P3D_HIP(hipMemcpy(t, d_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   }
   return P3D_OK;
 }
 int p3d_object_intercepts(p3d_scene* s, uint32_t object, uint32_t n, const float* origin, float* direction, uint8_t* hit, float* t) {
-  return object_query(s, 0, object, n, origin, direction, hit, t);
+  return object_query(s, ObjectQuery::Intercepts, object, n, origin, direction, hit, t);
 }
 int p3d_object_normal(p3d_scene* s, uint32_t object, uint32_t n, const float* point, float* normal) {
-  return object_query(s, 1, object, n, point, normal, nullptr, nullptr);
+  return object_query(s, ObjectQuery::Normal, object, n, point, normal, nullptr, nullptr);
 }
 int p3d_skybox_color(p3d_scene* s, uint32_t n, const float* direction, float* rgb) {
-  return object_query(s, 2, 0, n, direction, rgb, nullptr, nullptr);
+  return object_query(s, ObjectQuery::SkyboxColour, 0, n, direction, rgb, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@
 #include "capi_scene_layout.hpp"  // descriptor validation, BVH relabelling, blob assembly (host only)
 #include "capi_scene.hpp"         // scene create / destroy / skybox
 #include "capi_frame_plan.hpp"    // FramePlan: the decisions of one render call (host only)
-#include "capi_frame.hpp"         // dispatch, tile schedules, the enqueue steps, p3d_render_tile*
+#include "capi_dispatch.hpp"      // the kernel of every launch step: LiteralStep, the choosers, enqueue (host only)
+#include "capi_frame.hpp"         // tile schedules, the enqueue steps, p3d_render_tile*
 #include "capi_grid.hpp"          // the device-built uniform grid: build, rebuild, export
 #include "capi_update.hpp"        // camera and geometry updates, BVH export
 #include "capi_accum.hpp"         // p3d_accum
