@@ -1047,6 +1047,64 @@ int p3d_trace_any_device(p3d_scene* scene, uint32_t accel, uint32_t n,
                          const float* d_origin, const float* d_direction, const float* d_t_max /* may be NULL */,
                          uint8_t* d_occluded, void* hip_stream);
 /*
+ * The HITS IN ORDER along a ray, and the count of all of them: what lies behind the first surface - entry and exit, thickness,
+ * picking through a surface, and the sign of a point against a closed triangle mesh (the parity of the crossings).  The
+ * ray-side twin of p3d_nearest_k_device.  Detected by the symbol (P3D_ABI_VERSION is unchanged).
+ *
+ * For ray i let limit = +inf where d_t_max is NULL, else t_max[i]; a NaN limit, and a limit <= 0, keep nothing.
+ *   H(i) = the objects j for which Object::intercepts(object j, a fresh copy of ray i, t) is true and t < limit
+ * - the per-object predicate of the segment query of p3d_trace_any_device, exactly.  A NaN t is never in.  Every test runs on a
+ * copy of the caller's ray, so a sphere's normalisation reaches no other test; t is in the units the test reports (Q8), as in
+ * p3d_trace_closest_device.  H(i) is ordered by (t, object index): the smaller t first, equal t to the smaller index - a total
+ * order, so the answer is a function of the set and not of the order of the visits.
+ *   count[i] = min(|H(i)|, k)
+ *   row i*k + j, j < count[i] : the j-th element of H(i) - object: its index ; t: the t its test reported ; hit_point: o + d*t on
+ *       the copy of the ray its test ran on (a sphere has normalised d), spelt as the closest-hit query spells it: a lone
+ *       object reports the bits p3d_trace_closest_device reports for it ; normal: Object::getNormal at that point, NOT turned
+ *       against the ray - the bits of p3d_object_normal(object, hit_point)
+ *   row i*k + j, j >= count[i] : -1, FLT_MAX, zeros, zeros
+ *   total[i] = |H(i)|, the number of objects hit in front of the limit, whatever k is (only where d_total is not NULL)
+ * total counts OBJECTS, not crossings of a surface.  A sphere or a box reports ONE t, whether the ray starts inside or outside
+ * it: a ray through a sphere adds 1, not 2.  A closed triangle mesh is one object per triangle: there total is the number of
+ * crossings, and total & 1 says "the origin is inside" for a ray that grazes no edge or vertex (such a ray may count a
+ * crossing twice or not at all: send another direction).
+ * A smaller k gives a prefix of a larger one; count == k with d_total == NULL says that there may be more.
+ *
+ * k = 1 with d_t_max = NULL over P3D_ACCEL_NONE gives the minimum of the per-object tests under (t, index).  That is NOT in
+ * general p3d_trace_closest_device's answer: its traversals hand ONE ray from test to test, so that a sphere's normalisation
+ * reaches the tests after it (Q8), and break ties by the order of the visits.  Where no sphere re-normalises the ray (unit
+ * directions, or no spheres) and no two objects tie, the two agree.
+ *
+ * Buffers (addresses on the scene's device, 4-byte aligned; sizes are taken in 64 bits):
+ *   d_origin, d_direction : n*3 float32 (direction used as given) ; d_t_max : n float32, or NULL = no limit
+ *   d_count : n int32 ; d_total : n int32, or NULL ; d_object : n*k int32 ; d_t : n*k float32 ; d_hit_point, d_normal : n*k*3 float32
+ * 0 <= k <= P3D_TRACE_HITS_K_MAX.  k == 0 is the pure count: d_total is required, and d_count, d_object, d_t, d_hit_point and
+ * d_normal are ignored (they may be NULL) - no list is kept.  With k >= 1 d_count and d_object are required and d_t,
+ * d_hit_point and d_normal may be NULL.
+ *
+ *   P3D_ACCEL_NONE : a loop over all objects.
+ *   P3D_ACCEL_BVH  : the segment query's traversal, which does not stop at a hit.  While fewer than k hits are listed, and
+ *                    always when d_total is given, a child is skipped only if the ray misses its box or enters it behind the
+ *                    limit; with d_total == NULL and a full list, behind the k-th listed t.  So asking for total costs the
+ *                    whole segment, and a small k without it ends early.  Boxes are culled with the ray as given; for unit
+ *                    directions it answers as P3D_ACCEL_NONE does wherever no decision is a matter of the last bits.  Planes
+ *                    are lost by the BVH as everywhere (Q12), and not refused.
+ *   P3D_ACCEL_GRID : P3D_ERR_UNSUPPORTED.
+ *
+ * Stream, buffers, tail join and spill area as p3d_trace_closest_device: one kernel on `hip_stream`, no wait, no allocation
+ * once the spill area is large enough; behind p3d_scene_refit_device or p3d_scene_pose_device on the same stream it sees the
+ * moved geometry.  Refused as p3d_nearest_k_device, nothing enqueued and nothing written: P3D_ERR_INVALID for a null scene, an
+ * unknown accel or P3D_ACCEL_BVH on a scene without one, k > P3D_TRACE_HITS_K_MAX, with n > 0 a missing required pointer, a
+ * misaligned pointer, host memory, memory of another device or a buffer too short; P3D_ERR_CAPACITY where n x the tree's depth
+ * does not fit the spill area's 32-bit offsets.  n = 0 returns P3D_OK.
+ */
+#define P3D_TRACE_HITS_K_MAX 16u
+int p3d_trace_hits_device(p3d_scene* scene, uint32_t accel, uint32_t n, uint32_t k,
+                          const float* d_origin, const float* d_direction, const float* d_t_max /* may be NULL */,
+                          int32_t* d_count /* n */, int32_t* d_total /* n, may be NULL */,
+                          int32_t* d_object /* n*k */, float* d_t /* n*k */,
+                          float* d_hit_point /* n*k*3 */, float* d_normal /* n*k*3 */, void* hip_stream);
+/*
  * NEAREST-SURFACE queries: which object's surface is nearest to a point, how far away it is, and where on it - the contact
  * and proximity query of a particle or cloth step, and a distance field around a deforming mesh.  Detected by the symbols
  * (P3D_ABI_VERSION is unchanged).

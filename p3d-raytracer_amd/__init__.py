@@ -55,6 +55,7 @@ EXPORTS = [
     "p3d_scene_set_rig", "p3d_scene_rig", "p3d_scene_pose_device",
     "p3d_host_scene_nearest", "p3d_nearest_device",
     "p3d_host_scene_nearest_k", "p3d_nearest_k_device",
+    "p3d_trace_hits_device",
 ]
 
 
@@ -329,6 +330,8 @@ def lib():
                                                C.c_void_p]
         L.p3d_nearest_k_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p3d_trace_hits_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -550,6 +553,15 @@ NEAREST_K_MAX = 16  # P3D_NEAREST_K_MAX
 def _nearest_k_outputs(k):
     """name -> (dtype, columns) of p3d_nearest_k_device's outputs for this k: k rows per point"""
     return {"count": ("int32", None), "object": ("int32", k), "dist": ("float32", k), "closest": ("float32", (k, 3)), "normal": ("float32", (k, 3))}
+
+
+TRACE_HITS_K_MAX = 16  # P3D_TRACE_HITS_K_MAX
+
+
+def _trace_hits_outputs(k):
+    """name -> (dtype, columns) of p3d_trace_hits_device's outputs for this k: k rows per ray (k = 0: the count alone)"""
+    rows = {"count": ("int32", None), "object": ("int32", k), "t": ("float32", k), "hit_point": ("float32", (k, 3)), "normal": ("float32", (k, 3))}
+    return dict(rows if k else {}, total=("int32", None))
 
 
 class HostScene:
@@ -1265,6 +1277,35 @@ class DeviceScene:
         raw = getattr(stream, "cuda_stream", stream)
         _check(self._L.p3d_nearest_k_device(self._h, int(accel), n, k & 0xffffffff, C.c_void_p(d_p), C.c_void_p(d_m), ptr["count"],
                                             ptr["object"], ptr.get("dist"), ptr.get("closest"), ptr.get("normal"), C.c_void_p(raw or None)))
+        return {name: v[0] for name, v in res.items()}
+
+    def trace_hits_device(self, accel, origin, direction, k, t_max=None, want=("count", "object", "t"), stream=0, out=None):
+        """p3d_trace_hits_device: for n rays held in device memory the (at most) k objects hit in front of t_max, ordered by
+        (t, object index), and the number of all of them, enqueued on `stream` without a wait -> {name: tensor} for the names in
+        `want` ("count" (n,) and "object" (n, k), always there with k >= 1, "t" (n, k), "hit_point" and "normal" (n, k, 3), and
+        "total" (n,): every object hit, whatever k is); rows from count on hold -1, FLT_MAX and zeros, and count == k without
+        "total" says that there may be more.  0 <= k <= TRACE_HITS_K_MAX; k = 0 is the count alone: `want` must hold "total"
+        and nothing else comes back.  total counts objects, not crossings (a sphere or a box: one; a closed triangle mesh: one
+        per triangle crossed, so total & 1 is "the origin is inside").  ACCEL_NONE and ACCEL_BVH (the grid is refused); rays,
+        t_max, `out`, `stream` and the refusals as trace_closest_device."""
+        who = "trace_hits_device"
+        k = int(k)
+        table = _trace_hits_outputs(max(k, 0))
+        unknown = [w for w in want if w not in _trace_hits_outputs(1)]
+        if unknown:
+            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+        names = (["count", "object"] + [w for w in ("t", "hit_point", "normal") if w in want] if k != 0 else []) + [w for w in ("total",) if w in want]
+        d_o, d_d, d_tm, n = self._device_rays(who, origin, direction, t_max)
+        if k < 0 or (out is None and k > TRACE_HITS_K_MAX):  # (too large a k with the caller's outputs: the library says it)
+            raise P3DError(-1, "%s: k must be 0 .. %d, got %d" % (who, TRACE_HITS_K_MAX, k))
+        if not names:
+            raise P3DError(-1, "%s: k = 0 is the count alone: want must hold 'total'" % who)
+        res = self._device_outputs(who, names, n, out, origin, table)
+        ptr = {name: C.c_void_p(v[1]) for name, v in res.items()}
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(self._L.p3d_trace_hits_device(self._h, int(accel), n, k & 0xffffffff, C.c_void_p(d_o), C.c_void_p(d_d), C.c_void_p(d_tm),
+                                             ptr.get("count"), ptr.get("total"), ptr.get("object"), ptr.get("t"), ptr.get("hit_point"),
+                                             ptr.get("normal"), C.c_void_p(raw or None)))
         return {name: v[0] for name, v in res.items()}
 
 

@@ -1,8 +1,9 @@
-// capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_nearest_device, p3d_nearest_k_device,
-// p3d_object_*, p3d_skybox_color)
+// capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
+// p3d_nearest_k_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_update.hpp"  // device_buffer_usable
+#include "hit_list_query.hpp"
 #include "nearest_query.hpp"
 #include "ray_query.hpp"
 
@@ -112,6 +113,46 @@ int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_
   return P3D_OK;
 }
 
+// p3d_trace_hits_device: nearest_device's refusals, stack binding and tail wait, and one launch on the caller's stream.  k == 0
+// is the pure count: d_total is required and the row outputs are not looked at
+int trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_origin, const float* d_direction, const float* d_t_max,
+                      int32_t* d_count, int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point, float* d_normal, void* hip_stream) {
+  const std::string pre = "p3d_trace_hits_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no hit list through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (k > P3D_TRACE_HITS_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_TRACE_HITS_K_MAX (16)");
+  if (n == 0) return P3D_OK;
+  if (k == 0) d_count = d_object = nullptr, d_t = d_hit_point = d_normal = nullptr;
+  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (k == 0 && !d_total) return fail(P3D_ERR_INVALID, pre + "null argument (k = 0 is the count alone: d_total is needed)");
+  if (k > 0 && (!d_count || !d_object)) return fail(P3D_ERR_INVALID, pre + "null argument (d_count and d_object are needed with k >= 1)");
+  if (((uintptr_t)d_origin | (uintptr_t)d_direction | (uintptr_t)d_t_max | (uintptr_t)d_count | (uintptr_t)d_total | (uintptr_t)d_object |
+       (uintptr_t)d_t | (uintptr_t)d_hit_point | (uintptr_t)d_normal) & 3u)
+    return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
+  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
+  const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
+      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"}, {d_count, one, "d_count"},
+      {d_total, one, "d_total"}, {d_object, one * k, "d_object"}, {d_t, one * k, "d_t"}, {d_hit_point, vec * k, "d_hit_point"},
+      {d_normal, vec * k, "d_normal"}};
+  for (const auto& b : bufs)
+    if (b.p)
+      if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
+  QueryLaunch q;
+  if (int rc = bind_query_stack(s, accel, n, pre, "rays", q)) return rc;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
+  TraceHitsParams P{};
+  P.sc = s->dev; P.n = n; P.k = k; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
+  P.count = d_count; P.total = d_total; P.object = d_object; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.stack = q.stack;
+  const size_t lds = q.lds + nearest_k_lds_bytes(k);  // the lists of this call's k behind the stack window; none for k = 0
+  if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((trace_hits_kernel<P3D_ACCEL_BVH>), dim3(q.blocks), dim3(kBlock), lds, st, P);
+  else hipLaunchKernelGGL((trace_hits_kernel<P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), lds, st, P);
+  P3D_HIP(hipGetLastError());
+  return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -169,6 +210,12 @@ int p3d_trace_closest_device(p3d_scene* s, uint32_t accel, uint32_t n, const flo
 int p3d_trace_any_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
                          uint8_t* d_occluded, void* hip_stream) {
   return trace_device(s, accel, n, d_origin, d_direction, d_t_max, nullptr, nullptr, nullptr, nullptr, d_occluded, hip_stream, true);
+}
+
+int p3d_trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_origin, const float* d_direction,
+                          const float* d_t_max, int32_t* d_count, int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point,
+                          float* d_normal, void* hip_stream) {
+  return trace_hits_device(s, accel, n, k, d_origin, d_direction, d_t_max, d_count, d_total, d_object, d_t, d_hit_point, d_normal, hip_stream);
 }
 
 int p3d_nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist, int32_t* d_object,
