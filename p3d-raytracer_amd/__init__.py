@@ -1172,12 +1172,12 @@ class DeviceScene:
             raise P3DError(-1, "%s: %d origins, %d directions%s" % (who, n, n_d, "" if t_max is None else ", %d limits" % n_tm))
         return d_o, d_d, d_tm, n
 
-    def _device_outputs(self, who, names, n, out, like, table=_TRACE_OUTPUTS, rows_of="rays"):
+    def _device_outputs(self, who, names, n, out, like, table, rows_of):
         """name -> (tensor or None, address) for the outputs `names`: taken from the dict `out` (tensors or raw (address, rows)
         pairs, checked like the inputs), or allocated on the scene's device when `out` is None"""
         res = {}
         for name in names:
-            dtype, cols = table.get(name, ("uint8", None))
+            dtype, cols = table[name]
             if out is None:
                 import torch
                 dev = like.device if hasattr(like, "device") else torch.device("cuda", self.device)
@@ -1199,6 +1199,32 @@ class DeviceScene:
             res[name] = (tensor, ptr)
         return res
 
+    def _device_points(self, who, points, max_dist):
+        """(address of points, of max_dist or None, n) of the points of a device query, or P3DError"""
+        d_p, n = _device_rows(points, who + ": points", 3, ("float32",), self.device)
+        d_m, n_m = _device_vector(max_dist, who + ": max_dist", ("float32",), self.device) if max_dist is not None else (None, n)
+        if n_m != n:
+            raise P3DError(-1, "%s: %d points, %d limits" % (who, n, n_m))
+        return d_p, d_m, n
+
+    def _device_query(self, who, accel, inputs, table, names, want, order, stream, out, like, rows_of="rays", k=None, known=None, refusal=None):
+        """What the *_device queries share.  In this order: a name in `want` that `known` (default: `table`) does not hold is
+        refused; inputs() gives the input addresses and, last, n; `refusal`, the caller's own (about k), is raised if there is
+        one; the outputs `names` are resolved against `table`; and L.p3d_<who> is called with (scene, accel, n, [k,] inputs,
+        the outputs in the C order `order` - null where not in names -, stream) -> {name: tensor}"""
+        unknown = [w for w in want if w not in (table if known is None else known)]
+        if unknown:
+            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+        *addresses, n = inputs()
+        if refusal:
+            raise P3DError(-1, "%s: %s" % (who, refusal))
+        res = self._device_outputs(who, names, n, out, like, table, rows_of)
+        args = ([] if k is None else [k & 0xffffffff]) + [C.c_void_p(a) for a in addresses]
+        args += [C.c_void_p(res[name][1]) if name in res else None for name in order]
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(getattr(self._L, "p3d_" + who)(self._h, int(accel), n, *args, C.c_void_p(raw or None)))
+        return {name: v[0] for name, v in res.items()}
+
     def trace_closest_device(self, accel, origin, direction, t_max=None, want=("hit_id", "t"), stream=0, out=None):
         """p3d_trace_closest_device: the closest hits of n rays held in device memory, enqueued on `stream` (a torch.cuda.Stream
         or a raw hipStream_t; 0 = the default stream) without a wait -> {name: tensor} for the names in `want` ("hit_id", always
@@ -1208,28 +1234,16 @@ class DeviceScene:
         counts that differ raise P3DError before the library is called.  Read the results once the stream has passed the call."""
         who = "trace_closest_device"
         names = ["hit_id"] + [w for w in ("t", "hit_point", "normal") if w in want]
-        unknown = [w for w in want if w not in _TRACE_OUTPUTS]
-        if unknown:
-            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
-        d_o, d_d, d_tm, n = self._device_rays(who, origin, direction, t_max)
-        res = self._device_outputs(who, names, n, out, origin)
-        ptr = {k: C.c_void_p(v[1]) for k, v in res.items()}
-        raw = getattr(stream, "cuda_stream", stream)
-        _check(self._L.p3d_trace_closest_device(self._h, int(accel), n, C.c_void_p(d_o), C.c_void_p(d_d), C.c_void_p(d_tm), ptr["hit_id"],
-                                                ptr.get("t"), ptr.get("hit_point"), ptr.get("normal"), C.c_void_p(raw or None)))
-        return {k: v[0] for k, v in res.items()}
+        return self._device_query(who, accel, lambda: self._device_rays(who, origin, direction, t_max), _TRACE_OUTPUTS, names, want,
+                                  ("hit_id", "t", "hit_point", "normal"), stream, out, origin)
 
     def trace_any_device(self, accel, origin, direction, t_max=None, stream=0, out=None):
         """p3d_trace_any_device -> {"occluded": uint8 (n,) tensor}.  Without t_max the reference's shadow feeler (trace_any: no
         distance limit); with t_max (float32 (n,)) the segment query: 1 iff some object is hit at t < t_max, for ACCEL_NONE and
         ACCEL_BVH (the grid is refused).  Arguments and stream as trace_closest_device."""
         who = "trace_any_device"
-        d_o, d_d, d_tm, n = self._device_rays(who, origin, direction, t_max)
-        res = self._device_outputs(who, ["occluded"], n, out, origin)
-        raw = getattr(stream, "cuda_stream", stream)
-        _check(self._L.p3d_trace_any_device(self._h, int(accel), n, C.c_void_p(d_o), C.c_void_p(d_d), C.c_void_p(d_tm),
-                                            C.c_void_p(res["occluded"][1]), C.c_void_p(raw or None)))
-        return {k: v[0] for k, v in res.items()}
+        return self._device_query(who, accel, lambda: self._device_rays(who, origin, direction, t_max), {"occluded": ("uint8", None)},
+                                  ["occluded"], (), ("occluded",), stream, out, origin)
 
     def nearest_device(self, accel, points, max_dist=None, want=("object", "dist"), stream=0, out=None):
         """p3d_nearest_device: for n points held in device memory the object whose surface is nearest, enqueued on `stream`
@@ -1239,19 +1253,8 @@ class DeviceScene:
         HostScene.nearest's, bit for bit.  `out`, `stream` and the refusals as trace_closest_device."""
         who = "nearest_device"
         names = ["object"] + [w for w in ("dist", "closest", "normal") if w in want]
-        unknown = [w for w in want if w not in _NEAREST_OUTPUTS]
-        if unknown:
-            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
-        d_p, n = _device_rows(points, who + ": points", 3, ("float32",), self.device)
-        d_m, n_m = _device_vector(max_dist, who + ": max_dist", ("float32",), self.device) if max_dist is not None else (None, n)
-        if n_m != n:
-            raise P3DError(-1, "%s: %d points, %d limits" % (who, n, n_m))
-        res = self._device_outputs(who, names, n, out, points, _NEAREST_OUTPUTS, "points")
-        ptr = {k: C.c_void_p(v[1]) for k, v in res.items()}
-        raw = getattr(stream, "cuda_stream", stream)
-        _check(self._L.p3d_nearest_device(self._h, int(accel), n, C.c_void_p(d_p), C.c_void_p(d_m), ptr["object"], ptr.get("dist"),
-                                          ptr.get("closest"), ptr.get("normal"), C.c_void_p(raw or None)))
-        return {k: v[0] for k, v in res.items()}
+        return self._device_query(who, accel, lambda: self._device_points(who, points, max_dist), _NEAREST_OUTPUTS, names, want,
+                                  ("object", "dist", "closest", "normal"), stream, out, points, "points")
 
     def nearest_k_device(self, accel, points, k, max_dist=None, want=("count", "object", "dist"), stream=0, out=None):
         """p3d_nearest_k_device: for n points held in device memory the (at most) k objects whose surfaces are nearest, nearer
@@ -1261,23 +1264,12 @@ class DeviceScene:
         max_dist, `out`, `stream` and the refusals as nearest_device; the answers are HostScene.nearest_k's, bit for bit."""
         who = "nearest_k_device"
         k = int(k)
-        table = _nearest_k_outputs(max(k, 0))
         names = ["count", "object"] + [w for w in ("dist", "closest", "normal") if w in want]
-        unknown = [w for w in want if w not in table]
-        if unknown:
-            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
-        d_p, n = _device_rows(points, who + ": points", 3, ("float32",), self.device)
-        d_m, n_m = _device_vector(max_dist, who + ": max_dist", ("float32",), self.device) if max_dist is not None else (None, n)
-        if n_m != n:
-            raise P3DError(-1, "%s: %d points, %d limits" % (who, n, n_m))
+        refusal = None
         if out is None and not 1 <= k <= NEAREST_K_MAX:  # (with the caller's outputs the library says it)
-            raise P3DError(-1, "%s: k must be 1 .. %d, got %d" % (who, NEAREST_K_MAX, k))
-        res = self._device_outputs(who, names, n, out, points, table, "points")
-        ptr = {name: C.c_void_p(v[1]) for name, v in res.items()}
-        raw = getattr(stream, "cuda_stream", stream)
-        _check(self._L.p3d_nearest_k_device(self._h, int(accel), n, k & 0xffffffff, C.c_void_p(d_p), C.c_void_p(d_m), ptr["count"],
-                                            ptr["object"], ptr.get("dist"), ptr.get("closest"), ptr.get("normal"), C.c_void_p(raw or None)))
-        return {name: v[0] for name, v in res.items()}
+            refusal = "k must be 1 .. %d, got %d" % (NEAREST_K_MAX, k)
+        return self._device_query(who, accel, lambda: self._device_points(who, points, max_dist), _nearest_k_outputs(max(k, 0)), names, want,
+                                  ("count", "object", "dist", "closest", "normal"), stream, out, points, "points", k=k, refusal=refusal)
 
     def trace_hits_device(self, accel, origin, direction, k, t_max=None, want=("count", "object", "t"), stream=0, out=None):
         """p3d_trace_hits_device: for n rays held in device memory the (at most) k objects hit in front of t_max, ordered by
@@ -1290,23 +1282,15 @@ class DeviceScene:
         t_max, `out`, `stream` and the refusals as trace_closest_device."""
         who = "trace_hits_device"
         k = int(k)
-        table = _trace_hits_outputs(max(k, 0))
-        unknown = [w for w in want if w not in _trace_hits_outputs(1)]
-        if unknown:
-            raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
         names = (["count", "object"] + [w for w in ("t", "hit_point", "normal") if w in want] if k != 0 else []) + [w for w in ("total",) if w in want]
-        d_o, d_d, d_tm, n = self._device_rays(who, origin, direction, t_max)
+        refusal = None
         if k < 0 or (out is None and k > TRACE_HITS_K_MAX):  # (too large a k with the caller's outputs: the library says it)
-            raise P3DError(-1, "%s: k must be 0 .. %d, got %d" % (who, TRACE_HITS_K_MAX, k))
-        if not names:
-            raise P3DError(-1, "%s: k = 0 is the count alone: want must hold 'total'" % who)
-        res = self._device_outputs(who, names, n, out, origin, table)
-        ptr = {name: C.c_void_p(v[1]) for name, v in res.items()}
-        raw = getattr(stream, "cuda_stream", stream)
-        _check(self._L.p3d_trace_hits_device(self._h, int(accel), n, k & 0xffffffff, C.c_void_p(d_o), C.c_void_p(d_d), C.c_void_p(d_tm),
-                                             ptr.get("count"), ptr.get("total"), ptr.get("object"), ptr.get("t"), ptr.get("hit_point"),
-                                             ptr.get("normal"), C.c_void_p(raw or None)))
-        return {name: v[0] for name, v in res.items()}
+            refusal = "k must be 0 .. %d, got %d" % (TRACE_HITS_K_MAX, k)
+        elif not names:
+            refusal = "k = 0 is the count alone: want must hold 'total'"
+        return self._device_query(who, accel, lambda: self._device_rays(who, origin, direction, t_max), _trace_hits_outputs(max(k, 0)), names, want,
+                                  ("count", "total", "object", "t", "hit_point", "normal"), stream, out, origin, k=k, known=_trace_hits_outputs(1),
+                                  refusal=refusal)
 
 
 class Accumulator:

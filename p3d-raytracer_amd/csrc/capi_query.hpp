@@ -13,7 +13,7 @@ namespace {
 struct QueryLaunch {
   QueryStack stack;  // for the kernel's parameters
   uint32_t blocks;
-  size_t lds;        // bytes of the stack's LDS window
+  size_t lds;        // bytes of dynamic LDS: the stack's window and what enqueue_query puts behind it
 };
 
 // The stack of one query launch: a 16-entry LDS window (a power of two) and, for a tree deeper than that, its worst case in
@@ -40,8 +40,37 @@ void launch_ray_query(uint32_t accel, bool any, const QueryLaunch& q, hipStream_
   });
 }
 
-// p3d_trace_closest_device / p3d_trace_any_device: the refusals, the spill scratch and one launch on the caller's stream.
-// No wait anywhere but in a hipFree of a spill area that has to grow.
+// One buffer argument of a device-buffer query: null = not given
+struct QueryBuffer {
+  const void* p;
+  size_t bytes;
+  const char* name;
+  bool aligned4 = true;  // floats or int32s
+};
+
+// What the device-buffer queries do once their own refusals have passed: the refusals of the buffers in `bufs`, the stack
+// (`what` names the batch's elements), and one launch on the caller's stream; launch(q, st) enqueues the kernel, q.lds being
+// the stack window and `list_lds` bytes behind it.  No wait anywhere but in a hipFree of a spill area that has to grow.
+template <size_t N, class Launch>
+int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& pre, const char* what, const QueryBuffer (&bufs)[N],
+                  size_t list_lds, void* hip_stream, Launch&& launch) {
+  for (const auto& b : bufs)
+    if (b.aligned4 && ((uintptr_t)b.p & 3u)) return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
+  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
+  for (const auto& b : bufs)
+    if (b.p)
+      if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
+  QueryLaunch q;
+  if (int rc = bind_query_stack(s, accel, n, pre, what, q)) return rc;
+  q.lds += list_lds;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
+  launch(q, st);
+  P3D_HIP(hipGetLastError());
+  return P3D_OK;
+}
+
+// p3d_trace_closest_device / p3d_trace_any_device
 int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
                  int32_t* d_hit_id, float* d_t, float* d_hit_point, float* d_normal, uint8_t* d_occluded, void* hip_stream, bool any) {
   const std::string pre = any ? "p3d_trace_any_device: " : "p3d_trace_closest_device: ";
@@ -52,31 +81,20 @@ int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin
     return fail(P3D_ERR_UNSUPPORTED, pre + "no segment query through the grid (P3D_ACCEL_NONE gives the answer the grid's feeler would: it runs the brute-force loop as well)");
   if (n == 0) return P3D_OK;
   if (!d_origin || !d_direction || (any ? !d_occluded : !d_hit_id)) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (((uintptr_t)d_origin | (uintptr_t)d_direction | (uintptr_t)d_t_max | (uintptr_t)d_hit_id | (uintptr_t)d_t | (uintptr_t)d_hit_point |
-       (uintptr_t)d_normal) & 3u)
-    return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
-  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
   const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
-  const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
+  const QueryBuffer bufs[] = {
       {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"}, {d_hit_id, one, "d_hit_id"},
-      {d_t, one, "d_t"}, {d_hit_point, vec, "d_hit_point"}, {d_normal, vec, "d_normal"}, {d_occluded, (size_t)n, "d_occluded"}};
-  for (const auto& b : bufs)
-    if (b.p)
-      if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
-  QueryLaunch q;
-  if (int rc = bind_query_stack(s, accel, n, pre, "rays", q)) return rc;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
-  RayQueryParams P{};
-  P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
-  P.hit_id = d_hit_id; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.occluded = d_occluded; P.stack = q.stack;
-  launch_ray_query<true>(accel, any, q, st, P);
-  P3D_HIP(hipGetLastError());
-  return P3D_OK;
+      {d_t, one, "d_t"}, {d_hit_point, vec, "d_hit_point"}, {d_normal, vec, "d_normal"}, {d_occluded, (size_t)n, "d_occluded", false}};
+  return enqueue_query(s, accel, n, pre, "rays", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    RayQueryParams P{};
+    P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
+    P.hit_id = d_hit_id; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.occluded = d_occluded; P.stack = q.stack;
+    launch_ray_query<true>(accel, any, q, st, P);
+  });
 }
 
-// p3d_nearest_device (k_form false: k = 1, no d_count) and p3d_nearest_k_device: trace_device's refusals, stack binding and
-// tail wait, and one launch on the caller's stream.  One set of checks for both; the outputs hold k rows per point
+// p3d_nearest_device (k_form false: k = 1, no d_count) and p3d_nearest_k_device.  One set of checks for both; the outputs hold
+// k rows per point
 int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_form, const float* d_point, const float* d_max_dist,
                    int32_t* d_count, int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
   const std::string pre = k_form ? "p3d_nearest_k_device: " : "p3d_nearest_device: ";
@@ -88,69 +106,19 @@ int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_
   if (k == 0 || k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
   if (n == 0) return P3D_OK;
   if (!d_point || !d_object || (k_form && !d_count)) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (((uintptr_t)d_point | (uintptr_t)d_max_dist | (uintptr_t)d_count | (uintptr_t)d_object | (uintptr_t)d_dist | (uintptr_t)d_closest |
-       (uintptr_t)d_normal) & 3u)
-    return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
-  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
   const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
-  const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
+  const QueryBuffer bufs[] = {
       {d_point, vec, "d_point"}, {d_max_dist, one, "d_max_dist"}, {d_count, one, "d_count"}, {d_object, one * k, "d_object"},
       {d_dist, one * k, "d_dist"}, {d_closest, vec * k, "d_closest"}, {d_normal, vec * k, "d_normal"}};
-  for (const auto& b : bufs)
-    if (b.p)
-      if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
-  QueryLaunch q;
-  if (int rc = bind_query_stack(s, accel, n, pre, "points", q)) return rc;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
-  NearestKParams P{};
-  P.sc = s->dev; P.n = n; P.k = k; P.point = d_point; P.max_dist = d_max_dist;
-  P.count = d_count; P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal; P.stack = q.stack;
-  const size_t lds = q.lds + nearest_k_lds_bytes(k);  // the lists of this call's k behind the stack window
-  if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_BVH>), dim3(q.blocks), dim3(kBlock), lds, st, P);
-  else hipLaunchKernelGGL((nearest_k_device_kernel<P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), lds, st, P);
-  P3D_HIP(hipGetLastError());
-  return P3D_OK;
-}
-
-// p3d_trace_hits_device: nearest_device's refusals, stack binding and tail wait, and one launch on the caller's stream.  k == 0
-// is the pure count: d_total is required and the row outputs are not looked at
-int trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_origin, const float* d_direction, const float* d_t_max,
-                      int32_t* d_count, int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point, float* d_normal, void* hip_stream) {
-  const std::string pre = "p3d_trace_hits_device: ";
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no hit list through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
-  if (int rc = check_accel(s, accel)) return rc;
-  if (k > P3D_TRACE_HITS_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_TRACE_HITS_K_MAX (16)");
-  if (n == 0) return P3D_OK;
-  if (k == 0) d_count = d_object = nullptr, d_t = d_hit_point = d_normal = nullptr;
-  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (k == 0 && !d_total) return fail(P3D_ERR_INVALID, pre + "null argument (k = 0 is the count alone: d_total is needed)");
-  if (k > 0 && (!d_count || !d_object)) return fail(P3D_ERR_INVALID, pre + "null argument (d_count and d_object are needed with k >= 1)");
-  if (((uintptr_t)d_origin | (uintptr_t)d_direction | (uintptr_t)d_t_max | (uintptr_t)d_count | (uintptr_t)d_total | (uintptr_t)d_object |
-       (uintptr_t)d_t | (uintptr_t)d_hit_point | (uintptr_t)d_normal) & 3u)
-    return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
-  P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
-  const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
-      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"}, {d_count, one, "d_count"},
-      {d_total, one, "d_total"}, {d_object, one * k, "d_object"}, {d_t, one * k, "d_t"}, {d_hit_point, vec * k, "d_hit_point"},
-      {d_normal, vec * k, "d_normal"}};
-  for (const auto& b : bufs)
-    if (b.p)
-      if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
-  QueryLaunch q;
-  if (int rc = bind_query_stack(s, accel, n, pre, "rays", q)) return rc;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
-  TraceHitsParams P{};
-  P.sc = s->dev; P.n = n; P.k = k; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
-  P.count = d_count; P.total = d_total; P.object = d_object; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.stack = q.stack;
-  const size_t lds = q.lds + nearest_k_lds_bytes(k);  // the lists of this call's k behind the stack window; none for k = 0
-  if (accel == P3D_ACCEL_BVH) hipLaunchKernelGGL((trace_hits_kernel<P3D_ACCEL_BVH>), dim3(q.blocks), dim3(kBlock), lds, st, P);
-  else hipLaunchKernelGGL((trace_hits_kernel<P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), lds, st, P);
-  P3D_HIP(hipGetLastError());
-  return P3D_OK;
+  // (the lists of this call's k behind the stack window)
+  return enqueue_query(s, accel, n, pre, "points", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    NearestKParams P{};
+    P.sc = s->dev; P.n = n; P.k = k; P.point = d_point; P.max_dist = d_max_dist;
+    P.count = d_count; P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal; P.stack = q.stack;
+    with_flags([&](auto BVH) {
+      hipLaunchKernelGGL((nearest_k_device_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+    }, accel == P3D_ACCEL_BVH);
+  });
 }
 
 }  // namespace
@@ -212,10 +180,34 @@ int p3d_trace_any_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* 
   return trace_device(s, accel, n, d_origin, d_direction, d_t_max, nullptr, nullptr, nullptr, nullptr, d_occluded, hip_stream, true);
 }
 
+// k == 0 is the pure count: d_total is required and the row outputs are not looked at
 int p3d_trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_origin, const float* d_direction,
                           const float* d_t_max, int32_t* d_count, int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point,
                           float* d_normal, void* hip_stream) {
-  return trace_hits_device(s, accel, n, k, d_origin, d_direction, d_t_max, d_count, d_total, d_object, d_t, d_hit_point, d_normal, hip_stream);
+  const std::string pre = "p3d_trace_hits_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no hit list through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (k > P3D_TRACE_HITS_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_TRACE_HITS_K_MAX (16)");
+  if (n == 0) return P3D_OK;
+  if (k == 0) d_count = d_object = nullptr, d_t = d_hit_point = d_normal = nullptr;
+  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (k == 0 && !d_total) return fail(P3D_ERR_INVALID, pre + "null argument (k = 0 is the count alone: d_total is needed)");
+  if (k > 0 && (!d_count || !d_object)) return fail(P3D_ERR_INVALID, pre + "null argument (d_count and d_object are needed with k >= 1)");
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
+  const QueryBuffer bufs[] = {
+      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"}, {d_count, one, "d_count"},
+      {d_total, one, "d_total"}, {d_object, one * k, "d_object"}, {d_t, one * k, "d_t"}, {d_hit_point, vec * k, "d_hit_point"},
+      {d_normal, vec * k, "d_normal"}};
+  // (the lists of this call's k behind the stack window; none for k = 0)
+  return enqueue_query(s, accel, n, pre, "rays", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    TraceHitsParams P{};
+    P.sc = s->dev; P.n = n; P.k = k; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
+    P.count = d_count; P.total = d_total; P.object = d_object; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.stack = q.stack;
+    with_flags([&](auto BVH) {
+      hipLaunchKernelGGL((trace_hits_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+    }, accel == P3D_ACCEL_BVH);
+  });
 }
 
 int p3d_nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist, int32_t* d_object,

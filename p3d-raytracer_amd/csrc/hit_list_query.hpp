@@ -1,10 +1,10 @@
 // hit_list_query.hpp — the hits along a ray in order, over device buffers (p3d_trace_hits_device): one kernel,
-// trace_hits_kernel, and one traversal, bvh_segment_hits.  For every ray the (at most) k objects with the smallest
+// trace_hits_kernel, and one policy of the culled walk, bvh_segment_hits.  For every ray the (at most) k objects with the smallest
 // (t, object) among those its segment hits, in that order, and the number of all of them: the ray-side twin of
 // nearest_k_device_kernel.  The per-object predicate is ray_query.hpp's segment test (a fresh copy of the ray per test), the
 // candidate list, its admission and its LDS storage are the nearest-k query's (host/nearest_rule.hpp NearestKGate and
 // nearest_k_insert, nearest_query.hpp LdsNearestList) with t in the place of d2: `d2` is the name of the list's KEY there.
-// Of device_core.hpp the node and geometry records, the slab test, the stack and its push / pop are used.
+// Of device_core.hpp the node and geometry records and the slab test are used.
 #pragma once
 
 #include "nearest_query.hpp"  // LdsNearestList, nearest_k_lds_bytes
@@ -54,66 +54,31 @@ __device__ void brute_segment_hits(const DevScene& sc, const RayS& ray, HitListS
   for (uint32_t i = 0; i < sc.n_objs; ++i) hit_list_offer(load_geom(sc.ogeom, i), i, ray, s, ct);
 }
 
-// P3D_ACCEL_BVH: bvh_segment_any's traversal - its records, slab test, push / pop and wave-vote stepping - that never stops at
-// a hit.  What differs:
+// P3D_ACCEL_BVH: bvh_culled_walk (queries.hpp) with bvh_segment_any's key of a box, never stopped by a hit.  What differs:
 //   - a leaf offers each of its objects to the list; (t, object) is a total order and every object sits in one leaf, so the
 //     order of the visits does not show in the answer;
-//   - a child is skipped if the ray misses its box or its slab interval begins behind s.bound() (a positive test: a NaN t0
-//     or bound culls nothing).  The bound only shrinks when total is not wanted and the list is full;
-//   - the float of a stack entry is the child's t0, and a popped entry meets the cull again: the bound may have shrunk since
-//     the push;
-//   - the nearer child (by the slab test's t, as everywhere) goes first.
-// A lane pushes at most one entry per step down, so the stack is never deeper than the tree: the bound the host sizes the
-// spill area with.  The stack is empty on entry and on exit.
-// The steps are taken by wave vote as in bvh_segment_any; UNMEASURED for this traversal, the nested-loop form is the
-// alternative.
+//   - the cull is taken against s.bound(), not a constant.  The bound only shrinks when total is not wanted and the list is full;
+//   - so the float of a stack entry is the child's t0, and a popped entry meets the cull again.
+template <class CT>
+struct SegmentHitsWalk {
+  const RayS& ray;
+  HitListSearch& s;
+  bool fin;  // slab_fast_path of the ray
+  CT& ct;
+  __device__ __forceinline__ bool key(const NodeRec& n, float& order, float& stacked) const {
+    return segment_box(n, ray, fin, s.bound(), order, stacked);
+  }
+  __device__ __forceinline__ bool culled(float t0) const { return t0 > s.bound(); }
+  __device__ __forceinline__ bool left_first(float l_t, float r_t) const { return l_t < r_t; }
+  __device__ __forceinline__ bool leaf(const DevScene& sc, uint32_t first, uint32_t end) {
+    for (uint32_t g = first; g < end; ++g) hit_list_offer(load_geom(sc.bgeom, g), g, ray, s, ct);
+    return false;
+  }
+};
 template <class CT>
 __device__ void bvh_segment_hits(const DevScene& sc, Stack& st, const RayS& ray, HitListSearch& s, CT& ct) {
-  constexpr int SPILL = kStackWindow;
-  // (the ray never changes here - the tests run on copies - so one answer holds for the whole traversal)
-  const bool fin = slab_fast_path<true>(sc, ray);
-  float tmp, t0;
-  const NodeRec root = load_node(sc.nodes, 0);
-  ct.add(kNodeTests);
-  if (!aabb_intercepts(xyz(root.lo), xyz(root.hi), ray, tmp, fin, &t0) || t0 > s.bound()) return;
-  uint32_t desc = __float_as_uint(root.lo.w);  // a descriptor, or kDescDone
-  auto next_entry = [&]() {
-    desc = kDescDone;
-    bool more = st.sp > 0;
-    while (more) {
-      const uint2 e = pop<SPILL>(st);
-      const bool take = !(__uint_as_float(e.y) > s.bound());
-      if (take) desc = e.x;
-      more = !take && st.sp > 0;
-    }
-  };
-  while (true) {
-    const bool on_inner = !(desc & kDescLeaf), on_leaf = !on_inner && desc != kDescDone;
-    const unsigned long long m_inner = __ballot(on_inner), m_leaf = __ballot(on_leaf);
-    if ((m_inner | m_leaf) == 0) break;
-    const bool descend = m_leaf == 0 || __popcll(m_inner) * P3D_VOTE_DEN >= __popcll(m_leaf) * P3D_VOTE_NUM;  // wave-uniform
-    if (descend && on_inner) {
-      const uint32_t index = desc_index(desc);
-      const NodeRec l = load_node(sc.nodes, index), r = load_node(sc.nodes, index + 1);
-      float l_t, r_t, l_t0, r_t0;
-      ct.add(kNodeTests, 2);
-      const float bound = s.bound();
-      const bool l_hit = aabb_intercepts(xyz(l.lo), xyz(l.hi), ray, l_t, fin, &l_t0) && !(l_t0 > bound);
-      const bool r_hit = aabb_intercepts(xyz(r.lo), xyz(r.hi), ray, r_t, fin, &r_t0) && !(r_t0 > bound);
-      const uint32_t ld = __float_as_uint(l.lo.w), rd = __float_as_uint(r.lo.w);
-      if (l_hit && r_hit) {
-        if (l_t < r_t) { desc = ld; push<SPILL>(st, rd, r_t0, ct); }
-        else           { desc = rd; push<SPILL>(st, ld, l_t0, ct); }
-      } else if (l_hit) { desc = ld; }
-      else if (r_hit)   { desc = rd; }
-      else next_entry();
-    }
-    if (!descend && on_leaf) {
-      const uint32_t first = desc_index(desc), end = first + desc_count(desc);
-      for (uint32_t g = first; g < end; ++g) hit_list_offer(load_geom(sc.bgeom, g), g, ray, s, ct);
-      next_entry();
-    }
-  }
+  SegmentHitsWalk<CT> walk{ray, s, slab_fast_path<true>(sc, ray), ct};
+  bvh_culled_walk(sc, st, walk, ct);
 }
 
 struct TraceHitsParams {
@@ -144,7 +109,7 @@ __global__ void __launch_bounds__(kBlock) trace_hits_kernel(const TraceHitsParam
   Stack st;
   query_stack_bind(st, smem, P.stack, i);
   HitListSearch s;
-  s.list.base = (lds_u32*)(reinterpret_cast<uint32_t*>(smem + stack_lds_f4(kStackWindow, (uint32_t)P.stack.stack_cap))) + threadIdx.x;
+  s.list.base = query_list_base(smem, P.stack);
   s.k = P.k; s.want_total = P.total != nullptr;
   if (i >= P.n) return;
   Counters<false> ct;
@@ -178,12 +143,8 @@ __global__ void __launch_bounds__(kBlock) trace_hits_kernel(const TraceHitsParam
     }
     P.object[row] = object;
     if (P.t) P.t[row] = t;
-    if (P.hit_point) {
-      P.hit_point[3 * row] = hp.x; P.hit_point[3 * row + 1] = hp.y; P.hit_point[3 * row + 2] = hp.z;
-    }
-    if (P.normal) {
-      P.normal[3 * row] = nrm.x; P.normal[3 * row + 1] = nrm.y; P.normal[3 * row + 2] = nrm.z;
-    }
+    if (P.hit_point) store_f3(P.hit_point, row, hp);
+    if (P.normal) store_f3(P.normal, row, nrm);
   }
 }
 

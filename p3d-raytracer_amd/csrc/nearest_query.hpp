@@ -1,14 +1,14 @@
 // nearest_query.hpp — nearest-surface queries over device buffers (p3d_nearest_device, p3d_nearest_k_device): one kernel,
-// nearest_k_device_kernel, and one traversal, bvh_nearest_k.  For every point the (at most) k objects with the smallest
+// nearest_k_device_kernel, and one policy of the culled walk, bvh_nearest_k.  For every point the (at most) k objects with the smallest
 // (d2, object) under the limit, in that order, how far each is and where on it; p3d_nearest_device is k = 1 without a count.
 // The arithmetic, the candidate list, its admission and the bound a node is culled against are host/nearest_rule.hpp's,
 // shared with p3d_host_scene_nearest and p3d_host_scene_nearest_k, whose bits the kernel must give.  Not a ray traversal:
 // children are ordered by the distance of their boxes from the point, and the search radius shrinks as candidates are found.
-// Of device_core.hpp the node and geometry records, the stack and its push / pop are used.
+// Of device_core.hpp the node and geometry records are used.
 #pragma once
 
 #include "nearest_rule.hpp"
-#include "queries.hpp"  // QueryStack
+#include "queries.hpp"  // QueryStack, bvh_culled_walk, store_f3, query_list_base
 
 namespace p3d {
 
@@ -61,62 +61,33 @@ __device__ void brute_nearest_k(const DevScene& sc, const float p[3], NearestKSe
   for (uint32_t i = 0; i < sc.n_objs; ++i) nearest_k_offer(load_geom(sc.ogeom, i), i, p, s);
 }
 
-// P3D_ACCEL_BVH: a stack traversal over sc.nodes / sc.bgeom.  The float of a stack entry is the child's box d2.
-//   - an inner node fetches both children (64 contiguous bytes), visits the nearer one first and pushes the farther one if
-//     the cull lets it live;
-//   - a popped entry meets the cull again: the radius has shrunk since it was pushed;
-//   - a leaf offers each of its objects to the list; (d2, object) is a total order and every object sits in one leaf, so the
-//     order of the visits does not show in the list;
+// P3D_ACCEL_BVH: bvh_culled_walk (queries.hpp), not a ray traversal: a box is keyed, ordered and stacked by its d2 from the
+// point, the nearer child first (the left one on a tie).
 //   - the cull is nearest_culls, a positive test with slack: a NaN box drops nothing (odd_boxes scenes stay correct).  It is
 //     taken against s.gate.d2: the squared radius while the list is not full, the k-th entry's d2 once it is.  Until k
 //     candidates are in, nothing inside the radius is dropped, so a search is wider than a k = 1 search by what it takes to
-//     fill the list.
-// A lane pushes at most one entry per step down, so the stack is never deeper than the tree: the bound the host sizes the
-// spill area with.  The stack is empty on entry and on exit.
-// The steps are taken by wave vote as in bvh_segment_any, not as nested loops: neighbouring lanes hold unrelated points here
-// (no pixel coherence), so descents differ in length from lane to lane and the nested form would let the longest hold up every
-// lane that stands on a leaf; these scenes are traversed from global memory, where bvh_closest measured the vote ahead.
-// UNMEASURED for this traversal; the nested-loop form is the alternative.
-__device__ void bvh_nearest_k(const DevScene& sc, Stack& st, const float p[3], NearestKSearch& s) {
-  constexpr int SPILL = kStackWindow;
-  Counters<false> ct;
-  const NodeRec root = load_node(sc.nodes, 0);
-  if (nearest_culls(nearest_node_d2(root, p), s.gate.d2)) return;
-  uint32_t desc = __float_as_uint(root.lo.w);  // a descriptor, or kDescDone
-  auto next_entry = [&]() {
-    desc = kDescDone;
-    bool more = st.sp > 0;
-    while (more) {
-      const uint2 e = pop<SPILL>(st);
-      const bool take = !nearest_culls(__uint_as_float(e.y), s.gate.d2);
-      if (take) desc = e.x;
-      more = !take && st.sp > 0;
-    }
-  };
-  while (true) {
-    const bool on_inner = !(desc & kDescLeaf), on_leaf = !on_inner && desc != kDescDone;
-    const unsigned long long m_inner = __ballot(on_inner), m_leaf = __ballot(on_leaf);
-    if ((m_inner | m_leaf) == 0) break;
-    const bool descend = m_leaf == 0 || __popcll(m_inner) * P3D_VOTE_DEN >= __popcll(m_leaf) * P3D_VOTE_NUM;  // wave-uniform
-    if (descend && on_inner) {
-      const uint32_t index = desc_index(desc);
-      const NodeRec l = load_node(sc.nodes, index), r = load_node(sc.nodes, index + 1);
-      const float l_d2 = nearest_node_d2(l, p), r_d2 = nearest_node_d2(r, p);
-      const bool l_in = !nearest_culls(l_d2, s.gate.d2), r_in = !nearest_culls(r_d2, s.gate.d2);
-      const uint32_t ld = __float_as_uint(l.lo.w), rd = __float_as_uint(r.lo.w);
-      if (l_in && r_in) {
-        if (r_d2 < l_d2) { desc = rd; push<SPILL>(st, ld, l_d2, ct); }
-        else             { desc = ld; push<SPILL>(st, rd, r_d2, ct); }
-      } else if (l_in) { desc = ld; }
-      else if (r_in)   { desc = rd; }
-      else next_entry();
-    }
-    if (!descend && on_leaf) {
-      const uint32_t first = desc_index(desc), end = first + desc_count(desc);
-      for (uint32_t g = first; g < end; ++g) nearest_k_offer(load_geom(sc.bgeom, g), g, p, s);
-      next_entry();
-    }
+//     fill the list;
+//   - a popped entry meets the cull again: the radius has shrunk since it was pushed;
+//   - a leaf offers each of its objects to the list; (d2, object) is a total order and every object sits in one leaf, so the
+//     order of the visits does not show in the list.
+struct NearestKWalk {
+  const float* p;
+  NearestKSearch& s;
+  __device__ __forceinline__ bool key(const NodeRec& n, float& order, float& stacked) const {
+    order = stacked = nearest_node_d2(n, p);
+    return !nearest_culls(order, s.gate.d2);
   }
+  __device__ __forceinline__ bool culled(float d2) const { return nearest_culls(d2, s.gate.d2); }
+  __device__ __forceinline__ bool left_first(float l_d2, float r_d2) const { return !(r_d2 < l_d2); }
+  __device__ __forceinline__ bool leaf(const DevScene& sc, uint32_t first, uint32_t end) {
+    for (uint32_t g = first; g < end; ++g) nearest_k_offer(load_geom(sc.bgeom, g), g, p, s);
+    return false;
+  }
+};
+__device__ void bvh_nearest_k(const DevScene& sc, Stack& st, const float p[3], NearestKSearch& s) {
+  Counters<false> ct;
+  NearestKWalk walk{p, s};
+  bvh_culled_walk(sc, st, walk, ct);
 }
 
 struct NearestKParams {
@@ -150,7 +121,7 @@ __global__ void __launch_bounds__(kBlock) nearest_k_device_kernel(const NearestK
   Stack st;
   query_stack_bind(st, smem, P.stack, i);
   NearestKSearch s;
-  s.list.base = (lds_u32*)(reinterpret_cast<uint32_t*>(smem + stack_lds_f4(kStackWindow, (uint32_t)P.stack.stack_cap))) + threadIdx.x;
+  s.list.base = query_list_base(smem, P.stack);
   s.count = 0; s.k = P.k;
   if (i >= P.n) return;
   const float p[3] = {P.point[3 * i], P.point[3 * i + 1], P.point[3 * i + 2]};
@@ -179,12 +150,8 @@ __global__ void __launch_bounds__(kBlock) nearest_k_device_kernel(const NearestK
     }
     P.object[row] = object;
     if (P.dist) P.dist[row] = dist;
-    if (P.closest) {
-      P.closest[3 * row] = q.x; P.closest[3 * row + 1] = q.y; P.closest[3 * row + 2] = q.z;
-    }
-    if (P.normal) {
-      P.normal[3 * row] = nrm.x; P.normal[3 * row + 1] = nrm.y; P.normal[3 * row + 2] = nrm.z;
-    }
+    if (P.closest) store_f3(P.closest, row, q);
+    if (P.normal) store_f3(P.normal, row, nrm);
   }
 }
 

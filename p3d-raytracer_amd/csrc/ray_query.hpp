@@ -1,10 +1,10 @@
 // ray_query.hpp — the batched ray queries, from host arrays (p3d_trace_closest, p3d_trace_any) and over device buffers
 // (p3d_trace_closest_device, p3d_trace_any_device): ray_query_kernel, one body for both, and bvh_segment_any, the any-hit
 // with a distance limit.  The unlimited paths call device_core.hpp's closest_hit / any_hit (bvh.cpp:198-340,
-// grid.cpp:71-208, main.cpp:116-124,208-216), the segment query has a traversal of its own.
+// grid.cpp:71-208, main.cpp:116-124,208-216), the segment query is a policy of the culled walk.
 #pragma once
 
-#include "queries.hpp"  // QueryStack
+#include "queries.hpp"  // QueryStack, bvh_culled_walk, store_f3
 
 namespace p3d {
 
@@ -29,64 +29,48 @@ __device__ bool brute_segment_any(const DevScene& sc, const RayS& ray, float t_m
   return false;
 }
 
-// P3D_ACCEL_BVH: a stack traversal over sc.nodes / sc.bgeom with the records, the slab test and the stack of device_core.hpp.
-// What differs from bvh_any, the reference's feeler:
-//   - a child whose box the ray misses, or whose slab interval begins behind t_max, is not visited (t0 of aabb_intercepts, the
-//     ray as given, as bvh_closest prunes with it; a negative or NaN t0 culls nothing: never less conservative than the
-//     closest-hit traversal);
-//   - a primitive counts only with t < t_max;
+// The key of a box for a segment traversal: alive if the ray meets it and its slab interval does not begin behind `bound`
+// (t0 of aabb_intercepts, the ray as given, as bvh_closest prunes with it; a negative or NaN t0 or bound culls nothing: never
+// less conservative than the closest-hit traversal).  t orders the siblings, the nearer first, as everywhere
+__device__ __forceinline__ bool segment_box(const NodeRec& n, const RayS& ray, bool fin, float bound, float& t, float& t0) {
+  return aabb_intercepts(xyz(n.lo), xyz(n.hi), ray, t, fin, &t0) && !(t0 > bound);
+}
+
+// P3D_ACCEL_BVH: bvh_culled_walk (queries.hpp) with the records, the slab test and the stack of device_core.hpp.  What differs
+// from bvh_any, the reference's feeler:
+//   - a child whose box the ray misses, or whose slab interval begins behind t_max, is not visited (segment_box);
+//   - a primitive counts only with t < t_max, and the first one that does ends the lane;
 //   - a dead end pops the next entry: no restart from the bottom-most entry (Q1), so nothing the ray can reach is skipped.
-// The nearer child is visited first.  The stack is the caller's, empty on entry; a hit leaves its entries behind, which
-// nobody reads: the query kernel is the only caller and ends there.
-// The steps are taken by wave vote as in bvh_closest (VOTE): these scenes are traversed from global memory.  That choice
-// is UNMEASURED for this traversal; the nested-loop form is the alternative.
+//     t_max never moves, so a popped entry is not tested again; the float that travels with it is the child's t.
+template <class CT>
+struct SegmentAnyWalk {
+  const RayS& ray;
+  float t_max;
+  bool fin;  // slab_fast_path of the ray
+  CT& ct;
+  __device__ __forceinline__ bool key(const NodeRec& n, float& order, float& stacked) const {
+    float t0;
+    const bool alive = segment_box(n, ray, fin, t_max, order, t0);
+    stacked = order;
+    return alive;
+  }
+  __device__ __forceinline__ bool culled(float) const { return false; }
+  __device__ __forceinline__ bool left_first(float l_t, float r_t) const { return l_t < r_t; }
+  __device__ __forceinline__ bool leaf(const DevScene& sc, uint32_t s, uint32_t end) {
+    bool occluded = false, more = s < end;
+    while (more) {
+      const Geom g = load_geom(sc.bgeom, s);
+      occluded = segment_test(g, ray, t_max, ct);
+      ++s;
+      more = !occluded && s < end;
+    }
+    return occluded;
+  }
+};
 template <class CT>
 __device__ bool bvh_segment_any(const DevScene& sc, Stack& st, const RayS& ray, float t_max, CT& ct) {
-  constexpr int SPILL = kStackWindow;
-  // (the ray never changes here - the tests run on copies - so one answer holds for the whole traversal; lanes only leave)
-  const bool fin = slab_fast_path<true>(sc, ray);
-  float tmp, t0;
-  const NodeRec root = load_node(sc.nodes, 0);
-  ct.add(kNodeTests);
-  if (!aabb_intercepts(xyz(root.lo), xyz(root.hi), ray, tmp, fin, &t0) || t0 > t_max) return false;
-  // state word as in bvh_any: a descriptor, kDescDone or kDescHit
-  uint32_t desc = __float_as_uint(root.lo.w);
-  auto next_entry = [&]() { desc = st.sp > 0 ? pop<SPILL>(st).x : kDescDone; };
-  while (true) {
-    const bool on_inner = !(desc & kDescLeaf), on_leaf = !on_inner && desc < kDescHit;
-    const unsigned long long m_inner = __ballot(on_inner), m_leaf = __ballot(on_leaf);
-    if ((m_inner | m_leaf) == 0) break;
-    const bool descend = m_leaf == 0 || __popcll(m_inner) * P3D_VOTE_DEN >= __popcll(m_leaf) * P3D_VOTE_NUM;  // wave-uniform
-    if (descend && on_inner) {
-      const uint32_t index = desc_index(desc);
-      const NodeRec l = load_node(sc.nodes, index), r = load_node(sc.nodes, index + 1);
-      float l_t, r_t, l_t0, r_t0;
-      ct.add(kNodeTests, 2);
-      const bool l_hit = aabb_intercepts(xyz(l.lo), xyz(l.hi), ray, l_t, fin, &l_t0) && !(l_t0 > t_max);
-      const bool r_hit = aabb_intercepts(xyz(r.lo), xyz(r.hi), ray, r_t, fin, &r_t0) && !(r_t0 > t_max);
-      const uint32_t ld = __float_as_uint(l.lo.w), rd = __float_as_uint(r.lo.w);
-      if (l_hit && r_hit) {
-        if (l_t < r_t) { desc = ld; push<SPILL>(st, rd, r_t, ct); }
-        else           { desc = rd; push<SPILL>(st, ld, l_t, ct); }
-      } else if (l_hit) { desc = ld; }
-      else if (r_hit)   { desc = rd; }
-      else next_entry();
-    }
-    if (!descend && on_leaf) {
-      uint32_t s = desc_index(desc);
-      const uint32_t end = s + desc_count(desc);
-      bool occluded = false, more = s < end;
-      while (more) {
-        const Geom g = load_geom(sc.bgeom, s);
-        occluded = segment_test(g, ray, t_max, ct);
-        ++s;
-        more = !occluded && s < end;
-      }
-      if (occluded) desc = kDescHit;
-      else next_entry();
-    }
-  }
-  return desc == kDescHit;
+  SegmentAnyWalk<CT> walk{ray, t_max, slab_fast_path<true>(sc, ray), ct};
+  return bvh_culled_walk(sc, st, walk, ct);
 }
 
 struct RayQueryParams {
@@ -139,13 +123,8 @@ __global__ void __launch_bounds__(kBlock) ray_query_kernel(const RayQueryParams 
     P.hit_id[i] = obj;
     if (P.t) P.t[i] = obj < 0 ? FLT_MAX : t;
     if (obj < 0) hp = f3(0, 0, 0);
-    if (P.hit_point) {
-      P.hit_point[3 * i] = hp.x; P.hit_point[3 * i + 1] = hp.y; P.hit_point[3 * i + 2] = hp.z;
-    }
-    if (EXTRAS && P.normal) {
-      const F3 nrm = obj < 0 ? f3(0, 0, 0) : get_normal(g, P.sc.normals, hp);
-      P.normal[3 * i] = nrm.x; P.normal[3 * i + 1] = nrm.y; P.normal[3 * i + 2] = nrm.z;
-    }
+    if (P.hit_point) store_f3(P.hit_point, i, hp);
+    if (EXTRAS && P.normal) store_f3(P.normal, i, obj < 0 ? f3(0, 0, 0) : get_normal(g, P.sc.normals, hp));
   }
 }
 

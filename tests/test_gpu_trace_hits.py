@@ -236,6 +236,34 @@ def test_through_a_deep_device_tree(mesh):
     assert dev.status() == 0
 
 
+# ---- the two segment traversals against each other ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["mixed", "mesh"])
+def test_some_hit_is_a_total_above_zero(name, worlds, mesh):
+    """occluded of the segment any-hit = (total of the hit list > 0), on EVERY ray: both run the same per-object test on fresh
+    copies of the ray, and with total wanted the hit list culls with the same box test against the same limit, so it reaches
+    every leaf the any-hit reaches before it stops.  Always with a t_max tensor: without one the any-hit is the feeler"""
+    w = mesh if name == "mesh" else worlds[name]
+    dev = w.devs["device"]
+    first = dev.trace_closest_device(p3d.ACCEL_NONE, w.d_o[:N_MESH], w.d_d[:N_MESH], want=("t",))["t"].cpu().numpy()
+    with np.errstate(over="ignore"):  # (a miss: FLT_MAX, twice that: inf)
+        scaled = {by: np.where(first > 0, first * np.float32(by), INF).astype(np.float32) for by in (0.5, 2)}
+    sets = {"inf": np.full(N_MESH, INF, np.float32), "half the first hit": scaled[0.5], "twice the first hit": scaled[2]}
+    assert all(((t_max > 0) & ~np.isnan(t_max)).all() for t_max in sets.values())
+    for what, t_max in sets.items():
+        for accel in (p3d.ACCEL_NONE, p3d.ACCEL_BVH):
+            for n in (1, 65, N_MESH):
+                d_t = gpu(t_max[:n])
+                occluded = dev.trace_any_device(accel, w.d_o[:n], w.d_d[:n], t_max=d_t)["occluded"].cpu().numpy()
+                total = ask(dev, accel, w.d_o[:n], w.d_d[:n], 0, d_t, want=("total",))["total"]
+                differ = (occluded != 0) != (total > 0)
+                assert not differ.any(), "%s, accel %d, %d rays, limits %s: %d rays differ, first at ray %d" % (
+                    name, accel, n, what, int(differ.sum()), int(np.argmax(differ)))
+                if n == N_MESH and what != "half the first hit":
+                    assert occluded.any() and not occluded.all(), "%s, limits %s: the rays all hit or all miss" % (name, what)
+    assert dev.status() == 0
+
+
 # ---- hit_point and normal ---------------------------------------------------------------------------------------------------------
 
 def test_hit_points_and_normals(worlds):
