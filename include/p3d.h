@@ -786,8 +786,10 @@ int p3d_accum_render_device(p3d_accum* acc, uint32_t n, float* d_rgb, int32_t* d
  * Exactness: a pixel that stopped after k samples holds exactly the bits a plain p3d_accum holds for it after k samples
  * (same RNG streams, same additions in sample order, same epilogue); a pixel that never stops holds the one-shot frame's.
  *
- * Decision, at the end of a pass only: a pixel becomes inactive for good when samples_p >= min_samples and
- * rel_err_p < rel_error (strict: rel_error = 0 never stops a pixel).
+ * Decision, at the end of a pass only: a pixel becomes inactive for good when samples_p >= min_samples, the denominator
+ * m + 1.0e-3f of rel_err_p is positive (rel_err_p has a clear sign bit) and rel_err_p < rel_error (strict: rel_error = 0
+ * never stops a pixel).  The reference's radiance can be negative behind glass: a pixel whose mean luminance m is -1.0e-3f
+ * or less has no relative error to speak of (rel_err_p is negative, -0, inf or NaN) and goes on taking samples.
  * Error metric, float32 on the device in this order, without contraction:
  *   per sample radiance L added to the sum:  y = 0.2126f*L.x + 0.7152f*L.y + 0.0722f*L.z;  S2 += y*y  (sample order)
  *   n = (float)samples_p;  Y = 0.2126f*S.x + 0.7152f*S.y + 0.0722f*S.z;  m = Y / n;
@@ -805,7 +807,7 @@ int p3d_accum_render_device(p3d_accum* acc, uint32_t n, float* d_rgb, int32_t* d
  * 3 float; S2; samples_p; rel_err of the pixel's last pass) wait for the device.  Any output pointer may be NULL.
  */
 typedef struct p3d_adaptive_params {
-  float rel_error;       /* a pixel stops once its rel_err is < rel_error; 0 = no pixel ever stops */
+  float rel_error;       /* a pixel stops once its rel_err is < rel_error (see "Decision"); 0 = no pixel ever stops */
   uint32_t min_samples;  /* no pixel stops before this many samples; 2 <= min_samples <= SPP*SPP */
   uint32_t reserved[2];  /* must be 0 */
 } p3d_adaptive_params;

@@ -11,6 +11,7 @@ The directory name has a hyphen, so import it through the root-level shim:
     dev = p3d.DeviceScene(hs, bvh=True)
     rgb, hit, stats = dev.render(p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4))
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -165,6 +166,17 @@ class TemporalParams(C.Structure):
                 ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class DebugPlan(C.Structure):
+    """p3d_debug_plan (csrc/p3d_debug.h): what the kernel choosers read of the plan of one launch"""
+    _fields_ = [(k, C.c_uint32) for k in ("pt", "literal", "lds_scene", "lds_spill", "sub4", "per_level", "repair_tiles", "stack_mode",
+                                          "spill_entries", "bound", "cap", "zero_weight_reflections")]
+
+
+FramePlan = collections.namedtuple("FramePlan", [k for k, _ in DebugPlan._fields_])
+PLAN_MODES = {"frame": 0, "adaptive": 1, "features": 2}
+STACK_LDS6, STACK_WINDOW, STACK_LDS8 = 0, 1, 2  # FramePlan.stack_mode (csrc/device_core.hpp "Stack")
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_bounce", "rays_light",
@@ -250,6 +262,8 @@ def lib():
         L.p3d_scene_set_tail_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.p3d_scene_join.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.p3d_debug_scene_limits.argtypes = [C.c_void_p, C.c_void_p]  # csrc/p3d_debug.h: not part of include/p3d.h
+        L.p3d_debug_frame_plan.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Tile), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DebugPlan)]
+        L.p3d_debug_frame_plan_size.restype = C.c_uint32
         L.p3d_accum_create.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Tile), C.POINTER(C.c_void_p)]
         L.p3d_accum_destroy.argtypes = [C.c_void_p]
         L.p3d_accum_destroy.restype = None
@@ -1094,6 +1108,19 @@ class DeviceScene:
         self._L.p3d_debug_staged_f4.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         _check(self._L.p3d_debug_staged_f4(self._h, C.byref(cfg), C.byref(tile or self.full_tile()), C.byref(n)))
         return n.value
+
+    def frame_plan(self, cfg, tile=None, samples=None, mode="frame"):
+        """csrc/p3d_debug.h, read-only: the plan of one launch as the kernel choosers read it -> FramePlan (flags as bool).
+        samples: None = the whole frame (features: what render_features(cfg) takes, min(16, SPP*SPP)), n = samples [0, n),
+        (begin, end) = that range (a pass of an accumulator).  mode: "frame", "adaptive" (one pass) or "features"."""
+        total = cfg.spp_sqrt * cfg.spp_sqrt if cfg.antialiasing else 1
+        if samples is None:
+            samples = min(16, total) if mode == "features" else total
+        begin, end = samples if isinstance(samples, tuple) else (0, samples)
+        out = DebugPlan()
+        _check(self._L.p3d_debug_frame_plan(self._h, C.byref(cfg), C.byref(tile or self.full_tile()), begin, end, PLAN_MODES[mode], C.byref(out)))
+        ints = ("stack_mode", "spill_entries", "bound", "cap")
+        return FramePlan(**{k: getattr(out, k) if k in ints else bool(getattr(out, k)) for k, _ in DebugPlan._fields_})
 
     def render_features(self, cfg, samples=0, tile=None):
         """p3d_render_features: the feature buffers of the primary rays of samples [0, K) (0: min(16, SPP*SPP)) ->

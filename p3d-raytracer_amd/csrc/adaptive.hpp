@@ -69,7 +69,9 @@ __global__ void __launch_bounds__(kAdaptResolveThreads) adapt_resolve_kernel(con
       R.samples[p] = sp;
       const float e = adapt_rel_err(S, R.sum_y2[p], sp);
       R.rel_err[p] = e;
-      keep = !(sp >= R.min_samples && e < R.rel_error);
+      // (a mean luminance of -1e-3 or less - the reference's radiance can be negative behind glass - makes e negative, -0, inf
+      // or NaN: no estimate of a relative error, the pixel goes on; e of a positive denominator has a clear sign bit)
+      keep = !(sp >= R.min_samples && !(__float_as_uint(e) >> 31) && e < R.rel_error);
       if (!keep) R.active[p] = 0;  // for good
     }
     // the epilogue of pt_kernel for a frame of sp samples: the bits a plain accumulator has after sp samples

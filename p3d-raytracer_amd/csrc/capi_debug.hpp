@@ -25,6 +25,24 @@ int p3d_debug_staged_f4(p3d_scene* s, const p3d_config* cfg, const p3d_tile* til
   return P3D_OK;
 }
 
+// What the choosers of capi_dispatch.hpp read of the plan of one launch (read-only like p3d_debug_staged_f4)
+int p3d_debug_frame_plan(p3d_scene* s, const p3d_config* cfg, const p3d_tile* tile, uint32_t sample_begin, uint32_t sample_end, uint32_t mode,
+                         p3d_debug_plan* out) {
+  if (!s || !cfg || !tile || !out) return fail(P3D_ERR_INVALID, "p3d_debug_frame_plan: null argument");
+  if (mode > P3D_DEBUG_PLAN_FEATURES) return fail(P3D_ERR_INVALID, "p3d_debug_frame_plan: unknown mode " + std::to_string(mode));
+  if (int rc = check_frame(s, cfg, tile)) return rc;
+  const uint32_t total = cfg->antialiasing ? cfg->spp_sqrt * cfg->spp_sqrt : 1u;
+  if (sample_begin >= sample_end || sample_end > total)
+    return fail(P3D_ERR_INVALID, "p3d_debug_frame_plan: samples [" + std::to_string(sample_begin) + ", " + std::to_string(sample_end) + ") of a frame of " + std::to_string(total));
+  FramePlan plan{};
+  const FrameMode fm = mode == P3D_DEBUG_PLAN_ADAPTIVE ? kAdaptivePass : (mode == P3D_DEBUG_PLAN_FEATURES ? kFeatures : kFrame);
+  if (int rc = plan_frame(scene_facts(s), cfg, tile, sample_begin, sample_end, fm, 1, plan)) return rc;
+  *out = p3d_debug_plan{plan.pt, plan.literal, plan.lds_scene, plan.lds_spill, plan.sub4, plan.per_level, plan.repair_tiles, (uint32_t)plan.stack_mode,
+                        plan.spill_entries, plan.bound, plan.cap, s->zero_weight_reflections};
+  return P3D_OK;
+}
+uint32_t p3d_debug_frame_plan_size(void) { return (uint32_t)sizeof(p3d_debug_plan); }
+
 #ifdef P3D_PT_PROFILE
 int p3d_debug_set_pt_prof(void* device_ptr) {
   unsigned long long* p = static_cast<unsigned long long*>(device_ptr);

@@ -145,7 +145,7 @@ def test_decision_rule():
         # the next pass's active pixels are the ones with samples == done; the rule says who those are
         active_next = log[i + 1][3] if i + 1 < len(log) else None
         rendered = samples == done
-        should_stop = (samples >= min_samples) & (ref < np.float32(thr))
+        should_stop = (samples >= min_samples) & ~np.signbit(ref) & (ref < np.float32(thr))  # include/p3d.h "Decision"
         near = ulp_diff(ref, np.full_like(ref, thr)) <= 2
         still = rendered & ~should_stop
         if active_next is not None:

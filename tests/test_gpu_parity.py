@@ -89,7 +89,8 @@ def _render_with_tail_stream(dev, cfg):
 def check_whitted(dev, sc, cfg, tol=2e-6, counters=COUNTERS, max_stack=False):
     """cfg as given: for the BVH under P3D_STACK_LITERAL the frame must be bit-identical to the oracle's serial
     order and every ray / test counter equal to the oracle's.  Then (BVH) the per-pixel stack, or (other back ends) the one render there is: frame within `tol` of the
-    oracle in the same semantics and every counter equal.  Returns the first render's (rgb, hit, stats)."""
+    oracle in the same semantics and every counter equal, and the frame of the kernels without counters (collect_stats = 0)
+    within the same `tol` of the same oracle frame.  Returns the first render's (rgb, hit, stats)."""
     cfg.collect_stats = 1
     first = dev.render(cfg)
     if literal_applies(cfg):
@@ -110,10 +111,15 @@ def check_whitted(dev, sc, cfg, tol=2e-6, counters=COUNTERS, max_stack=False):
     else:
         rgb, hit, st = first
     o_rgb, o_hit, o_st = sc.render(oracle_cfg_like(cfg))
-    assert (hit == o_hit).all(), "hit IDs differ in %d pixels" % int((hit != o_hit).sum())
+    # ... and the instantiation without counters - the one a caller who asks for no stats runs - against the same oracle frame
+    plain_cfg = p3d.Config.from_buffer_copy(bytes(cfg))
+    plain_cfg.collect_stats = 0
     m = np.isfinite(o_rgb).all(-1)
-    assert (np.isfinite(rgb).all(-1) == m).all()  # NaN pixels (if any) are NaN on both sides
-    assert np.abs(rgb[m] - o_rgb[m]).max() <= tol
+    for what, (f_rgb, f_hit) in (("with counters", (rgb, hit)), ("kernels without counters", dev.render(plain_cfg)[:2])):
+        assert (f_hit == o_hit).all(), "%s: hit IDs differ in %d pixels" % (what, int((f_hit != o_hit).sum()))
+        assert (np.isfinite(f_rgb).all(-1) == m).all(), what  # NaN pixels (if any) are NaN on both sides
+        err = np.abs(f_rgb[m] - o_rgb[m])
+        assert err.max() <= tol, "%s: max |diff| %g, %d pixels over %g" % (what, err.max(), int((err.max(-1) > tol).sum()), tol)
     for k in counters:
         assert getattr(st, k) == getattr(o_st, k), k
     if max_stack:
