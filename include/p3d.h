@@ -1107,6 +1107,12 @@ int p3d_trace_hits_device(p3d_scene* scene, uint32_t accel, uint32_t n, uint32_t
                           int32_t* d_object /* n*k */, float* d_t /* n*k */,
                           float* d_hit_point /* n*k*3 */, float* d_normal /* n*k*3 */, void* hip_stream);
 /*
+ * WHAT A RAY SEES - the Whitted radiance along rays held in device memory, p3d_trace_radiance_device, and the primary rays of
+ * a camera, p3d_camera_rays_device - is declared in p3d_radiance.h, which this header includes: the entry points added after
+ * the list of this file was closed.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ */
+#include "p3d_radiance.h"
+/*
  * NEAREST-SURFACE queries: which object's surface is nearest to a point, how far away it is, and where on it - the contact
  * and proximity query of a particle or cloth step, and a distance field around a deforming mesh.  Detected by the symbols
  * (P3D_ABI_VERSION is unchanged).

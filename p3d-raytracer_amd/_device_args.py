@@ -64,3 +64,9 @@ def _trace_hits_outputs(k):
     """name -> (dtype, columns) of p3d_trace_hits_device's outputs for this k: k rows per ray (k = 0: the count alone)"""
     rows = {"count": ("int32", None), "object": ("int32", k), "t": ("float32", k), "hit_point": ("float32", (k, 3)), "normal": ("float32", (k, 3))}
     return dict(rows if k else {}, total=("int32", None))
+
+
+RADIANCE_MAX_DEPTH = 16  # P3D_RADIANCE_MAX_DEPTH
+RADIANCE_SKYBOX = 1      # P3D_RADIANCE_SKYBOX
+_RADIANCE_OUTPUTS = {"rgb": ("float32", 3), "hit_id": ("int32", None)}
+_CAMERA_RAYS_OUTPUTS = {"origin": ("float32", 3), "direction": ("float32", 3)}

@@ -1,10 +1,12 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
-// p3d_nearest_k_device, p3d_object_*, p3d_skybox_color)
+// p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
+#include "capi_frame_plan.hpp"  // stack_bound
 #include "capi_update.hpp"  // device_buffer_usable
 #include "hit_list_query.hpp"
 #include "nearest_query.hpp"
+#include "radiance_query.hpp"
 #include "ray_query.hpp"
 
 namespace {
@@ -18,9 +20,12 @@ struct QueryLaunch {
 
 // The stack of one query launch: a 16-entry LDS window (a power of two) and, for a tree deeper than that, its worst case in
 // the scene's spill area, which grows here if it has to (the one place a query may wait: in the hipFree of the old area).
-// Refuses a batch whose spill entries 32-bit offsets cannot address (device_core.hpp Stack); `what` names its elements
-int bind_query_stack(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& pre, const char* what, QueryLaunch& out) {
-  const uint32_t bound = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
+// Refuses a batch whose spill entries 32-bit offsets cannot address (device_core.hpp Stack); `what` names its elements.
+// chain: the lane runs a Whitted chain on its stack, whose feelers leave entries behind (Q2): the frames' worst case
+// (capi_frame_plan.hpp stack_bound), not the depth of one traversal
+int bind_query_stack(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& pre, const char* what, QueryLaunch& out, bool chain = false) {
+  const uint32_t one = accel == P3D_ACCEL_BVH ? std::max<uint32_t>(1, s->bvh_max_depth) : 1;
+  const uint32_t bound = chain ? std::max(one, stack_bound(scene_facts(s), accel, true)) : one;
   const uint32_t cap = 16;
   out.blocks = (n + kBlock - 1) / kBlock;
   const uint64_t spill_entries = (uint64_t)(bound > cap ? bound : 0) * out.blocks * kBlock;
@@ -50,10 +55,11 @@ struct QueryBuffer {
 
 // What the device-buffer queries do once their own refusals have passed: the refusals of the buffers in `bufs`, the stack
 // (`what` names the batch's elements), and one launch on the caller's stream; launch(q, st) enqueues the kernel, q.lds being
-// the stack window and `list_lds` bytes behind it.  No wait anywhere but in a hipFree of a spill area that has to grow.
+// the stack window and `list_lds` bytes behind it; `chain`: see bind_query_stack.  No wait anywhere but in a hipFree of a spill
+// area that has to grow.
 template <size_t N, class Launch>
 int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& pre, const char* what, const QueryBuffer (&bufs)[N],
-                  size_t list_lds, void* hip_stream, Launch&& launch) {
+                  size_t list_lds, void* hip_stream, Launch&& launch, bool chain = false) {
   for (const auto& b : bufs)
     if (b.aligned4 && ((uintptr_t)b.p & 3u)) return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
   P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
@@ -61,7 +67,7 @@ int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& p
     if (b.p)
       if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
   QueryLaunch q;
-  if (int rc = bind_query_stack(s, accel, n, pre, what, q)) return rc;
+  if (int rc = bind_query_stack(s, accel, n, pre, what, q, chain)) return rc;
   q.lds += list_lds;
   hipStream_t st = (hipStream_t)hip_stream;
   if (int rc = wait_for_tail(s, st)) return rc;  // the spill area is in use until the previous frame's tail has run (p3d_scene_set_tail_stream)
@@ -124,6 +130,68 @@ int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_
 }  // namespace
 
 extern "C" {
+
+int p3d_trace_radiance_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, int32_t max_depth,
+                              uint32_t flags, float* d_rgb, int32_t* d_hit_id, void* hip_stream) {
+  const std::string pre = "p3d_trace_radiance_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (accel == P3D_ACCEL_GRID && s->dev.n_objs == 0) return fail(P3D_ERR_UNSUPPORTED, "grid over an empty scene");
+  if (max_depth < 0 || max_depth > (int32_t)P3D_RADIANCE_MAX_DEPTH) return fail(P3D_ERR_INVALID, pre + "max_depth must be 0 .. P3D_RADIANCE_MAX_DEPTH (16)");
+  if (flags & ~P3D_RADIANCE_SKYBOX) return fail(P3D_ERR_INVALID, pre + "unknown flag");
+  if ((flags & P3D_RADIANCE_SKYBOX) && !s->has_sky)
+    return fail(P3D_ERR_INVALID, pre + "P3D_RADIANCE_SKYBOX but no cubemap was supplied (p3d_scene_set_skybox)");
+  if (n == 0) return P3D_OK;
+  if (!d_origin || !d_direction || !d_rgb) return fail(P3D_ERR_INVALID, pre + "null argument");
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const QueryBuffer bufs[] = {{d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_rgb, vec, "d_rgb"}, {d_hit_id, one, "d_hit_id"}};
+  // (the level records of this call's depth behind the stack window; the stack of a chain)
+  return enqueue_query(s, accel, n, pre, "rays", bufs, radiance_lds_bytes((uint32_t)max_depth), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    RadianceQueryParams P{};
+    P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.max_depth = max_depth;
+    P.skybox = (flags & P3D_RADIANCE_SKYBOX) ? 1u : 0u; P.rgb = d_rgb; P.hit_id = d_hit_id; P.stack = q.stack;
+    with_accel(accel, [&](auto A) {
+      hipLaunchKernelGGL((radiance_query_kernel<decltype(A)::value>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+    });
+  }, true);
+}
+
+// One launch on the caller's stream, no wait, nothing of the scene's scratch
+int p3d_camera_rays_device(p3d_scene* s, const p3d_camera* camera, const p3d_tile* tile, float* d_origin, float* d_direction, void* hip_stream) {
+  const std::string pre = "p3d_camera_rays_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  const DevCamera& own = s->dev.cam;
+  if (own.res_x <= 0 || own.res_y <= 0) return fail(P3D_ERR_INVALID, pre + "scene has no camera");
+  if (camera) {
+    if (camera->res_x != own.res_x || camera->res_y != own.res_y)
+      return fail(P3D_ERR_INVALID, pre + "the camera is for " + std::to_string(camera->res_x) + "x" + std::to_string(camera->res_y) +
+                                       ", the scene renders " + std::to_string(own.res_x) + "x" + std::to_string(own.res_y));
+    if (!camera_usable(*camera)) return fail(P3D_ERR_INVALID, pre + "every field of the camera must be finite, and w, h and plane_dist > 0");
+  }
+  const DevCamera cam = camera ? dev_camera(*camera) : own;
+  if (cam.aperture != 0.0f) return fail(P3D_ERR_UNSUPPORTED, pre + "a lens camera (aperture != 0): its rays need the sampler");
+  const p3d_tile whole{0, 0, own.res_x, own.res_y, 0, 1};
+  const p3d_tile& t = tile ? *tile : whole;
+  const int sh = t.stripe_h > 0 ? t.stripe_h : 1, ss = t.stripe_h > 0 ? t.stripe_stride : 1;
+  if (t.w <= 0 || t.h <= 0 || t.x0 < 0 || t.y0 < 0 || ss < 1 || t.x0 + t.w > cam.res_x) return fail(P3D_ERR_INVALID, pre + "tile outside the image");
+  {
+    const int last = t.h - 1;
+    const long long ylast = (long long)t.y0 + (long long)(last / sh) * sh * ss + (last % sh);
+    if (ylast >= cam.res_y) return fail(P3D_ERR_INVALID, pre + "tile rows outside the image");
+  }
+  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (((uintptr_t)d_origin | (uintptr_t)d_direction) & 3u) return fail(P3D_ERR_INVALID, pre + "the float buffers must be 4-byte aligned");
+  const size_t pixels = (size_t)t.w * (size_t)t.h, vec = pixels * 3 * sizeof(float);
+  P3D_HIP(hipSetDevice(s->device));
+  if (int rc = device_buffer_usable(s, d_origin, vec, pre + "d_origin")) return rc;
+  if (int rc = device_buffer_usable(s, d_direction, vec, pre + "d_direction")) return rc;
+  CameraRaysParams C{};
+  C.cam = cam; C.x0 = t.x0; C.y0 = t.y0; C.w = t.w; C.h = t.h; C.stripe_h = sh; C.stripe_stride = ss;
+  C.origin = d_origin; C.direction = d_direction;
+  hipLaunchKernelGGL(camera_rays_kernel, dim3((uint32_t)((pixels + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, C);
+  P3D_HIP(hipGetLastError());
+  return P3D_OK;
+}
 
 static int trace_common(p3d_scene* s, uint32_t accel, uint32_t n, const float* origin, const float* direction, int32_t* hit_id,
                         float* t_host, float* hit_point, uint8_t* occluded, bool any) {
