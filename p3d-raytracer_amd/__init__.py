@@ -21,11 +21,11 @@ from ._abi import (ACCEL_BVH, ACCEL_GRID, ACCEL_NONE, CHAIN_AUTO, CHAIN_MEGAKERN
                    Config, DebugPlan, DenoiseParams, FramePlan, GeomSource, GridDesc, Light, Material, P3DError, Prim, SceneDesc,
                    SkyboxDesc, SkyboxFace, Stats, TemporalParams, Tile, Xform, XformRange, _check, _Handle, _lib, _ptr, _stream, build,
                    device_count, lib)
-from ._device_args import (NEAREST_K_MAX, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, TRACE_HITS_K_MAX, _CAMERA_RAYS_OUTPUTS, _NEAREST_OUTPUTS,
-                           _RADIANCE_OUTPUTS, _TRACE_OUTPUTS, _device_blocks, _device_rows, _device_vector, _nearest_k_outputs,
-                           _trace_hits_outputs)
+from ._device_args import (NEAREST_K_MAX, PATH_ACCUMULATE, PATH_MAX_DEPTH, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, TRACE_HITS_K_MAX,
+                           _CAMERA_RAYS_OUTPUTS, _CAMERA_SAMPLE_RAYS_OUTPUTS, _NEAREST_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS, _TRACE_OUTPUTS,
+                           _device_blocks, _device_rows, _device_vector, _nearest_k_outputs, _trace_hits_outputs)
 from .config import _f3, default_config, denoise_params, look_at, pathtrace_config, temporal_params, whitted_config
-from .device_queries import camera_rays_device, trace_radiance_device
+from .device_queries import camera_rays_device, camera_sample_rays_device, trace_path_device, trace_radiance_device
 from .device_scene import SKYBOX_FACE_FILES, DeviceScene, load_skybox_dir
 from .geometry import _xform_arrays, deformed, deformed_spheres, transformed, tree_cost
 from .host_scene import HostScene

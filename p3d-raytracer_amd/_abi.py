@@ -250,6 +250,8 @@ PROTOTYPES = {
     "p3d_trace_hits_device": (DEFAULT, [VP, U32, U32, U32] + [VP] * 10),
     "p3d_trace_radiance_device": (DEFAULT, [VP, U32, U32, VP, VP, I32, U32, VP, VP, VP]),
     "p3d_camera_rays_device": (DEFAULT, [VP, PTR(Camera), PTR(Tile), VP, VP, VP]),
+    "p3d_trace_path_device": (DEFAULT, [VP, U32, U32, VP, VP, I32, U32, U32, C.c_uint64, VP, U32, VP, VP, VP]),
+    "p3d_camera_sample_rays_device": (DEFAULT, [VP, PTR(Camera), PTR(Tile), PTR(Config), U32, VP, VP, VP, VP]),
     "p3d_debug_scene_limits": (DEFAULT, [VP, VP]),
     "p3d_debug_frame_plan": (DEFAULT, [VP, PTR(Config), PTR(Tile), U32, U32, U32, PTR(DebugPlan)]),
     "p3d_debug_frame_plan_size": (U32, None),
@@ -257,7 +259,7 @@ PROTOTYPES = {
 }
 # EXPORTS: what include/p3d.h itself declares, the entry points of the recorded surface (tests/python_api_surface.json holds the
 # list to what it was).  EXPORTS_ADDED: those declared since, in include/p3d_radiance.h, which p3d.h includes; detected by their symbols
-EXPORTS_ADDED = ["p3d_trace_radiance_device", "p3d_camera_rays_device"]
+EXPORTS_ADDED = ["p3d_trace_radiance_device", "p3d_camera_rays_device", "p3d_trace_path_device", "p3d_camera_sample_rays_device"]
 EXPORTS = [name for name in PROTOTYPES if not name.startswith("p3d_debug_") and name not in EXPORTS_ADDED]
 
 

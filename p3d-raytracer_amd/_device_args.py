@@ -70,3 +70,7 @@ RADIANCE_MAX_DEPTH = 16  # P3D_RADIANCE_MAX_DEPTH
 RADIANCE_SKYBOX = 1      # P3D_RADIANCE_SKYBOX
 _RADIANCE_OUTPUTS = {"rgb": ("float32", 3), "hit_id": ("int32", None)}
 _CAMERA_RAYS_OUTPUTS = {"origin": ("float32", 3), "direction": ("float32", 3)}
+PATH_ACCUMULATE = 2      # P3D_PATH_ACCUMULATE
+PATH_MAX_DEPTH = 1024    # of a path-traced frame
+_PATH_OUTPUTS = {"rgb": ("float32", 3), "hit_id": ("int32", None)}
+_CAMERA_SAMPLE_RAYS_OUTPUTS = {"origin": ("float32", 3), "direction": ("float32", 3), "rng": ("int64", 2)}

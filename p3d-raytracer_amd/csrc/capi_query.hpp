@@ -1,11 +1,13 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
-// p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_object_*, p3d_skybox_color)
+// p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device,
+// p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
 #include "capi_update.hpp"  // device_buffer_usable
 #include "hit_list_query.hpp"
 #include "nearest_query.hpp"
+#include "path_query.hpp"
 #include "radiance_query.hpp"
 #include "ray_query.hpp"
 
@@ -51,6 +53,7 @@ struct QueryBuffer {
   size_t bytes;
   const char* name;
   bool aligned4 = true;  // floats or int32s
+  bool aligned8 = false; // uint64s
 };
 
 // What the device-buffer queries do once their own refusals have passed: the refusals of the buffers in `bufs`, the stack
@@ -62,6 +65,8 @@ int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& p
                   size_t list_lds, void* hip_stream, Launch&& launch, bool chain = false) {
   for (const auto& b : bufs)
     if (b.aligned4 && ((uintptr_t)b.p & 3u)) return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
+  for (const auto& b : bufs)
+    if (b.aligned8 && ((uintptr_t)b.p & 7u)) return fail(P3D_ERR_INVALID, pre + b.name + " must be 8-byte aligned");
   P3D_HIP(hipSetDevice(s->device));  // the pointer queries below answer for the current device's context
   for (const auto& b : bufs)
     if (b.p)
@@ -127,6 +132,47 @@ int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_
   });
 }
 
+// What p3d_camera_rays_device and p3d_camera_sample_rays_device refuse alike, and what they then work with: the camera (the
+// argument's or the scene's), the tile with its stripes resolved, and the two ray buffers checked for w*h rows
+struct CameraRaysCall {
+  DevCamera cam;
+  p3d_tile tile;  // stripe_h >= 1
+  size_t pixels;
+};
+int check_camera_rays(p3d_scene* s, const p3d_camera* camera, const std::string& pre, CameraRaysCall& out) {
+  const DevCamera& own = s->dev.cam;
+  if (own.res_x <= 0 || own.res_y <= 0) return fail(P3D_ERR_INVALID, pre + "scene has no camera");
+  if (camera) {
+    if (camera->res_x != own.res_x || camera->res_y != own.res_y)
+      return fail(P3D_ERR_INVALID, pre + "the camera is for " + std::to_string(camera->res_x) + "x" + std::to_string(camera->res_y) +
+                                       ", the scene renders " + std::to_string(own.res_x) + "x" + std::to_string(own.res_y));
+    if (!camera_usable(*camera)) return fail(P3D_ERR_INVALID, pre + "every field of the camera must be finite, and w, h and plane_dist > 0");
+  }
+  out.cam = camera ? dev_camera(*camera) : own;
+  return P3D_OK;
+}
+int check_camera_rays_tile(p3d_scene* s, const p3d_tile* tile, float* d_origin, float* d_direction, const std::string& pre, CameraRaysCall& out) {
+  const DevCamera& cam = out.cam;
+  const p3d_tile whole{0, 0, cam.res_x, cam.res_y, 0, 1};
+  const p3d_tile& t = tile ? *tile : whole;
+  const int sh = t.stripe_h > 0 ? t.stripe_h : 1, ss = t.stripe_h > 0 ? t.stripe_stride : 1;
+  if (t.w <= 0 || t.h <= 0 || t.x0 < 0 || t.y0 < 0 || ss < 1 || t.x0 + t.w > cam.res_x) return fail(P3D_ERR_INVALID, pre + "tile outside the image");
+  {
+    const int last = t.h - 1;
+    const long long ylast = (long long)t.y0 + (long long)(last / sh) * sh * ss + (last % sh);
+    if (ylast >= cam.res_y) return fail(P3D_ERR_INVALID, pre + "tile rows outside the image");
+  }
+  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (((uintptr_t)d_origin | (uintptr_t)d_direction) & 3u) return fail(P3D_ERR_INVALID, pre + "the float buffers must be 4-byte aligned");
+  out.tile = p3d_tile{t.x0, t.y0, t.w, t.h, sh, ss};
+  out.pixels = (size_t)t.w * (size_t)t.h;
+  const size_t vec = out.pixels * 3 * sizeof(float);
+  P3D_HIP(hipSetDevice(s->device));
+  if (int rc = device_buffer_usable(s, d_origin, vec, pre + "d_origin")) return rc;
+  if (int rc = device_buffer_usable(s, d_direction, vec, pre + "d_direction")) return rc;
+  return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -160,35 +206,75 @@ int p3d_trace_radiance_device(p3d_scene* s, uint32_t accel, uint32_t n, const fl
 int p3d_camera_rays_device(p3d_scene* s, const p3d_camera* camera, const p3d_tile* tile, float* d_origin, float* d_direction, void* hip_stream) {
   const std::string pre = "p3d_camera_rays_device: ";
   if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  const DevCamera& own = s->dev.cam;
-  if (own.res_x <= 0 || own.res_y <= 0) return fail(P3D_ERR_INVALID, pre + "scene has no camera");
-  if (camera) {
-    if (camera->res_x != own.res_x || camera->res_y != own.res_y)
-      return fail(P3D_ERR_INVALID, pre + "the camera is for " + std::to_string(camera->res_x) + "x" + std::to_string(camera->res_y) +
-                                       ", the scene renders " + std::to_string(own.res_x) + "x" + std::to_string(own.res_y));
-    if (!camera_usable(*camera)) return fail(P3D_ERR_INVALID, pre + "every field of the camera must be finite, and w, h and plane_dist > 0");
-  }
-  const DevCamera cam = camera ? dev_camera(*camera) : own;
-  if (cam.aperture != 0.0f) return fail(P3D_ERR_UNSUPPORTED, pre + "a lens camera (aperture != 0): its rays need the sampler");
-  const p3d_tile whole{0, 0, own.res_x, own.res_y, 0, 1};
-  const p3d_tile& t = tile ? *tile : whole;
-  const int sh = t.stripe_h > 0 ? t.stripe_h : 1, ss = t.stripe_h > 0 ? t.stripe_stride : 1;
-  if (t.w <= 0 || t.h <= 0 || t.x0 < 0 || t.y0 < 0 || ss < 1 || t.x0 + t.w > cam.res_x) return fail(P3D_ERR_INVALID, pre + "tile outside the image");
-  {
-    const int last = t.h - 1;
-    const long long ylast = (long long)t.y0 + (long long)(last / sh) * sh * ss + (last % sh);
-    if (ylast >= cam.res_y) return fail(P3D_ERR_INVALID, pre + "tile rows outside the image");
-  }
-  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (((uintptr_t)d_origin | (uintptr_t)d_direction) & 3u) return fail(P3D_ERR_INVALID, pre + "the float buffers must be 4-byte aligned");
-  const size_t pixels = (size_t)t.w * (size_t)t.h, vec = pixels * 3 * sizeof(float);
-  P3D_HIP(hipSetDevice(s->device));
-  if (int rc = device_buffer_usable(s, d_origin, vec, pre + "d_origin")) return rc;
-  if (int rc = device_buffer_usable(s, d_direction, vec, pre + "d_direction")) return rc;
+  CameraRaysCall call;
+  if (int rc = check_camera_rays(s, camera, pre, call)) return rc;
+  if (call.cam.aperture != 0.0f) return fail(P3D_ERR_UNSUPPORTED, pre + "a lens camera (aperture != 0): its rays need the sampler");
+  if (int rc = check_camera_rays_tile(s, tile, d_origin, d_direction, pre, call)) return rc;
+  const p3d_tile& t = call.tile;
   CameraRaysParams C{};
-  C.cam = cam; C.x0 = t.x0; C.y0 = t.y0; C.w = t.w; C.h = t.h; C.stripe_h = sh; C.stripe_stride = ss;
+  C.cam = call.cam; C.x0 = t.x0; C.y0 = t.y0; C.w = t.w; C.h = t.h; C.stripe_h = t.stripe_h; C.stripe_stride = t.stripe_stride;
   C.origin = d_origin; C.direction = d_direction;
-  hipLaunchKernelGGL(camera_rays_kernel, dim3((uint32_t)((pixels + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, C);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3((uint32_t)((call.pixels + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, C);
+  P3D_HIP(hipGetLastError());
+  return P3D_OK;
+}
+
+// The sum of `samples` path-traced samples per ray, one kernel on the caller's stream
+int p3d_trace_path_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, int32_t max_depth,
+                          uint32_t sample_begin, uint32_t samples, uint64_t seed, uint64_t* d_rng, uint32_t flags, float* d_rgb,
+                          int32_t* d_hit_id, void* hip_stream) {
+  const std::string pre = "p3d_trace_path_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (accel == P3D_ACCEL_GRID && s->dev.n_objs == 0) return fail(P3D_ERR_UNSUPPORTED, "grid over an empty scene");
+  if (max_depth < 0 || max_depth > 1024) return fail(P3D_ERR_INVALID, pre + "max_depth must be 0 .. 1024, as in a path-traced frame");
+  if (samples == 0) return fail(P3D_ERR_INVALID, pre + "samples must be at least 1");
+  if ((uint64_t)sample_begin + samples > 0x100000000ull) return fail(P3D_ERR_INVALID, pre + "sample_begin + samples must not pass 2^32");
+  if (flags & ~(P3D_RADIANCE_SKYBOX | P3D_PATH_ACCUMULATE)) return fail(P3D_ERR_INVALID, pre + "unknown flag");
+  if ((flags & P3D_RADIANCE_SKYBOX) && !s->has_sky)
+    return fail(P3D_ERR_INVALID, pre + "P3D_RADIANCE_SKYBOX but no cubemap was supplied (p3d_scene_set_skybox)");
+  if (n == 0) return P3D_OK;
+  if (!d_origin || !d_direction || !d_rgb) return fail(P3D_ERR_INVALID, pre + "null argument");
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const QueryBuffer bufs[] = {{d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_rgb, vec, "d_rgb"}, {d_hit_id, one, "d_hit_id"},
+                              {d_rng, (size_t)n * 2 * sizeof(uint64_t), "d_rng", false, true}};
+  // (the pending dielectric branches behind the stack window; the stack of one traversal: closest-hit queries leave it empty)
+  return enqueue_query(s, accel, n, pre, "rays", bufs, path_lds_bytes(), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    PathQueryParams P{};
+    P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.max_depth = max_depth;
+    P.skybox = (flags & P3D_RADIANCE_SKYBOX) ? 1u : 0u; P.accumulate = (flags & P3D_PATH_ACCUMULATE) ? 1u : 0u;
+    P.sample_begin = sample_begin; P.samples = samples; P.seed = seed; P.rng = (RngWords*)d_rng;
+    P.rgb = d_rgb; P.hit_id = d_hit_id; P.stack = q.stack;
+    with_accel(accel, [&](auto A) {
+      hipLaunchKernelGGL((path_query_kernel<decltype(A)::value>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+    });
+  });
+}
+
+// One launch on the caller's stream, no wait, nothing of the scene's scratch
+int p3d_camera_sample_rays_device(p3d_scene* s, const p3d_camera* camera, const p3d_tile* tile, const p3d_config* cfg, uint32_t sample,
+                                  float* d_origin, float* d_direction, uint64_t* d_rng, void* hip_stream) {
+  const std::string pre = "p3d_camera_sample_rays_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  CameraRaysCall call;
+  if (int rc = check_camera_rays(s, camera, pre, call)) return rc;
+  if (!cfg) return fail(P3D_ERR_INVALID, pre + "null config");
+  if (cfg->spp_sqrt == 0 || cfg->spp_sqrt > 1024) return fail(P3D_ERR_INVALID, pre + "spp_sqrt out of range");
+  if (sample >= cfg->spp_sqrt * cfg->spp_sqrt) return fail(P3D_ERR_INVALID, pre + "sample must be below spp_sqrt * spp_sqrt");
+  if (cfg->sample_mode > P3D_SAMPLE_TENT) return fail(P3D_ERR_INVALID, pre + "bad sample_mode");
+  // (depth_of_field through a camera without an aperture: the frames take it, and so does this)
+  if (int rc = check_camera_rays_tile(s, tile, d_origin, d_direction, pre, call)) return rc;
+  if (d_rng) {
+    if ((uintptr_t)d_rng & 7u) return fail(P3D_ERR_INVALID, pre + "d_rng must be 8-byte aligned");
+    if (int rc = device_buffer_usable(s, d_rng, call.pixels * 2 * sizeof(uint64_t), pre + "d_rng")) return rc;
+  }
+  const p3d_tile& t = call.tile;
+  CameraSampleRaysParams C{};
+  C.cam = call.cam; C.x0 = t.x0; C.y0 = t.y0; C.w = t.w; C.h = t.h; C.stripe_h = t.stripe_h; C.stripe_stride = t.stripe_stride;
+  C.spp_sqrt = cfg->spp_sqrt; C.antialiasing = cfg->antialiasing; C.depth_of_field = cfg->depth_of_field;
+  C.sample_disk = cfg->sample_disk; C.sample_mode = cfg->sample_mode; C.sample = sample; C.seed = cfg->seed;
+  C.origin = d_origin; C.direction = d_direction; C.rng = (RngWords*)d_rng;
+  hipLaunchKernelGGL(camera_sample_rays_kernel, dim3((uint32_t)((call.pixels + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, C);
   P3D_HIP(hipGetLastError());
   return P3D_OK;
 }

@@ -1,11 +1,11 @@
 """What the *_device queries of a DeviceScene share: their inputs and outputs resolved to addresses, and the one call; and the
 queries added since the class's surface was recorded (tests/python_api_surface.json holds DeviceScene to its members of then):
-trace_radiance_device and camera_rays_device, functions of a DeviceScene."""
+trace_radiance_device, camera_rays_device, trace_path_device and camera_sample_rays_device, functions of a DeviceScene."""
 import ctypes as C
 
 from ._abi import P3DError, _check, _stream
-from ._device_args import (RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, _CAMERA_RAYS_OUTPUTS, _RADIANCE_OUTPUTS, _device_blocks, _device_rows,
-                           _device_vector)
+from ._device_args import (PATH_ACCUMULATE, PATH_MAX_DEPTH, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, _CAMERA_RAYS_OUTPUTS,
+                           _CAMERA_SAMPLE_RAYS_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS, _device_blocks, _device_rows, _device_vector)
 
 
 def _device_rays(scene, who, origin, direction, t_max):
@@ -112,4 +112,69 @@ def camera_rays_device(scene, camera=None, tile=None, stream=0, out=None):
     res = _device_outputs(scene, who, ("origin", "direction"), n, out, None, _CAMERA_RAYS_OUTPUTS, "pixels")
     _check(scene._L.p3d_camera_rays_device(scene._h, C.byref(camera) if camera is not None else None, C.byref(t),
                                            C.c_void_p(res["origin"][1]), C.c_void_p(res["direction"][1]), _stream(stream)))
+    return {name: v[0] for name, v in res.items()}
+
+
+def trace_path_device(scene, accel, origin, direction, max_depth, samples=1, sample_begin=0, seed=0, rng=None, flags=0, want=("hit_id",),
+                      out=None, stream=0):
+    """p3d_trace_path_device: the path-traced radiance n rays held in device memory see in the DeviceScene `scene` - the SUM of
+    Radiance over the samples sample_begin .. sample_begin + samples - 1 of each ray as a primary ray, max_depth bounces deep,
+    enqueued on `stream` without a wait -> {"rgb": (n, 3), and, if in `want`, "hit_id": (n,)}.  Nothing is divided.
+    rng None: sample s of ray i draws from the stream a frame seeds for (pixel i, sample s) with `seed`.  rng given: an int64
+    (n, 2) tensor (or a raw pair) of {state, inc} bit patterns, e.g. camera_sample_rays_device's; ray i draws all its samples
+    from that one stream, which is written back.  flags: RADIANCE_SKYBOX, PATH_ACCUMULATE (the sum starts from what
+    out["rgb"] holds and is added to in place; needs out={"rgb": ...}).  Every accel; rays, `out`, `stream` and the refusals
+    as trace_radiance_device."""
+    who = "trace_path_device"
+    max_depth, flags, samples, sample_begin = int(max_depth), int(flags), int(samples), int(sample_begin)
+    names = ["rgb"] + [w for w in ("hit_id",) if w in want]
+    refusal = None
+    if not 0 <= max_depth <= PATH_MAX_DEPTH:
+        refusal = "max_depth must be 0 .. %d, got %d" % (PATH_MAX_DEPTH, max_depth)
+    elif samples < 1:
+        refusal = "samples must be at least 1, got %d" % samples
+    elif sample_begin < 0 or sample_begin + samples > 1 << 32:
+        refusal = "sample_begin + samples must stay within 0 .. 2^32, got %d + %d" % (sample_begin, samples)
+    elif flags & ~(RADIANCE_SKYBOX | PATH_ACCUMULATE):
+        refusal = "unknown flag in %#x (RADIANCE_SKYBOX is %d, PATH_ACCUMULATE is %d)" % (flags, RADIANCE_SKYBOX, PATH_ACCUMULATE)
+    elif (flags & PATH_ACCUMULATE) and (out is None or "rgb" not in out):
+        refusal = "PATH_ACCUMULATE adds to out['rgb'], which is not given"
+
+    unknown = [w for w in want if w not in _PATH_OUTPUTS]
+    if unknown:
+        raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+    d_o, d_d, _, n = _device_rays(scene, who, origin, direction, None)
+    d_r = None
+    if rng is not None:
+        d_r, n_r = _device_rows(rng, who + ": rng", 2, ("int64",), scene.device)
+        if n_r != n:
+            raise P3DError(-1, "%s: %d rays, %d rng states" % (who, n, n_r))
+    if refusal:
+        raise P3DError(-1, "%s: %s" % (who, refusal))
+    res = _device_outputs(scene, who, names, n, out, origin, _PATH_OUTPUTS, "rays")
+    _check(scene._L.p3d_trace_path_device(scene._h, int(accel), n, C.c_void_p(d_o), C.c_void_p(d_d), max_depth, sample_begin, samples,
+                                          int(seed) & 0xffffffffffffffff, C.c_void_p(d_r), flags, C.c_void_p(res["rgb"][1]),
+                                          C.c_void_p(res["hit_id"][1]) if "hit_id" in res else None, _stream(stream)))
+    return {name: v[0] for name, v in res.items()}
+
+
+def camera_sample_rays_device(scene, cfg, sample, camera=None, tile=None, want=("rng",), out=None, stream=0):
+    """p3d_camera_sample_rays_device: sample `sample` (0 .. spp_sqrt^2 - 1) of every pixel of `tile` (None = the whole frame)
+    through `camera` (None = the scene's) as a frame of the Config `cfg` casts it - jittered or tent-filtered, through the
+    lens with depth_of_field - enqueued on `stream` without a wait -> {"origin", "direction": float32 (w * h, 3), and, if in
+    `want`, "rng": int64 (w * h, 2), the uint64 bit patterns {state, inc} of the pixel's stream after the sample's draws}, in
+    the row order of scene.render(cfg, tile): what trace_path_device takes.  `out` as camera_rays_device."""
+    who = "camera_sample_rays_device"
+    unknown = [w for w in want if w not in ("rng",)]
+    if unknown:
+        raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+    t = tile or scene.full_tile()
+    n = t.w * t.h
+    if n <= 0:
+        raise P3DError(-1, "%s: an empty tile" % who)
+    names = ("origin", "direction") + (("rng",) if "rng" in want else ())
+    res = _device_outputs(scene, who, names, n, out, None, _CAMERA_SAMPLE_RAYS_OUTPUTS, "pixels")
+    _check(scene._L.p3d_camera_sample_rays_device(scene._h, C.byref(camera) if camera is not None else None, C.byref(t), C.byref(cfg),
+                                                  int(sample) & 0xffffffff, C.c_void_p(res["origin"][1]), C.c_void_p(res["direction"][1]),
+                                                  C.c_void_p(res["rng"][1]) if "rng" in res else None, _stream(stream)))
     return {name: v[0] for name, v in res.items()}
