@@ -19,10 +19,10 @@ if torch.cuda.is_available():  # (torch's HIP runtime first, as tests/conftest.p
     torch.cuda.init()
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import p3d_amd as p3d  # noqa: E402
+from frame_checks import check_whitted, oracle_cfg_like
 from fuzz_scenes import random_scene  # noqa: E402
 from oracle import binding as ob  # noqa: E402
-from test_gpu_parity import check_whitted, oracle_cfg_like  # noqa: E402
+import p3d_amd as p3d  # noqa: E402
 
 COUNTERS = ("rays", "node_tests", "sphere_tests", "tri_tests", "box_tests", "plane_tests")
 

@@ -2,14 +2,13 @@
 the ABI version is unchanged, and the front end refuses a malformed --passes before it loads a scene."""
 import os
 import re
-import subprocess
 
-import p3d_amd as p3d
+from api_checks import cli
 from conftest import ROOT
+import p3d_amd as p3d
 
 ACCUM_SYMBOLS = ["p3d_accum_create", "p3d_accum_destroy", "p3d_accum_reset", "p3d_accum_samples_done", "p3d_accum_render",
                  "p3d_accum_render_device"]
-EXE = os.path.join(ROOT, "p3d-raytracer_amd", "p3d_render")
 
 
 def test_library_exports_the_accumulator():
@@ -34,24 +33,19 @@ def test_python_wrapper():
     assert hasattr(p3d.DeviceScene, "accumulator") and hasattr(p3d.DeviceScene, "render_progressive")
 
 
-def _cli(*args):
-    subprocess.check_call(["make", "-s", "-C", os.path.dirname(EXE), "p3d_render"], stdout=subprocess.DEVNULL)
-    return subprocess.run([EXE, *args], capture_output=True, text=True, timeout=60)
-
-
 def test_cli_refuses_zero_passes():
-    r = _cli("--passes", "0", "x.p3f")
+    r = cli("--passes", "0", "x.p3f")
     assert r.returncode == 2
     assert "--passes" in r.stderr and "unknown option" not in r.stderr, r.stderr
 
 
 def test_cli_refuses_passes_without_a_count():
-    r = _cli("x.p3f", "--passes")
+    r = cli("x.p3f", "--passes")
     assert r.returncode == 2 and "--passes" in r.stderr, r.stderr
 
 
 def test_cli_refuses_more_passes_than_samples_and_passes_with_gpus():
-    r = _cli("x.p3f", "--spp", "2", "--aa", "1", "--passes", "5")
+    r = cli("x.p3f", "--spp", "2", "--aa", "1", "--passes", "5")
     assert r.returncode == 2 and "--passes" in r.stderr, r.stderr
-    r = _cli("x.p3f", "--gpus", "2", "--passes", "2")
+    r = cli("x.p3f", "--gpus", "2", "--passes", "2")
     assert r.returncode == 2 and "--gpus" in r.stderr, r.stderr

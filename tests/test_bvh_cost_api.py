@@ -3,20 +3,15 @@ p3d_scene_auto_rebuild, include/p3d.h) without a GPU: the entry points and the 3
 wrapped, p3d_update_mode keeps its two values, and p3d.tree_cost - the numpy float64 statement of the cost - gives the values
 worked out by hand."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 
+from api_checks import header_code
 import p3d_amd as p3d
-from conftest import ROOT
 
 SYMBOLS = ["p3d_scene_bvh_cost", "p3d_scene_set_auto_rebuild", "p3d_scene_auto_rebuild"]
 LEAF = 0x80000000
-
-
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
 
 
 def _tree(bmin, bmax, index, count_leaf, order):
@@ -25,7 +20,7 @@ def _tree(bmin, bmax, index, count_leaf, order):
 
 
 def test_header_declares_the_entry_points_and_the_structure():
-    code = _header_code()
+    code = header_code()
     assert re.search(r"typedef\s+struct\s+p3d_bvh_cost\s*\{\s*double\s+sah\s*;\s*double\s+sah_baseline\s*;\s*uint32_t\s+n_inner\s*,\s*n_leaves\s*;"
                      r"\s*uint32_t\s+refits_since_build\s*;\s*uint32_t\s+last_update_rebuilt\s*;\s*\}\s*p3d_bvh_cost\s*;", code)
     assert re.search(r"\bint\s+p3d_scene_bvh_cost\s*\(\s*p3d_scene\s*\*\s*\w+,\s*p3d_bvh_cost\s*\*\s*\w+\)", code)
@@ -36,7 +31,7 @@ def test_header_declares_the_entry_points_and_the_structure():
 
 def test_the_update_modes_are_the_two_there_were():
     assert re.search(r"typedef\s+enum\s+p3d_update_mode\s*\{\s*P3D_UPDATE_REFIT\s*=\s*0\s*,\s*P3D_UPDATE_REBUILD\s*=\s*1\s*\}\s*p3d_update_mode\s*;",
-                     _header_code())
+                     header_code())
     assert (p3d.UPDATE_REFIT, p3d.UPDATE_REBUILD) == (0, 1)
 
 

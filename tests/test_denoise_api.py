@@ -1,15 +1,13 @@
 """Denoising (p3d_render_features / p3d_denoise / p3d_denoise_variance, include/p3d.h) without a GPU: the entry points are
 exported, declared and wrapped, the p3d_accum / p3d_adaptive sets and the ABI version are untouched, the front end refuses
 bad --denoise options before it loads a scene, and the numpy statement of the filter behaves on hand-made cases."""
-import os
 import re
-import subprocess
 
 import numpy as np
 
-import p3d_amd as p3d
+from api_checks import cli, header_code, refused
 from atrous_reference import atrous
-from conftest import ROOT
+import p3d_amd as p3d
 
 DENOISE_SYMBOLS = ["p3d_render_features", "p3d_render_features_device", "p3d_denoise_params_default", "p3d_denoiser_create",
                    "p3d_denoiser_destroy", "p3d_denoise", "p3d_denoise_device", "p3d_denoise_variance",
@@ -19,11 +17,6 @@ ADAPTIVE_SYMBOLS = ["p3d_adaptive_create", "p3d_adaptive_destroy", "p3d_adaptive
                     "p3d_adaptive_read_state"]
 ACCUM_SYMBOLS = ["p3d_accum_create", "p3d_accum_destroy", "p3d_accum_reset", "p3d_accum_samples_done", "p3d_accum_render",
                  "p3d_accum_render_device"]
-EXE = os.path.join(ROOT, "p3d-raytracer_amd", "p3d_render")
-
-
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
 
 
 def test_library_exports_the_denoise_entry_points():
@@ -34,7 +27,7 @@ def test_library_exports_the_denoise_entry_points():
 
 
 def test_header_declares_them_and_leaves_accum_and_adaptive_alone():
-    code = _header_code()
+    code = header_code()
     assert "typedef struct p3d_denoiser p3d_denoiser;" in code
     assert "p3d_denoise_params" in code
     declared = set(re.findall(r"\b(p3d_(?:render_features|denoise|denoiser)[a-z_]*)\s*\(", code))
@@ -59,30 +52,20 @@ def test_python_wrappers():
         assert name in p3d.EXPORTS
 
 
-def _cli(*args):
-    subprocess.check_call(["make", "-s", "-C", os.path.dirname(EXE), "p3d_render"], stdout=subprocess.DEVNULL)
-    return subprocess.run([EXE, *args], capture_output=True, text=True, timeout=60)
-
-
-def _refused(r, option):
-    assert r.returncode == 2, (r.returncode, r.stderr)
-    assert option in r.stderr and "unknown option" not in r.stderr, r.stderr
-
-
 def test_cli_refuses_denoise_with_whitted_or_gpus():
-    _refused(_cli("x.p3f", "--whitted", "--aa", "1", "--denoise", "d.png"), "--whitted")
-    _refused(_cli("x.p3f", "--pathtrace", "--aa", "1", "--gpus", "2", "--denoise", "d.png"), "--gpus")
-    _refused(_cli("x.p3f", "--pathtrace", "--aa", "0", "--denoise", "d.png"), "--aa")
+    refused(cli("x.p3f", "--whitted", "--aa", "1", "--denoise", "d.png"), "--whitted")
+    refused(cli("x.p3f", "--pathtrace", "--aa", "1", "--gpus", "2", "--denoise", "d.png"), "--gpus")
+    refused(cli("x.p3f", "--pathtrace", "--aa", "0", "--denoise", "d.png"), "--aa")
 
 
 def test_cli_refuses_malformed_values():
     for v in ("-1", "9", "abc", "2x", ""):
-        _refused(_cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise", "d.png", "--denoise-iter", v), "--denoise-iter")
+        refused(cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise", "d.png", "--denoise-iter", v), "--denoise-iter")
     for v in ("-1", "abc", "4.5"):
-        _refused(_cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise", "d.png", "--feature-spp", v), "--feature-spp")
-    _refused(_cli("x.p3f", "--pathtrace", "--aa", "1", "--spp", "2", "--denoise", "d.png", "--feature-spp", "5"), "--feature-spp")
-    _refused(_cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise-iter", "3"), "--denoise")
-    _refused(_cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise"), "--denoise")
+        refused(cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise", "d.png", "--feature-spp", v), "--feature-spp")
+    refused(cli("x.p3f", "--pathtrace", "--aa", "1", "--spp", "2", "--denoise", "d.png", "--feature-spp", "5"), "--feature-spp")
+    refused(cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise-iter", "3"), "--denoise")
+    refused(cli("x.p3f", "--pathtrace", "--aa", "1", "--denoise"), "--denoise")
 
 
 def _features(h, w, normal=(0.0, 0.0, 1.0), t=5.0, albedo=(0.5, 0.5, 0.5), cov=1.0):

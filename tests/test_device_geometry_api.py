@@ -4,22 +4,22 @@ gathers that return the input bits, in soup and indexed form alike, and produce 
 result a scene file holding those numbers gives; and the tensor wrappers refuse what they cannot pass on before the library
 is called."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
-from conftest import ROOT, scene_path
+from api_checks import header_code, scene_without_a_library
+from conftest import scene_path
 from device_geometry_helpers import deformed_mesh, indexed, moved_spheres
+import p3d_amd as p3d
 from scene_update_helpers import SPHERE, TRIANGLE, write_moved_p3f
 
 DESC_KEYS = ("prim_v", "prim_type", "prim_material", "prim_n", "prim_bmin", "prim_bmax")
 
 
 def test_header_declares_the_structure_and_the_entry_point():
-    code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
+    code = header_code()
     assert re.search(r"typedef\s+struct\s+p3d_geom_source\s*\{\s*uint32_t\s+first\s*,\s*count\s*;\s*uint32_t\s+kind\s*;\s*uint32_t\s+n_elems\s*;"
                      r"\s*const\s+void\s*\*\s*d_data\s*;\s*const\s+uint32_t\s*\*\s*d_index\s*;\s*uint64_t\s+reserved\[2\]\s*;\s*\}\s*p3d_geom_source\s*;", code)
     assert re.search(r"\bint\s+p3d_scene_update_geometry_device\s*\(\s*p3d_scene\s*\*\s*\w+,\s*uint32_t\s+\w+,\s*const\s+p3d_geom_source\s*\*\s*\w+,"
@@ -110,22 +110,9 @@ def test_deformed_spheres_likewise(tmp_path):
         p3d.deformed_spheres(a["prim_v"], first + 1, cr)
 
 
-class _Untouchable:
-    """Stands where the library would: any use of it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was called (%s)" % name)
-
-
-def _scene_without_a_library():
-    dev = p3d.DeviceScene.__new__(p3d.DeviceScene)
-    dev._L, dev._h, dev.device, dev.host = _Untouchable(), None, 0, None
-    return dev
-
-
 def test_wrappers_refuse_bad_tensors_before_the_library():
     import torch
-    dev = _scene_without_a_library()
+    dev = scene_without_a_library()
     good_pos = torch.zeros((6, 3), dtype=torch.float32)
     good_idx = torch.zeros((2, 3), dtype=torch.int32)
     cases = [

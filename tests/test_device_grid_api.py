@@ -7,18 +7,15 @@ import re
 
 import pytest
 
-import p3d_amd as p3d
+from api_checks import header_code
 from conftest import ROOT, scene_path
+import p3d_amd as p3d
 
 SYMBOLS = ["p3d_scene_build_grid", "p3d_scene_export_grid"]
 
 
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
-
-
 def test_header_declares_the_entry_points_and_keeps_the_abi_version():
-    code = _header_code()
+    code = header_code()
     assert re.search(r"\bint\s+p3d_scene_build_grid\s*\(\s*p3d_scene\s*\*\s*\w+,\s*float\s*\*\s*\w+\s*\)\s*;", code)
     assert re.search(r"\bint\s+p3d_scene_export_grid\s*\(\s*p3d_scene\s*\*\s*\w+,\s*p3d_grid_desc\s*\*\s*\w+,\s*uint32_t\s*\*\s*\w+,\s*uint32_t\s*\*\s*\w+,"
                      r"\s*uint32_t\s*\*\s*\w+,\s*uint32_t\s*\*\s*\w+\s*\)\s*;", code)

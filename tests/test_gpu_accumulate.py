@@ -9,32 +9,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from conftest import ROOT, scene_path
+from frame_checks import CORNELL, RENDER_COUNTERS, assert_same_bits, cached_device_scenes
 import p3d_amd as p3d
-from conftest import GOLDEN, ROOT, scene_path
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
 SUB_RECT = p3d.Tile(13, 9, 67, 45, 0, 1)  # edges that are not whole 4x4 / 8x8 tiles (scene at 96x64)
-COUNTERS = ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_bounce", "rays_light", "node_tests",
-            "sphere_tests", "tri_tests", "box_tests", "plane_tests", "shaded_hits")
-
 LEGACY = ("balls_high.p3f",)  # 11-number `f` lines (P3D_LOAD_LEGACY_F11): the shipped parser would load no objects
-_scenes = {}
-
-
-def device_scene(path, res, lens=None, sky=False, bvh=True, grid=True):
-    key = (path, res, lens, sky)
-    if key not in _scenes:
-        hs = p3d.HostScene(path, legacy_f11=os.path.basename(path) in LEGACY)
-        hs.set_resolution(*res)
-        if lens:
-            hs.set_lens(*lens)
-        dev = p3d.DeviceScene(hs, bvh=bvh, grid=grid)
-        if sky:
-            dev.set_skybox(p3d.load_skybox_dir(os.path.join(GOLDEN, "skybox")))
-        _scenes[key] = dev
-    return _scenes[key]
+device_scene = cached_device_scenes()
 
 
 def partitions(total, shapes):
@@ -49,16 +32,6 @@ def partitions(total, shapes):
         rest = total - sum(lead)
         out.append(list(lead) + ([rest] if rest else []))
     return out
-
-
-def assert_same_bits(a, b, what):
-    rgb_a, hit_a, u8_a = a
-    rgb_b, hit_b, u8_b = b
-    assert np.array_equal(hit_a, hit_b), "%s: hit IDs differ in %d pixels" % (what, int((hit_a != hit_b).sum()))
-    bad = (rgb_a.view(np.uint32) != rgb_b.view(np.uint32)).any(-1)
-    assert not bad.any(), "%s: %d pixels differ in some colour bit, max |diff| %g" % (
-        what, int(bad.sum()), float(np.abs(rgb_a - rgb_b).max()))
-    assert np.array_equal(u8_a, u8_b), "%s: rgb8 differs" % what
 
 
 def accumulate(dev, cfg, tile, parts):
@@ -119,7 +92,7 @@ WHITTED_CASES = [("balls_low_aa3_soft", "balls_low.p3f", dict(spp_sqrt=3, soft_s
 @pytest.mark.parametrize("accel", [p3d.ACCEL_BVH, p3d.ACCEL_GRID], ids=["bvh_per_pixel", "grid"])
 @pytest.mark.parametrize("sub_rect", [False, True], ids=["frame", "subrect"])
 def test_whitted_passes_equal_the_one_shot_frame(name, scene, kw, accel, sub_rect):
-    dev = device_scene(scene_path(scene), (96, 64) if sub_rect else (64, 64))
+    dev = device_scene(scene_path(scene), (96, 64) if sub_rect else (64, 64), legacy_f11=scene in LEGACY)
     cfg = p3d.whitted_config(accel=accel, max_depth=4, antialiasing=1, seed=77, stack_mode=p3d.STACK_PER_PIXEL, **kw)
     check_partitions(dev, cfg, SUB_RECT if sub_rect else None, WHITTED_SHAPES, name)
 
@@ -131,7 +104,7 @@ def test_partial_frames_do_not_depend_on_the_partition(integrator):
         cfg = p3d.pathtrace_config(accel=p3d.ACCEL_BVH, spp_sqrt=8, max_depth=20, seed=5)
         splits = ([40], [1, 15, 24], [7, 16, 17], [20, 20])
     else:
-        dev = device_scene(scene_path("balls_high.p3f"), (64, 64))
+        dev = device_scene(scene_path("balls_high.p3f"), (64, 64), legacy_f11=True)
         cfg = p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4, antialiasing=1, spp_sqrt=4, seed=9,
                                  stack_mode=p3d.STACK_PER_PIXEL, soft_shadows=1)
         splits = ([11], [1, 3, 7], [2, 4, 5], [1] * 11)
@@ -188,20 +161,20 @@ def test_counters_summed_over_the_passes_equal_the_frame(integrator):
         cfg = p3d.pathtrace_config(accel=p3d.ACCEL_BVH, spp_sqrt=8, max_depth=20, seed=3, collect_stats=1)
         parts = [1, 15, 7, 16, 25]
     else:
-        dev = device_scene(scene_path("balls_high.p3f"), (64, 64))
+        dev = device_scene(scene_path("balls_high.p3f"), (64, 64), legacy_f11=True)
         cfg = p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4, antialiasing=1, spp_sqrt=3, seed=3, soft_shadows=1,
                                  stack_mode=p3d.STACK_PER_PIXEL, collect_stats=1)
         parts = [1, 3, 5]
     _, _, one = dev.render(cfg)
     acc = dev.accumulator(cfg)
-    sums = dict.fromkeys(COUNTERS, 0)
+    sums = dict.fromkeys(RENDER_COUNTERS, 0)
     for n in parts:
         _, _, st = acc.render(n)
         assert st.pixels == 64 * 64
-        for k in COUNTERS:
+        for k in RENDER_COUNTERS:
             sums[k] += getattr(st, k)
     acc.close()
-    assert sums == {k: getattr(one, k) for k in COUNTERS}
+    assert sums == {k: getattr(one, k) for k in RENDER_COUNTERS}
     assert sums["rays_primary"] == 64 * 64 * cfg.spp_sqrt ** 2
 
 

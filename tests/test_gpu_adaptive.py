@@ -3,42 +3,23 @@
 Every (pixel, sample) has its own RNG stream and a pixel's samples are added in sample order, so a pixel that stopped
 after k samples must hold exactly the bits a plain accumulator (p3d_accum) holds for it after k samples, and with
 rel_error = 0 the frame is the one-shot frame."""
-import os
 
 import numpy as np
 import pytest
 
+from conftest import scene_path
+from frame_checks import CORNELL, assert_same_bits, cached_device_scenes
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
+device_scene = cached_device_scenes()
+
 SUB_RECT = p3d.Tile(13, 9, 67, 45, 0, 1)  # edges that are not whole 4x4 / 8x8 tiles (scene at 96x64)
-_scenes = {}
-
-
-def device_scene(path, res):
-    key = (path, res)
-    if key not in _scenes:
-        hs = p3d.HostScene(path)
-        hs.set_resolution(*res)
-        _scenes[key] = p3d.DeviceScene(hs, bvh=True, grid=True)
-    return _scenes[key]
 
 
 def cornell_cfg(accel=p3d.ACCEL_BVH, spp=8, **kw):
     return p3d.pathtrace_config(accel=accel, spp_sqrt=spp, max_depth=20, dof=0, seed=0x5EED, **kw)
-
-
-def assert_same_bits(a, b, what, where=None):
-    rgb_a, hit_a, u8_a = a
-    rgb_b, hit_b, u8_b = b
-    m = np.ones(hit_a.shape, bool) if where is None else where
-    assert np.array_equal(hit_a[m], hit_b[m]), "%s: hit IDs differ" % what
-    bad = (rgb_a.view(np.uint32) != rgb_b.view(np.uint32)).any(-1) & m
-    assert not bad.any(), "%s: %d pixels differ in some colour bit" % (what, int(bad.sum()))
-    assert np.array_equal(u8_a[m], u8_b[m]), "%s: rgb8 differs" % what
 
 
 def ulp_diff(a, b):

@@ -9,26 +9,23 @@ the total - below 5e-10 for N <= 2^22.  The bound used is 1e-9.
 A promoted update must leave what the same update leaves when called with UPDATE_REBUILD - the tree of a scene created fresh
 from the moved objects, to the byte - and one that is not promoted what a plain UPDATE_REFIT leaves."""
 import math
-import os
 
 import numpy as np
 import pytest
 
+from conftest import scene_path
+from frame_checks import CORNELL, RENDER_COUNTERS, f64_bytes
 import fuzz_scenes
 import lbvh_reference as ref
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
 from scene_update_helpers import random_moves, translated
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
 COUNTS = [1, 2, 3, 4, 255, 256, 257, 513]
 SCENES = ["count%d" % n for n in COUNTS] + ["balls_low", "cornell", "mixed", "tri100k"]
 LEAF = 0x80000000
 RATIO = 1.25
-COUNTERS = ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_bounce", "rays_light", "node_tests",
-            "sphere_tests", "tri_tests", "box_tests", "plane_tests", "shaded_hits")
 IDENTITY = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32)
 
 
@@ -52,10 +49,6 @@ def statement(tree):
     count = (tree["bvh_count_leaf"] & 0x7fffffff).astype(np.float64)
     total = math.fsum(area[~leaf].tolist() + (count[leaf] * area[leaf]).tolist())  # (count is 1 or 2: the product is exact)
     return (total / area[0] if area[0] > 0 else 0.0), int((~leaf).sum()), int(leaf.sum())
-
-
-def bits(x):
-    return np.float64(x).tobytes()
 
 
 def same_export(a, b):
@@ -84,11 +77,11 @@ def big_move(hs):
     return objs
 
 
-def frames(dev):
+def frame_bytes(dev):
     out = []
     for mode in (p3d.STACK_LITERAL, p3d.STACK_PER_PIXEL):
         rgb, hit, st = dev.render(p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4, stack_mode=mode, collect_stats=1))
-        out.append((rgb.tobytes(), hit.tobytes(), {k: getattr(st, k) for k in COUNTERS}))
+        out.append((rgb.tobytes(), hit.tobytes(), {k: getattr(st, k) for k in RENDER_COUNTERS}))
     return out
 
 
@@ -109,7 +102,7 @@ def test_the_cost_is_the_statement_over_the_exported_tree(name, paths):
     assert (c["n_inner"], c["n_leaves"]) == (n_inner, n_leaves)
     assert c["n_inner"] + c["n_leaves"] == len(tree["bvh_index"])
     assert (c["refits_since_build"], c["last_update_rebuilt"]) == (0, 0)
-    assert bits(c["sah_baseline"]) == bits(c["sah"])  # create, and no refit since
+    assert f64_bytes(c["sah_baseline"]) == f64_bytes(c["sah"])  # create, and no refit since
     if name == "count1":
         assert c["sah"] == 1.0 and (c["n_inner"], c["n_leaves"]) == (0, 1)
     if name == "count2":
@@ -135,7 +128,7 @@ def test_a_rebuilt_tree_costs_what_a_fresh_scenes_does(name, paths):
     objs = big_move(hs) if name == "count513" else small_move(hs)
     assert dev.update_prims(objs, p3d.UPDATE_REBUILD) > 0
     got, want = dev.bvh_cost(), p3d.DeviceScene(hs, bvh="device").bvh_cost()
-    assert bits(got["sah"]) == bits(want["sah"]) and (got["n_inner"], got["n_leaves"]) == (want["n_inner"], want["n_leaves"])
+    assert f64_bytes(got["sah"]) == f64_bytes(want["sah"]) and (got["n_inner"], got["n_leaves"]) == (want["n_inner"], want["n_leaves"])
     assert (got["refits_since_build"], got["last_update_rebuilt"]) == (0, 1)
     assert abs(got["sah"] - statement(dev.export_bvh())[0]) <= 1e-9 * got["sah"]
 
@@ -163,7 +156,7 @@ def pair(paths, grid=False, ratio=RATIO):
     assert same_export(dev.export_bvh(), before), "switching the policy on changed the tree"
     built = statement(before)[0]
     c = dev.bvh_cost()
-    assert bits(c["sah_baseline"]) == bits(c["sah"]) and abs(c["sah"] - built) <= 1e-9 * built
+    assert f64_bytes(c["sah_baseline"]) == f64_bytes(c["sah"]) and abs(c["sah"] - built) <= 1e-9 * built
     return hs, dev, twin, built
 
 
@@ -191,7 +184,7 @@ def check_rebuilt(hs, dev, twin, built, grid=False):
     assert not same_export(got, twin.export_bvh())
     c = dev.bvh_cost()
     assert (c["last_update_rebuilt"], c["refits_since_build"]) == (1, 0)
-    assert bits(c["sah_baseline"]) == bits(c["sah"]) == bits(fresh.bvh_cost()["sah"])
+    assert f64_bytes(c["sah_baseline"]) == f64_bytes(c["sah"]) == f64_bytes(fresh.bvh_cost()["sah"])
     return fresh
 
 
@@ -207,7 +200,7 @@ def test_the_policy_rebuilds_a_bad_tree(paths):
     objs = big_move(hs)
     assert dev.update_prims(objs, p3d.UPDATE_REFIT) > 0 and twin.update_prims(objs, p3d.UPDATE_REFIT) > 0
     fresh = check_rebuilt(hs, dev, twin, built)
-    for (rgb_a, hit_a, st_a), (rgb_b, hit_b, st_b) in zip(frames(dev), frames(fresh)):
+    for (rgb_a, hit_a, st_a), (rgb_b, hit_b, st_b) in zip(frame_bytes(dev), frame_bytes(fresh)):
         assert hit_a == hit_b and rgb_a == rgb_b
         assert st_a == st_b, "counters %s / %s" % (st_a, st_b)
     # ... and the topology a later REFIT keeps is the rebuilt one
@@ -223,7 +216,7 @@ def test_a_rebuild_with_the_policy_on_records_the_baseline(paths):
     assert dev.update_prims(objs, p3d.UPDATE_REBUILD) > 0 and twin.update_prims(objs, p3d.UPDATE_REBUILD) > 0
     assert same_export(dev.export_bvh(), twin.export_bvh())
     c = dev.bvh_cost()
-    assert bits(c["sah_baseline"]) == bits(c["sah"]) and c["sah"] != built
+    assert f64_bytes(c["sah_baseline"]) == f64_bytes(c["sah"]) and c["sah"] != built
     assert (c["last_update_rebuilt"], c["refits_since_build"]) == (1, 0)
 
 

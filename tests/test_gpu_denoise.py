@@ -7,33 +7,21 @@ import subprocess
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
 from atrous_reference import atrous, u8
 from conftest import ROOT, scene_path
+from frame_checks import CORNELL, cached_device_scenes, same_bits
+import p3d_amd as p3d
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
+device_scene = cached_device_scenes()
+
 BALLS = scene_path("balls_low.p3f")
 TOL = 1e-5  # |gpu - ref| <= TOL * max(1, |ref|) per channel
-_scenes = {}
-
-
-def device_scene(path, res):
-    key = (path, res)
-    if key not in _scenes:
-        hs = p3d.HostScene(path)
-        hs.set_resolution(*res)
-        _scenes[key] = p3d.DeviceScene(hs, bvh=True, grid=True)
-    return _scenes[key]
 
 
 def cornell_cfg(spp=4, **kw):
     return p3d.pathtrace_config(accel=kw.pop("accel", p3d.ACCEL_BVH), spp_sqrt=spp, max_depth=20, dof=0, seed=0x5EED, **kw)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
 
 
 def assert_close_to_reference(gpu, ref, what):

@@ -12,30 +12,27 @@ import numpy as np
 import pytest
 import torch
 
-import p3d_amd as p3d
-import test_gpu_scene_transform as T
 from device_geometry_helpers import deformed_mesh, diagonal, moved_spheres
+from frame_checks import CORNELL, assert_same_frames, assert_same_tree, frames, frames_differ, gpu, load
+from live_scene_checks import GRID_SCENES, IDENTITY, LEAF, RES, assert_same_scene, configs, device, host_route, rigid
+import p3d_amd as p3d
 from scene_update_helpers import SPHERE, TRIANGLE, translated
+from variant_scenes import scene_path
 
 pytestmark = pytest.mark.gpu
 
-LEAF = np.uint32(0x80000000)
 MODES = [p3d.UPDATE_REFIT, p3d.UPDATE_REBUILD]
 
 
 @pytest.fixture
 def paths(tri5k_path):
-    return {"balls_low": T.scene_path("balls_low.p3f"), "tri5k": tri5k_path, "cornell": T.CORNELL}
+    return {"balls_low": scene_path("balls_low.p3f"), "tri5k": tri5k_path, "cornell": CORNELL}
 
 
 def twins(path, name):
     """(host scene, its arrays, scene A for the host route, scene B for the device route)"""
-    hs = T.load(path)
-    return hs, hs.arrays(), T.device(hs, name), T.device(hs, name)
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    hs = load(path, RES)
+    return hs, hs.arrays(), device(hs, name), device(hs, name)
 
 
 def host_triangles(hs, dev, a, first, positions, indices, mode, only=None):
@@ -57,9 +54,9 @@ def host_spheres(hs, dev, a, first, cr, mode, only=None):
 def assert_same(dev_a, dev_b, name, what):
     """Frames with the BVH in both stack modes (or the path-traced frame), tree, and for the scenes with a device grid the
     grid and the frames through it in both stack modes -> B's BVH frames"""
-    now = T.assert_same_scene(dev_a, dev_b, name, what)
-    if name in T.GRID_SCENES:
-        T.assert_same_frames(T.frames(dev_a, name, p3d.ACCEL_GRID), T.frames(dev_b, name, p3d.ACCEL_GRID), what + ", grid frames")
+    now = assert_same_scene(dev_a, dev_b, name, what)
+    if name in GRID_SCENES:
+        assert_same_frames(frames(dev_a, configs(name, p3d.ACCEL_GRID)), frames(dev_b, configs(name, p3d.ACCEL_GRID)), what + ", grid frames")
     return now
 
 
@@ -67,14 +64,14 @@ def assert_same(dev_a, dev_b, name, what):
 @pytest.mark.parametrize("mode", MODES)
 def test_a_soup_of_the_whole_mesh(mode, paths):
     hs, a, dev_a, dev_b = twins(paths["tri5k"], "tri5k")
-    before = T.frames(dev_b, "tri5k")
+    before = frames(dev_b, configs("tri5k"))
     _, _, soup = deformed_mesh(a, seed=11)
     moved = np.linalg.norm(soup.astype(np.float64) - a["prim_v"].reshape(-1, 3), axis=1).max()
     assert 0 < moved <= 0.02 * diagonal(a) * (1 + 1e-6)
     assert host_triangles(hs, dev_a, a, 0, soup, None, mode) > 0
     assert dev_b.update_triangles(0, gpu(soup), mode=mode) > 0
     now = assert_same(dev_a, dev_b, "tri5k", "soup, mode %d" % mode)
-    assert T.frames_differ(now, before), "the deformation changed no pixel"
+    assert frames_differ(now, before), "the deformation changed no pixel"
     assert dev_b.status() == 0
 
 
@@ -151,12 +148,12 @@ def test_spheres(mode, paths):
     hs, a, dev_a, dev_b = twins(paths["balls_low"], "balls_low")
     spheres = np.nonzero(a["prim_type"] == SPHERE)[0]
     first, count = int(spheres[0]), len(spheres)
-    before = T.frames(dev_b, "balls_low")
+    before = frames(dev_b, configs("balls_low"))
     cr = moved_spheres(a, first, count, seed=21)
     assert host_spheres(hs, dev_a, a, first, cr, mode) > 0
     assert dev_b.update_spheres(first, gpu(cr), mode=mode) > 0
     now = assert_same(dev_a, dev_b, "balls_low", "spheres, mode %d" % mode)
-    assert T.frames_differ(now, before)
+    assert frames_differ(now, before)
 
 
 def test_triangles_and_spheres_in_one_call(paths):
@@ -165,7 +162,7 @@ def test_triangles_and_spheres_in_one_call(paths):
     tri, sph = np.nonzero(kinds == TRIANGLE)[0], np.nonzero(kinds == SPHERE)[0]
     t0, s0 = int(tri[0]), int(sph[0])
     assert np.array_equal(tri, np.arange(t0, t0 + len(tri))) and np.array_equal(sph, np.arange(s0, s0 + len(sph)))
-    before = T.frames(dev_b, "cornell")
+    before = frames(dev_b, configs("cornell"))
     rng = np.random.default_rng(22)
     soup = a["prim_v"][tri].reshape(-1, 3).astype(np.float64)
     soup = (soup + rng.uniform(-1, 1, soup.shape) * 0.01 * diagonal(a, tri)).astype(np.float32)
@@ -176,7 +173,7 @@ def test_triangles_and_spheres_in_one_call(paths):
     assert dev_b.update_geometry_device([dev_b.sphere_source(s0, d_cr), dev_b.triangle_source(t0, d_soup)], p3d.UPDATE_REFIT) > 0
     # (A took two refits, B one: a refit depends on the boxes alone)
     now = assert_same(dev_a, dev_b, "cornell", "triangles and spheres")
-    assert T.frames_differ(now, before)
+    assert frames_differ(now, before)
 
 
 # 5. per-object failures
@@ -233,7 +230,7 @@ def _raw(dev, sources, mode=p3d.UPDATE_REFIT, n=None, null=False):
 
 def test_refusals_leave_the_scene_as_it_was(paths):
     name = "balls_low"
-    hs = T.load(paths[name])
+    hs = load(paths[name], RES)
     a = hs.arrays()
     n = a["n_prims"]
     tri, sph = np.nonzero(a["prim_type"] == TRIANGLE)[0], np.nonzero(a["prim_type"] == SPHERE)[0]
@@ -254,11 +251,11 @@ def test_refusals_leave_the_scene_as_it_was(paths):
 
     good = [src(s0, ns, S, ns, cr.data_ptr())]
     for what, scene in (("a scene with the host's tree", host_tree), ("a scene with an uploaded grid", with_grid)):
-        was = T.frames(scene, name)
+        was = frames(scene, configs(name))
         assert _raw(scene, good) == -1, what
-        T.assert_same_frames(T.frames(scene, name), was, what)
+        assert_same_frames(frames(scene, configs(name)), was, what)
     assert _raw(None, good) == -1
-    was, tree = T.frames(dev, name), dev.export_bvh()
+    was, tree = frames(dev, configs(name)), dev.export_bvh()
     # Host memory must be refused BEFORE any launch.  Each such source goes in twice first: were the pointer check to let it
     # through, the overlap (found behind it) would still refuse the call, and no kernel would ever be given a host address.
     for what, bad in (("d_data", src(s0, ns, S, ns, host_cr.ctypes.data)),
@@ -300,42 +297,42 @@ def test_refusals_leave_the_scene_as_it_was(paths):
         kw = kw if isinstance(kw, dict) else dict(sources=kw)
         assert _raw(dev, **kw) == -1, what
         assert p3d.lib().p3d_last_error().startswith(b"p3d_scene_update_geometry_device"), what
-        T.assert_same_frames(T.frames(dev, name), was, what)
+        assert_same_frames(frames(dev, configs(name)), was, what)
     assert b"ends behind its allocation" in p3d.lib().p3d_last_error()
-    T.assert_same_tree(dev.export_bvh(), tree, "after the refusals")
+    assert_same_tree(dev.export_bvh(), tree, "after the refusals")
     assert dev.status() == 0
     # the same calls without a fault are accepted, in any order, with update_ms == NULL
     arr = (p3d.GeomSource * 2)(src(s0, ns, S, ns, cr.data_ptr()), src(t0, nt, TRI, 3 * nt, soup.data_ptr(), index.data_ptr()))
     assert p3d.lib().p3d_scene_update_geometry_device(dev._h, 2, C.cast(arr, C.c_void_p), p3d.UPDATE_REBUILD, None) == 0
-    assert T.frames_differ(T.frames(dev, name), was)
+    assert frames_differ(frames(dev, configs(name)), was)
 
 
 # 7. rest pose
 def test_a_deformed_object_rests_where_it_is_put(paths):
     hs, a, dev_a, dev_b = twins(paths["tri5k"], "tri5k")
     n = a["n_prims"]
-    move = T.rigid(a, np.random.default_rng(51))
+    move = rigid(a, np.random.default_rng(51))
     for dev in (dev_a, dev_b):
         dev.transform_prims([(0, n, 0)], move[None], p3d.UPDATE_REFIT)  # makes the rest copy
-    moved = T.frames(dev_b, "tri5k")
+    moved = frames(dev_b, configs("tri5k"))
     first, count = 300, 700
     _, _, soup = deformed_mesh(a, seed=52)
     part = soup[3 * first:3 * (first + count)]
     host_triangles(hs, dev_a, a, first, part, None, p3d.UPDATE_REFIT)
     dev_b.update_triangles(first, gpu(part), mode=p3d.UPDATE_REFIT)
     deformed = assert_same(dev_a, dev_b, "tri5k", "a deformation after a transform")
-    assert T.frames_differ(deformed, moved)
+    assert frames_differ(deformed, moved)
     for dev in (dev_a, dev_b):
-        dev.transform_prims([(first, count, 0)], T.IDENTITY[None], p3d.UPDATE_REFIT)
+        dev.transform_prims([(first, count, 0)], IDENTITY[None], p3d.UPDATE_REFIT)
     back = assert_same(dev_a, dev_b, "tri5k", "the identity on the deformed objects")
     # the deformed geometry, not the original one (the identity of the ORIGINAL rest pose would show the unmoved triangles)
-    T.assert_same_frames(back, deformed, "the identity returns what the device update put there")
+    assert_same_frames(back, deformed, "the identity returns what the device update put there")
 
 
 # 8. policy and bookkeeping
 def test_a_refit_the_policy_promotes(paths):
     hs, a, dev_a, dev_b = twins(paths["tri5k"], "tri5k")
-    dev_c = T.device(hs, "tri5k")
+    dev_c = device(hs, "tri5k")
     n = a["n_prims"]
     rng = np.random.default_rng(61)
     # every triangle thrown somewhere else in the scene: the refitted tree is far worse than a built one
@@ -354,7 +351,7 @@ def test_a_refit_the_policy_promotes(paths):
     assert cost_b["last_update_rebuilt"] == 1 and cost_b["refits_since_build"] == 0
     assert cost_a == cost_b == cost_c, (cost_a, cost_b, cost_c)
     assert_same(dev_a, dev_b, "tri5k", "a promoted refit, host and device route")
-    T.assert_same_tree(dev_b.export_bvh(), dev_c.export_bvh(), "a promoted refit and a rebuild")
+    assert_same_tree(dev_b.export_bvh(), dev_c.export_bvh(), "a promoted refit and a rebuild")
     # a small deformation afterwards, under a ratio it cannot reach, is a plain refit on both routes
     for dev in (dev_a, dev_b):
         dev.set_auto_rebuild(4.0)
@@ -363,11 +360,11 @@ def test_a_refit_the_policy_promotes(paths):
     dev_b.update_triangles(0, gpu(small), mode=p3d.UPDATE_REFIT)
     cost_a, cost_b = dev_a.bvh_cost(), dev_b.bvh_cost()
     assert cost_a == cost_b and cost_b["last_update_rebuilt"] == 0 and cost_b["refits_since_build"] == 1, (cost_a, cost_b)
-    T.assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "a refit that stays a refit")
+    assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "a refit that stays a refit")
 
 
 def test_an_accumulator_refuses_passes_until_reset(paths):
-    hs = T.load(paths["cornell"], 64)
+    hs = load(paths["cornell"], 64)
     a = hs.arrays()
     dev = p3d.DeviceScene(hs, bvh="device")
     cfg = p3d.pathtrace_config(accel=p3d.ACCEL_BVH, spp_sqrt=3, max_depth=8, seed=9)
@@ -423,7 +420,7 @@ def test_no_sources_is_update_prims_of_nothing(paths):
     assert dev_b.bvh_cost()["last_update_rebuilt"] == 1
     assert _raw(dev_b, [], mode=p3d.UPDATE_REFIT) == 0 and _raw(dev_b, [], mode=p3d.UPDATE_REFIT, null=True) == 0
     assert dev_b.update_triangles(0, d_soup, mode=p3d.UPDATE_REFIT) > 0  # the same size again: the staging is kept
-    T.assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "the same geometry once more")
+    assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "the same geometry once more")
 
 
 # 11. the three routes in turn, through the one staging buffer they share
@@ -443,13 +440,13 @@ def test_the_three_routes_share_one_stage(paths):
     with np.errstate(over="ignore"):
         assert np.isinf(np.float32(3e38) + a["prim_v"][victim, 3] * np.float32(3e38))
     rng = np.random.default_rng(81)
-    xforms = np.stack([T.rigid(a, rng, reach=0.02 + 0.002 * i) for i in range(n)])
-    xforms[victim] = T.IDENTITY
+    xforms = np.stack([rigid(a, rng, reach=0.02 + 0.002 * i) for i in range(n)])
+    xforms[victim] = IDENTITY
     xforms[victim][:, 3] = 3e38
     scale = np.full(n, 1.25, np.float32)
     scale[victim] = 3e38
     ranges = [(i, 1, i) for i in range(n)]
-    T.host_route(hs, dev_a, a, [r for r in ranges if r[0] != victim], xforms, scale, p3d.UPDATE_REFIT)  # A: the victim is left out
+    host_route(hs, dev_a, a, [r for r in ranges if r[0] != victim], xforms, scale, p3d.UPDATE_REFIT)  # A: the victim is left out
     with pytest.raises(p3d.P3DError) as e:
         dev_b.transform_prims(ranges, xforms, p3d.UPDATE_REFIT, sphere_scale=scale)
     assert e.value.code == -1 and "1 object" in str(e.value), e.value
@@ -459,7 +456,7 @@ def test_the_three_routes_share_one_stage(paths):
     host_spheres(hs, dev_a, a, s0, cr, p3d.UPDATE_REFIT)
     assert dev_b.update_spheres(s0, gpu(cr), mode=p3d.UPDATE_REFIT) > 0
     now = assert_same(dev_a, dev_b, "cornell", "step 2: two spheres from device memory")
-    assert T.frames_differ(now, moved)
+    assert frames_differ(now, moved)
     # 3. three objects from the host scene, which both scenes are bound to
     objs = np.array([t0, t0 + len(tri) // 2, s0 + 1], np.uint32)
     offsets = np.random.default_rng(83).uniform(-0.05, 0.05, (3, 3)).astype(np.float32)
@@ -475,6 +472,6 @@ def test_the_three_routes_share_one_stage(paths):
     assert dev_b.update_triangles(t0, gpu(soup), mode=p3d.UPDATE_REFIT) > 0
     last = assert_same(dev_a, dev_b, "cornell", "step 4: the triangle soup")
     # the triangles rest where step 4 put them (not where step 3, step 1 or the scene's file had them)
-    dev_b.transform_prims([(t0, len(tri), 0)], T.IDENTITY[None], p3d.UPDATE_REFIT)
-    T.assert_same_frames(assert_same(dev_a, dev_b, "cornell", "the identity on the triangles"), last, "the identity moved a triangle")
+    dev_b.transform_prims([(t0, len(tri), 0)], IDENTITY[None], p3d.UPDATE_REFIT)
+    assert_same_frames(assert_same(dev_a, dev_b, "cornell", "the identity on the triangles"), last, "the identity moved a triangle")
     assert dev_b.status() == 0

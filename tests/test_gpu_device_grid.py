@@ -4,22 +4,18 @@ The yardstick is the host builder, Grid::Build, through HostScene.arrays(grid=Tr
 the device grid must be that grid to the bit, so every comparison here is equality of bytes - exported arrays, colour bits,
 hit IDs, counters and query results against a scene created with the host's grid uploaded."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+from conftest import scene_path
+from frame_checks import CORNELL, RENDER_COUNTERS, assert_same_frames, assert_same_grid, frames, frames_differ, load, rays
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
 from scene_update_helpers import SPHERE, random_moves, translated
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
 RES = 192
-COUNTERS = ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_bounce", "rays_light", "node_tests",
-            "sphere_tests", "tri_tests", "box_tests", "plane_tests", "shaded_hits")
-GRID_KEYS = ("grid_bmin", "grid_bmax", "grid_cell_start", "grid_cell_items")
 SCENES = ["balls_low", "path_glass", "cornell", "tri5k", "tri100k", "one_sphere"]
 SEED = {"balls_low": 21, "tri5k": 22, "cornell": 24}
 SHAPE = {"balls_low": (49, 49, 3), "path_glass": (49, 49, 10), "cornell": (5, 5, 5), "tri5k": (5, 5, 5), "tri100k": (5, 5, 5),
@@ -55,12 +51,6 @@ def paths(tri5k_path, tri100k_path, tmp_path_factory):
     return out
 
 
-def load(path, res=RES):
-    hs = p3d.HostScene(path)
-    hs.set_resolution(res, res)
-    return hs
-
-
 _hosts = {}
 
 
@@ -79,53 +69,15 @@ def lists(a):
     return np.diff(a["grid_cell_start"].astype(np.int64))
 
 
-def assert_same_grid(got, want, what):
-    assert tuple(got["grid_n"]) == tuple(want["grid_n"]), "%s: %s cells, the host has %s" % (what, got["grid_n"], want["grid_n"])
-    for k in GRID_KEYS:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, "%s: %s has shape %s, the host's %s" % (what, k, got[k].shape, want[k].shape)
-        assert got[k].tobytes() == want[k].tobytes(), "%s: %s differs in %d entries" % (what, k, int((got[k] != want[k]).sum()))
-
-
-def configs(name):
+def grid_configs(name):
     out = [("whitted", p3d.whitted_config(accel=p3d.ACCEL_GRID, max_depth=4, collect_stats=1))]
     if name == "cornell":
         out.append(("path trace 4 spp", p3d.pathtrace_config(accel=p3d.ACCEL_GRID, spp_sqrt=2, max_depth=8, seed=3, collect_stats=1)))
     return out
 
 
-def frames(dev, name):
-    out = []
-    for label, cfg in configs(name):
-        rgb, hit, st = dev.render(cfg)
-        out.append((label, rgb, hit, {k: getattr(st, k) for k in COUNTERS}))
-    return out
-
-
-def assert_same_frames(a, b, what):
-    assert [f[0] for f in a] == [f[0] for f in b]
-    for (label, rgb_a, hit_a, st_a), (_, rgb_b, hit_b, st_b) in zip(a, b):
-        assert np.array_equal(hit_a, hit_b), "%s, %s: hit IDs differ in %d pixels" % (what, label, int((hit_a != hit_b).sum()))
-        bad = (rgb_a.view(np.uint32) != rgb_b.view(np.uint32)).any(-1)
-        assert not bad.any(), "%s, %s: %d pixels differ in some colour bit, max |diff| %g" % (
-            what, label, int(bad.sum()), float(np.abs(rgb_a - rgb_b).max()))
-        assert st_a == st_b, "%s, %s: counters %s / %s" % (what, label, st_a, st_b)
-
-
-def frames_differ(a, b):
-    return any((ra.view(np.uint32) != rb.view(np.uint32)).any() or (ha != hb).any() for (_, ra, ha, _), (_, rb, hb, _) in zip(a, b))
-
-
-def rays(n=40000, seed=5):
-    rng = np.random.default_rng(seed)
-    o = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
-    d = (rng.uniform(-1, 1, (n, 3)) - o).astype(np.float32)
-    d[: n // 8, rng.integers(0, 3)] = 0
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return o, d
-
-
 def assert_same_queries(a, b, what):
-    o, d = rays()
+    o, d = rays(axis_parallel=True)
     hit_a, p_a, t_a = a.trace_closest(p3d.ACCEL_GRID, o, d, want_t=True)
     hit_b, p_b, t_b = b.trace_closest(p3d.ACCEL_GRID, o, d, want_t=True)
     assert np.array_equal(hit_a, hit_b), what
@@ -155,7 +107,7 @@ def test_grid_frames_match_the_uploaded_grid(name, host):
     hs, _ = host(name)
     dev = p3d.DeviceScene(hs, bvh="device", grid="device")
     twin = p3d.DeviceScene(hs, bvh="device", grid=True)
-    assert_same_frames(frames(dev, name), frames(twin, name), name)
+    assert_same_frames(frames(dev, grid_configs(name), skip_unsupported=False), frames(twin, grid_configs(name), skip_unsupported=False), name)
     assert_same_queries(dev, twin, name)
     dev.close()
     twin.close()
@@ -172,9 +124,9 @@ def moves(hs, name, round_):
 @pytest.mark.parametrize("mode", [p3d.UPDATE_REFIT, p3d.UPDATE_REBUILD], ids=["refit", "rebuild"])
 @pytest.mark.parametrize("name", ["balls_low", "tri5k", "cornell"])
 def test_update_rebuilds_the_grid(name, mode, paths):
-    hs = load(paths[name])
+    hs = load(paths[name], RES)
     dev = p3d.DeviceScene(hs, bvh="device", grid="device")
-    last = frames(dev, name)
+    last = frames(dev, grid_configs(name), skip_unsupported=False)
     for round_ in range(2):  # the second rebuild runs in the arrays the first ones left
         objs, new_v = moves(hs, name, round_)
         hs.set_geometry(objs, new_v)
@@ -182,8 +134,8 @@ def test_update_rebuilds_the_grid(name, mode, paths):
         what = "%s, update %d" % (name, round_)
         assert_same_grid(dev.export_grid(), hs.arrays(grid=True), what)
         fresh = p3d.DeviceScene(hs, bvh="device", grid=True)
-        now = frames(dev, name)
-        assert_same_frames(now, frames(fresh, name), what)
+        now = frames(dev, grid_configs(name), skip_unsupported=False)
+        assert_same_frames(now, frames(fresh, grid_configs(name), skip_unsupported=False), what)
         assert frames_differ(now, last), "the move changed no pixel"
         last = now
         fresh.close()
@@ -194,7 +146,7 @@ def test_update_rebuilds_the_grid(name, mode, paths):
 
 
 def test_grid_arrays_grow_and_shrink(paths):
-    hs = load(paths["balls_low"])
+    hs = load(paths["balls_low"], RES)
     original = hs.arrays(grid=True)
     sphere = int(np.nonzero(original["prim_type"] == SPHERE)[0][0])
     objs = np.array([sphere], np.uint32)
@@ -211,7 +163,7 @@ def test_grid_arrays_grow_and_shrink(paths):
     dev.update_prims(objs, p3d.UPDATE_REFIT)
     assert_same_grid(dev.export_grid(), grown, "grown")
     twin = p3d.DeviceScene(hs, bvh="device", grid=True)
-    assert_same_frames(frames(dev, "balls_low"), frames(twin, "balls_low"), "grown")
+    assert_same_frames(frames(dev, grid_configs("balls_low"), skip_unsupported=False), frames(twin, grid_configs("balls_low"), skip_unsupported=False), "grown")
     twin.close()
     hs.set_geometry(objs, home)
     dev.update_prims(objs, p3d.UPDATE_REFIT)
@@ -231,13 +183,13 @@ def _export_raw(dev, n_start, n_items):
 
 
 def test_refusals(paths):
-    hs = load(paths["balls_low"])
+    hs = load(paths["balls_low"], RES)
     cfg = p3d.whitted_config(accel=p3d.ACCEL_GRID, max_depth=4, collect_stats=1)
     lib = p3d.lib()
 
     def frame(s, c=cfg):
         rgb, hit, st = s.render(c)
-        return rgb.tobytes(), hit.tobytes(), tuple(getattr(st, k) for k in COUNTERS)
+        return rgb.tobytes(), hit.tobytes(), tuple(getattr(st, k) for k in RENDER_COUNTERS)
 
     host_tree = p3d.DeviceScene(hs, bvh=True)
     with pytest.raises(p3d.P3DError) as e:

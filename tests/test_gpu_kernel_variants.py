@@ -24,70 +24,16 @@ the grid (bound 1), which would land on kernels other tests cover: those two acc
 import numpy as np
 import pytest
 
+from frame_checks import TOL, _pair, assert_same_bits, check_whitted, oracle_cfg_like
 import p3d_amd as p3d
-from conftest import scene_path
-from fuzz_scenes import random_scene
-from test_gpu_adaptive import assert_same_bits
-from test_gpu_parity import TOL, _pair, check_whitted, oracle_cfg_like
+from variant_scenes import ACCEL_IDS, ACCEL_VALUES, FRAMES, PT_FRAME, scene_files  # noqa: F401 (scene_files is a fixture)
 
 pytestmark = pytest.mark.gpu
 
-ACCELS = [p3d.ACCEL_NONE, p3d.ACCEL_GRID, p3d.ACCEL_BVH]
-ACCEL_IDS = ["none", "grid", "bvh"]
-FRAMES = [(64, 48), (72, 40)]  # several waves per launch and several tile bands, whole tiles
-PT_FRAME = (48, 40)
 PT_COUNTERS = ("rays_primary", "rays_bounce", "rays_light", "node_tests", "sphere_tests", "tri_tests", "shaded_hits")  # test_path_tracer
 
 
-def staged_bytes(path, accel, legacy=False):
-    """Bytes of the staged range of a Whitted frame by the layout rule, from the host-side descriptor alone."""
-    d = p3d.HostScene(path, legacy_f11=legacy).desc(bvh=True)
-    f4 = 2 * d.n_bvh_nodes + 3 * d.n_bvh_prim_index + d.n_prims + 4 * d.n_materials + 2 * d.n_lights
-    return 16 * (f4 + (3 * d.n_prims if accel != p3d.ACCEL_BVH else 0))
-
-
-def write_spheres(path, n, mats, lights, seed=1, glass=0):
-    """test_gpu_stage_entry.write_spheres with a glass option: n spheres on a jittered lattice, the first `mats` of them with
-    a material of their own (every second one reflective; with glass = g, every g-th transmissive AND reflective), `lights` lights."""
-    rng = np.random.default_rng(seed)
-    lines = ["bclr 0.1 0.2 0.3", "v", "from 0 -7 2", "at 0 0 0", "up 0 0 1", "angle 45", "hither 0.01", "resolution 64 64",
-             "aperture 0", "focal 1"]
-    for k in range(lights):
-        lines.append("l %g %g %g 0.6 0.6 0.6" % (3 - 2 * k, -4, 5 + k))
-    side = max(1, int(np.ceil(n ** (1 / 3))))
-    for k in range(n):
-        if k < mats:
-            if glass and k % glass == glass - 1:
-                lines.append("f %g %g %g 0.3 1 1 1 0.4 40 0.8 1.5 0 0 0" % (0.2 + 0.6 * rng.random(), 0.3, 0.8 * rng.random()))
-            else:
-                lines.append("f %g %g %g 0.7 1 1 1 %g 20 0 1 0 0 0" % (0.2 + 0.6 * rng.random(), 0.3, 0.8 * rng.random(), 0.3 if k % 2 else 0.0))
-        x, y, z = k % side, (k // side) % side, k // (side * side)
-        s = 3.0 / side
-        lines.append("s %g %g %g %g" % ((x - side / 2 + 0.5) * s + 0.1 * s * rng.random(), (y - side / 2 + 0.5) * s, (z - side / 2 + 0.5) * s, 0.33 * s))
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    return path
-
-
-# ---- scenes: (path, legacy) by name, device scene + oracle scene per (name, frame) made once ----
-
-@pytest.fixture(scope="module")
-def scene_files(tmp_path_factory, tri5k_path):
-    d = tmp_path_factory.mktemp("variants")
-    return {
-        # PT-L2: 543 objects, 104 KB, tree depth 12 - the oracle's deepest stack over the BVH is 11 entries, 3 beyond the window
-        "pt_l2": (random_scene(2100, str(d / "pt_l2.p3f"), n_spheres=260, n_tris=260, n_boxes=20, n_lights=0, emitters=3, res=PT_FRAME), False),
-        "path_glass": (scene_path("path_glass.p3f"), False),
-        # W-SPILL
-        "balls_medium": (scene_path("balls_medium.p3f"), True),
-        # W-SPILL-GHOSTS: 150 spheres, 40 materials (13 of them glass), 3 lights
-        "spill_spheres": (write_spheres(str(d / "spill_spheres.p3f"), 150, 40, 3, glass=3), False),
-        # W-L2-GHOSTS: 232 objects, 33 KB over the BVH; the "glass" kind of random_scene is transmissive and reflective
-        "l2_ghosts": (random_scene(1000, str(d / "l2_ghosts.p3f"), n_spheres=100, n_tris=120, n_boxes=12, res=FRAMES[0]), False),
-        # W-L2
-        "tri5k": (tri5k_path, False),
-        "balls_low": (scene_path("balls_low.p3f"), False),
-    }
+# ---- device scene + oracle scene per (name, frame), made once ----
 
 
 @pytest.fixture(scope="module")
@@ -159,7 +105,7 @@ STAGED_PT = dict(lds_scene=True, lds_spill=False, stack_mode=p3d.STACK_LDS8)
 
 @pytest.mark.parametrize("stats", [1, 0], ids=["stats", "plain"])
 @pytest.mark.parametrize("spp_sqrt", [3, 4], ids=["sub1", "sub4"])
-@pytest.mark.parametrize("accel", ACCELS, ids=ACCEL_IDS)
+@pytest.mark.parametrize("accel", ACCEL_VALUES, ids=ACCEL_IDS)
 def test_path_tracer_over_a_scene_traversed_from_l2(pt_frame, accel, spp_sqrt, stats):
     """pt_kernel<A, false, STATS, SUB>: windowed stack, emitters and deferred dielectric branches from global memory."""
     pt_frame("pt_l2", accel, spp_sqrt, stats, want=L2)
@@ -177,7 +123,7 @@ def test_path_tracer_staged_grid_one_lane_per_pixel_with_counters(pt_frame):
 # ---- 2. pt_adaptive_kernel: with rel_error = 0 the passes add up to the one-shot frame, bit for bit ----
 
 @pytest.mark.parametrize("spp_sqrt,passes", [(3, (1,) * 9), (6, (16, 20))], ids=["sub1", "sub4"])
-@pytest.mark.parametrize("accel", ACCELS, ids=ACCEL_IDS)
+@pytest.mark.parametrize("accel", ACCEL_VALUES, ids=ACCEL_IDS)
 @pytest.mark.parametrize("name,stats", [("pt_l2", 1), ("pt_l2", 0), ("path_glass", 1)], ids=["l2-stats", "l2-plain", "staged-stats"])
 def test_adaptive_passes_with_zero_threshold_are_the_one_shot_frame(pairs, pt_frame, name, accel, spp_sqrt, passes, stats):
     """pt_adaptive_kernel<A, false, *, *> over PT-L2 and <A, true, true, *> over a staged scene (tests/test_gpu_adaptive.py
@@ -267,11 +213,11 @@ def test_a_pixel_with_negative_mean_luminance_never_counts_as_converged(pairs):
 
 # (scene, accel) of the staged + spill cases: balls_medium over the BVH, the generated scene on every accel.  balls_medium
 # over the object loop and the grid fits LDS whole (module docstring) and would land on kernels other tests cover.
-SPILL_CASES = [("balls_medium", p3d.ACCEL_BVH)] + [("spill_spheres", a) for a in ACCELS]
+SPILL_CASES = [("balls_medium", p3d.ACCEL_BVH)] + [("spill_spheres", a) for a in ACCEL_VALUES]
 SPILL_IDS = ["balls_medium-bvh"] + ["spill_spheres-" + a for a in ACCEL_IDS]
 
 
-@pytest.mark.parametrize("name,accel", [("tri5k", a) for a in ACCELS] + SPILL_CASES, ids=["tri5k-" + a for a in ACCEL_IDS] + SPILL_IDS)
+@pytest.mark.parametrize("name,accel", [("tri5k", a) for a in ACCEL_VALUES] + SPILL_CASES, ids=["tri5k-" + a for a in ACCEL_IDS] + SPILL_IDS)
 def test_pixel_centre_features_with_the_window_stack(pairs, name, accel):
     """test_gpu_denoise.test_pixel_centre_features_match_the_traversal over a scene traversed from L2 and over staged + spill
     scenes (feature_kernel<A, false, kStackWindow>, <A, true, kStackWindow>), the first hits also held to the oracle's."""

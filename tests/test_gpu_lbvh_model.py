@@ -4,24 +4,21 @@ The tree is a function of the object boxes, so p3d_scene_export_bvh must return 
 model's depth: after create, after a REBUILD, and, boxes only, after a REFIT.  The degenerate scenes (coincident centres, flat
 axes, an outlier, cell edges, a deep chain) are traversed as well: closest hits over the device tree against the object
 loop of the same scene, and Whitted frames of the two deepest against a scene uploaded with the exported tree."""
-import os
 
 import numpy as np
 import pytest
 
+from conftest import scene_path
+from frame_checks import CORNELL, frames
 import fuzz_scenes
 import lbvh_reference as ref
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
 from scene_update_helpers import SPHERE, random_moves
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
 COUNTS = [1, 2, 3, 4, 5, 255, 256, 257, 511, 512, 513]
 SYNTHETIC = [name for name, _, _ in ref.synthetic_scenes()]
-COUNTERS = ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_bounce", "rays_light", "node_tests",
-            "sphere_tests", "tri_tests", "box_tests", "plane_tests", "shaded_hits")
 
 
 @pytest.fixture(scope="module")
@@ -155,18 +152,10 @@ def test_closest_hits_over_a_degenerate_tree_are_the_object_loops(name, paths):
         assert name == "duplicates" or diff < 1e-3
 
 
-def frames(dev, accel=p3d.ACCEL_BVH):
-    out = []
-    for label, mode in (("literal", p3d.STACK_LITERAL), ("per pixel", p3d.STACK_PER_PIXEL)):
-        try:
-            rgb, hit, st = dev.render(p3d.whitted_config(accel=accel, max_depth=2, stack_mode=mode, collect_stats=1))
-        except p3d.P3DError as e:
-            if e.code != -3:  # P3D_ERR_UNSUPPORTED: this scene has no such mode
-                raise
-            continue
-        out.append((label, rgb, hit, {k: getattr(st, k) for k in COUNTERS}))
-    assert out
-    return out
+def stack_modes(accel=p3d.ACCEL_BVH):
+    """(label, cfg): Whitted depth 2 in both stack modes"""
+    return [(label, p3d.whitted_config(accel=accel, max_depth=2, stack_mode=mode, collect_stats=1))
+            for label, mode in (("literal", p3d.STACK_LITERAL), ("per pixel", p3d.STACK_PER_PIXEL))]
 
 
 @pytest.mark.parametrize("name", ["chain", "outlier"])
@@ -179,13 +168,13 @@ def test_frames_over_a_deep_device_tree(name, paths):
     tree = dev.export_bvh()
     ref.assert_same_tree(tree, model(hs.arrays()), name)
     twin = p3d.DeviceScene(hs, bvh=tree)
-    mine, theirs = frames(dev), frames(twin)
+    mine, theirs = frames(dev, stack_modes()), frames(twin, stack_modes())
     assert [f[0] for f in mine] == [f[0] for f in theirs]
     for (label, rgb_a, hit_a, st_a), (_, rgb_b, hit_b, st_b) in zip(mine, theirs):
         assert np.array_equal(hit_a, hit_b), "%s, %s: hit IDs differ in %d pixels" % (name, label, int((hit_a != hit_b).sum()))
         assert rgb_a.tobytes() == rgb_b.tobytes(), "%s, %s: max |diff| %g" % (name, label, float(np.abs(rgb_a - rgb_b).max()))
         assert st_a == st_b, "%s, %s: counters %s / %s" % (name, label, st_a, st_b)
-    plain = frames(dev, p3d.ACCEL_NONE)[0][2]
+    plain = frames(dev, stack_modes(p3d.ACCEL_NONE))[0][2]
     for label, _, hit, _ in mine:
         px = float((hit != plain).mean())
         print("%s, %s (depth %d): %.3f of the pixels hit, hit IDs differ from the object loop's on %.3g" % (

@@ -12,11 +12,12 @@ import numpy as np
 import pytest
 import torch
 
+from device_geometry_helpers import deformed_mesh
+from frame_checks import as_bytes, gpu
 import intersect_reference as ref
+from live_scene_checks import plan
 import nearest_reference as near
 import p3d_amd as p3d
-import test_gpu_scene_transform as T
-from device_geometry_helpers import deformed_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -25,14 +26,6 @@ ALL = ("object", "dist", "closest", "normal")
 FLT_MAX = near.FLT_MAX
 INVALID, UNSUPPORTED = -1, -3
 SEED = {"mixed": 400, "mixed_planes": 401, "planes": 402, "axis_aligned": 403, "tri5k": 404}  # the CPU suite's
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 class World:
@@ -73,19 +66,19 @@ def assert_answers(got, want, what):
     """object, dist and closest equal `want` = (object, dist, closest) bit for bit; the no-answer values are exact"""
     n = len(got["object"])
     assert got["object"].dtype == np.int32 and (got["object"] == want[0][:n]).all(), what + ": object"
-    assert bits(got["dist"]) == bits(want[1][:n]), what + ": dist"
-    assert bits(got["closest"]) == bits(want[2][:n]), what + ": closest"
+    assert as_bytes(got["dist"]) == as_bytes(want[1][:n]), what + ": dist"
+    assert as_bytes(got["closest"]) == as_bytes(want[2][:n]), what + ": closest"
     none = got["object"] < 0
-    assert (got["dist"][none] == FLT_MAX).all() and bits(got["closest"][none]) == bits(np.zeros((int(none.sum()), 3), np.float32)), what + ": the no-answer values"
+    assert (got["dist"][none] == FLT_MAX).all() and as_bytes(got["closest"][none]) == as_bytes(np.zeros((int(none.sum()), 3), np.float32)), what + ": the no-answer values"
 
 
 def assert_normals(dev, got, what, most=24):
     obj, q, nrm = got["object"], got["closest"], got["normal"]
     none = obj < 0
-    assert bits(nrm[none]) == bits(np.zeros((int(none.sum()), 3), np.float32)), what + ": a normal where nothing was found"
+    assert as_bytes(nrm[none]) == as_bytes(np.zeros((int(none.sum()), 3), np.float32)), what + ": a normal where nothing was found"
     for j in np.unique(obj[~none])[:most]:
         m = obj == j
-        assert bits(nrm[m]) == bits(dev.object_normal(int(j), q[m])), "%s: the normal of object %d" % (what, j)
+        assert as_bytes(nrm[m]) == as_bytes(dev.object_normal(int(j), q[m])), "%s: the normal of object %d" % (what, j)
 
 
 @pytest.mark.parametrize("n", BATCHES)
@@ -107,7 +100,7 @@ def test_the_device_form_is_the_host_form(n, worlds):
                 mine = {"object": torch.full((n,), 77, dtype=torch.int32, device="cuda"), "closest": torch.full((n, 3), 5.0, device="cuda")}
                 back = dev.nearest_device(accel, w.d_p[:n], max_dist=w.d_limits[:n], want=("closest",), out=mine)
                 assert list(back) == ["object", "closest"] and back["object"] is mine["object"] and back["closest"] is mine["closest"]
-                assert (mine["object"].cpu().numpy() == w.limited[0][:n]).all() and bits(mine["closest"].cpu().numpy()) == bits(w.limited[2][:n]), what
+                assert (mine["object"].cpu().numpy() == w.limited[0][:n]).all() and as_bytes(mine["closest"].cpu().numpy()) == as_bytes(w.limited[2][:n]), what
                 only = dev.nearest_device(accel, w.d_p[:n], want=())
                 assert list(only) == ["object"] and (only["object"].cpu().numpy() == w.free[0][:n]).all(), what
             assert dev.status() == 0
@@ -123,7 +116,7 @@ def test_limits_that_keep_nothing_or_everything(worlds):
                     got = ask(dev, accel, w.d_p[:n], gpu(np.full(n, value, np.float32)))
                     assert (got["object"] == -1).all() and (got["dist"] == FLT_MAX).all(), "%s: a limit of %g" % (what, value)
                     for k in ("closest", "normal"):
-                        assert bits(got[k]) == bits(np.zeros((n, 3), np.float32)), "%s: a limit of %g, %s" % (what, value, k)
+                        assert as_bytes(got[k]) == as_bytes(np.zeros((n, 3), np.float32)), "%s: a limit of %g, %s" % (what, value, k)
                 assert_answers(ask(dev, accel, w.d_p[:n], gpu(np.full(n, np.inf, np.float32))), w.free, what + ", infinite limits")
                 # the limit at the distance itself (d2 against the float32 square of sqrtf(d2): the host form says which way), and twice it
                 d = w.free[1][:n]
@@ -238,15 +231,15 @@ def test_behind_a_refit_on_the_same_stream(worlds, tri5k_path):
         dev.nearest_device(p3d.ACCEL_BVH, w.d_p[:n], max_dist=w.d_limits[:n], want=ALL, stream=side, out=outs)
     side.synchronize()
     got = {k: v.cpu().numpy() for k, v in outs.items()}
-    assert bits(moved.cpu().numpy()) == bits(soup)
+    assert as_bytes(moved.cpu().numpy()) == as_bytes(soup)
     hs.set_geometry(*p3d.deformed(a["prim_v"], 0, soup))
     want = hs.nearest(w.p[:n], max_dist=w.limits[:n])
     assert_answers(got, want, "tri5k behind a refit")
-    assert (want[0] != w.limited[0][:n]).any() or bits(want[1]) != bits(w.limited[1][:n]), "the refit moved nothing the points can see"
+    assert (want[0] != w.limited[0][:n]).any() or as_bytes(want[1]) != as_bytes(w.limited[1][:n]), "the refit moved nothing the points can see"
     fresh = p3d.DeviceScene(hs, bvh=False)
     again = ask(fresh, p3d.ACCEL_NONE, w.d_p[:n], w.d_limits[:n])
     for k in ALL:
-        assert bits(got[k]) == bits(again[k]), "tri5k behind a refit, against a fresh scene: " + k
+        assert as_bytes(got[k]) == as_bytes(again[k]), "tri5k behind a refit, against a fresh scene: " + k
     assert 0 < (got["object"] >= 0).sum() < n
     assert dev.status() == 0 and fresh.status() == 0
 
@@ -256,7 +249,7 @@ def test_behind_a_pose_on_the_same_stream(worlds):
     hs = p3d.HostScene(w.path)
     a = hs.arrays()
     dev = p3d.DeviceScene(hs, bvh="device")
-    ranges, xforms, scale = T.plan(a, 93)  # spheres and triangles under a rigid move, boxes under a positive-diagonal one
+    ranges, xforms, scale = plan(a, 93)  # spheres and triangles under a rigid move, boxes under a positive-diagonal one
     dev.set_rig(ranges, 2)
     n = 4099
     side = torch.cuda.Stream()
@@ -272,9 +265,9 @@ def test_behind_a_pose_on_the_same_stream(worlds):
     want = hs.nearest(w.p[:n])
     assert_answers(got, want, "mixed behind a pose")
     assert_answers(lim, hs.nearest(w.p[:n], max_dist=w.limits[:n]), "mixed behind a pose, limits")
-    assert bits(want[1]) != bits(w.free[1][:n]), "the pose moved nothing"
+    assert as_bytes(want[1]) != as_bytes(w.free[1][:n]), "the pose moved nothing"
     fresh = p3d.DeviceScene(hs, bvh=False)
     again = ask(fresh, p3d.ACCEL_NONE, w.d_p[:n])
     for k in ALL:
-        assert bits(got[k]) == bits(again[k]), "mixed behind a pose, against a fresh scene: " + k
+        assert as_bytes(got[k]) == as_bytes(again[k]), "mixed behind a pose, against a fresh scene: " + k
     assert dev.status() == 0 and fresh.status() == 0

@@ -10,12 +10,13 @@ import numpy as np
 import pytest
 import torch
 
+from device_geometry_helpers import deformed_mesh
+from frame_checks import as_bytes, gpu
 import intersect_reference as ref
+from live_scene_checks import plan
 import nearest_k_reference as nk
 import nearest_reference as near
 import p3d_amd as p3d
-import test_gpu_scene_transform as T
-from device_geometry_helpers import deformed_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -26,14 +27,6 @@ FLT_MAX = near.FLT_MAX
 INVALID, UNSUPPORTED = -1, -3
 SEED = {"mixed": 400, "mixed_planes": 401, "planes": 402, "axis_aligned": 403, "tri5k": 404}  # the CPU suite's
 TREES = {"mixed": ("host", "device"), "axis_aligned": ("host",), "tri5k": ("device",), "mixed_planes": ("none",), "planes": ("none",)}
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 class World:
@@ -89,21 +82,21 @@ def assert_answers(got, want, k, what):
     n = len(got["count"])
     assert got["count"].dtype == np.int32 and got["count"].shape == (n,) and (got["count"] == want[0][:n]).all(), what + ": count"
     assert got["object"].dtype == np.int32 and got["object"].shape == (n, k) and (got["object"] == want[1][:n]).all(), what + ": object"
-    assert got["dist"].shape == (n, k) and bits(got["dist"]) == bits(want[2][:n]), what + ": dist"
-    assert got["closest"].shape == (n, k, 3) and bits(got["closest"]) == bits(want[3][:n]), what + ": closest"
+    assert got["dist"].shape == (n, k) and as_bytes(got["dist"]) == as_bytes(want[2][:n]), what + ": dist"
+    assert got["closest"].shape == (n, k, 3) and as_bytes(got["closest"]) == as_bytes(want[3][:n]), what + ": closest"
     none = np.arange(k)[None, :] >= got["count"][:, None]
     assert (got["object"][none] == -1).all() and (got["object"][~none] >= 0).all(), what + ": the rows behind count"
-    assert (got["dist"][none] == FLT_MAX).all() and bits(got["closest"][none]) == bits(np.zeros((int(none.sum()), 3), np.float32)), what + ": the no-answer values"
+    assert (got["dist"][none] == FLT_MAX).all() and as_bytes(got["closest"][none]) == as_bytes(np.zeros((int(none.sum()), 3), np.float32)), what + ": the no-answer values"
 
 
 def assert_normals(dev, got, what, most=24):
     obj, q, nrm = got["object"], got["closest"], got["normal"]
     assert nrm.shape == q.shape
     none = obj < 0
-    assert bits(nrm[none]) == bits(np.zeros((int(none.sum()), 3), np.float32)), what + ": a normal in a row behind count"
+    assert as_bytes(nrm[none]) == as_bytes(np.zeros((int(none.sum()), 3), np.float32)), what + ": a normal in a row behind count"
     for j in np.unique(obj[~none])[:most]:
         m = obj == j
-        assert bits(nrm[m]) == bits(dev.object_normal(int(j), q[m])), "%s: the normal of object %d" % (what, j)
+        assert as_bytes(nrm[m]) == as_bytes(dev.object_normal(int(j), q[m])), "%s: the normal of object %d" % (what, j)
 
 
 @pytest.mark.parametrize("k", KS)
@@ -131,7 +124,7 @@ def test_the_device_form_is_the_host_form(n, k, worlds):
                 assert list(back) == ["count", "object", "closest"] and all(back[key] is mine[key] for key in mine)
                 want = w.limited(k)
                 assert (mine["count"].cpu().numpy() == want[0][:n]).all() and (mine["object"].cpu().numpy() == want[1][:n]).all(), what
-                assert bits(mine["closest"].cpu().numpy()) == bits(want[3][:n]), what
+                assert as_bytes(mine["closest"].cpu().numpy()) == as_bytes(want[3][:n]), what
                 only = dev.nearest_k_device(accel, w.d_p[:n], k, want=())
                 assert list(only) == ["count", "object"] and (only["object"].cpu().numpy() == w.free(k)[1][:n]).all(), what
                 assert (only["count"].cpu().numpy() == w.free(k)[0][:n]).all(), what
@@ -149,13 +142,13 @@ def test_k_1_is_nearest_device(worlds):
             one = {name: v.cpu().numpy() for name, v in dev.nearest_device(accel, w.d_p, max_dist=d_m, want=("object", "dist", "closest", "normal")).items()}
             got = ask(dev, accel, w.d_p, 1, d_m)
             for name in ("object", "dist", "closest", "normal"):
-                assert bits(got[name]) == bits(one[name]), "accel %d, %s: %s" % (accel, "no limit" if d_m is None else "limits", name)
+                assert as_bytes(got[name]) == as_bytes(one[name]), "accel %d, %s: %s" % (accel, "no limit" if d_m is None else "limits", name)
             assert (got["count"] == (one["object"] >= 0)).all()
             assert d_m is None or 0 < got["count"].sum() < n
             # (nearest_device is the k = 1 launch of the same kernel: the independent statement is the host's k = 1 brute force)
             h_object, h_dist, h_closest = host[d_m is not None]
             assert (got["object"][:, 0] == h_object).all(), "accel %d: HostScene.nearest's object" % accel
-            assert bits(got["dist"][:, 0]) == bits(h_dist) and bits(got["closest"][:, 0]) == bits(h_closest), "accel %d: HostScene.nearest's bits" % accel
+            assert as_bytes(got["dist"][:, 0]) == as_bytes(h_dist) and as_bytes(got["closest"][:, 0]) == as_bytes(h_closest), "accel %d: HostScene.nearest's bits" % accel
     assert dev.status() == 0
 
 
@@ -169,7 +162,7 @@ def test_limits_that_keep_nothing_or_everything(worlds):
                     got = ask(dev, accel, w.d_p[:n], k, gpu(np.full(n, value, np.float32)))
                     assert (got["count"] == 0).all() and (got["object"] == -1).all() and (got["dist"] == FLT_MAX).all(), "%s: a limit of %g" % (what, value)
                     for key in ("closest", "normal"):
-                        assert bits(got[key]) == bits(np.zeros((n, k, 3), np.float32)), "%s: a limit of %g, %s" % (what, value, key)
+                        assert as_bytes(got[key]) == as_bytes(np.zeros((n, k, 3), np.float32)), "%s: a limit of %g, %s" % (what, value, key)
                 assert_answers(ask(dev, accel, w.d_p[:n], k, gpu(np.full(n, np.inf, np.float32))), w.free(k), k, what + ", infinite limits")
 
 
@@ -303,16 +296,16 @@ def test_behind_a_refit_on_the_same_stream(worlds, tri5k_path):
         dev.nearest_k_device(p3d.ACCEL_BVH, w.d_p[:n], k, max_dist=d_lim[:n], want=ALL, stream=side, out=outs)
     side.synchronize()
     got = {name: v.cpu().numpy() for name, v in outs.items()}
-    assert bits(moved.cpu().numpy()) == bits(soup)
+    assert as_bytes(moved.cpu().numpy()) == as_bytes(soup)
     hs.set_geometry(*p3d.deformed(a["prim_v"], 0, soup))
     want = hs.nearest_k(w.p[:n], k, max_dist=lim[:n])
     assert_answers(got, want, k, "tri5k behind a refit")
     before = w.limited(k)
-    assert (want[1] != before[1][:n]).any() or bits(want[2]) != bits(before[2][:n]), "the refit moved nothing the points can see"
+    assert (want[1] != before[1][:n]).any() or as_bytes(want[2]) != as_bytes(before[2][:n]), "the refit moved nothing the points can see"
     fresh = p3d.DeviceScene(hs, bvh=False)
     again = ask(fresh, p3d.ACCEL_NONE, w.d_p[:n], k, d_lim[:n])
     for name in ALL:
-        assert bits(got[name]) == bits(again[name]), "tri5k behind a refit, against a fresh scene: " + name
+        assert as_bytes(got[name]) == as_bytes(again[name]), "tri5k behind a refit, against a fresh scene: " + name
     assert (got["count"] == 0).any() and (got["count"] == k).any() and ((got["count"] > 0) & (got["count"] < k)).any()
     assert dev.status() == 0 and fresh.status() == 0
 
@@ -322,7 +315,7 @@ def test_behind_a_pose_on_the_same_stream(worlds):
     hs = p3d.HostScene(w.path)
     a = hs.arrays()
     dev = p3d.DeviceScene(hs, bvh="device")
-    ranges, xforms, scale = T.plan(a, 93)  # spheres and triangles under a rigid move, boxes under a positive-diagonal one
+    ranges, xforms, scale = plan(a, 93)  # spheres and triangles under a rigid move, boxes under a positive-diagonal one
     dev.set_rig(ranges, 2)
     n, k = 4099, 4
     lim, d_lim = w.limits(k)
@@ -339,10 +332,10 @@ def test_behind_a_pose_on_the_same_stream(worlds):
     want = hs.nearest_k(w.p[:n], k)
     assert_answers(got, want, k, "mixed behind a pose")
     assert_answers(lim_got, hs.nearest_k(w.p[:n], k, max_dist=lim[:n]), k, "mixed behind a pose, limits")
-    assert bits(want[2]) != bits(w.free(k)[2][:n]), "the pose moved nothing"
+    assert as_bytes(want[2]) != as_bytes(w.free(k)[2][:n]), "the pose moved nothing"
     fresh = p3d.DeviceScene(hs, bvh=False)
     for d_m, mine in ((None, got), (d_lim[:n], lim_got)):
         again = ask(fresh, p3d.ACCEL_NONE, w.d_p[:n], k, d_m)
         for name in ALL:
-            assert bits(mine[name]) == bits(again[name]), "mixed behind a pose, against a fresh scene: " + name
+            assert as_bytes(mine[name]) == as_bytes(again[name]), "mixed behind a pose, against a fresh scene: " + name
     assert dev.status() == 0 and fresh.status() == 0

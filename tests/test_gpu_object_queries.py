@@ -8,13 +8,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from frame_checks import ACCELS, same_bits_or_nan
 import intersect_reference as ref
-import p3d_amd as p3d
 from oracle import binding as ob
+import p3d_amd as p3d
 
 pytestmark = pytest.mark.gpu
 
-ACCELS = {"none": p3d.ACCEL_NONE, "grid": p3d.ACCEL_GRID, "bvh": p3d.ACCEL_BVH}
 SENTINEL = np.float32(123.0)
 BATCHES = [1, 63, 64, 65, 129, 4099]  # kBlock is 64: a lone lane, a full wave, one lane over, a ragged last block of many
 
@@ -44,12 +44,6 @@ def objects(worlds):
     return {name: w.objs for name, w in worlds.items() if name != "edges"}
 
 
-def same_bits(a, b):
-    """float32 arrays equal in bits, a NaN on both sides counting as equal -> mask"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
 def oracle_answers(sc, i, o, d):
     """-> (hit, t, direction out, normal at the point o + t d of a hit or at the origin of a miss, those points)"""
     out = [sc.object_intercepts(i, o[k], d[k]) for k in range(len(o))]
@@ -66,10 +60,10 @@ def assert_equals_oracle(dev, i, o, d, want, what):
     hit, t, d_out, nrm, p = want
     g_hit, g_t, g_d = dev.object_intercepts(i, o, d, t_init=SENTINEL)
     assert (g_hit == hit).all(), "%s: %d decisions differ from the oracle's" % (what, int((g_hit != hit).sum()))
-    assert same_bits(g_t[hit], t[hit]).all(), what + ": t differs in some bit"
+    assert same_bits_or_nan(g_t[hit], t[hit]).all(), what + ": t differs in some bit"
     assert (g_t[~hit].view(np.uint32) == SENTINEL.view(np.uint32)).all(), what + ": t was written on a miss"
-    assert same_bits(g_d, d_out).all(), what + ": the direction out differs in some bit"
-    assert same_bits(dev.object_normal(i, p), nrm).all(), what + ": a normal differs in some bit"
+    assert same_bits_or_nan(g_d, d_out).all(), what + ": the direction out differs in some bit"
+    assert same_bits_or_nan(dev.object_normal(i, p), nrm).all(), what + ": a normal differs in some bit"
     return g_hit, g_t, g_d
 
 
@@ -187,7 +181,7 @@ def test_crafted_box_normal_points(case, worlds):
     p = np.array(pts, np.float32)
     got = w.dev.object_normal(i, p)
     want = np.stack([w.sc.object_normal(i, q) for q in p])
-    assert same_bits(got, want).all(), case
+    assert same_bits_or_nan(got, want).all(), case
     model, margin = ref.normal(w.objs[i], p)
     ok = margin >= ref.THRESHOLD
     assert (got[ok] == model[ok]).all(), case
@@ -248,7 +242,7 @@ def test_closest_hits_on_a_scene_built_on_the_device(name, worlds):
     i = 0
     a = w.dev.object_intercepts(i, o[:129], d[:129], t_init=SENTINEL)
     b = dev.object_intercepts(i, o[:129], d[:129], t_init=SENTINEL)
-    assert all(same_bits(x.astype(np.float32), y.astype(np.float32)).all() for x, y in zip(a, b))
+    assert all(same_bits_or_nan(x.astype(np.float32), y.astype(np.float32)).all() for x, y in zip(a, b))
 
 
 # ---- the contract of the calls ----------------------------------------------------------------------------------------------------
@@ -318,8 +312,8 @@ def test_queries_right_after_a_frame_with_a_tail_stream(worlds):
     finally:
         dev.set_tail_stream(None)
     for a, b in zip(before, after):
-        assert same_bits(a.astype(np.float32), b.astype(np.float32)).all()
+        assert same_bits_or_nan(a.astype(np.float32), b.astype(np.float32)).all()
     rgb, hit, _ = dev.render(cfg)  # and the frame was not disturbed by the queries
     host = buf.cpu().numpy()
     assert (host[n * 12:].view(np.int32).reshape(tile.h, tile.w) == hit).all()
-    assert same_bits(host[: n * 12].view(np.float32).reshape(tile.h, tile.w, 3), rgb).all()
+    assert same_bits_or_nan(host[: n * 12].view(np.float32).reshape(tile.h, tile.w, 3), rgb).all()

@@ -15,126 +15,12 @@ import os
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
 from conftest import scene_path
+from frame_checks import COUNTERS, TOL, _pair, assert_bit_identical, check_whitted, oracle_cfg_like, per_pixel
 from oracle import binding as ob
+import p3d_amd as p3d
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4
-
-
-def literal_applies(cfg):
-    """P3D_STACK_LITERAL changes something only where the reference has a stack that outlives a query:
-    rayTracing over the BVH (include/p3d.h)."""
-    pt = cfg.integrator == p3d.PATHTRACE and cfg.antialiasing
-    return cfg.stack_mode == p3d.STACK_LITERAL and cfg.accel == p3d.ACCEL_BVH and not pt
-
-
-def oracle_cfg_like(cfg, **kw):
-    lit = literal_applies(cfg)
-    base = dict(integrator=cfg.integrator, accel=cfg.accel, max_depth=cfg.max_depth, spp_sqrt=cfg.spp_sqrt,
-                antialiasing=cfg.antialiasing, depth_of_field=cfg.depth_of_field, sample_disk=cfg.sample_disk,
-                soft_shadows=cfg.soft_shadows, sample_mode=cfg.sample_mode, light_side=cfg.light_side,
-                gamma=cfg.gamma, skybox=cfg.skybox, seed=cfg.seed, debug_view=cfg.debug_view, rng_mode=0, stack_mode=1 if lit else 0,
-                trace_zero_weight=1 if lit else 0, math_mode=0, threads=1 if lit else 8)
-    base.update(kw)
-    return ob.default_config(**base)
-
-
-def per_pixel(cfg):
-    """The same configuration with the stack emptied at every primary sample (P3D_STACK_PER_PIXEL)."""
-    c = p3d.Config.from_buffer_copy(bytes(cfg))
-    c.stack_mode = p3d.STACK_PER_PIXEL
-    return c
-
-
-def assert_bit_identical(gpu, orc, what=""):
-    rgb_g, hit_g = gpu
-    rgb_o, hit_o = orc
-    assert (hit_g == hit_o).all(), "%s: hit IDs differ in %d pixels" % (what, int((hit_g != hit_o).sum()))
-    diff = rgb_g.view(np.uint32) != rgb_o.view(np.uint32)
-    nan_both = np.isnan(rgb_g) & np.isnan(rgb_o)
-    bad = (diff & ~nan_both).any(-1)
-    assert not bad.any(), "%s: %d pixels differ in some colour bit, max |diff| %g" % (
-        what, int(bad.sum()), float(np.nanmax(np.abs(rgb_g - rgb_o))))
-
-
-COUNTERS = ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "node_tests", "sphere_tests", "tri_tests",
-            "box_tests", "plane_tests", "shaded_hits", "pixels")
-
-
-_TAIL = []
-
-
-def _render_with_tail_stream(dev, cfg):
-    """The device-buffer call without stats, the launches behind pass 1 on a second stream; -> (rgb, hit) on the host."""
-    import torch
-    if not _TAIL:
-        _TAIL.append(torch.cuda.Stream())
-    tile = dev.full_tile()
-    n = tile.w * tile.h
-    buf = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
-    dev.set_tail_stream(_TAIL[0])
-    try:
-        dev.render_device(cfg, tile, d_rgb=buf.data_ptr(), d_hit=buf.data_ptr() + n * 12, stream=torch.cuda.current_stream().cuda_stream)
-        dev.join(host_wait=True)
-        assert dev.status() == 0, p3d.lib().p3d_last_error().decode()
-    finally:
-        dev.set_tail_stream(None)
-    host = buf.cpu().numpy()
-    return host[: n * 12].view(np.float32).reshape(tile.h, tile.w, 3), host[n * 12:].view(np.int32).reshape(tile.h, tile.w)
-
-
-def check_whitted(dev, sc, cfg, tol=2e-6, counters=COUNTERS, max_stack=False):
-    """cfg as given: for the BVH under P3D_STACK_LITERAL the frame must be bit-identical to the oracle's serial
-    order and every ray / test counter equal to the oracle's.  Then (BVH) the per-pixel stack, or (other back ends) the one render there is: frame within `tol` of the
-    oracle in the same semantics and every counter equal, and the frame of the kernels without counters (collect_stats = 0)
-    within the same `tol` of the same oracle frame.  Returns the first render's (rgb, hit, stats)."""
-    cfg.collect_stats = 1
-    first = dev.render(cfg)
-    if literal_applies(cfg):
-        o_rgb, o_hit, o_st = sc.render(oracle_cfg_like(cfg))
-        assert_bit_identical(first[:2], (o_rgb, o_hit), "literal hit_stack")
-        for k in counters:  # what the final frame traced, query by query: redone pixels count once, stale entries visited count
-            assert getattr(first[2], k) == getattr(o_st, k), "literal " + k
-        assert first[2].max_stack >= o_st.max_stack  # (the deepest stack of anything traced, speculative passes included)
-        # ... and the instantiation without counters - the one bench.py times - renders the same bits
-        plain_cfg = p3d.Config.from_buffer_copy(bytes(cfg))
-        plain_cfg.collect_stats = 0
-        plain = dev.render(plain_cfg)
-        assert_bit_identical(plain[:2], (o_rgb, o_hit), "literal hit_stack, kernels without counters")
-        # ... also with the hand-off launches on a tail stream (p3d_scene_set_tail_stream: how bench.py enqueues literal frames)
-        assert_bit_identical(_render_with_tail_stream(dev, plain_cfg), (o_rgb, o_hit), "literal hit_stack, hand-off on a tail stream")
-        cfg = per_pixel(cfg)
-        rgb, hit, st = dev.render(cfg)
-    else:
-        rgb, hit, st = first
-    o_rgb, o_hit, o_st = sc.render(oracle_cfg_like(cfg))
-    # ... and the instantiation without counters - the one a caller who asks for no stats runs - against the same oracle frame
-    plain_cfg = p3d.Config.from_buffer_copy(bytes(cfg))
-    plain_cfg.collect_stats = 0
-    m = np.isfinite(o_rgb).all(-1)
-    for what, (f_rgb, f_hit) in (("with counters", (rgb, hit)), ("kernels without counters", dev.render(plain_cfg)[:2])):
-        assert (f_hit == o_hit).all(), "%s: hit IDs differ in %d pixels" % (what, int((f_hit != o_hit).sum()))
-        assert (np.isfinite(f_rgb).all(-1) == m).all(), what  # NaN pixels (if any) are NaN on both sides
-        err = np.abs(f_rgb[m] - o_rgb[m])
-        assert err.max() <= tol, "%s: max |diff| %g, %d pixels over %g" % (what, err.max(), int((err.max(-1) > tol).sum()), tol)
-    for k in counters:
-        assert getattr(st, k) == getattr(o_st, k), k
-    if max_stack:
-        assert st.max_stack == o_st.max_stack
-    return first
-
-
-def compare(gpu, orc, tol):
-    rgb_g, hit_g = gpu
-    rgb_o, hit_o = orc
-    assert (hit_g == hit_o).all(), "hit IDs differ in %d pixels" % int((hit_g != hit_o).sum())
-    d = np.abs(rgb_g - rgb_o)
-    assert np.isfinite(rgb_g).all()
-    assert d.max() <= tol, "max |diff| %g in %d px" % (d.max(), int((d.max(-1) > tol).sum()))
-    return d.max()
 
 
 @pytest.mark.parametrize("accel", [p3d.ACCEL_NONE, p3d.ACCEL_GRID, p3d.ACCEL_BVH])
@@ -149,18 +35,6 @@ def test_whitted_balls_low_256(accel, depth):
     _, _, st = check_whitted(dev, sc, p3d.whitted_config(accel=accel, max_depth=depth))
     if accel == p3d.ACCEL_BVH:  # the hand-off really happened: some pixels start on a leftover that changes their first hit
         assert st.handoff_checked > 100 and st.handoff_redone > 10 and 1 <= st.handoff_rounds <= 4
-
-
-def _pair(scene_file, res=None, legacy=False, bvh=True, grid=True, lens=None):
-    hs = p3d.HostScene(scene_file, legacy_f11=legacy)
-    sc = ob.Scene(scene_file, legacy_f11=legacy)
-    if res:
-        hs.set_resolution(*res)
-        sc.set_resolution(*res)
-    if lens:
-        hs.set_lens(*lens)
-        sc.set_lens(*lens)
-    return p3d.DeviceScene(hs, bvh=bvh, grid=grid), sc
 
 
 @pytest.mark.parametrize("accel", [p3d.ACCEL_NONE, p3d.ACCEL_GRID, p3d.ACCEL_BVH])

@@ -14,62 +14,16 @@ import numpy as np
 import pytest
 import torch
 
+from frame_checks import ACCELS, gpu, same_bits_or_nan
 import intersect_reference as ref
-import p3d_amd as p3d
-import segment_reference as seg
 from oracle import binding as ob
+import p3d_amd as p3d
+from ray_query_checks import BATCHES, CLOSEST_ALL, INF, N_MESH, N_MODEL, World, limit_sets
+import segment_reference as seg
 
 pytestmark = pytest.mark.gpu
 
-ACCELS = {"none": p3d.ACCEL_NONE, "grid": p3d.ACCEL_GRID, "bvh": p3d.ACCEL_BVH}
-BATCHES = [1, 63, 64, 65, 129, 4099]  # kBlock is 64: a lone lane, a full wave, one lane over, a ragged last block of many
-ALL = ("hit_id", "t", "hit_point", "normal")
 FLT_MAX = np.finfo(np.float32).max
-INF = np.float32(np.inf)
-N_MODEL = 2000   # rays of the comparisons with the oracle's per-object test (the CPU suite's set)
-N_MESH = 515     # rays on the triangle mesh: eight blocks and three lanes
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def same_bits(a, b):
-    """float32 arrays equal in bits, a NaN on both sides counting as equal -> mask"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
-class World:
-    """One scene: host scene, model objects, the device scene(s), max(BATCHES) shuffled rays on the device and the host"""
-
-    def __init__(self, path, trees, seed=8, n=max(BATCHES), oracle=True):
-        self.hs = p3d.HostScene(path)
-        self.objs = ref.load_objects(path)
-        self.sc = ob.Scene(path) if oracle else None
-        self.devs = {}
-        if "host" in trees:
-            self.devs["host"] = p3d.DeviceScene(self.hs, bvh=True, grid=True)
-        if "device" in trees:
-            self.devs["device"] = p3d.DeviceScene(self.hs, bvh="device", grid="device")
-        o, d = ref.scene_rays(self.objs, seed, n)
-        order = np.random.default_rng(seed + 100).permutation(len(o))  # every prefix holds aimed and random rays
-        self.o, self.d = np.ascontiguousarray(o[order]), np.ascontiguousarray(d[order])
-        self.d_o, self.d_d = gpu(self.o), gpu(self.d)
-        self._tests = self._table = None
-
-    @property
-    def tests(self):
-        """The oracle's per-object answers for the first N_MODEL rays"""
-        if self._tests is None:
-            self._tests = seg.per_object(self.sc.object_intercepts, len(self.objs), self.o[:N_MODEL], self.d[:N_MODEL])
-        return self._tests
-
-    def table(self, n):
-        """The model's per-object answers for the first n rays"""
-        if self._table is None or self._table[0].shape[1] < n:
-            self._table = ref._all(self.objs, self.o[:n], self.d[:n])
-        return tuple(a[:, :n] for a in self._table)
 
 
 @pytest.fixture(scope="module")
@@ -100,7 +54,7 @@ def assert_normals(dev, hit, hp, nrm, what, most=24):
     assert not nrm[miss].any() and not np.signbit(nrm[miss]).any(), what + ": a normal on a miss"
     for obj in np.unique(hit[~miss])[:most]:
         m = hit == obj
-        assert same_bits(nrm[m], dev.object_normal(int(obj), hp[m])).all(), "%s: the normal of object %d" % (what, obj)
+        assert same_bits_or_nan(nrm[m], dev.object_normal(int(obj), hp[m])).all(), "%s: the normal of object %d" % (what, obj)
 
 
 @pytest.mark.parametrize("n", BATCHES)
@@ -112,10 +66,10 @@ def test_device_forms_equal_the_host_forms(n, worlds, mesh):
         for accel_name, accel in ACCELS.items():
             what = "%s over %s, %d rays" % (label, accel_name, n_here)
             hit, hp, t = dev.trace_closest(accel, o, d, want_t=True)
-            got = {k: v.cpu().numpy() for k, v in dev.trace_closest_device(accel, d_o, d_d, want=ALL).items()}
+            got = {k: v.cpu().numpy() for k, v in dev.trace_closest_device(accel, d_o, d_d, want=CLOSEST_ALL).items()}
             assert (got["hit_id"] == hit).all(), what + ": hit_id"
-            assert same_bits(got["t"], t).all(), what + ": t"
-            assert same_bits(got["hit_point"], hp).all(), what + ": hit_point"
+            assert same_bits_or_nan(got["t"], t).all(), what + ": t"
+            assert same_bits_or_nan(got["hit_point"], hp).all(), what + ": hit_point"
             assert (got["t"][hit < 0] == FLT_MAX).all() and not got["hit_point"][hit < 0].any(), what + ": the miss values"
             assert_normals(dev, hit, hp, got["normal"], what)
             occ = dev.trace_any_device(accel, d_o, d_d)["occluded"].cpu().numpy()
@@ -146,34 +100,24 @@ def test_closest_hit_with_a_limit(accel_name, worlds, mesh):
     accel = ACCELS[accel_name]
     for label, w, dev in scenes_of(worlds, mesh):
         what = "%s over %s" % (label, accel_name)
-        free = {k: v.cpu().numpy() for k, v in dev.trace_closest_device(accel, w.d_o, w.d_d, want=ALL).items()}
+        free = {k: v.cpu().numpy() for k, v in dev.trace_closest_device(accel, w.d_o, w.d_d, want=CLOSEST_ALL).items()}
         t_max, pick = limits_around(free["t"], 31)
-        got = {k: v.cpu().numpy() for k, v in dev.trace_closest_device(accel, w.d_o, w.d_d, t_max=gpu(t_max), want=ALL).items()}
+        got = {k: v.cpu().numpy() for k, v in dev.trace_closest_device(accel, w.d_o, w.d_d, t_max=gpu(t_max), want=CLOSEST_ALL).items()}
         with np.errstate(invalid="ignore"):
             keep = (free["hit_id"] >= 0) & (free["t"] < t_max)
         hits = free["hit_id"] >= 0
         assert not keep[hits & (pick == 0)].any() and keep[hits & (pick == 1)].all() and not keep[np.isin(pick, (2, 4))].any()
         assert keep[hits & (pick == 3)].all() and (0 < keep.sum() < hits.sum() or not hits.any()), what
         assert (got["hit_id"] == np.where(keep, free["hit_id"], -1)).all(), what + ": hit_id"
-        assert same_bits(got["t"], np.where(keep, free["t"], FLT_MAX)).all(), what + ": t"
+        assert same_bits_or_nan(got["t"], np.where(keep, free["t"], FLT_MAX)).all(), what + ": t"
         for k in ("hit_point", "normal"):
-            assert same_bits(got[k], np.where(keep[:, None], free[k], np.float32(0))).all(), "%s: %s" % (what, k)
+            assert same_bits_or_nan(got[k], np.where(keep[:, None], free[k], np.float32(0))).all(), "%s: %s" % (what, k)
 
 
 # ---- the segment query, accel None: the oracle's brute force on every ray ---------------------------------------------------------
 
 def segment(dev, accel, d_o, d_d, t_max):
     return dev.trace_any_device(accel, d_o, d_d, t_max=gpu(np.asarray(t_max, np.float32)))["occluded"].cpu().numpy().astype(bool)
-
-
-def limit_sets(w, n):
-    """name -> n limits: the seeded draws of the CPU suite, and the ties: the nearest of the oracle's hits, its two
-    neighbours (1 where nothing is hit), then 0, inf and NaN"""
-    t_near, has = seg.nearest(w.tests)
-    same, up, down = seg.tie_limits(np.where(has, t_near, np.float32(1)))
-    sets = {"draws": seg.draw_limits(w.objs, w.o[:n], w.d[:n], 18, table=w.table(n)), "t itself": same, "the float above t": up,
-            "the float below t": down, "zero": np.zeros(n, np.float32), "inf": np.full(n, INF), "NaN": np.full(n, np.nan, np.float32)}
-    return sets, has
 
 
 @pytest.mark.parametrize("name", ["mixed", "mixed_planes", "planes", "axis_aligned"])
@@ -358,7 +302,7 @@ def test_refusals_enqueue_nothing(worlds, mesh):
                 hit_point=torch.full((n, 3), 123.0, device="cuda"), normal=torch.full((n, 3), 123.0, device="cuda"),
                 occluded=torch.full((n,), 9, dtype=torch.uint8, device="cuda"))
     host = np.zeros((n, 3), np.float32)
-    closest_out = {k: outs[k] for k in ALL}
+    closest_out = {k: outs[k] for k in CLOSEST_ALL}
     any_out = {"occluded": outs["occluded"]}
 
     def raw_closest(hit_id, origin=None):
@@ -368,9 +312,9 @@ def test_refusals_enqueue_nothing(worlds, mesh):
 
     cases = [
         ("the grid with a limit", -3, "grid", lambda: dev.trace_any_device(p3d.ACCEL_GRID, o, d, t_max=t_max, out=any_out)),
-        ("a misaligned origin", -1, "aligned", lambda: dev.trace_closest_device(p3d.ACCEL_BVH, (o.data_ptr() + 2, n), d, want=ALL, out=closest_out)),
+        ("a misaligned origin", -1, "aligned", lambda: dev.trace_closest_device(p3d.ACCEL_BVH, (o.data_ptr() + 2, n), d, want=CLOSEST_ALL, out=closest_out)),
         ("a misaligned limit", -1, "aligned", lambda: dev.trace_any_device(p3d.ACCEL_BVH, o, d, t_max=(t_max.data_ptr() + 1, n), out=any_out)),
-        ("a host origin", -1, "host memory", lambda: dev.trace_closest_device(p3d.ACCEL_BVH, (host.ctypes.data, n), d, want=ALL, out=closest_out)),
+        ("a host origin", -1, "host memory", lambda: dev.trace_closest_device(p3d.ACCEL_BVH, (host.ctypes.data, n), d, want=CLOSEST_ALL, out=closest_out)),
         ("a host direction", -1, "host memory", lambda: dev.trace_any_device(p3d.ACCEL_NONE, o, (host.ctypes.data, n), out=any_out)),
         ("an unknown accel", -1, "accel", lambda: dev.trace_any_device(7, o, d, out=any_out)),
     ]

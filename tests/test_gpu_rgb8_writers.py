@@ -1,24 +1,17 @@
 """Every kernel that writes the u8 image (the Whitted megakernel, the fold of the per-level launches, the path tracer, the
 adaptive resolve, the denoiser's last pass) ends with the same step: colour -> gamma -> u8.  The same floats must give the
 same bytes whichever of them wrote the frame; test_rgb8_and_gamma anchors one of them to the oracle."""
-import os
 
 import numpy as np
 import pytest
 
+from conftest import scene_path
+from frame_checks import CORNELL, device_scene
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
 
 pytestmark = pytest.mark.gpu
 
 W, H, GAMMA = 64, 48, 2.2
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
-
-
-def device_scene(path):
-    hs = p3d.HostScene(path)
-    hs.set_resolution(W, H)
-    return p3d.DeviceScene(hs, bvh=True, grid=False)
 
 
 def whitted(dev, **kw):
@@ -45,12 +38,12 @@ def adaptive(dev, spp):
 
 
 WRITERS = {
-    "megakernel": lambda tri5k: whitted(device_scene(scene_path("balls_low.p3f"))),
-    "megakernel_aa": lambda tri5k: whitted(device_scene(scene_path("balls_low.p3f")), antialiasing=1, spp_sqrt=2),
-    "per_level_fold": lambda tri5k: whitted(device_scene(tri5k), chain_launch=p3d.CHAIN_PER_LEVEL),
-    "path_tracer_one_lane": lambda tri5k: pathtraced(device_scene(CORNELL), 2),
-    "path_tracer_four_lanes": lambda tri5k: pathtraced(device_scene(CORNELL), 4),
-    "adaptive_resolve": lambda tri5k: adaptive(device_scene(CORNELL), 4),
+    "megakernel": lambda tri5k: whitted(device_scene(scene_path("balls_low.p3f"), (W, H), grid=False)),
+    "megakernel_aa": lambda tri5k: whitted(device_scene(scene_path("balls_low.p3f"), (W, H), grid=False), antialiasing=1, spp_sqrt=2),
+    "per_level_fold": lambda tri5k: whitted(device_scene(tri5k, (W, H), grid=False), chain_launch=p3d.CHAIN_PER_LEVEL),
+    "path_tracer_one_lane": lambda tri5k: pathtraced(device_scene(CORNELL, (W, H), grid=False), 2),
+    "path_tracer_four_lanes": lambda tri5k: pathtraced(device_scene(CORNELL, (W, H), grid=False), 4),
+    "adaptive_resolve": lambda tri5k: adaptive(device_scene(CORNELL, (W, H), grid=False), 4),
 }
 
 

@@ -4,28 +4,18 @@ The yardstick is exact: the device route (ranges + matrices -> kernel -> BVH / g
 route gives for the same numbers (p3d.transformed -> HostScene.set_geometry -> update_prims): colours as uint32, hit IDs,
 counters, the exported tree and the exported grid.  Every comparison here has tolerance 0."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
+from conftest import scene_path
 from scene_update_helpers import BOX, PLANE, SPHERE, TRIANGLE, random_moves
+from frame_checks import CORNELL, PLANES, assert_same_frames, assert_same_tree, frames, frames_differ, load, rays
+from live_scene_checks import (IDENTITY, RES, SCENES, SEED, assert_same_scene, configs, device, host_route, legacy, plan, rigid,
+                               rotation, runs)
 
 pytestmark = pytest.mark.gpu
-
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
-PLANES = os.path.join(ROOT, "scenes", "planes.p3f")
-RES = 96
-COUNTERS = ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_bounce", "rays_light", "node_tests",
-            "sphere_tests", "tri_tests", "box_tests", "plane_tests", "shaded_hits")
-TREE_KEYS = ("bvh_bmin", "bvh_index", "bvh_bmax", "bvh_count_leaf", "bvh_order")
-GRID_KEYS = ("grid_bmin", "grid_bmax", "grid_cell_start", "grid_cell_items")
-SCENES = ["balls_low", "tri5k", "balls_box", "cornell"]
-GRID_SCENES = ("balls_low", "tri5k")
-SEED = {"balls_low": 31, "tri5k": 32, "balls_box": 33, "cornell": 34}
-IDENTITY = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32)
 
 
 @pytest.fixture
@@ -33,148 +23,12 @@ def paths(tri5k_path):
     return {"balls_low": scene_path("balls_low.p3f"), "tri5k": tri5k_path, "balls_box": scene_path("balls_box.p3f"), "cornell": CORNELL}
 
 
-def load(path, res=RES):
-    hs = p3d.HostScene(path, legacy_f11=os.path.basename(path) == "balls_box.p3f")  # (11-number `f` lines)
-    hs.set_resolution(res, res)
-    return hs
-
-
-def device(hs, name):
-    return p3d.DeviceScene(hs, bvh="device", grid="device" if name in GRID_SCENES else False)
-
-
-def runs(kinds, wanted):
-    """Maximal runs of consecutive objects whose kind is in `wanted` -> [(first, count)]"""
-    out, start = [], None
-    for i, k in enumerate(list(kinds) + [None]):
-        if k in wanted and start is None:
-            start = i
-        elif k not in wanted and start is not None:
-            out.append((start, i - start))
-            start = None
-    return out
-
-
-def rotation(rng):
-    q = rng.standard_normal(4)
-    w, x, y, z = q / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-
-
-def rigid(a, rng, reach=0.05):
-    """A seeded rotation about the centre of the non-plane objects plus a translation of `reach` x their diagonal -> (3, 4) float32"""
-    movable = a["prim_type"] != PLANE
-    lo = a["prim_bmin"][movable].min(0).astype(np.float64)
-    hi = a["prim_bmax"][movable].max(0).astype(np.float64)
-    centre = (lo + hi) / 2
-    rot = rotation(rng)
-    d = rng.standard_normal(3)
-    d *= reach * np.linalg.norm(hi - lo) / np.linalg.norm(d)
-    m = np.zeros((3, 4))
-    m[:, :3] = rot
-    m[:, 3] = centre - rot @ centre + d
-    return m.astype(np.float32)
-
-
-def box_move(a, rng):
-    """A positive scale per axis and a translation: what a box takes"""
-    m = np.zeros((3, 4), np.float32)
-    m[:, :3] = np.diag(rng.uniform(0.7, 1.3, 3)).astype(np.float32)
-    m[:, 3] = rng.uniform(-0.1, 0.1, 3).astype(np.float32)
-    return m
-
-
-def plan(a, seed):
-    """Every sphere and triangle under one rigid move with sphere_scale 1.25, boxes in ranges of their own under a
-    positive-diagonal one -> (ranges, xforms, sphere_scale)"""
-    rng = np.random.default_rng(seed)
-    xforms = np.stack([rigid(a, rng), box_move(a, rng)])
-    ranges = [(f, c, 0) for f, c in runs(a["prim_type"], (SPHERE, TRIANGLE))] + [(f, c, 1) for f, c in runs(a["prim_type"], (BOX,))]
-    return ranges, xforms, np.array([1.25, 1.0], np.float32)
-
-
-def configs(name, accel=p3d.ACCEL_BVH):
-    """(label, cfg): Whitted depth 4 in both stack modes, or the 4-spp path-traced frame of cornell"""
-    if name == "cornell":
-        return [("path trace 4 spp", p3d.pathtrace_config(accel=accel, spp_sqrt=2, max_depth=8, seed=3, collect_stats=1))]
-    return [("whitted %s" % label, p3d.whitted_config(accel=accel, max_depth=4, stack_mode=mode, collect_stats=1))
-            for label, mode in (("literal", p3d.STACK_LITERAL), ("per pixel", p3d.STACK_PER_PIXEL))]
-
-
-def frames(dev, name, accel=p3d.ACCEL_BVH):
-    out = []
-    for label, cfg in configs(name, accel):
-        try:
-            rgb, hit, st = dev.render(cfg)
-        except p3d.P3DError as e:
-            if e.code != -3:  # P3D_ERR_UNSUPPORTED: this scene has no such mode
-                raise
-            continue
-        out.append((label, rgb, hit, {k: getattr(st, k) for k in COUNTERS}))
-    assert out
-    return out
-
-
-def assert_same_frames(a, b, what):
-    assert [f[0] for f in a] == [f[0] for f in b]
-    for (label, rgb_a, hit_a, st_a), (_, rgb_b, hit_b, st_b) in zip(a, b):
-        assert np.array_equal(hit_a, hit_b), "%s, %s: hit IDs differ in %d pixels" % (what, label, int((hit_a != hit_b).sum()))
-        bad = (rgb_a.view(np.uint32) != rgb_b.view(np.uint32)).any(-1)
-        assert not bad.any(), "%s, %s: %d pixels differ in some colour bit, max |diff| %g" % (
-            what, label, int(bad.sum()), float(np.abs(rgb_a - rgb_b).max()))
-        assert st_a == st_b, "%s, %s: counters %s / %s" % (what, label, st_a, st_b)
-
-
-def frames_differ(a, b):
-    return any((ra.view(np.uint32) != rb.view(np.uint32)).any() or (ha != hb).any() for (_, ra, ha, _), (_, rb, hb, _) in zip(a, b))
-
-
-def assert_same_tree(a, b, what):
-    for k in TREE_KEYS:
-        assert a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), "%s: %s differs" % (what, k)
-    assert a["bvh_max_depth"] == b["bvh_max_depth"], what
-
-
-def assert_same_grid(a, b, what):
-    assert tuple(a["grid_n"]) == tuple(b["grid_n"]), what
-    for k in GRID_KEYS:
-        assert a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), "%s: %s differs" % (what, k)
-
-
-def assert_same_scene(dev_a, dev_b, name, what):
-    """Frames and trees, and for the scenes with a device grid the grids and one grid frame -> dev_b's BVH frames"""
-    now = frames(dev_b, name)
-    assert_same_frames(frames(dev_a, name), now, what)
-    assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), what)
-    if name in GRID_SCENES:
-        assert_same_grid(dev_a.export_grid(), dev_b.export_grid(), what)
-        assert_same_frames(frames(dev_a, name, p3d.ACCEL_GRID)[:1], frames(dev_b, name, p3d.ACCEL_GRID)[:1], what + ", grid frame")
-    return now
-
-
-def host_route(hs, dev, rest, ranges, xforms, scale, mode):
-    """What there was before: the transform in numpy from the REST geometry, the constructors on the host, 112 bytes per object"""
-    objs, new_v = p3d.transformed(rest["prim_type"], rest["prim_v"], ranges, xforms, scale)
-    hs.set_geometry(objs, new_v)
-    return dev.update_prims(objs, mode)
-
-
-def rays(n=40000, seed=5):
-    rng = np.random.default_rng(seed)
-    o = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
-    d = (rng.uniform(-1, 1, (n, 3)) - o).astype(np.float32)
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return o, d
-
-
 @pytest.mark.parametrize("name", SCENES)
 def test_the_device_route_is_the_host_route(name, paths):
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     dev_a, dev_b = device(hs, name), device(hs, name)
-    last = frames(dev_b, name)
+    last = frames(dev_b, configs(name))
     for round_ in range(2):  # round two: A computes from the ORIGINAL prim_v, B from its rest copy - not from round one's result
         ranges, xforms, scale = plan(rest, SEED[name] + 100 * round_)
         assert host_route(hs, dev_a, rest, ranges, xforms, scale, p3d.UPDATE_REBUILD) > 0
@@ -187,11 +41,11 @@ def test_the_device_route_is_the_host_route(name, paths):
 
 @pytest.mark.parametrize("name", SCENES)
 def test_refit_keeps_the_topology_on_both_routes(name, paths):
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     dev_a, dev_b = device(hs, name), device(hs, name)
     t0 = dev_b.export_bvh()
-    before = frames(dev_b, name)
+    before = frames(dev_b, configs(name))
     ranges, xforms, scale = plan(rest, SEED[name] + 7)
     assert host_route(hs, dev_a, rest, ranges, xforms, scale, p3d.UPDATE_REFIT) > 0
     assert dev_b.transform_prims(ranges, xforms, p3d.UPDATE_REFIT, sphere_scale=scale) > 0
@@ -205,13 +59,13 @@ def test_refit_keeps_the_topology_on_both_routes(name, paths):
 
 @pytest.mark.parametrize("name", ["balls_low", "tri5k"])
 def test_the_identity_brings_the_rest_pose_back(name, paths):
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     assert not (np.signbit(rest["prim_v"]) & (rest["prim_v"] == 0)).any()  # (1 * -0 + 0 is +0: the one value the identity changes)
     dev, fresh = device(hs, name), device(hs, name)
     ranges, xforms, scale = plan(rest, SEED[name] + 3)
     dev.transform_prims(ranges, xforms, p3d.UPDATE_REFIT, sphere_scale=scale)
-    assert frames_differ(frames(dev, name), frames(fresh, name))
+    assert frames_differ(frames(dev, configs(name)), frames(fresh, configs(name)))
     dev.transform_prims([(f, c, 0) for f, c, _ in ranges], IDENTITY[None], p3d.UPDATE_REBUILD)
     assert_same_scene(fresh, dev, name, "%s, identity after a move" % name)
 
@@ -221,7 +75,7 @@ def test_update_prims_moves_the_rest_pose(first, paths):
     """update_prims of a few objects BEFORE the first transform (the rest copy is taken from what it left) and AFTER it (it
     writes the rest copy too): the identity then gives a fresh scene of the updated host scene"""
     name = "balls_low"
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     dev = device(hs, name)
     ranges, xforms, scale = plan(rest, SEED[name] + 5)
@@ -233,7 +87,7 @@ def test_update_prims_moves_the_rest_pose(first, paths):
     if first == "update":
         dev.transform_prims(ranges, xforms, p3d.UPDATE_REFIT, sphere_scale=scale)
     fresh = device(hs, name)
-    assert frames_differ(frames(dev, name), frames(fresh, name))
+    assert frames_differ(frames(dev, configs(name)), frames(fresh, configs(name)))
     dev.transform_prims([(f, c, 0) for f, c, _ in ranges], IDENTITY[None], p3d.UPDATE_REBUILD)
     assert_same_scene(fresh, dev, name, "identity after update_prims (%s first)" % first)
 
@@ -242,7 +96,7 @@ def test_update_prims_moves_the_rest_pose(first, paths):
 def test_every_object_finds_its_range(name, paths):
     """tri5k split at 1, 63, 64, 65 and 257 (one object, a wave's end, a block's end + 1), balls_low with one range per object;
     every range with a matrix of its own, in shuffled order"""
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     n = rest["n_prims"]
     assert (rest["prim_type"] != PLANE).all() and not (rest["prim_type"] == BOX).any()
@@ -260,7 +114,7 @@ def test_every_object_finds_its_range(name, paths):
 
 def test_unnamed_objects_are_untouched(paths):
     name = "tri5k"
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     n = rest["n_prims"]
     dev_a, dev_b = device(hs, name), device(hs, name)
@@ -297,7 +151,7 @@ def _raw(dev, ranges, xforms, mode=p3d.UPDATE_REFIT, n_ranges=None, n_xforms=Non
 
 def test_refusals_leave_the_scene_as_it_was(paths):
     name = "balls_box"
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     a = hs.arrays()
     n = a["n_prims"]
     box = int(np.nonzero(a["prim_type"] == BOX)[0][0])
@@ -305,13 +159,13 @@ def test_refusals_leave_the_scene_as_it_was(paths):
     dev = p3d.DeviceScene(hs, bvh="device")  # (before the host scene builds a grid: its descriptor carries one from then on)
     host_tree = p3d.DeviceScene(hs, bvh=True)
     with_grid = p3d.DeviceScene(hs, bvh="device", grid=True)
-    hp = load(PLANES)
+    hp = load(PLANES, RES)
     ap = hp.arrays()
     plane = int(np.nonzero(ap["prim_type"] == PLANE)[0][0])
     dev_planes = p3d.DeviceScene(hp, bvh="device")
 
     def state(s):
-        return frames(s, name)
+        return frames(s, configs(name))
 
     slide = IDENTITY.copy()
     slide[:, 3] = (0.25, 0.1, -0.2)
@@ -382,7 +236,7 @@ def test_an_object_that_overflows_keeps_its_geometry(paths):
     is 3.4e38), so the sphere also takes sphere_scale 3e38: its radius, and with it its box, becomes infinite.  The kernel
     leaves that object unwritten and counts it: no fault is provoked."""
     name = "balls_low"
-    hs = load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     spheres = np.nonzero(rest["prim_type"] == SPHERE)[0]
     victim = int(spheres[np.argmax(rest["prim_v"][spheres, 3])])
@@ -395,7 +249,7 @@ def test_an_object_that_overflows_keeps_its_geometry(paths):
     scale = np.array([1.25, 3e38], np.float32)
     others = [(f, c, 0) for f, c in runs([int(k) if i != victim else -1 for i, k in enumerate(rest["prim_type"])], (SPHERE, TRIANGLE))]
     dev_a, dev_b = device(hs, name), device(hs, name)
-    before = frames(dev_b, name)
+    before = frames(dev_b, configs(name))
     host_route(hs, dev_a, rest, others, xforms, scale, p3d.UPDATE_REBUILD)  # A: the victim is left out of the move
     with pytest.raises(p3d.P3DError) as e:
         dev_b.transform_prims(others + [(victim, 1, 1)], xforms, p3d.UPDATE_REBUILD, sphere_scale=scale)
@@ -445,7 +299,7 @@ def test_recorded_schedules_are_forgotten_and_staging_is_kept(paths):
     twice so that the memo exists; after the transform the cost-ordered frame is the frame-ordered one."""
     res = 1024
     name = "balls_low"
-    hs = load(paths[name], res)
+    hs = load(paths[name], res, legacy_f11=legacy(paths[name]))
     rest = hs.arrays()
     dev = p3d.DeviceScene(hs, bvh="device")
     cost = p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4, tile_order=p3d.TILE_ORDER_COST)

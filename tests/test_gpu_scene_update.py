@@ -6,24 +6,21 @@ uploaded with that exported tree (p3d_scene_create) renders and traces the same 
 cannot depend on a tree is compared, with the bounds test_device_built_bvh_finds_the_same_closest_hits uses (grazing rays,
 Q8).  All comparisons of one tree against itself have tolerance 0."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
-from conftest import ROOT, scene_path
+from conftest import scene_path
+from frame_checks import CORNELL, RENDER_COUNTERS, assert_same_frames, assert_same_tree, frames, frames_differ, load, rays
 from lbvh_reference import check_boxes
+from live_scene_checks import configs
 from oracle import binding as ob
+import p3d_amd as p3d
 from scene_update_helpers import PLANE, SPHERE, random_moves, write_moved_p3f
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
 RES = 192
-COUNTERS = ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_bounce", "rays_light", "node_tests",
-            "sphere_tests", "tri_tests", "box_tests", "plane_tests", "shaded_hits")
-TREE_KEYS = ("bvh_bmin", "bvh_index", "bvh_bmax", "bvh_count_leaf", "bvh_order")
 WHITTED_SCENES = ["balls_low", "tri5k", "path_glass"]
 SEED = {"balls_low": 11, "tri5k": 12, "path_glass": 13, "cornell": 14}
 
@@ -32,12 +29,6 @@ SEED = {"balls_low": 11, "tri5k": 12, "path_glass": 13, "cornell": 14}
 def paths(tri5k_path):
     return {"balls_low": scene_path("balls_low.p3f"), "tri5k": tri5k_path, "path_glass": scene_path("path_glass.p3f"),
             "cornell": CORNELL}
-
-
-def load(path, res=RES):
-    hs = p3d.HostScene(path)
-    hs.set_resolution(res, res)
-    return hs
 
 
 def emissive_spheres(a):
@@ -53,71 +44,19 @@ def moves(hs, name, round_=0):
     return random_moves(a, SEED[name] + 100 * round_, include=emissive_spheres(a) if name == "cornell" else spheres)
 
 
-def configs(name):
-    """(label, cfg): Whitted depth 4 in both stack modes, or the 4-spp path-traced frame of cornell"""
-    if name == "cornell":
-        return [("path trace 4 spp", p3d.pathtrace_config(accel=p3d.ACCEL_BVH, spp_sqrt=2, max_depth=8, seed=3, collect_stats=1))]
-    return [("whitted %s" % label, p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4, stack_mode=mode, collect_stats=1))
-            for label, mode in (("literal", p3d.STACK_LITERAL), ("per pixel", p3d.STACK_PER_PIXEL))]
-
-
-def frames(dev, name):
-    out = []
-    for label, cfg in configs(name):
-        try:
-            rgb, hit, st = dev.render(cfg)
-        except p3d.P3DError as e:
-            if e.code != -3:  # P3D_ERR_UNSUPPORTED: this scene has no such mode
-                raise
-            continue
-        out.append((label, rgb, hit, {k: getattr(st, k) for k in COUNTERS}))
-    assert out
-    return out
-
-
-def assert_same_frames(a, b, what):
-    assert [f[0] for f in a] == [f[0] for f in b]
-    for (label, rgb_a, hit_a, st_a), (_, rgb_b, hit_b, st_b) in zip(a, b):
-        assert np.array_equal(hit_a, hit_b), "%s, %s: hit IDs differ in %d pixels" % (what, label, int((hit_a != hit_b).sum()))
-        bad = (rgb_a.view(np.uint32) != rgb_b.view(np.uint32)).any(-1)
-        assert not bad.any(), "%s, %s: %d pixels differ in some colour bit, max |diff| %g" % (
-            what, label, int(bad.sum()), float(np.abs(rgb_a - rgb_b).max()))
-        assert st_a == st_b, "%s, %s: counters %s / %s" % (what, label, st_a, st_b)
-
-
-def frames_differ(a, b):
-    """Some pixel's colour bits or hit ID changed (a Whitted frame of a scene without lights is black: the IDs tell)"""
-    return any((ra.view(np.uint32) != rb.view(np.uint32)).any() or (ha != hb).any() for (_, ra, ha, _), (_, rb, hb, _) in zip(a, b))
-
-
-def assert_same_tree(a, b, what):
-    for k in TREE_KEYS:
-        assert a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), "%s: %s differs" % (what, k)
-    assert a["bvh_max_depth"] == b["bvh_max_depth"], what
-
-
-def rays(n=40000, seed=5):
-    rng = np.random.default_rng(seed)
-    o = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
-    d = (rng.uniform(-1, 1, (n, 3)) - o).astype(np.float32)
-    d[: n // 8, rng.integers(0, 3)] = 0
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return o, d
-
-
 @pytest.mark.parametrize("name", WHITTED_SCENES + ["cornell"])
 def test_rebuild_is_a_fresh_create(name, paths):
-    hs = load(paths[name])
+    hs = load(paths[name], RES)
     dev = p3d.DeviceScene(hs, bvh="device")
-    last = frames(dev, name)
+    last = frames(dev, configs(name))
     for round_ in range(2):  # the second update runs in the workspace the first one allocated
         objs, new_v = moves(hs, name, round_)
         hs.set_geometry(objs, new_v)
         ms = dev.update_prims(objs, p3d.UPDATE_REBUILD)
         assert ms > 0
         fresh = p3d.DeviceScene(hs, bvh="device")
-        now = frames(dev, name)
-        assert_same_frames(now, frames(fresh, name), "%s, rebuild %d" % (name, round_))
+        now = frames(dev, configs(name))
+        assert_same_frames(now, frames(fresh, configs(name)), "%s, rebuild %d" % (name, round_))
         assert_same_tree(dev.export_bvh(), fresh.export_bvh(), "%s, rebuild %d" % (name, round_))
         assert frames_differ(now, last), "the move changed no pixel"
         last = now
@@ -126,17 +65,17 @@ def test_rebuild_is_a_fresh_create(name, paths):
     tree = dev.export_bvh()
     assert dev.update_prims([], p3d.UPDATE_REBUILD) > 0
     assert_same_tree(dev.export_bvh(), tree, "rebuild of nothing")
-    assert_same_frames(frames(dev, name), last, "rebuild of nothing")
+    assert_same_frames(frames(dev, configs(name)), last, "rebuild of nothing")
 
 
 @pytest.mark.parametrize("name", WHITTED_SCENES + ["cornell"])
 def test_refit_is_exact_for_its_tree(name, paths):
-    hs = load(paths[name])
+    hs = load(paths[name], RES)
     dev = p3d.DeviceScene(hs, bvh="device")
-    before = frames(dev, name)
+    before = frames(dev, configs(name))
     t0 = dev.export_bvh()
     check_boxes(t0, hs.arrays(), "%s as created" % name)
-    o, d = rays()
+    o, d = rays(axis_parallel=True)
     for round_ in range(2):
         objs, new_v = moves(hs, name, round_)
         hs.set_geometry(objs, new_v)
@@ -148,8 +87,8 @@ def test_refit_is_exact_for_its_tree(name, paths):
         assert t0["bvh_bmin"].tobytes() != t1["bvh_bmin"].tobytes()
         check_boxes(t1, hs.arrays(), "%s, refit %d" % (name, round_))
         twin = p3d.DeviceScene(hs, bvh=t1)  # p3d_scene_create of the exported tree and the moved objects
-        now = frames(dev, name)
-        assert_same_frames(now, frames(twin, name), "%s, refit %d against the uploaded tree" % (name, round_))
+        now = frames(dev, configs(name))
+        assert_same_frames(now, frames(twin, configs(name)), "%s, refit %d against the uploaded tree" % (name, round_))
         assert frames_differ(now, before), "the move changed no pixel"
         hit_a, p_a, t_a = dev.trace_closest(p3d.ACCEL_BVH, o, d, want_t=True)
         hit_b, p_b, t_b = twin.trace_closest(p3d.ACCEL_BVH, o, d, want_t=True)
@@ -162,7 +101,7 @@ def test_refit_is_exact_for_its_tree(name, paths):
 
 @pytest.mark.parametrize("name", WHITTED_SCENES)
 def test_refit_finds_the_same_surfaces_as_rebuild(name, paths, tmp_path):
-    hs = load(paths[name])
+    hs = load(paths[name], RES)
     refit = p3d.DeviceScene(hs, bvh="device")
     rebuilt = p3d.DeviceScene(hs, bvh="device")
     a = hs.arrays()
@@ -170,7 +109,7 @@ def test_refit_finds_the_same_surfaces_as_rebuild(name, paths, tmp_path):
     hs.set_geometry(objs, new_v)
     refit.update_prims(objs, p3d.UPDATE_REFIT)
     rebuilt.update_prims(objs, p3d.UPDATE_REBUILD)
-    o, d = rays()
+    o, d = rays(axis_parallel=True)
     hit_f, _ = refit.trace_closest(p3d.ACCEL_BVH, o, d)
     hit_b, _ = rebuilt.trace_closest(p3d.ACCEL_BVH, o, d)
     sc = ob.Scene(write_moved_p3f(paths[name], str(tmp_path / "moved.p3f"), a["prim_type"], objs, new_v))
@@ -251,7 +190,7 @@ def _update_raw(dev, objs, recs, mode=p3d.UPDATE_REFIT):
 
 
 def test_refusals_leave_the_scene_as_it_was(paths):
-    hs = load(paths["balls_low"])
+    hs = load(paths["balls_low"], RES)
     d = hs.desc(False, False)
     n = d.n_prims
 
@@ -272,7 +211,7 @@ def test_refusals_leave_the_scene_as_it_was(paths):
 
     def frame(s):
         rgb, hit, st = s.render(cfg)
-        return rgb.tobytes(), hit.tobytes(), tuple(getattr(st, k) for k in COUNTERS)
+        return rgb.tobytes(), hit.tobytes(), tuple(getattr(st, k) for k in RENDER_COUNTERS)
 
     moved = records([n - 1])
     moved[0].v[0] += 0.25

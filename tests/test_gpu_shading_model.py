@@ -7,12 +7,12 @@ set_camera that is not another GPU route.  Nothing here reads the reference tree
 import numpy as np
 import pytest
 
+from frame_checks import ACCELS
 import p3d_amd as p3d
 import shading_reference as sh
 
 pytestmark = pytest.mark.gpu
 
-ACCELS = {"none": p3d.ACCEL_NONE, "grid": p3d.ACCEL_GRID, "bvh": p3d.ACCEL_BVH}
 VARIANTS = {"literal": dict(stack_mode=p3d.STACK_LITERAL, collect_stats=1), "per_pixel": dict(stack_mode=p3d.STACK_PER_PIXEL, collect_stats=1),
             "no_counters": dict(stack_mode=p3d.STACK_LITERAL, collect_stats=0)}
 BIG = (192, 160)

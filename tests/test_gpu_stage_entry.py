@@ -23,37 +23,16 @@ multiple" can only be had exactly from an object-loop frame:
 The primitive, material and light counts below were picked on the CPU (HostScene descriptor -> the sum above); every test
 asserts that the plan stages exactly that many float4.
 """
-import numpy as np
 import pytest
 
+from frame_checks import _pair, check_whitted
 import p3d_amd as p3d
-from oracle import binding as ob
-from test_gpu_parity import check_whitted
+from variant_scenes import write_spheres
 
 pytestmark = pytest.mark.gpu
 
 LIMIT_F4 = 26 * 1024 // 16  # kLdsSceneLimitBytes (capi_frame_plan.hpp)
 FRAMES = ((64, 64), (72, 40))
-
-
-def write_spheres(path, n, mats, lights, seed=1):
-    """n spheres on a jittered lattice, the first `mats` of them with a material of their own (every second one
-    reflective), `lights` lights."""
-    rng = np.random.default_rng(seed)
-    lines = ["bclr 0.1 0.2 0.3", "v", "from 0 -7 2", "at 0 0 0", "up 0 0 1", "angle 45", "hither 0.01", "resolution 64 64",
-             "aperture 0", "focal 1"]
-    for k in range(lights):
-        lines.append("l %g %g %g 0.6 0.6 0.6" % (3 - 2 * k, -4, 5 + k))
-    side = max(1, int(np.ceil(n ** (1 / 3))))
-    for k in range(n):
-        if k < mats:
-            lines.append("f %g %g %g 0.7 1 1 1 %g 20 0 1 0 0 0" % (0.2 + 0.6 * rng.random(), 0.3, 0.8 * rng.random(), 0.3 if k % 2 else 0.0))
-        x, y, z = k % side, (k // side) % side, k // (side * side)
-        s = 3.0 / side
-        lines.append("s %g %g %g %g" % ((x - side / 2 + 0.5) * s + 0.1 * s * rng.random(), (y - side / 2 + 0.5) * s, (z - side / 2 + 0.5) * s, 0.33 * s))
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    return path
 
 
 def layout_f4(path, accel):
@@ -62,14 +41,6 @@ def layout_f4(path, accel):
     d = d.contents if hasattr(d, "contents") else d
     bvh_frame = 2 * d.n_bvh_nodes + 3 * d.n_bvh_prim_index + d.n_prims + 4 * d.n_materials + 2 * d.n_lights
     return bvh_frame + (3 * d.n_prims if accel != p3d.ACCEL_BVH else 0)
-
-
-def pair(path, res):
-    hs = p3d.HostScene(path)
-    sc = ob.Scene(path)
-    hs.set_resolution(*res)
-    sc.set_resolution(*res)
-    return p3d.DeviceScene(hs, bvh=True, grid=False), sc
 
 
 #                  staged float4, accel, spheres, materials, lights
@@ -83,7 +54,7 @@ def test_frames_over_a_staged_range_of_every_critical_size(want, accel, n, mats,
     path = write_spheres(str(tmp_path / "spheres.p3f"), n, mats, lights)
     assert layout_f4(path, accel) == want
     for res in FRAMES:
-        dev, sc = pair(path, res)
+        dev, sc = _pair(path, res=res, grid=False)
         cfg = p3d.whitted_config(accel=accel, max_depth=3)
         assert dev.staged_f4(cfg) == want  # the plan stages this scene, and exactly the range the layout rules give
         if accel == p3d.ACCEL_BVH:
@@ -97,7 +68,7 @@ def test_the_largest_staged_range_is_the_limit(tmp_path):
     """One sphere more than the 1664-float4 scene: over 26 KB, traversed from global memory (nothing staged)."""
     path = write_spheres(str(tmp_path / "spheres.p3f"), 266, 9, 1)
     assert layout_f4(path, p3d.ACCEL_BVH) == LIMIT_F4 + 4
-    dev, sc = pair(path, FRAMES[0])
+    dev, sc = _pair(path, res=FRAMES[0], grid=False)
     cfg = p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=3)
     assert dev.staged_f4(cfg) == 0
     check_whitted(dev, sc, cfg)

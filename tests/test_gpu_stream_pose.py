@@ -21,29 +21,29 @@ import pytest
 import torch
 
 import p3d_amd as p3d
-import test_gpu_scene_transform as T
-import test_gpu_stream_refit as R
 from conftest import scene_path
 from device_geometry_helpers import deformed_mesh
 from scene_update_helpers import BOX, PLANE, SPHERE, TRIANGLE, random_moves
+from frame_checks import CORNELL, PLANES, RENDER_COUNTERS, assert_same_frames, assert_same_tree, frames, frames_differ, gpu, load
+from live_scene_checks import (HEAD, IDENTITY, LEAF, RES, SCENES, SEED, TRACE_OUT, assert_same_frames_and_tree, box_move,
+                               camera_rays, configs, kinds_of, last_error, legacy, plan, produced, rigid, runs, scene,
+                               trace_outputs)
 
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = -1, -3
-LEAF = R.LEAF
-gpu = R.gpu
 MOVABLE = (SPHERE, TRIANGLE)
 
 
 @pytest.fixture
 def paths(tri5k_path):
-    return {"balls_low": scene_path("balls_low.p3f"), "tri5k": tri5k_path, "balls_box": scene_path("balls_box.p3f"), "cornell": T.CORNELL}
+    return {"balls_low": scene_path("balls_low.p3f"), "tri5k": tri5k_path, "balls_box": scene_path("balls_box.p3f"), "cornell": CORNELL}
 
 
-def twins(path, res=T.RES):
+def twins(path, res=RES):
     """(host scene, its arrays, scene A for the waiting form, scene B for the stream form)"""
-    hs = T.load(path, res)
-    return hs, hs.arrays(), R.scene(hs), R.scene(hs)
+    hs = load(path, res, legacy_f11=legacy(path))
+    return hs, hs.arrays(), scene(hs), scene(hs)
 
 
 def both(dev_a, dev_b, ranges, xforms, scale=None, twin_ranges=None):
@@ -59,7 +59,7 @@ def both(dev_a, dev_b, ranges, xforms, scale=None, twin_ranges=None):
 
 def moves(a, seed, k, reach=0.05):
     rng = np.random.default_rng(seed)
-    return np.stack([T.rigid(a, rng, reach=reach * (1 + 0.1 * i)) for i in range(k)])
+    return np.stack([rigid(a, rng, reach=reach * (1 + 0.1 * i)) for i in range(k)])
 
 
 def untouched_leaves(tree, covered):
@@ -79,26 +79,26 @@ def covered_by(ranges, n):
 
 
 # 1. every scene of the transform tests, the matrices produced on a stream that is still working on them
-@pytest.mark.parametrize("name", T.SCENES)
+@pytest.mark.parametrize("name", SCENES)
 def test_the_stream_form_is_the_waiting_form(name, paths):
     hs, a, dev_a, dev_b = twins(paths[name])
-    before = T.frames(dev_b, name)
-    ranges, _, _ = T.plan(a, 0)  # spheres and triangles on slot 0, boxes on slot 1; a plane is in no range
+    before = frames(dev_b, configs(name))
+    ranges, _, _ = plan(a, 0)  # spheres and triangles on slot 0, boxes on slot 1; a plane is in no range
     posed = sum(c for _, c, _ in ranges)
     assert posed == int((a["prim_type"] != PLANE).sum()) > 0
     assert dev_b.rig() == dict(n_ranges=0, n_xforms=0, n_posed_objects=0)
     dev_b.set_rig(ranges, 2)
     assert dev_b.rig() == dict(n_ranges=len(ranges), n_xforms=2, n_posed_objects=posed)
-    T.assert_same_frames(T.frames(dev_b, name), before, "set_rig moves nothing")
+    assert_same_frames(frames(dev_b, configs(name)), before, "set_rig moves nothing")
     side = torch.cuda.Stream()
     ballast = torch.linspace(0, 1, 1 << 20, device="cuda")
     last = before
     for round_ in range(2):  # round two: both start from the REST pose, not from round one's result
-        _, xforms, scale = T.plan(a, T.SEED[name] + 40 + 100 * round_)  # rigid + spheres that grow; positive-diagonal for boxes
+        _, xforms, scale = plan(a, SEED[name] + 40 + 100 * round_)  # rigid + spheres that grow; positive-diagonal for boxes
         base_x, base_s = gpu(xforms), gpu(scale)
         torch.cuda.synchronize()
         with torch.cuda.stream(side):
-            slow = R.produced(ballast, 1.0, rounds=20)
+            slow = produced(ballast, 1.0, rounds=20)
             d_x = (base_x + 0.0 * slow[:24].view(2, 3, 4)).contiguous()
             d_s = (base_s + 0.0 * slow[24:26]).contiguous()
             dev_b.pose_device(d_x, d_s, stream=side)  # no synchronisation between producer and call
@@ -106,8 +106,8 @@ def test_the_stream_form_is_the_waiting_form(name, paths):
         x_bits, s_bits = d_x.cpu().numpy(), d_s.cpu().numpy()
         assert np.isfinite(x_bits).all() and np.array_equal(x_bits, xforms) and np.array_equal(s_bits, scale)
         assert dev_a.transform_prims(ranges, x_bits, p3d.UPDATE_REFIT, sphere_scale=s_bits) > 0
-        now = R.assert_same(dev_a, dev_b, name, "%s, round %d" % (name, round_))
-        assert T.frames_differ(now, last), "the pose changed no pixel"
+        now = assert_same_frames_and_tree(dev_a, dev_b, name, "%s, round %d" % (name, round_))
+        assert frames_differ(now, last), "the pose changed no pixel"
         last = now
     assert dev_b.status() == 0
 
@@ -124,15 +124,15 @@ def test_tiny_scenes(n_objs, kind, tmp_path):
         objs = ["p 3 %g -0.2 -0.6 %g 0.1 -0.5 %g 0 0.7" % (1.4 * k - 1.9, 1.4 * k - 0.8, 1.4 * k - 1.4) for k in range(n_objs)]
     path = str(tmp_path / "tiny.p3f")
     with open(path, "w") as f:
-        f.write("\n".join(R.HEAD + objs) + "\n")
+        f.write("\n".join(HEAD + objs) + "\n")
     hs, a, dev_a, dev_b = twins(path, 64)
     assert a["n_prims"] == n_objs
-    before = T.frames(dev_b, "tiny")
+    before = frames(dev_b, configs("tiny"))
     ranges = [(k, 1, n_objs - 1 - k) for k in range(n_objs)]
     dev_b.set_rig(ranges, n_objs)
     rng = np.random.default_rng(140 + n_objs)
     both(dev_a, dev_b, ranges, moves(a, 150 + n_objs, n_objs), rng.uniform(0.7, 1.2, n_objs))
-    assert T.frames_differ(R.assert_same(dev_a, dev_b, "tiny", "%d %s" % (n_objs, kind)), before)
+    assert frames_differ(assert_same_frames_and_tree(dev_a, dev_b, "tiny", "%d %s" % (n_objs, kind)), before)
     assert dev_b.status() == 0
 
 
@@ -151,7 +151,7 @@ def test_range_boundaries_and_untouched_objects(paths):
     dev_b.set_rig(ranges, len(ranges))
     assert dev_b.rig()["n_posed_objects"] == int(covered.sum())
     both(dev_a, dev_b, ranges, moves(a, 301, len(ranges), reach=0.02))
-    R.assert_same(dev_a, dev_b, "tri5k", "seven ranges")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "seven ranges")
     # the unnamed objects keep their exact bits: every leaf that holds none of the covered objects has the box it had
     tree1 = dev_b.export_bvh()
     for k in ("bvh_index", "bvh_count_leaf", "bvh_order"):
@@ -176,7 +176,7 @@ def test_forty_ranges_and_shared_slots(paths):
     dev_b.set_rig(ranges, 20)
     assert dev_b.rig() == dict(n_ranges=40, n_xforms=20, n_posed_objects=sum(c for _, c, _ in ranges))
     both(dev_a, dev_b, ranges, moves(a, 303, 20, reach=0.02))
-    R.assert_same(dev_a, dev_b, "tri5k", "forty ranges")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "forty ranges")
     assert dev_b.export_bvh()["bvh_bmin"].tobytes() != before["bvh_bmin"].tobytes()
     assert dev_b.status() == 0
 
@@ -186,17 +186,17 @@ def test_the_identity_brings_the_rest_pose_back_and_a_pose_is_idempotent(paths):
     name = "balls_low"
     hs, a, dev, fresh = twins(paths[name])
     assert not (np.signbit(a["prim_v"]) & (a["prim_v"] == 0)).any()  # (1 * -0 + 0 is +0: the one value the identity changes)
-    ranges, xforms, scale = T.plan(a, T.SEED[name] + 43)
+    ranges, xforms, scale = plan(a, SEED[name] + 43)
     dev.set_rig(ranges, 2)
     d_x, d_s = gpu(xforms), gpu(scale)
     dev.pose_device(d_x, d_s)
-    once_frames, once_tree = T.frames(dev, name), dev.export_bvh()
-    assert T.frames_differ(once_frames, T.frames(fresh, name))
+    once_frames, once_tree = frames(dev, configs(name)), dev.export_bvh()
+    assert frames_differ(once_frames, frames(fresh, configs(name)))
     dev.pose_device(d_x, d_s)  # T(rest) again, not T(T(rest))
-    T.assert_same_frames(T.frames(dev, name), once_frames, "the same pose twice")
-    T.assert_same_tree(dev.export_bvh(), once_tree, "the same pose twice")
-    dev.pose_device(gpu(np.stack([T.IDENTITY, T.IDENTITY])))  # no scales: 1 for every slot
-    R.assert_same(fresh, dev, name, "the identity after a pose")
+    assert_same_frames(frames(dev, configs(name)), once_frames, "the same pose twice")
+    assert_same_tree(dev.export_bvh(), once_tree, "the same pose twice")
+    dev.pose_device(gpu(np.stack([IDENTITY, IDENTITY])))  # no scales: 1 for every slot
+    assert_same_frames_and_tree(fresh, dev, name, "the identity after a pose")
     assert dev.status() == 0
 
 
@@ -207,7 +207,7 @@ def test_another_route_moves_the_rest_pose(route, paths):
     name = "balls_low" if route == "update_prims" else "tri5k"
     hs, a, dev_a, dev_b = twins(paths[name])
     n = a["n_prims"]
-    ranges = [(f, c, k % 2) for k, (f, c) in enumerate(T.runs(a["prim_type"], MOVABLE))] if name == "balls_low" else [(0, n // 2, 0), (n // 2, n - n // 2, 1)]
+    ranges = [(f, c, k % 2) for k, (f, c) in enumerate(runs(a["prim_type"], MOVABLE))] if name == "balls_low" else [(0, n // 2, 0), (n // 2, n - n // 2, 1)]
     dev_b.set_rig(ranges, 2)
     if route == "update_prims":
         objs, new_v = random_moves(a, 77, fraction=0.5)
@@ -220,14 +220,14 @@ def test_another_route_moves_the_rest_pose(route, paths):
         dev_b.refit_triangles(0, soup, stream=side)
         side.synchronize()
         dev_a.update_triangles(0, soup, mode=p3d.UPDATE_REFIT)
-    moved = R.assert_same(dev_a, dev_b, name, "the other route")
+    moved = assert_same_frames_and_tree(dev_a, dev_b, name, "the other route")
     both(dev_a, dev_b, ranges, moves(a, 79, 2))
-    assert T.frames_differ(R.assert_same(dev_a, dev_b, name, "a pose from the new rest"), moved)
+    assert frames_differ(assert_same_frames_and_tree(dev_a, dev_b, name, "a pose from the new rest"), moved)
     if route == "update_prims":  # the identity gives the updated host scene: after a rebuild, a fresh scene of it, tree and all
         assert not (np.signbit(hs.arrays()["prim_v"]) & (hs.arrays()["prim_v"] == 0)).any()
-        dev_b.pose_device(gpu(np.stack([T.IDENTITY, T.IDENTITY])))
+        dev_b.pose_device(gpu(np.stack([IDENTITY, IDENTITY])))
         dev_b.update_geometry_device([], p3d.UPDATE_REBUILD)
-        R.assert_same(R.scene(hs), dev_b, name, "the identity after update_prims")
+        assert_same_frames_and_tree(scene(hs), dev_b, name, "the identity after update_prims")
     assert dev_b.status() == 0
 
 
@@ -245,7 +245,7 @@ def test_after_a_rebuild_that_changed_the_order(paths):
     assert built["bvh_order"].tobytes() != refitted["bvh_order"].tobytes()
     assert dev_b.rig()["n_ranges"] == k  # the rig stands: a rebuild reorders leaves, not objects
     both(dev_a, dev_b, ranges, moves(a, 305, k, reach=0.29))  # over the NEW topology, with the new tree's depth
-    R.assert_same(dev_a, dev_b, "tri5k", "a pose of a rebuilt tree")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "a pose of a rebuilt tree")
     assert dev_b.export_bvh()["bvh_order"].tobytes() == built["bvh_order"].tobytes()
     assert dev_b.status() == 0
 
@@ -255,10 +255,10 @@ def test_three_steps_without_a_host_wait(paths):
     hs, a, dev_a, dev_b = twins(paths["tri5k"])
     n, k, n_rays = a["n_prims"], 8, 4096
     ranges = [(i * (n // k), n // k, i) for i in range(k)]
-    o, d = R.camera_rays(a, n_rays, seed=31)
+    o, d = camera_rays(a, n_rays, seed=31)
     base = [gpu(moves(a, 310 + step, k, reach=0.04)) for step in range(3)]
-    want = [w for w, _, _ in R.TRACE_OUT]
-    outs_b = [R.trace_outputs(n_rays) for _ in base]
+    want = [w for w, _, _ in TRACE_OUT]
+    outs_b = [trace_outputs(n_rays) for _ in base]
     dev_b.set_rig(ranges, k)
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
@@ -272,7 +272,7 @@ def test_three_steps_without_a_host_wait(paths):
     outs_a = []
     for x in poses:
         dev_a.transform_prims(ranges, x.cpu().numpy(), p3d.UPDATE_REFIT)
-        outs_a.append(dev_a.trace_closest_device(p3d.ACCEL_BVH, o, d, want=want, out=R.trace_outputs(n_rays)))
+        outs_a.append(dev_a.trace_closest_device(p3d.ACCEL_BVH, o, d, want=want, out=trace_outputs(n_rays)))
         torch.cuda.synchronize()
     for step, (got, ref) in enumerate(zip(outs_b, outs_a)):
         # (a check of this test's rays, not of the pose: hundreds of them end on the mesh, which is sparse; that they tell
@@ -292,7 +292,7 @@ def run_skip_case(a, dev_a, dev_b, name, ranges, first, xforms, scale, bad_slots
     first pose put them, on both."""
     k = len(xforms)
     both(dev_a, dev_b, ranges, first)  # a good pose: what the skipped objects must keep
-    posed = R.assert_same(dev_a, dev_b, name, "the good pose")
+    posed = assert_same_frames_and_tree(dev_a, dev_b, name, "the good pose")
     xforms = np.ascontiguousarray(xforms, np.float32).reshape(k, 3, 4)
     scale = np.ones(k, np.float32) if scale is None else np.ascontiguousarray(scale, np.float32)
     d_x, d_s = gpu(xforms), gpu(scale)
@@ -302,25 +302,25 @@ def run_skip_case(a, dev_a, dev_b, name, ranges, first, xforms, scale, bad_slots
     good = [r for r in ranges if r[2] not in bad_slots]
     safe_x, safe_s = xforms.copy(), scale.copy()
     for s in bad_slots:
-        safe_x[s], safe_s[s] = T.IDENTITY, 1.0
+        safe_x[s], safe_s[s] = IDENTITY, 1.0
     assert dev_a.transform_prims(good, safe_x, p3d.UPDATE_REFIT, sphere_scale=safe_s) > 0
     # frames rendered with stats in between neither report the skips nor clear them (B's renders return normally)
-    now = R.assert_same(dev_a, dev_b, name, "the skipped objects where they were, the others moved")
-    assert T.frames_differ(now, posed)
+    now = assert_same_frames_and_tree(dev_a, dev_b, name, "the skipped objects where they were, the others moved")
+    assert frames_differ(now, posed)
     assert dev_b.status() == INVALID
-    msg = R.last_error()
+    msg = last_error()
     assert "p3d_scene_pose_device: %d object(s) with an unusable transform" % counts[0] in msg, msg
     assert "%d object(s) with a non-finite or inverted box" % counts[1] in msg, msg
     assert dev_b.status() == 0
     # the scene goes on: the next pose is exact again, and the counts start from zero
     both(dev_a, dev_b, ranges, first)
-    R.assert_same(dev_a, dev_b, name, "after the skips")
+    assert_same_frames_and_tree(dev_a, dev_b, name, "after the skips")
     assert dev_b.status() == 0
 
 
 def three_bodies(a):
     """balls_low: the triangles on slot 0, the spheres in two halves on slots 1 and 2"""
-    tri, sph = R.kinds_of(a)
+    tri, sph = kinds_of(a)
     half = len(sph) // 2
     assert len(tri) >= 2 and half >= 2
     return [(int(tri[0]), len(tri), 0), (int(sph[0]), half, 1), (int(sph[0]) + half, len(sph) - half, 2)]
@@ -361,17 +361,17 @@ def test_a_rotation_on_a_slot_that_holds_a_box(paths):
     assert boxes >= 1
     ranges = [(0, n, 0)]
     dev_b.set_rig(ranges, 1)
-    first = T.box_move(a, np.random.default_rng(325))[None]
+    first = box_move(a, np.random.default_rng(325))[None]
     k = 1
     both(dev_a, dev_b, ranges, first)
-    posed = R.assert_same(dev_a, dev_b, name, "a positive-diagonal pose of everything")
+    posed = assert_same_frames_and_tree(dev_a, dev_b, name, "a positive-diagonal pose of everything")
     turn = moves(a, 326, 1)
     d_x = gpu(turn)
     assert p3d.lib().p3d_scene_pose_device(dev_b._h, k, d_x.data_ptr(), None, None) == 0
-    assert dev_a.transform_prims([(f, c, 0) for f, c in T.runs(kinds, MOVABLE)], turn, p3d.UPDATE_REFIT) > 0
-    assert T.frames_differ(R.assert_same(dev_a, dev_b, name, "the box where it was, the others turned"), posed)
+    assert dev_a.transform_prims([(f, c, 0) for f, c in runs(kinds, MOVABLE)], turn, p3d.UPDATE_REFIT) > 0
+    assert frames_differ(assert_same_frames_and_tree(dev_a, dev_b, name, "the box where it was, the others turned"), posed)
     assert dev_b.status() == INVALID
-    msg = R.last_error()
+    msg = last_error()
     assert "%d object(s) with an unusable transform" % boxes in msg and " 0 object(s) with a non-finite or inverted box" in msg, msg
     assert dev_b.status() == 0
 
@@ -382,16 +382,16 @@ def test_a_box_that_overflows(paths):
     name = "balls_box"
     hs, a, dev_a, dev_b = twins(paths[name])
     kinds = a["prim_type"]
-    ranges, _, _ = T.plan(a, 0)
+    ranges, _, _ = plan(a, 0)
     box_rows = a["prim_v"][kinds == BOX]
-    far = T.IDENTITY.copy()
+    far = IDENTITY.copy()
     far[0, 0], far[0, 3] = 3e38, 3e38
     with np.errstate(over="ignore"):
         assert np.isinf(np.float32(3e38) * box_rows[:, 3] + np.float32(3e38)).all()
     dev_b.set_rig(ranges, 2)
     rng = np.random.default_rng(327)
-    first = np.stack([T.rigid(a, rng), T.box_move(a, rng)])
-    xforms = np.stack([T.rigid(a, rng), far])
+    first = np.stack([rigid(a, rng), box_move(a, rng)])
+    xforms = np.stack([rigid(a, rng), far])
     run_skip_case(a, dev_a, dev_b, name, ranges, first, xforms, [1.25, 1.0], {1}, (0, len(box_rows)))
 
 
@@ -408,19 +408,19 @@ def _pose(dev, k, d_x, d_s=None, stream=None):
 
 def test_refusals_leave_the_scene_as_it_was(paths):
     name = "balls_box"
-    hs = T.load(paths[name])
+    hs = load(paths[name], RES, legacy_f11=legacy(paths[name]))
     a = hs.arrays()
     n = a["n_prims"]
     sphere = int(np.nonzero(a["prim_type"] == SPHERE)[0][0])
     box = int(np.nonzero(a["prim_type"] == BOX)[0][0])
-    dev, twin, policy = R.scene(hs), R.scene(hs), R.scene(hs)  # (before the host scene builds a grid: its descriptor carries one from then on)
+    dev, twin, policy = scene(hs), scene(hs), scene(hs)  # (before the host scene builds a grid: its descriptor carries one from then on)
     host_tree = p3d.DeviceScene(hs, bvh=True)
     device_grid = p3d.DeviceScene(hs, bvh="device", grid="device")
     uploaded_grid = p3d.DeviceScene(hs, bvh="device", grid=True)
-    hp = T.load(T.PLANES)
+    hp = load(PLANES, RES)
     plane = int(np.nonzero(hp.arrays()["prim_type"] == PLANE)[0][0])
-    dev_planes = R.scene(hp)
-    slide = T.IDENTITY.copy()
+    dev_planes = scene(hp)
+    slide = IDENTITY.copy()
     slide[:, 3] = (0.25, 0.1, -0.2)
     d_x = gpu(np.stack([slide, slide]))
     d_s = gpu(np.array([1.1, 1.0], np.float32))
@@ -431,19 +431,19 @@ def test_refusals_leave_the_scene_as_it_was(paths):
 
     # set_rig
     for what, other in (("a scene with the host's tree", host_tree), ("a scene with an uploaded grid", uploaded_grid)):
-        was = T.frames(other, name)
+        was = frames(other, configs(name))
         assert _set_rig(other, good, 2) == INVALID, what
-        assert R.last_error().startswith("p3d_scene_set_rig"), what
+        assert last_error().startswith("p3d_scene_set_rig"), what
         assert _pose(other, 2, d_x.data_ptr()) == INVALID, what
-        assert R.last_error().startswith("p3d_scene_pose_device"), what
+        assert last_error().startswith("p3d_scene_pose_device"), what
         assert other.rig() == none
-        T.assert_same_frames(T.frames(other, name), was, what)
+        assert_same_frames(frames(other, configs(name)), was, what)
     assert _set_rig(None, good, 2) == INVALID and _pose(None, 2, d_x.data_ptr()) == INVALID
-    was_planes = T.frames(dev_planes, name)
-    assert _set_rig(dev_planes, [(plane, 1, 0, 0)], 1) == INVALID and "plane" in R.last_error()
+    was_planes = frames(dev_planes, configs(name))
+    assert _set_rig(dev_planes, [(plane, 1, 0, 0)], 1) == INVALID and "plane" in last_error()
     assert dev_planes.rig() == none
-    T.assert_same_frames(T.frames(dev_planes, name), was_planes, "a range that covers a plane")
-    was, tree = T.frames(dev, name), dev.export_bvh()
+    assert_same_frames(frames(dev_planes, configs(name)), was_planes, "a range that covers a plane")
+    was, tree = frames(dev, configs(name)), dev.export_bvh()
     rig_cases = [
         ("null ranges with a count", dict(ranges=good, n_xforms=2, null=True)),
         ("ranges without transforms", dict(ranges=good, n_xforms=0)),
@@ -461,17 +461,17 @@ def test_refusals_leave_the_scene_as_it_was(paths):
     for rigged in (False, True):  # without a rig, and with one that every refusal must leave standing
         for what, kw in rig_cases:
             assert _set_rig(dev, **kw) == INVALID, what
-            assert R.last_error().startswith("p3d_scene_set_rig"), what
+            assert last_error().startswith("p3d_scene_set_rig"), what
             assert dev.rig() == (dict(n_ranges=2, n_xforms=2, n_posed_objects=4) if rigged else none), what
-        T.assert_same_frames(T.frames(dev, name), was, "set_rig refusals")
-        T.assert_same_tree(dev.export_bvh(), tree, "set_rig refusals")
+        assert_same_frames(frames(dev, configs(name)), was, "set_rig refusals")
+        assert_same_tree(dev.export_bvh(), tree, "set_rig refusals")
         if not rigged:
             # pose without a rig
-            assert _pose(dev, 2, d_x.data_ptr(), d_s.data_ptr()) == INVALID and "no rig" in R.last_error()
+            assert _pose(dev, 2, d_x.data_ptr(), d_s.data_ptr()) == INVALID and "no rig" in last_error()
             assert _set_rig(dev, good, 2) == 0
-            T.assert_same_frames(T.frames(dev, name), was, "set_rig moves nothing")
+            assert_same_frames(frames(dev, configs(name)), was, "set_rig moves nothing")
     # overlap is worded as in the waiting form
-    assert _set_rig(dev, [(sphere, 3, 0, 0), (sphere + 2, 2, 0, 0)], 1) == INVALID and "object %d is in two ranges" % (sphere + 2) in R.last_error()
+    assert _set_rig(dev, [(sphere, 3, 0, 0), (sphere + 2, 2, 0, 0)], 1) == INVALID and "object %d is in two ranges" % (sphere + 2) in last_error()
 
     # pose_device, on the rigged scene
     big = 1 << 24
@@ -490,33 +490,33 @@ def test_refusals_leave_the_scene_as_it_was(paths):
     device_grid.set_rig([r[:3] for r in good], 2)
     for what, px, ps in (("d_xforms", host_x.ctypes.data, None), ("d_sphere_scale", d_x.data_ptr(), host_s.ctypes.data)):
         assert _pose(device_grid, 2, px, ps) == INVALID, what
-        assert "is host memory" in R.last_error() and what in R.last_error(), R.last_error()
+        assert "is host memory" in last_error() and what in last_error(), last_error()
     for what, (k, px, ps) in pose_cases:
         assert _pose(dev, k, px, ps) == INVALID, what
-        assert R.last_error().startswith("p3d_scene_pose_device"), what
-        T.assert_same_frames(T.frames(dev, name), was, what)
-        T.assert_same_tree(dev.export_bvh(), tree, what)
-    assert _pose(dev, 2, host_x.ctypes.data, None) == INVALID and "is host memory" in R.last_error() and "d_xforms" in R.last_error()
+        assert last_error().startswith("p3d_scene_pose_device"), what
+        assert_same_frames(frames(dev, configs(name)), was, what)
+        assert_same_tree(dev.export_bvh(), tree, what)
+    assert _pose(dev, 2, host_x.ctypes.data, None) == INVALID and "is host memory" in last_error() and "d_xforms" in last_error()
     # matrices that end behind their allocation: a rig of 2^24 slots whose ranges name the first two (were the runtime unable
     # to report the range, the kernel would still read nothing outside the tensor)
     assert _set_rig(dev, good, big) == 0
-    assert _pose(dev, big, d_x.data_ptr(), None) == INVALID and "ends behind its allocation" in R.last_error(), R.last_error()
+    assert _pose(dev, big, d_x.data_ptr(), None) == INVALID and "ends behind its allocation" in last_error(), last_error()
     assert _pose(dev, big, d_x.data_ptr(), d_s.data_ptr()) == INVALID
-    T.assert_same_frames(T.frames(dev, name), was, "matrices that end behind their allocation")
+    assert_same_frames(frames(dev, configs(name)), was, "matrices that end behind their allocation")
     assert _set_rig(dev, good, 2) == 0
     # a device grid, and the policy: the stream form is refused, the waiting form works
     xf = np.stack([slide, slide])
     scale = np.array([1.1, 1.0], np.float32)
     plain = [r[:3] for r in good]
     assert device_grid.rig()["n_posed_objects"] == 4
-    was_grid = T.frames(device_grid, name)
+    was_grid = frames(device_grid, configs(name))
     assert _pose(device_grid, 2, d_x.data_ptr(), d_s.data_ptr()) == UNSUPPORTED
-    assert R.last_error().startswith("p3d_scene_pose_device") and "p3d_scene_transform_prims" in R.last_error()
-    T.assert_same_frames(T.frames(device_grid, name), was_grid, "a scene with a device-built grid")
+    assert last_error().startswith("p3d_scene_pose_device") and "p3d_scene_transform_prims" in last_error()
+    assert_same_frames(frames(device_grid, configs(name)), was_grid, "a scene with a device-built grid")
     assert device_grid.transform_prims(plain, xf, p3d.UPDATE_REFIT, sphere_scale=scale) > 0
     dev.set_auto_rebuild(1.01)
-    assert _pose(dev, 2, d_x.data_ptr(), d_s.data_ptr()) == UNSUPPORTED and "auto-rebuild" in R.last_error()
-    T.assert_same_frames(T.frames(dev, name), was, "the policy is on")
+    assert _pose(dev, 2, d_x.data_ptr(), d_s.data_ptr()) == UNSUPPORTED and "auto-rebuild" in last_error()
+    assert_same_frames(frames(dev, configs(name)), was, "the policy is on")
     policy.set_auto_rebuild(1.01)
     assert policy.transform_prims(plain, xf, p3d.UPDATE_REFIT, sphere_scale=scale) > 0
     dev.set_auto_rebuild(0)
@@ -525,22 +525,22 @@ def test_refusals_leave_the_scene_as_it_was(paths):
     # the same call without a fault is accepted
     assert _pose(dev, 2, d_x.data_ptr(), d_s.data_ptr()) == 0
     twin.transform_prims(plain, xf, p3d.UPDATE_REFIT, sphere_scale=scale)
-    assert T.frames_differ(R.assert_same(twin, dev, name, "the accepted call"), was)
+    assert frames_differ(assert_same_frames_and_tree(twin, dev, name, "the accepted call"), was)
     # no ranges: the rig goes, and rig() says so
     assert _set_rig(dev, [], 0) == 0 and dev.rig() == none
-    assert _pose(dev, 2, d_x.data_ptr(), d_s.data_ptr()) == INVALID and "no rig" in R.last_error()
+    assert _pose(dev, 2, d_x.data_ptr(), d_s.data_ptr()) == INVALID and "no rig" in last_error()
     dev.set_rig([], 5)
     assert dev.rig() == none
-    R.assert_same(twin, dev, name, "after the rig is gone")
+    assert_same_frames_and_tree(twin, dev, name, "after the rig is gone")
     assert dev.status() == 0
 
 
 # 8. accumulators and the cost record
 def test_accumulators_and_bvh_cost(paths):
-    hs = T.load(paths["cornell"], 64)
+    hs = load(paths["cornell"], 64)
     a = hs.arrays()
-    dev_a, dev_b = R.scene(hs), R.scene(hs)
-    ranges, xforms, scale = T.plan(a, T.SEED["cornell"] + 45)
+    dev_a, dev_b = scene(hs), scene(hs)
+    ranges, xforms, scale = plan(a, SEED["cornell"] + 45)
     cfg = p3d.pathtrace_config(accel=p3d.ACCEL_BVH, spp_sqrt=3, max_depth=8, seed=9)
     dev_b.set_rig(ranges, 2)
     acc = dev_b.accumulator(cfg)
@@ -563,10 +563,10 @@ def test_accumulators_and_bvh_cost(paths):
 
 # 9. a frame that reads the root box
 def test_a_per_level_frame_after_a_pose(paths):
-    hs = T.load(paths["tri5k"], 128)
+    hs = load(paths["tri5k"], 128)
     a = hs.arrays()
     n = a["n_prims"]
-    dev_a, dev_b = R.scene(hs), R.scene(hs)
+    dev_a, dev_b = scene(hs), scene(hs)
     cfg = p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4, chain_launch=p3d.CHAIN_PER_LEVEL, collect_stats=1)
     before = dev_b.render(cfg)
     # the mesh grows by a fifth about a corner: the root box it is binned by moves
@@ -582,9 +582,9 @@ def test_a_per_level_frame_after_a_pose(paths):
     rgb_a, hit_a, st_a = dev_a.render(cfg)
     rgb_b, hit_b, st_b = dev_b.render(cfg)
     assert np.array_equal(hit_a, hit_b) and rgb_a.tobytes() == rgb_b.tobytes()
-    assert {k: getattr(st_a, k) for k in T.COUNTERS} == {k: getattr(st_b, k) for k in T.COUNTERS}
+    assert {k: getattr(st_a, k) for k in RENDER_COUNTERS} == {k: getattr(st_b, k) for k in RENDER_COUNTERS}
     assert rgb_b.tobytes() != before[0].tobytes()
-    T.assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "the grown mesh")
+    assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "the grown mesh")
     assert dev_b.status() == 0
 
 
@@ -606,7 +606,7 @@ def test_the_call_returns_ahead_of_the_stream(paths):
     begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.cuda.stream(side):
         begin.record(side)
-        slow = R.produced(big, 1.0, rounds=300)
+        slow = produced(big, 1.0, rounds=300)
         end.record(side)
         x = (base + 0.01 * torch.sin(2.0 * base) + 0.0 * slow[:base.numel()].view(base.shape)).contiguous()
         t0 = time.perf_counter()
@@ -619,5 +619,5 @@ def test_the_call_returns_ahead_of_the_stream(paths):
     assert producer_ms >= 100 * 1e3 * call_s, (producer_ms, call_s)
     assert busy, "the stream had passed the call when it returned"
     dev_a.transform_prims(ranges, x.cpu().numpy(), p3d.UPDATE_REFIT)
-    R.assert_same(dev_a, dev_b, "tri5k", "a pose behind a long producer")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "a pose behind a long producer")
     assert dev_b.status() == 0

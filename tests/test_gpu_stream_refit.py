@@ -16,67 +16,33 @@ import pytest
 import torch
 
 import p3d_amd as p3d
-import test_gpu_scene_transform as T
 from device_geometry_helpers import deformed_mesh, diagonal, moved_spheres
 from scene_update_helpers import SPHERE, TRIANGLE
+from frame_checks import CORNELL, RENDER_COUNTERS, assert_same_frames, assert_same_tree, frames, frames_differ, gpu, load
+from live_scene_checks import (HEAD, IDENTITY, LEAF, RES, TRACE_OUT, assert_same_frames_and_tree, camera_rays, configs, kinds_of,
+                               last_error, produced, rigid, scene, trace_outputs)
+from variant_scenes import scene_path
 
 pytestmark = pytest.mark.gpu
 
-LEAF = np.uint32(0x80000000)
 INVALID, UNSUPPORTED, CAPACITY = -1, -3, -4
-TRACE_OUT = (("hit_id", torch.int32, None), ("t", torch.float32, None), ("hit_point", torch.float32, 3), ("normal", torch.float32, 3))
 
 
 @pytest.fixture
 def paths(tri5k_path):
-    return {"balls_low": T.scene_path("balls_low.p3f"), "tri5k": tri5k_path, "cornell": T.CORNELL}
-
-
-def scene(hs):
-    return p3d.DeviceScene(hs, bvh="device")
+    return {"balls_low": scene_path("balls_low.p3f"), "tri5k": tri5k_path, "cornell": CORNELL}
 
 
 def twins(path):
     """(host scene arrays, scene A for the waiting form, scene B for the stream form)"""
-    hs = T.load(path)
+    hs = load(path, RES)
     return hs.arrays(), scene(hs), scene(hs)
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def assert_same(dev_a, dev_b, name, what):
-    """T.assert_same_scene for scenes without a grid -> B's frames"""
-    now = T.frames(dev_b, name)
-    T.assert_same_frames(T.frames(dev_a, name), now, what)
-    T.assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), what)
-    return now
-
-
-def last_error():
-    return p3d.lib().p3d_last_error().decode()
-
-
-def produced(base, amount, rounds=50):
-    """base + amount * a smooth field of it, by a chain of torch operations on the current stream"""
-    wave = base
-    for _ in range(rounds):
-        wave = torch.sin(wave * 1.5 + 0.25)
-    return (base + amount * wave).contiguous()
-
-
-def kinds_of(a):
-    tri, sph = np.nonzero(a["prim_type"] == TRIANGLE)[0], np.nonzero(a["prim_type"] == SPHERE)[0]
-    for run in (tri, sph):
-        assert len(run) == 0 or np.array_equal(run, np.arange(run[0], run[0] + len(run)))
-    return tri, sph
 
 
 # 1. whole-mesh soup, produced on the stream the call is given
 def test_a_soup_produced_on_the_side_stream(paths):
     a, dev_a, dev_b = twins(paths["tri5k"])
-    before = T.frames(dev_b, "tri5k")
+    before = frames(dev_b, configs("tri5k"))
     base = gpu(a["prim_v"].reshape(-1, 3))
     torch.cuda.synchronize()
     side = torch.cuda.Stream()
@@ -87,8 +53,8 @@ def test_a_soup_produced_on_the_side_stream(paths):
     bits = pos.cpu().numpy()
     assert np.isfinite(bits).all() and bits.tobytes() != a["prim_v"].tobytes()
     assert dev_a.update_triangles(0, pos, mode=p3d.UPDATE_REFIT) > 0
-    now = assert_same(dev_a, dev_b, "tri5k", "a soup from the side stream")
-    assert T.frames_differ(now, before), "the deformation changed no pixel"
+    now = assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "a soup from the side stream")
+    assert frames_differ(now, before), "the deformation changed no pixel"
     assert dev_b.status() == 0
 
 
@@ -107,7 +73,7 @@ def test_indexed_triangles_with_shared_vertices(dtype, paths):
     dev_b.refit_triangles(0, d_pos, d_idx, stream=side)
     side.synchronize()
     dev_a.update_triangles(0, d_pos, d_idx, mode=p3d.UPDATE_REFIT)
-    assert_same(dev_a, dev_b, "tri5k", "indexed, %s" % dtype.__name__)
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "indexed, %s" % dtype.__name__)
     assert dev_b.status() == 0
 
 
@@ -115,13 +81,13 @@ def test_spheres(paths):
     a, dev_a, dev_b = twins(paths["balls_low"])
     _, sph = kinds_of(a)
     first, count = int(sph[0]), len(sph)
-    before = T.frames(dev_b, "balls_low")
+    before = frames(dev_b, configs("balls_low"))
     cr = gpu(moved_spheres(a, first, count, seed=21))
     side = torch.cuda.Stream()
     dev_b.refit_spheres(first, cr, stream=side)
     side.synchronize()
     dev_a.update_spheres(first, cr, mode=p3d.UPDATE_REFIT)
-    assert T.frames_differ(assert_same(dev_a, dev_b, "balls_low", "spheres"), before)
+    assert frames_differ(assert_same_frames_and_tree(dev_a, dev_b, "balls_low", "spheres"), before)
     assert dev_b.status() == 0
 
 
@@ -129,14 +95,14 @@ def test_triangles_and_spheres_in_one_call(paths):
     a, dev_a, dev_b = twins(paths["cornell"])
     tri, sph = kinds_of(a)
     t0, s0 = int(tri[0]), int(sph[0])
-    before = T.frames(dev_b, "cornell")
+    before = frames(dev_b, configs("cornell"))
     rng = np.random.default_rng(22)
     soup = a["prim_v"][tri].reshape(-1, 3).astype(np.float64)
     d_soup = gpu((soup + rng.uniform(-1, 1, soup.shape) * 0.01 * diagonal(a, tri)).astype(np.float32))
     d_cr = gpu(moved_spheres(a, s0, len(sph), seed=23))
     dev_b.refit_device([dev_b.sphere_source(s0, d_cr), dev_b.triangle_source(t0, d_soup)])  # the default stream
     dev_a.update_geometry_device([dev_a.sphere_source(s0, d_cr), dev_a.triangle_source(t0, d_soup)], p3d.UPDATE_REFIT)
-    assert T.frames_differ(assert_same(dev_a, dev_b, "cornell", "triangles and spheres"), before)
+    assert frames_differ(assert_same_frames_and_tree(dev_a, dev_b, "cornell", "triangles and spheres"), before)
 
 
 def test_sources_in_descending_order_and_untouched_objects(paths):
@@ -160,7 +126,7 @@ def test_sources_in_descending_order_and_untouched_objects(paths):
     dev_b.refit_triangles(meshes, stream=side)
     side.synchronize()
     dev_a.update_triangles(meshes, mode=p3d.UPDATE_REFIT)
-    assert_same(dev_a, dev_b, "tri5k", "five sources")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "five sources")
     # the uncovered objects keep their exact bits: every leaf that holds none of the covered objects has the box it had
     tree1 = dev_b.export_bvh()
     for k in ("bvh_index", "bvh_count_leaf", "bvh_order"):
@@ -177,17 +143,6 @@ def test_sources_in_descending_order_and_untouched_objects(paths):
 
 
 # 3. three steps in a row on one stream, no host wait between them
-def camera_rays(a, n, seed):
-    lo, hi = a["prim_bmin"].min(0).astype(np.float64), a["prim_bmax"].max(0).astype(np.float64)
-    rng = np.random.default_rng(seed)
-    o = np.tile((lo + hi) / 2 + (hi - lo) * np.array([1.1, 0.9, 1.3]), (n, 1))
-    d = rng.uniform(lo, hi, (n, 3)) - o
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return gpu(o.astype(np.float32)), gpu(d.astype(np.float32))
-
-
-def trace_outputs(n):
-    return {name: torch.zeros((n,) if cols is None else (n, cols), dtype=dtype, device="cuda") for name, dtype, cols in TRACE_OUT}
 
 
 def test_three_steps_without_a_host_wait(paths):
@@ -219,8 +174,6 @@ def test_three_steps_without_a_host_wait(paths):
 
 
 # 4. the smallest trees
-HEAD = ["bclr 0.1 0.2 0.3", "v", "from 0 -6 1", "at 0 0 0", "up 0 0 1", "angle 40", "hither 0.01", "resolution 64 64",
-        "aperture 0", "focal 1", "l 3 -4 5 1 1 1", "f 0.8 0.3 0.3 0.7 1 1 1 0.3 20 0 1 0 0 0"]
 
 
 @pytest.mark.parametrize("kind", ["spheres", "triangles"])
@@ -237,7 +190,7 @@ def test_tiny_scenes(n_objs, kind, tmp_path):
         f.write("\n".join(HEAD + objs) + "\n")
     a, dev_a, dev_b = twins(path)
     assert a["n_prims"] == n_objs
-    before = T.frames(dev_b, "tiny")
+    before = frames(dev_b, configs("tiny"))
     rng = np.random.default_rng(40 + n_objs)
     side = torch.cuda.Stream()
     if kind == "spheres":
@@ -254,7 +207,7 @@ def test_tiny_scenes(n_objs, kind, tmp_path):
         dev_b.refit_triangles(0, d_new, stream=side)
         side.synchronize()
         dev_a.update_triangles(0, d_new, mode=p3d.UPDATE_REFIT)
-    assert T.frames_differ(assert_same(dev_a, dev_b, "tiny", "%d %s" % (n_objs, kind)), before)
+    assert frames_differ(assert_same_frames_and_tree(dev_a, dev_b, "tiny", "%d %s" % (n_objs, kind)), before)
     assert dev_b.status() == 0
 
 
@@ -279,7 +232,7 @@ def test_failed_triangles_keep_their_geometry_and_show_in_status(paths):
     msg = last_error()
     assert "%d triangle(s) with an index >= n_elems" % len(oob_set) in msg and "%d object(s) with a non-finite or inverted box" % len(nan_set) in msg, msg
     assert dev_b.status() == 0
-    assert_same(dev_a, dev_b, "tri5k", "two bad indices and a NaN position")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "two bad indices and a NaN position")
     # the named objects kept their geometry, the others moved
     tree1 = dev_b.export_bvh()
     order = tree1["bvh_order"]
@@ -308,7 +261,7 @@ def test_a_frame_with_stats_leaves_the_report_to_status(paths):
     side.synchronize()
     with pytest.raises(p3d.P3DError):
         dev_a.update_spheres(first, d_cr, mode=p3d.UPDATE_REFIT)
-    assert_same(dev_a, dev_b, "balls_low", "frames with stats before the status is asked")  # (B's renders return normally)
+    assert_same_frames_and_tree(dev_a, dev_b, "balls_low", "frames with stats before the status is asked")  # (B's renders return normally)
     assert dev_b.status() == INVALID and "1 object(s) with a non-finite or inverted box" in last_error(), last_error()
     assert dev_b.status() == 0
 
@@ -328,7 +281,7 @@ def test_a_sphere_with_a_bad_radius_keeps_its_geometry(radius, paths):
     assert dev_b.status() == INVALID
     assert "0 triangle(s)" in last_error() and "1 object(s) with a non-finite or inverted box" in last_error(), last_error()
     assert dev_b.status() == 0
-    assert_same(dev_a, dev_b, "balls_low", "one bad radius")
+    assert_same_frames_and_tree(dev_a, dev_b, "balls_low", "one bad radius")
 
 
 # 6. refusals, nothing changed
@@ -340,7 +293,7 @@ def _raw(dev, sources, n=None, null=False, stream=None):
 
 def test_refusals_leave_the_scene_as_it_was(paths):
     name = "balls_low"
-    hs = T.load(paths[name])
+    hs = load(paths[name], RES)
     a = hs.arrays()
     n = a["n_prims"]
     tri, sph = kinds_of(a)
@@ -363,13 +316,13 @@ def test_refusals_leave_the_scene_as_it_was(paths):
     good = [src(s0, ns, S, ns, cr.data_ptr())]
     for what, other, code in (("a scene with the host's tree", host_tree, INVALID), ("a scene with an uploaded grid", uploaded_grid, INVALID),
                               ("a scene with a device-built grid", device_grid, UNSUPPORTED)):
-        was = T.frames(other, name)
+        was = frames(other, configs(name))
         assert _raw(other, good) == code, what
         assert last_error().startswith("p3d_scene_refit_device"), what
-        T.assert_same_frames(T.frames(other, name), was, what)
+        assert_same_frames(frames(other, configs(name)), was, what)
     assert "p3d_scene_update_geometry_device" in last_error()  # the grid scene is pointed to the waiting form
     assert _raw(None, good) == INVALID
-    was, tree = T.frames(dev, name), dev.export_bvh()
+    was, tree = frames(dev, configs(name)), dev.export_bvh()
     # host memory is refused BEFORE any launch; each such source goes in twice (test_gpu_device_geometry.py says why)
     for what, bad in (("d_data", src(s0, ns, S, ns, host_cr.ctypes.data)),
                       ("d_index", src(t0, nt, TRI, 3 * nt, soup.data_ptr(), host_index.ctypes.data))):
@@ -407,8 +360,8 @@ def test_refusals_leave_the_scene_as_it_was(paths):
         kw = kw if isinstance(kw, dict) else dict(sources=kw)
         assert _raw(dev, **kw) == INVALID, what
         assert last_error().startswith("p3d_scene_refit_device"), what
-        T.assert_same_frames(T.frames(dev, name), was, what)
-        T.assert_same_tree(dev.export_bvh(), tree, what)
+        assert_same_frames(frames(dev, configs(name)), was, what)
+        assert_same_tree(dev.export_bvh(), tree, what)
     assert _raw(dev, cases[-1][1]) == INVALID and "ends behind its allocation" in last_error()
     # the policy: refused while it is on, accepted again once it is off
     dev.set_auto_rebuild(1.01)
@@ -417,15 +370,15 @@ def test_refusals_leave_the_scene_as_it_was(paths):
     # no sources: nothing enqueued, nothing changed
     assert _raw(dev, []) == 0 and _raw(dev, [], null=True) == 0
     assert dev.refit_device([]) is None
-    T.assert_same_tree(dev.export_bvh(), tree, "after the refusals")
-    T.assert_same_frames(T.frames(dev, name), was, "after the refusals")
+    assert_same_tree(dev.export_bvh(), tree, "after the refusals")
+    assert_same_frames(frames(dev, configs(name)), was, "after the refusals")
     cost = dev.bvh_cost()
     assert cost["refits_since_build"] == 0
     assert dev.status() == 0
     # the same calls without a fault are accepted, in any order
     assert _raw(dev, [src(s0, ns, S, ns, cr.data_ptr()), src(t0, nt, TRI, 3 * nt, soup.data_ptr(), index.data_ptr())]) == 0
     twin.update_geometry_device([twin.triangle_source(t0, soup, index), twin.sphere_source(s0, cr)], p3d.UPDATE_REFIT)
-    assert T.frames_differ(assert_same(twin, dev, name, "the accepted call"), was)
+    assert frames_differ(assert_same_frames_and_tree(twin, dev, name, "the accepted call"), was)
     assert dev.status() == 0
 
 
@@ -439,13 +392,13 @@ def test_sixteen_sources_and_one_too_many(paths):
     with pytest.raises(p3d.P3DError) as e:
         dev_b.refit_triangles(meshes)
     assert e.value.code == CAPACITY and "p3d_scene_update_geometry_device" in str(e.value), e.value
-    T.assert_same_tree(dev_b.export_bvh(), tree, "seventeen sources")
+    assert_same_tree(dev_b.export_bvh(), tree, "seventeen sources")
     assert dev_b.bvh_cost()["refits_since_build"] == 0
     side = torch.cuda.Stream()
     dev_b.refit_triangles(meshes[:16][::-1], stream=side)
     side.synchronize()
     dev_a.update_triangles(meshes[:16], mode=p3d.UPDATE_REFIT)
-    assert_same(dev_a, dev_b, "tri5k", "sixteen sources")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "sixteen sources")
     assert dev_b.export_bvh()["bvh_bmin"].tobytes() != tree["bvh_bmin"].tobytes()
     assert dev_b.status() == 0
 
@@ -457,7 +410,7 @@ def test_the_first_update_of_a_scene(paths):
     cr = gpu(moved_spheres(a, int(sph[0]), len(sph), seed=71))
     dev_b.refit_spheres(int(sph[0]), cr)  # nothing has made the builder's state: this call does
     dev_a.update_spheres(int(sph[0]), cr, mode=p3d.UPDATE_REFIT)
-    assert_same(dev_a, dev_b, "cornell", "the first update is a stream refit")
+    assert_same_frames_and_tree(dev_a, dev_b, "cornell", "the first update is a stream refit")
 
 
 # 8. topology and depth of a new tree
@@ -481,7 +434,7 @@ def test_after_a_rebuild_that_changed_the_order(paths):
     dev_b.refit_triangles(0, d_small, stream=side)  # over the NEW topology, with the new tree's depth
     side.synchronize()
     dev_a.update_triangles(0, d_small, mode=p3d.UPDATE_REFIT)
-    assert_same(dev_a, dev_b, "tri5k", "a stream refit of a rebuilt tree")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "a stream refit of a rebuilt tree")
     assert dev_b.export_bvh()["bvh_order"].tobytes() == built["bvh_order"].tobytes()
     assert dev_b.status() == 0
 
@@ -491,7 +444,7 @@ def test_the_forms_in_turn(paths):
     a, dev_a, dev_b = twins(paths["cornell"])
     tri, sph = kinds_of(a)
     t0, s0 = int(tri[0]), int(sph[0])
-    move = T.rigid(a, np.random.default_rng(91))
+    move = rigid(a, np.random.default_rng(91))
     for dev in (dev_a, dev_b):
         dev.transform_prims([(t0, len(tri), 0)], move[None], p3d.UPDATE_REFIT)  # makes the rest copy
     side = torch.cuda.Stream()
@@ -502,28 +455,28 @@ def test_the_forms_in_turn(paths):
     dev_b.refit_triangles(t0, d_soup, stream=side)
     side.synchronize()
     dev_a.update_triangles(t0, d_soup, mode=p3d.UPDATE_REFIT)
-    deformed = assert_same(dev_a, dev_b, "cornell", "step 1: a stream refit")
+    deformed = assert_same_frames_and_tree(dev_a, dev_b, "cornell", "step 1: a stream refit")
     cr = gpu(moved_spheres(a, s0, 2, seed=93))
     for dev in (dev_a, dev_b):
         assert dev.update_spheres(s0, cr, mode=p3d.UPDATE_REFIT) > 0
-    assert_same(dev_a, dev_b, "cornell", "step 2: the waiting form")
+    assert_same_frames_and_tree(dev_a, dev_b, "cornell", "step 2: the waiting form")
     for dev in (dev_a, dev_b):
-        dev.transform_prims([(t0, len(tri), 0)], T.IDENTITY[None], p3d.UPDATE_REFIT)
-    back = assert_same(dev_a, dev_b, "cornell", "step 3: the identity")
+        dev.transform_prims([(t0, len(tri), 0)], IDENTITY[None], p3d.UPDATE_REFIT)
+    back = assert_same_frames_and_tree(dev_a, dev_b, "cornell", "step 3: the identity")
     # (B's identity read the rest copy the stream form wrote, A's the one the waiting form wrote: a deformed object rests
     # where it is put, on both)
-    assert T.frames_differ(back, deformed)  # (step 2 moved two spheres)
+    assert frames_differ(back, deformed)  # (step 2 moved two spheres)
     cr2 = gpu(moved_spheres(a, s0, len(sph), seed=94))
     dev_b.refit_spheres(s0, cr2, stream=side)
     side.synchronize()
     dev_a.update_spheres(s0, cr2, mode=p3d.UPDATE_REFIT)
-    assert T.frames_differ(assert_same(dev_a, dev_b, "cornell", "step 4: a stream refit again"), deformed)
+    assert frames_differ(assert_same_frames_and_tree(dev_a, dev_b, "cornell", "step 4: a stream refit again"), deformed)
     assert dev_b.status() == 0
 
 
 # 10. accumulators and the cost record
 def test_accumulators_and_bvh_cost(paths):
-    hs = T.load(paths["cornell"], 64)
+    hs = load(paths["cornell"], 64)
     a = hs.arrays()
     dev_a, dev_b = scene(hs), scene(hs)
     _, sph = kinds_of(a)
@@ -549,7 +502,7 @@ def test_accumulators_and_bvh_cost(paths):
 
 # 11. a frame that reads the root box
 def test_a_per_level_frame_after_a_stream_refit(paths):
-    hs = T.load(paths["tri5k"], 128)
+    hs = load(paths["tri5k"], 128)
     a = hs.arrays()
     dev_a, dev_b = scene(hs), scene(hs)
     cfg = p3d.whitted_config(accel=p3d.ACCEL_BVH, max_depth=4, chain_launch=p3d.CHAIN_PER_LEVEL, collect_stats=1)
@@ -564,9 +517,9 @@ def test_a_per_level_frame_after_a_stream_refit(paths):
     rgb_a, hit_a, st_a = dev_a.render(cfg)
     rgb_b, hit_b, st_b = dev_b.render(cfg)
     assert np.array_equal(hit_a, hit_b) and rgb_a.tobytes() == rgb_b.tobytes()
-    assert {k: getattr(st_a, k) for k in T.COUNTERS} == {k: getattr(st_b, k) for k in T.COUNTERS}
+    assert {k: getattr(st_a, k) for k in RENDER_COUNTERS} == {k: getattr(st_b, k) for k in RENDER_COUNTERS}
     assert rgb_b.tobytes() != before[0].tobytes()
-    T.assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "the grown mesh")
+    assert_same_tree(dev_a.export_bvh(), dev_b.export_bvh(), "the grown mesh")
     assert dev_b.status() == 0
 
 
@@ -599,5 +552,5 @@ def test_the_call_returns_ahead_of_the_stream(paths):
     assert producer_ms >= 100 * 1e3 * call_s, (producer_ms, call_s)
     assert busy, "the stream had passed the call when it returned"
     dev_a.update_triangles(0, pos, mode=p3d.UPDATE_REFIT)
-    assert_same(dev_a, dev_b, "tri5k", "a refit behind a long producer")
+    assert_same_frames_and_tree(dev_a, dev_b, "tri5k", "a refit behind a long producer")
     assert dev_b.status() == 0

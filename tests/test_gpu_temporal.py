@@ -10,20 +10,16 @@ import subprocess
 import numpy as np
 import pytest
 
+from api_checks import EXE
+from conftest import scene_path
+from frame_checks import CORNELL, device_scene, same_bits
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
 from temporal_reference import TemporalReference
 
 pytestmark = pytest.mark.gpu
 
-CORNELL = os.path.join(ROOT, "scenes", "cornell.p3f")
 BALLS = scene_path("balls_low.p3f")
 TOL = 1e-5  # |gpu - ref| <= TOL * max(1, |ref|); the variance: TOL * max(1, the largest m2 it is computed from)
-EXE = os.path.join(ROOT, "p3d-raytracer_amd", "p3d_render")
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
 
 
 def orbit(view, deg):
@@ -59,12 +55,6 @@ def write_view(path, tmp_path, from_, at=None):
     out = str(tmp_path / ("view_" + os.path.basename(path)))
     open(out, "w").write(text)
     return out
-
-
-def device_scene(path, res):
-    hs = p3d.HostScene(path)
-    hs.set_resolution(*res)
-    return p3d.DeviceScene(hs, bvh=True, grid=True)
 
 
 def renders(dev, cfg, tiles):
@@ -158,7 +148,7 @@ def test_accumulators_refuse_a_pass_after_a_camera_change(kind):
 
 # ---- the formula ----
 
-def compare(gpu, ref, what):
+def compare_with_model(gpu, ref, what):
     out, var, hist = gpu
     r_out, r_var, r_n, info = ref
     amb, vamb = info["ambiguous"], info["var_ambiguous"]
@@ -215,7 +205,7 @@ def test_formula_on_random_inputs():
             cam = camera_of(view, (w, h), from_=orbit(view, 0.8 * k))
             rgb, nd, ac = synthetic_frame(cam, w, h, rng)
             gpu = tp.run(cam, rgb, nd, ac, params=p3d.temporal_params(**params))
-            compare(gpu, ref.run(cam, rgb, nd, ac, **params), "random frame %d %s" % (k, params))
+            compare_with_model(gpu, ref.run(cam, rgb, nd, ac, **params), "random frame %d %s" % (k, params))
         assert tp.frames == 6
         assert (gpu[2] > 1).mean() > 0.5  # most pixels carry a history
 
@@ -245,7 +235,7 @@ def test_formula_on_a_cornell_orbit_and_pan():
     ref = TemporalReference(*res)
     for k, (cam, rgb, nd, ac, hit) in enumerate(cornell_frames(dev, cams)):
         assert (hit < 0).any() and (hit >= 0).any()  # misses and hits in view
-        compare(tp.run(cam, rgb, nd, ac), ref.run(cam, rgb, nd, ac), "cornell frame %d" % k)
+        compare_with_model(tp.run(cam, rgb, nd, ac), ref.run(cam, rgb, nd, ac), "cornell frame %d" % k)
 
 
 def test_static_camera_is_a_running_mean_and_reset_starts_again():

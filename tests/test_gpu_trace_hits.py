@@ -11,33 +11,27 @@ import numpy as np
 import pytest
 import torch
 
+from frame_checks import as_bytes, gpu
 import hits_reference as hr
 import intersect_reference as ref
+from live_scene_checks import plan
 import p3d_amd as p3d
-import segment_reference as seg
-import test_gpu_ray_query as rq
-import test_gpu_scene_transform as T
+from ray_query_checks import BATCHES, CLOSEST_ALL, N_MESH, N_MODEL, World, limit_sets
 from scene_update_helpers import BOX, SPHERE, TRIANGLE
+import segment_reference as seg
 
 pytestmark = pytest.mark.gpu
 
-BATCHES = rq.BATCHES  # 1, 63, 64, 65, 129, 4099
 KS = (1, 2, 5, 16)
-N_MODEL, N_MESH = rq.N_MODEL, rq.N_MESH
 ROWS = ("count", "object", "t", "hit_point", "normal")
 ALL = ROWS + ("total",)
 FLT_MAX = hr.FLT_MAX
 INF = np.float32(np.inf)
 INVALID, UNSUPPORTED = -1, -3
-gpu, same_bits = rq.gpu, rq.same_bits
 
 
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-class RayWorld(rq.World):
-    """rq.World with rays of the caller's"""
+class RayWorld(World):
+    """World with rays of the caller's"""
 
     def __init__(self, path, trees, o, d, oracle=True):
         super().__init__(path, trees, n=8, oracle=oracle)
@@ -48,7 +42,7 @@ class RayWorld(rq.World):
 @pytest.fixture(scope="module")
 def worlds(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("trace_hits")
-    w = {name: rq.World(path, ("host", "device") if name == "mixed" else ("host",)) for name, path in ref.scene_paths(tmp).items()}
+    w = {name: World(path, ("host", "device") if name == "mixed" else ("host",)) for name, path in ref.scene_paths(tmp).items()}
     w["slats"] = RayWorld(hr.write_slats(tmp / "slats.p3f"), ("device",), *hr.slat_rays(21, max(BATCHES)))
     return w
 
@@ -93,7 +87,7 @@ def assert_rows(got, k, what):
         assert got["t"].shape == (n, k) and (got["t"][none] == FLT_MAX).all(), what + ": t behind count"
     for name in ("hit_point", "normal"):
         if name in got:
-            assert got[name].shape == (n, k, 3) and bits(got[name][none]) == bits(np.zeros((int(none.sum()), 3), np.float32)), "%s: %s behind count" % (what, name)
+            assert got[name].shape == (n, k, 3) and as_bytes(got[name][none]) == as_bytes(np.zeros((int(none.sum()), 3), np.float32)), "%s: %s behind count" % (what, name)
     if "total" in got:
         assert got["total"].dtype == np.int32 and (got["count"] == np.minimum(got["total"], k)).all(), what + ": count = min(total, k)"
 
@@ -104,7 +98,7 @@ def assert_is_brute(got, want, k, what):
     assert (got["count"] == count).all(), "%s: count, first at ray %d" % (what, int(np.argmax(got["count"] != count)))
     assert (got["total"] == total).all(), "%s: total, first at ray %d" % (what, int(np.argmax(got["total"] != total)))
     assert (got["object"] == obj).all(), "%s: object, first at ray %d" % (what, int(np.argmax((got["object"] != obj).any(1))))
-    assert bits(got["t"]) == bits(t), what + ": t"
+    assert as_bytes(got["t"]) == as_bytes(t), what + ": t"
 
 
 # ---- accel None: the oracle's brute force on every ray ---------------------------------------------------------------------------
@@ -114,7 +108,7 @@ def test_brute_force_equals_the_oracle(name, worlds):
     w = worlds[name]
     dev = w.devs["host"]
     n = N_MODEL
-    sets, has = rq.limit_sets(w, n)
+    sets, has = limit_sets(w, n)
     sets["no limit"] = None
     for what, t_max in sets.items():
         for k in KS:
@@ -128,13 +122,13 @@ def test_brute_force_equals_the_oracle(name, worlds):
                 assert not got["total"][has].any()
             if what == "the float above t":
                 t_near = seg.nearest(w.tests)[0]
-                assert (got["total"][has] >= 1).all() and bits(got["t"][has, 0]) == bits(t_near[has])
+                assert (got["total"][has] >= 1).all() and as_bytes(got["t"][has, 0]) == as_bytes(t_near[has])
             if what == "the float below t":
                 assert not got["total"][has].any()
             if what in ("inf", "no limit"):
-                assert bits(got["t"][has, 0]) == bits(seg.nearest(w.tests)[0][has]) and (got["count"][~has] == 0).all()
+                assert as_bytes(got["t"][has, 0]) == as_bytes(seg.nearest(w.tests)[0][has]) and (got["count"][~has] == 0).all()
         free, unlimited = ask(dev, p3d.ACCEL_NONE, w.d_o[:n], w.d_d[:n], 5, None), ask(dev, p3d.ACCEL_NONE, w.d_o[:n], w.d_d[:n], 5, sets["inf"])
-    assert all(bits(free[key]) == bits(unlimited[key]) for key in ALL)
+    assert all(as_bytes(free[key]) == as_bytes(unlimited[key]) for key in ALL)
     assert (hr.brute_hits(w.tests, None, 0)[1] >= 2).any()  # hits behind the first one
     assert dev.status() == 0
 
@@ -162,7 +156,7 @@ def test_slats_fill_the_list(worlds):
                 assert_rows(part, k, label)
                 assert (part["total"] == full["total"]).all() and (part["count"] == np.minimum(full["total"], k)).all(), label + ": k = %d" % k
                 for key in ("object", "t", "hit_point", "normal"):
-                    assert bits(part[key]) == bits(full[key][:, :k]), "%s: %s of k = %d is no prefix of k = 16" % (label, key, k)
+                    assert as_bytes(part[key]) == as_bytes(full[key][:, :k]), "%s: %s of k = %d is no prefix of k = 16" % (label, key, k)
             assert (ask(dev, accel, d_o, d_d, 0, t_max, want=("total",))["total"] == full["total"]).all(), label + ": k = 0"
             # without total a full list culls against its last entry: the same count, object and t
             for k in (1, 4, 16):
@@ -171,7 +165,7 @@ def test_slats_fill_the_list(worlds):
                 assert_rows(lean, k, label)
                 assert (lean["count"] == np.minimum(full["total"], k)).all(), label
                 for key in ("object", "t", "hit_point", "normal"):
-                    assert bits(lean[key]) == bits(full[key][:, :k]), "%s: %s without total, k = %d" % (label, key, k)
+                    assert as_bytes(lean[key]) == as_bytes(full[key][:, :k]), "%s: %s without total, k = %d" % (label, key, k)
     assert dev.status() == 0
 
 
@@ -204,7 +198,7 @@ def test_bvh_equals_the_brute_force(name, tree, worlds):
                     want = ask(dev, p3d.ACCEL_NONE, w.d_o[:n], w.d_d[:n], k, t_max, want=want_names)
                     assert_rows(got, k, what)
                     if n == 1:
-                        assert all(bits(got[key]) == bits(want[key]) for key in got) or margin[0] < ref.THRESHOLD, what
+                        assert all(as_bytes(got[key]) == as_bytes(want[key]) for key in got) or margin[0] < ref.THRESHOLD, what
                         continue
                     ok, left = ref.well_conditioned(margin[:n], what)
                     assert_bvh_is_brute(got, want, ok, what)
@@ -277,7 +271,7 @@ def test_hit_points_and_normals(worlds):
         assert (obj[:, 1:] >= 0).any() and (obj[:, 0] < 0).any()  # hits behind the first one, and rays that hit nothing
         for j in np.unique(obj[obj >= 0]):
             m = obj == j
-            assert bits(nrm[m]) == bits(dev.object_normal(int(j), hp[m])), "accel %d: the normal of object %d" % (accel, j)
+            assert as_bytes(nrm[m]) == as_bytes(dev.object_normal(int(j), hp[m])), "accel %d: the normal of object %d" % (accel, j)
     # a lone object on a triangle-only scene reports the closest-hit query's bits: the slats under a limit behind the first one
     s = worlds["slats"]
     sdev = s.devs["device"]
@@ -286,10 +280,10 @@ def test_hit_points_and_normals(worlds):
     limit = ((ts[0] + ts[1]) / 2).astype(np.float32)
     for accel in (p3d.ACCEL_NONE, p3d.ACCEL_BVH):
         got = ask(sdev, accel, s.d_o[:n], s.d_d[:n], 3, limit)
-        one = {key: v.cpu().numpy() for key, v in sdev.trace_closest_device(accel, s.d_o[:n], s.d_d[:n], t_max=gpu(limit), want=rq.ALL).items()}
+        one = {key: v.cpu().numpy() for key, v in sdev.trace_closest_device(accel, s.d_o[:n], s.d_d[:n], t_max=gpu(limit), want=CLOSEST_ALL).items()}
         assert (got["total"] == 1).all() and (got["count"] == 1).all() and (one["hit_id"] == 0).all()
-        assert (got["object"][:, 0] == one["hit_id"]).all() and bits(got["t"][:, 0]) == bits(one["t"])
-        assert bits(got["hit_point"][:, 0]) == bits(one["hit_point"]) and bits(got["normal"][:, 0]) == bits(one["normal"])
+        assert (got["object"][:, 0] == one["hit_id"]).all() and as_bytes(got["t"][:, 0]) == as_bytes(one["t"])
+        assert as_bytes(got["hit_point"][:, 0]) == as_bytes(one["hit_point"]) and as_bytes(got["normal"][:, 0]) == as_bytes(one["normal"])
 
 
 # ---- inside or outside: the parity of the crossings of a closed mesh -----------------------------------------------------------
@@ -326,8 +320,8 @@ def assert_sees_the_moved_scene(hs, o, d, d_o, d_d, k, t_max, on_stream, before,
     fresh = p3d.DeviceScene(hs, bvh=False)
     again = ask(fresh, p3d.ACCEL_NONE, d_o, d_d, k, t_max)
     for key in ALL:
-        assert bits(on_stream[p3d.ACCEL_NONE][key]) == bits(again[key]), "%s, against a fresh scene: %s" % (what, key)
-    assert bits(again["t"]) != bits(before["t"]), what + ": the update moved nothing the rays can see"
+        assert as_bytes(on_stream[p3d.ACCEL_NONE][key]) == as_bytes(again[key]), "%s, against a fresh scene: %s" % (what, key)
+    assert as_bytes(again["t"]) != as_bytes(before["t"]), what + ": the update moved nothing the rays can see"
     objs = model_objects(hs.arrays())
     ok, left = ref.well_conditioned(hr.all_hits_margin(objs, o, d, t_max, ref._all(objs, o, d)), what)
     assert_bvh_is_brute(on_stream[p3d.ACCEL_BVH], again, ok, what)
@@ -366,7 +360,7 @@ def test_behind_a_pose_on_the_same_stream(worlds):
     hs = p3d.HostScene(w.hs.path)
     a = hs.arrays()
     dev = p3d.DeviceScene(hs, bvh="device")
-    ranges, xforms, scale = T.plan(a, 93)  # spheres and triangles under a rigid move, boxes under a positive-diagonal one
+    ranges, xforms, scale = plan(a, 93)  # spheres and triangles under a rigid move, boxes under a positive-diagonal one
     dev.set_rig(ranges, 2)
     n, k = 4099, 4
     before = ask(dev, p3d.ACCEL_NONE, w.d_o[:n], w.d_d[:n], k)

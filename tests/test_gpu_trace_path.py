@@ -14,12 +14,12 @@ import os
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
-import shading_reference as sh
 from conftest import GOLDEN, scene_path
+from frame_checks import ACCELS, assert_bits, f32_bits, tile_of
 from oracle import binding as ob
-from test_gpu_trace_radiance import ACCELS, assert_bits, bits, tile_of
-from test_trace_path_api import next31, seed_stream
+import p3d_amd as p3d
+from rng_reference import next31, seed_stream
+import shading_reference as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -202,7 +202,7 @@ def test_sample_rays_are_the_oracles(mode, scenes):
         assert_bits(got["direction"].cpu().numpy(), d, what + ": direction")
         assert (got["rng"].cpu().numpy().view(np.uint64) == states).all(), what + ": the state after the draws"
     if lens:
-        assert (bits(o) != bits(o[0])).any(), "every ray starts at the eye: no lens sample"
+        assert (f32_bits(o) != f32_bits(o[0])).any(), "every ray starts at the eye: no lens sample"
 
 
 def test_sample_rays_refusals(scenes):
@@ -256,7 +256,7 @@ def test_the_sample_rays_traced_and_summed_are_the_frame(name, accel, scenes):
             lit += int((f_hit >= 0).sum())
             if depth == 8 and spp_sqrt == 2:
                 shallow = frame(dev, pt_cfg(accel, 2, 1, dof=dof, sample_mode=mode))[0]
-                differ = int((bits(shallow) != bits(f_rgb)).any(axis=1).sum())
+                differ = int((f32_bits(shallow) != f32_bits(f_rgb)).any(axis=1).sum())
     assert lit > 0 and differ > 20, "%s: the bounces add nothing to the frame" % name
     assert dev.status() == 0
 
@@ -271,7 +271,7 @@ def test_a_sub_tile_and_the_skybox(scenes):
     for accel in ACCELS:
         sky, _ = check_reconstruction(dev, pt_cfg(accel, 2, 5, skybox=1), "skybox over %s" % accel, flags=p3d.RADIANCE_SKYBOX)
         plain, _ = check_reconstruction(dev, pt_cfg(accel, 2, 5), "no flag over %s" % accel)
-        assert (bits(sky) != bits(plain)).any(axis=1).sum() > 100, "the cubemap shows nowhere"
+        assert (f32_bits(sky) != f32_bits(plain)).any(axis=1).sum() > 100, "the cubemap shows nowhere"
 
 
 # ---- 3. the seeded mode is the state mode ----------------------------------------------------------------------------------------------
@@ -296,7 +296,7 @@ def test_seeded_and_state_modes(accel, scenes):
         one(s, flags=ACC, want=(), out={"rgb": total})
     assert_bits(five, total.cpu().numpy(), "five seeded samples over %s" % accel)
     assert_bits(hit, one(2)["hit_id"].cpu().numpy(), "hit_id of five samples over %s" % accel)
-    assert (bits(five) != bits(one(2)["rgb"].cpu().numpy())).any(), "the samples after the first add nothing"
+    assert (f32_bits(five) != f32_bits(one(2)["rgb"].cpu().numpy())).any(), "the samples after the first add nothing"
     # with a state: the stream goes on from sample to sample and is written back
     start = states_tensor([seed_stream(77, i, 0) for i in range(n)])
     carried, chained = start.clone(), start.clone()
@@ -357,7 +357,7 @@ def test_behind_pose_device_on_one_stream(tmp_path):
         rgb, hit = path(dev_a, accel, rays, 5, samples=2, seed=SEED)
         assert_bits(out["hit_id"].cpu().numpy(), hit, "after pose_device over %s: hit_id" % accel)
         assert_bits(out["rgb"].cpu().numpy(), rgb, "after pose_device over %s: rgb" % accel)
-        assert (bits(rgb) != bits(before)).any(axis=1).sum() > 100, "the move shows nowhere"
+        assert (f32_bits(rgb) != f32_bits(before)).any(axis=1).sum() > 100, "the move shows nowhere"
     assert dev_a.status() == 0 and dev_b.status() == 0
 
 

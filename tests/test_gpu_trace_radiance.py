@@ -12,34 +12,19 @@ import os
 import numpy as np
 import pytest
 
+from conftest import GOLDEN, scene_path
+from frame_checks import ACCELS, assert_bits, f32_bits, tile_of
+from oracle import binding as ob
 import p3d_amd as p3d
 import shading_reference as sh
-from conftest import GOLDEN, scene_path
-from oracle import binding as ob
 
 pytestmark = pytest.mark.gpu
 
-ACCELS = {"none": p3d.ACCEL_NONE, "grid": p3d.ACCEL_GRID, "bvh": p3d.ACCEL_BVH}
 RES = (64, 48)
 SMALL = (48, 40)       # the glass / TIR scenes
 SUB_TILE = (5, 7, 27, 13)  # x0, y0, w, h: a width that is no multiple of 8, rows that start inside a wave tile
 VIEW_A = dict(from_=(-1.6, 2.2, 1.1), at=(0.1, 0, 0.1), up=(0, 0, 1), angle=50.0)  # of balls_low
 VIEW_B = dict(from_=(0.4, -2.6, 0.9), at=(0, 0.2, 0), up=(0, 0, 1), angle=38.0)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, "%s: shape %s for %s" % (what, got.shape, want.shape)
-    same = (bits(got) == bits(want)) if got.dtype == np.float32 else (got == want)
-    assert same.all(), "%s: %d of %d values differ, first at %s" % (what, int((~same).sum()), same.size, np.argwhere(~same)[0])
-
-
-def tile_of(t):
-    return None if t is None else p3d.Tile(t[0], t[1], t[2], t[3], 0, 1)
 
 
 def frame(dev, accel, depth, tile=None, skybox=0):
@@ -161,7 +146,7 @@ def test_radiance_of_the_cameras_rays_is_the_per_pixel_frame(name, device_built,
             lit += int((f_hit >= 0).sum())
             if depth == 4 and accel == "bvh":
                 deeper = frame(dev, accel, 0)[0]
-                assert (bits(deeper) != bits(f_rgb)).any(axis=1).sum() > 50, "%s: the chain adds nothing to the frame" % what
+                assert (f32_bits(deeper) != f32_bits(f_rgb)).any(axis=1).sum() > 50, "%s: the chain adds nothing to the frame" % what
     assert lit > 9 * res[0] * res[1] // 8
     check_view(dev, "bvh", 4, what + ", sub-tile", tile=SUB_TILE)
     check_view(dev, "none", 1, what + ", sub-tile", tile=SUB_TILE)
@@ -197,7 +182,7 @@ def test_the_largest_record_block():
     dev = p3d.DeviceScene(host(scene_path("balls_low.p3f"), RES), bvh=True)
     f16, _ = check_view(dev, "bvh", p3d.RADIANCE_MAX_DEPTH, "balls_low")
     f4, _ = frame(dev, "bvh", 4)
-    assert (bits(f16) != bits(f4)).any(), "no chain of this frame is deeper than 4"
+    assert (f32_bits(f16) != f32_bits(f4)).any(), "no chain of this frame is deeper than 4"
     check_view(dev, "none", p3d.RADIANCE_MAX_DEPTH, "balls_low")
 
 
@@ -245,7 +230,7 @@ def test_skybox_flag():
         assert_bits(with_sky, f_rgb, "skybox over %s: rgb" % accel)
         without, _ = radiance(dev, accel, rays, 4)
         assert_bits(without, frame(dev, accel, 4, skybox=0)[0], "no flag over %s: rgb" % accel)
-        assert (bits(with_sky) != bits(without)).any(axis=1).sum() > 100, "the cubemap shows nowhere"
+        assert (f32_bits(with_sky) != f32_bits(without)).any(axis=1).sum() > 100, "the cubemap shows nowhere"
 
 
 # ---- 5. the float64 model --------------------------------------------------------------------------------------------------------------
@@ -297,7 +282,7 @@ def test_behind_pose_device_on_one_stream(files):
         f_rgb, f_hit = frame(dev_a, accel, 4)
         assert_bits(out["hit_id"].cpu().numpy(), f_hit, "after pose_device over %s: hit_id" % accel)
         assert_bits(out["rgb"].cpu().numpy(), f_rgb, "after pose_device over %s: rgb" % accel)
-        assert (bits(f_rgb) != bits(before)).any(axis=1).sum() > 100, "the move shows nowhere"
+        assert (f32_bits(f_rgb) != f32_bits(before)).any(axis=1).sum() > 100, "the move shows nowhere"
     assert dev_a.status() == 0 and dev_b.status() == 0
 
 

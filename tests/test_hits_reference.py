@@ -8,8 +8,8 @@ import pytest
 
 import hits_reference as hr
 import intersect_reference as ref
-import segment_reference as seg
 from oracle import binding as ob
+import segment_reference as seg
 
 INF = np.float32(np.inf)
 

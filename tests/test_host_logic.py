@@ -8,9 +8,9 @@ import re
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
 from conftest import ROOT, SCENES, scene_path
 from oracle import binding as ob
+import p3d_amd as p3d
 
 ALL_SCENES = sorted(f for f in os.listdir(SCENES) if f.endswith(".p3f"))
 

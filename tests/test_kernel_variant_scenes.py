@@ -1,10 +1,8 @@
 """The scenes of tests/test_gpu_kernel_variants.py without a GPU: the layout rule of csrc/capi_scene_layout.hpp on the host-side
 descriptors puts each scene on the side of the 16 / 20 / 26 KB limits of plan_frame its cases claim, and the generated
 sphere scene has the transmissive and reflective material its GHOSTS cases need."""
-import numpy as np
-
 import p3d_amd as p3d
-from test_gpu_kernel_variants import ACCELS, scene_files, staged_bytes  # noqa: F401 (scene_files is a fixture)
+from variant_scenes import ACCEL_VALUES, scene_files, staged_bytes  # noqa: F401 (scene_files is a fixture)
 
 
 def test_scene_sizes_are_what_the_cases_need(scene_files):
@@ -15,7 +13,7 @@ def test_scene_sizes_are_what_the_cases_need(scene_files):
     assert 20 * 1024 < size("spill_spheres", p3d.ACCEL_NONE) <= 26 * 1024 and size("spill_spheres", p3d.ACCEL_BVH) <= 20 * 1024
     assert size("balls_medium", p3d.ACCEL_BVH) <= 20 * 1024 and size("balls_medium", p3d.ACCEL_NONE) <= 19 * 1024
     assert size("balls_low", p3d.ACCEL_NONE) <= 19 * 1024
-    for accel in ACCELS:
+    for accel in ACCEL_VALUES:
         assert size("l2_ghosts", accel) > 26 * 1024 and size("tri5k", accel) > 26 * 1024
 
 

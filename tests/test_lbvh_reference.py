@@ -4,9 +4,9 @@ degenerate as the GPU tests take them to be."""
 import numpy as np
 import pytest
 
+from conftest import scene_path
 import lbvh_reference as ref
 import p3d_amd as p3d
-from conftest import scene_path
 
 SYNTHETIC = {name: (objects, view) for name, objects, view in ref.synthetic_scenes()}
 COUNTS = [1, 2, 3, 4, 5, 255, 256, 257, 511, 512, 513]

@@ -1,18 +1,17 @@
 """Nearest-surface queries (p3d_host_scene_nearest, p3d_nearest_device, include/p3d.h) without a GPU: the entry points are
 declared, exported and wrapped, a null scene is refused by name, and the tensor wrapper refuses what it cannot pass on before
 the library is called."""
-import os
 import re
 
 import numpy as np
 import pytest
 
+from api_checks import header_code, scene_without_a_library
 import p3d_amd as p3d
-from conftest import ROOT
 
 
 def test_header_declares_the_prototypes():
-    code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
+    code = header_code()
     cf, f, i32 = r"\s*const\s+float\s*\*\s*\w+\s*,", r"\s*float\s*\*\s*\w+\s*,", r"\s*int32_t\s*\*\s*\w+\s*,"
     assert re.search(r"\bint\s+p3d_nearest_device\s*\(\s*p3d_scene\s*\*\s*\w+,\s*uint32_t\s+\w+,\s*uint32_t\s+\w+," + cf + cf + i32 + f + f + f
                      + r"\s*void\s*\*\s*\w+\)", code)
@@ -35,22 +34,9 @@ def test_library_exports_them_and_python_wraps_them():
     assert b"p3d_host_scene_nearest" in lib.p3d_last_error() and b"null scene" in lib.p3d_last_error()
 
 
-class _Untouchable:
-    """Stands where the library would: any use of it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was called (%s)" % name)
-
-
-def _scene_without_a_library():
-    dev = p3d.DeviceScene.__new__(p3d.DeviceScene)
-    dev._L, dev._h, dev.device, dev.host = _Untouchable(), None, 0, None
-    return dev
-
-
 def test_the_wrapper_refuses_bad_arguments_before_the_library():
     import torch
-    dev = _scene_without_a_library()
+    dev = scene_without_a_library()
     q = dev.nearest_device
     raw = (0x1000, 6)  # a raw (address, rows) pair is taken at its word
     f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32)

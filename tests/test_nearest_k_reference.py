@@ -4,6 +4,7 @@ HostScene.nearest at k = 1; the prefix property; the cases whose answer is exact
 import numpy as np
 import pytest
 
+from frame_checks import as_bytes
 import intersect_reference as ref
 import nearest_k_reference as nk
 import nearest_reference as near
@@ -14,10 +15,6 @@ SEED = {name: 400 + k for k, name in enumerate(SCENES)}  # test_nearest_referenc
 KS = nk.KS
 FLT_MAX = near.FLT_MAX
 INVALID = -1
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 @pytest.fixture(scope="module")
@@ -62,7 +59,7 @@ def test_limits(name, k, worlds):
             c = count[start:start + 63]
             assert (c == 0).any() and (c == k).any() and (k == 1 or ((c > 0) & (c < k)).any()), "%s, k = %d, batch at %d" % (name, k, start)
     everything = hs.nearest_k(pts, k, max_dist=np.full(len(pts), np.inf, np.float32))
-    assert all(bits(a) == bits(b) for a, b in zip(everything, hs.nearest_k(pts, k)))
+    assert all(as_bytes(a) == as_bytes(b) for a, b in zip(everything, hs.nearest_k(pts, k)))
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -71,7 +68,7 @@ def test_k_1_is_the_nearest_query(name, worlds):
     for limits in (None, limits_of(name, srt, 1), near.draw_limits(tab.min(0), SEED[name] + 50)):
         count, obj, dist, closest = hs.nearest_k(pts, 1, max_dist=limits)
         one = hs.nearest(pts, max_dist=limits)
-        assert bits(obj[:, 0]) == bits(one[0]) and bits(dist[:, 0]) == bits(one[1]) and bits(closest[:, 0]) == bits(one[2])
+        assert as_bytes(obj[:, 0]) == as_bytes(one[0]) and as_bytes(dist[:, 0]) == as_bytes(one[1]) and as_bytes(closest[:, 0]) == as_bytes(one[2])
         assert (count == (one[0] >= 0)).all()
 
 
@@ -85,7 +82,7 @@ def test_a_smaller_k_is_a_prefix(name, worlds):
             assert (small[0] == np.minimum(big[0], k)).all(), "%s: count at k = %d" % (name, k)
             keep = np.arange(k)[None, :] < small[0][:, None]
             for a, b in zip(small[1:], big[1:]):
-                assert bits(a[keep]) == bits(b[:, :k][keep]), "%s: the first rows at k = %d" % (name, k)
+                assert as_bytes(a[keep]) == as_bytes(b[:, :k][keep]), "%s: the first rows at k = %d" % (name, k)
             nk.check_rows(pts, k, small, "%s, k = %d" % (name, k))
 
 
@@ -195,4 +192,4 @@ def test_edge_inputs(tmp_path):
     cnt = np.zeros(4, np.int32)
     obj2 = np.zeros((4, 3), np.int32)
     assert lib.p3d_host_scene_nearest_k(hs._h, 4, 3, pts.ctypes.data, None, cnt.ctypes.data, obj2.ctypes.data, None, None) == 0
-    assert bits(cnt) == bits(count) and bits(obj2) == bits(obj)
+    assert as_bytes(cnt) == as_bytes(count) and as_bytes(obj2) == as_bytes(obj)

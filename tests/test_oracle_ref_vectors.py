@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from frame_checks import f32_bits
 from oracle import binding as ob
 
 
@@ -31,10 +32,6 @@ def fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def test_vector_ops_bit_exact(g, L):
     a, b, f = g["vec_a"], g["vec_b"], g["scal_f"]
     n = len(a)
@@ -49,11 +46,11 @@ def test_vector_ops_bit_exact(g, L):
         dot[i] = L.orc_vec_dot(fp(a[i]), fp(b[i]))
         L.orc_vec_cross(fp(a[i]), fp(b[i]), fp(cross[i]))
         L.orc_vec_div(fp(a[i]), C.c_float(f[i]), fp(div[i]))
-    assert (bits(norm) == bits(g["normalize"])).all()      # vector.cpp:65-70
-    assert (bits(length) == bits(g["length"])).all()       # vector.cpp:10-13
-    assert (bits(dot) == bits(g["dot"])).all()             # vector.cpp:55-58
-    assert (bits(cross) == bits(g["cross"])).all()         # vector.cpp:84-99
-    assert (bits(div) == bits(g["div"])).all()             # vector.cpp:60-63
+    assert (f32_bits(norm) == f32_bits(g["normalize"])).all()      # vector.cpp:65-70
+    assert (f32_bits(length) == f32_bits(g["length"])).all()       # vector.cpp:10-13
+    assert (f32_bits(dot) == f32_bits(g["dot"])).all()             # vector.cpp:55-58
+    assert (f32_bits(cross) == f32_bits(g["cross"])).all()         # vector.cpp:84-99
+    assert (f32_bits(div) == f32_bits(g["div"])).all()             # vector.cpp:60-63
 
 
 def test_get_direction_mutates_and_is_not_idempotent(g, L):
@@ -63,9 +60,9 @@ def test_get_direction_mutates_and_is_not_idempotent(g, L):
         d = a.copy()
         for i in range(len(d)):
             L.orc_get_direction(fp(d[i]), k)
-        assert (bits(d) == bits(g[key])).all()
+        assert (f32_bits(d) == f32_bits(g[key])).all()
     # the golden data itself shows that a second normalisation can still move the vector
-    assert (bits(g["getdir1"]) != bits(g["getdir2"])).any()
+    assert (f32_bits(g["getdir1"]) != f32_bits(g["getdir2"])).any()
 
 
 def test_camera_rays_bit_exact(g, L):
@@ -78,11 +75,11 @@ def test_camera_rays_bit_exact(g, L):
         st = np.zeros(2, np.float32)
         p15 = np.ascontiguousarray(cams[c])
         L.orc_camera_rays(fp(p15), m, fp(px), fp(lens), fp(ro), fp(rd), fp(lo), fp(ld), fp(st))
-        assert (bits(st) == bits(g["cam_state"][c])).all()      # camera.h:34-63
-        assert (bits(ro) == bits(g["cam_ray_o"][c])).all()      # camera.h:65-82
-        assert (bits(rd) == bits(g["cam_ray_d"][c])).all()
-        assert (bits(lo) == bits(g["cam_lray_o"][c])).all()     # camera.h:84-115
-        assert (bits(ld) == bits(g["cam_lray_d"][c])).all()
+        assert (f32_bits(st) == f32_bits(g["cam_state"][c])).all()      # camera.h:34-63
+        assert (f32_bits(ro) == f32_bits(g["cam_ray_o"][c])).all()      # camera.h:65-82
+        assert (f32_bits(rd) == f32_bits(g["cam_ray_d"][c])).all()
+        assert (f32_bits(lo) == f32_bits(g["cam_lray_o"][c])).all()     # camera.h:84-115
+        assert (f32_bits(ld) == f32_bits(g["cam_lray_d"][c])).all()
 
 
 def test_rand_float_and_unit_disk_on_libc_stream(g, L):
@@ -90,21 +87,21 @@ def test_rand_float_and_unit_disk_on_libc_stream(g, L):
     for s, seed in enumerate(g["rand_seeds"]):
         rf = np.zeros(64, np.float32)
         L.orc_libc_rand_floats(int(seed), 64, fp(rf))
-        assert (bits(rf) == bits(g["rand_float"][s])).all()
+        assert (f32_bits(rf) == f32_bits(g["rand_float"][s])).all()
         disk = np.zeros((64, 2), np.float32)
         L.orc_libc_unit_disk(int(seed), 64, 0, fp(disk))
-        assert (bits(disk) == bits(g["unit_disk"][s])).all()
+        assert (f32_bits(disk) == f32_bits(g["unit_disk"][s])).all()
         other = np.zeros((64, 2), np.float32)
         L.orc_libc_unit_disk(int(seed), 64, 1, fp(other))
-        assert (bits(other) != bits(g["unit_disk"][s])).any()  # the other operand order is observable
+        assert (f32_bits(other) != f32_bits(g["unit_disk"][s])).any()  # the other operand order is observable
 
 
 def test_u8_pack_and_clamp(g, L):
     u8 = np.array([L.orc_u8fromfloat(float(x)) for x in g["u8_in"]], np.uint8)
     assert (u8 == g["u8_out"]).all()                                  # maths.h:81-86
     tof = np.array([L.orc_u8tofloat(i) for i in range(256)], np.float32)
-    assert (bits(tof) == bits(g["u8tofloat"])).all()                  # maths.h:89-92
+    assert (f32_bits(tof) == f32_bits(g["u8tofloat"])).all()                  # maths.h:89-92
     cl = g["clamp_in"].copy()
     for i in range(len(cl)):
         L.orc_color_clamp(fp(cl[i]))
-    assert (bits(cl) == bits(g["clamp_out"])).all()                   # color.h:39-44
+    assert (f32_bits(cl) == f32_bits(g["clamp_out"])).all()                   # color.h:39-44

@@ -3,14 +3,14 @@ structures are declared, exported and wrapped, and p3d.transformed - the numpy f
 device kernel runs - returns the input bits for the identity, equals scene_update_helpers.translated for a pure translation,
 stays within 4 ulp of the largest term of a float64 evaluation, and produces rows HostScene.set_geometry accepts."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+from api_checks import header_code
+from conftest import scene_path
 import p3d_amd as p3d
-from conftest import ROOT, scene_path
 from scene_update_helpers import BOX, PLANE, SPHERE, TRIANGLE, translated
 
 LEGACY = ("tri_low.p3f", "box.p3f", "balls_box.p3f")  # 11-number `f` lines (P3D_LOAD_LEGACY_F11)
@@ -43,7 +43,7 @@ def _rotation(rng):
 
 
 def test_header_declares_the_entry_point_and_its_structures():
-    code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
+    code = header_code()
     assert re.search(r"typedef\s+struct\s+p3d_xform\s*\{\s*float\s+m\[12\]\s*;\s*float\s+sphere_scale\s*;\s*uint32_t\s+reserved\[3\]\s*;\s*\}\s*p3d_xform\s*;", code)
     assert re.search(r"typedef\s+struct\s+p3d_xform_range\s*\{\s*uint32_t\s+first\s*,\s*count\s*,\s*xform\s*,\s*reserved\s*;\s*\}\s*p3d_xform_range\s*;", code)
     assert re.search(r"\bint\s+p3d_scene_transform_prims\s*\(\s*p3d_scene\s*\*\s*\w+,\s*uint32_t\s+\w+,\s*const\s+p3d_xform_range\s*\*\s*\w+,\s*uint32_t\s+\w+,"

@@ -9,18 +9,15 @@ import re
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
+from api_checks import header_code
 from conftest import ROOT, scene_path
+import p3d_amd as p3d
 from scene_update_helpers import PLANE, translated, write_moved_p3f
 
 SYMBOLS = ["p3d_scene_update_prims", "p3d_scene_export_bvh", "p3d_host_scene_set_geometry"]
 PRIM_KEYS = ("prim_v", "prim_type", "prim_material", "prim_n", "prim_bmin", "prim_bmax")
 BVH_KEYS = ("bvh_bmin", "bvh_index", "bvh_bmax", "bvh_count_leaf", "bvh_order")
 LEGACY = ("tri_low.p3f", "box.p3f")  # 11-number `f` lines (P3D_LOAD_LEGACY_F11): the shipped parser would load no objects
-
-
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
 
 
 def _same_bytes(a, b, keys, what):
@@ -30,7 +27,7 @@ def _same_bytes(a, b, keys, what):
 
 
 def test_header_declares_the_entry_points_and_keeps_the_abi_version():
-    code = _header_code()
+    code = header_code()
     for name in SYMBOLS:
         assert re.search(r"\bint\s+%s\s*\(" % name, code), name
     assert re.search(r"typedef\s+enum\s+p3d_update_mode\s*\{\s*P3D_UPDATE_REFIT\s*=\s*0\s*,\s*P3D_UPDATE_REBUILD\s*=\s*1\s*\}\s*p3d_update_mode\s*;", code)

@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import intersect_reference as ref
-import segment_reference as seg
 from oracle import binding as ob
+import segment_reference as seg
 
 
 def test_model_on_a_closed_form_case():

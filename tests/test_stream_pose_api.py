@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
+from api_checks import scene_without_a_library
 from conftest import ROOT
-from test_device_geometry_api import _scene_without_a_library
+import p3d_amd as p3d
 
 NAMES = ("p3d_scene_set_rig", "p3d_scene_rig", "p3d_scene_pose_device")
 
@@ -55,7 +55,7 @@ def test_python_wraps_them():
 
 def test_the_wrapper_refuses_bad_tensors_before_the_library():
     import torch
-    dev = _scene_without_a_library()
+    dev = scene_without_a_library()
     good = (0x1000, 4)  # a raw pair is taken at its word: the fault is in the other argument
     cases = [
         ("a CPU tensor", "host memory", lambda: dev.pose_device(torch.zeros((4, 3, 4), dtype=torch.float32))),

@@ -9,10 +9,10 @@ import re
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
+from api_checks import scene_without_a_library
 from conftest import ROOT
+import p3d_amd as p3d
 from scene_update_helpers import SPHERE, TRIANGLE
-from test_device_geometry_api import _scene_without_a_library
 
 
 def test_header_declares_the_entry_point():
@@ -46,7 +46,7 @@ def test_python_wraps_it():
 
 def test_wrappers_refuse_bad_tensors_before_the_library():
     import torch
-    dev = _scene_without_a_library()
+    dev = scene_without_a_library()
     good_pos = torch.zeros((6, 3), dtype=torch.float32)
     good_idx = torch.zeros((2, 3), dtype=torch.int32)
     cases = [

@@ -7,8 +7,9 @@ import re
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
+from api_checks import scene_without_a_library
 from conftest import ROOT
+import p3d_amd as p3d
 
 NO_ARGS = (None,) * 10  # the ten pointers behind (scene, accel, n, k)
 
@@ -36,22 +37,9 @@ def test_library_exports_it_and_python_wraps_it():
     assert lib.p3d_trace_hits_device(None, p3d.ACCEL_NONE, 0, 0, *NO_ARGS) == -1
 
 
-class _Untouchable:
-    """Stands where the library would: any use of it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was called (%s)" % name)
-
-
-def _scene_without_a_library():
-    dev = p3d.DeviceScene.__new__(p3d.DeviceScene)
-    dev._L, dev._h, dev.device, dev.host = _Untouchable(), None, 0, None
-    return dev
-
-
 def test_the_wrapper_refuses_bad_arguments_before_the_library():
     import torch
-    dev = _scene_without_a_library()
+    dev = scene_without_a_library()
     q = dev.trace_hits_device
     B, N = p3d.ACCEL_BVH, p3d.ACCEL_NONE
     raw = (0x1000, 6)  # a raw (address, rows) pair is taken at its word

@@ -2,44 +2,20 @@
 p3d_camera_sample_rays_device, include/p3d_radiance.h) without a GPU: the entry points are declared, exported and in the
 prototype table, a null scene is refused with a message, the tensor wrappers refuse what they cannot pass on before the
 library is called, and the RNG state arithmetic tests/test_gpu_trace_path.py builds its states with is the oracle's."""
-import os
 import re
 
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
-from conftest import ROOT
+from api_checks import header_code, scene_without_a_library
 from oracle import binding as ob
-from test_ray_query_api import _scene_without_a_library
-
-M64 = (1 << 64) - 1
-PCG_MUL = 6364136223846793005
-
-
-def mix64(z):
-    z = (z + 0x9E3779B97F4A7C15) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return z ^ (z >> 31)
-
-
-def seed_stream(seed, pixel, sample):
-    """-> (state, inc) of the stream of (pixel, sample), as csrc/device_core.hpp Rng::seed_stream"""
-    k = mix64(seed ^ mix64((pixel << 32) | sample))
-    inc = ((mix64(k) << 1) | 1) & M64
-    return (k * PCG_MUL + inc) & M64, inc
-
-
-def next31(state, inc):
-    """-> (the state after the draw, the draw)"""
-    xs, rot = (((state >> 18) ^ state) >> 27) & 0xffffffff, state >> 59
-    return (state * PCG_MUL + inc) & M64, (((xs >> rot) | (xs << ((-rot) & 31))) & 0xffffffff) >> 1
+import p3d_amd as p3d
+from rng_reference import M64, next31, seed_stream
 
 
 def test_header_declares_the_two_prototypes():
-    code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d_radiance.h")).read(), flags=re.S)
-    main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p3d.h")).read(), flags=re.S)
+    code = header_code("p3d_radiance.h")
+    main = header_code()
     f, u32, u64 = r"\s*float\s*\*\s*\w+\s*,", r"\s*uint32_t\s+\w+\s*,", r"\s*uint64_t\s*\*\s*\w+\s*,"
     cf = r"\s*const\s+float\s*\*\s*\w+\s*,"
     assert re.search(r"\bint\s+p3d_trace_path_device\s*\(\s*p3d_scene\s*\*\s*\w+," + u32 + u32 + cf + cf + r"\s*int32_t\s+\w+," + u32 + u32 +
@@ -69,7 +45,7 @@ def test_library_exports_them_and_python_wraps_them():
 
 def test_wrappers_refuse_bad_arguments_before_the_library():
     import torch
-    dev = _scene_without_a_library()
+    dev = scene_without_a_library()
     dev.res = (8, 6)
     raw = (0x1000, 6)  # a raw (address, rows) pair is taken at its word
     f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32)

@@ -7,9 +7,9 @@ import re
 import numpy as np
 import pytest
 
-import p3d_amd as p3d
+from api_checks import scene_without_a_library
 from conftest import ROOT
-from test_ray_query_api import _scene_without_a_library
+import p3d_amd as p3d
 
 
 def test_header_declares_the_two_prototypes():
@@ -45,7 +45,7 @@ def test_library_exports_them_and_python_wraps_them():
 
 def test_wrappers_refuse_bad_arguments_before_the_library():
     import torch
-    dev = _scene_without_a_library()
+    dev = scene_without_a_library()
     dev.res = (8, 6)
     raw = (0x1000, 6)  # a raw (address, rows) pair is taken at its word
     f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32)
