@@ -1113,6 +1113,12 @@ int p3d_trace_hits_device(p3d_scene* scene, uint32_t accel, uint32_t n, uint32_t
  */
 #include "p3d_radiance.h"
 /*
+ * HOW OPEN A SURFACE POINT IS - the free share of the hemisphere above points held in device memory, p3d_occlusion_device, and
+ * its rays written out, p3d_occlusion_rays_device and p3d_occlusion_rays - is declared in p3d_occlusion.h, which this header
+ * includes likewise.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ */
+#include "p3d_occlusion.h"
+/*
  * NEAREST-SURFACE queries: which object's surface is nearest to a point, how far away it is, and where on it - the contact
  * and proximity query of a particle or cloth step, and a distance field around a deforming mesh.  Detected by the symbols
  * (P3D_ABI_VERSION is unchanged).

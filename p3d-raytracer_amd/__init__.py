@@ -18,14 +18,15 @@ from ._abi import (ACCEL_BVH, ACCEL_GRID, ACCEL_NONE, CHAIN_AUTO, CHAIN_MEGAKERN
                    DEBUG_TEST_INTERSECT, EXPORTS, EXPORTS_ADDED, HANDOFF_COMPACT, HANDOFF_DENSE, HERE, LIB_PATH, LOAD_LEGACY_F11, PATHTRACE,
                    PLAN_MODES, PROTOTYPES, SAMPLE_JITTER, SAMPLE_TENT, STACK_LDS6, STACK_LDS8, STACK_LITERAL, STACK_PER_PIXEL, STACK_WINDOW,
                    TILE_ORDER_COST, TILE_ORDER_FRAME, UPDATE_REBUILD, UPDATE_REFIT, WHITTED, AdaptiveParams, BvhCost, BvhNode, Camera,
-                   Config, DebugPlan, DenoiseParams, FramePlan, GeomSource, GridDesc, Light, Material, P3DError, Prim, SceneDesc,
+                   Config, DebugPlan, DenoiseParams, FramePlan, GeomSource, GridDesc, Light, Material, OcclusionParams, P3DError, Prim, SceneDesc,
                    SkyboxDesc, SkyboxFace, Stats, TemporalParams, Tile, Xform, XformRange, _check, _Handle, _lib, _ptr, _stream, build,
                    device_count, lib)
-from ._device_args import (NEAREST_K_MAX, PATH_ACCUMULATE, PATH_MAX_DEPTH, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, TRACE_HITS_K_MAX,
-                           _CAMERA_RAYS_OUTPUTS, _CAMERA_SAMPLE_RAYS_OUTPUTS, _NEAREST_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS, _TRACE_OUTPUTS,
+from ._device_args import (NEAREST_K_MAX, OCCLUSION_ACCUMULATE, PATH_ACCUMULATE, PATH_MAX_DEPTH, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, TRACE_HITS_K_MAX,
+                           _CAMERA_RAYS_OUTPUTS, _CAMERA_SAMPLE_RAYS_OUTPUTS, _NEAREST_OUTPUTS, _OCCLUSION_OUTPUTS, _OCCLUSION_RAYS_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS, _TRACE_OUTPUTS,
                            _device_blocks, _device_rows, _device_vector, _nearest_k_outputs, _trace_hits_outputs)
 from .config import _f3, default_config, denoise_params, look_at, pathtrace_config, temporal_params, whitted_config
-from .device_queries import camera_rays_device, camera_sample_rays_device, trace_path_device, trace_radiance_device
+from .device_queries import (camera_rays_device, camera_sample_rays_device, occlusion_device, occlusion_rays, occlusion_rays_device,
+                             trace_path_device, trace_radiance_device)
 from .device_scene import SKYBOX_FACE_FILES, DeviceScene, load_skybox_dir
 from .geometry import _xform_arrays, deformed, deformed_spheres, transformed, tree_cost
 from .host_scene import HostScene

@@ -126,6 +126,12 @@ class TemporalParams(C.Structure):
                 ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class OcclusionParams(C.Structure):
+    """p3d_occlusion_params (include/p3d_occlusion.h)"""
+    _fields_ = [("seed", C.c_uint64), ("samples", C.c_uint32), ("sample_begin", C.c_uint32), ("point_offset", C.c_uint32),
+                ("flags", C.c_uint32), ("bias", C.c_float), ("team", C.c_uint32)]
+
+
 class DebugPlan(C.Structure):
     """p3d_debug_plan (csrc/p3d_debug.h): what the kernel choosers read of the plan of one launch"""
     _fields_ = [(k, C.c_uint32) for k in ("pt", "literal", "lds_scene", "lds_spill", "sub4", "per_level", "repair_tiles", "stack_mode",
@@ -252,14 +258,19 @@ PROTOTYPES = {
     "p3d_camera_rays_device": (DEFAULT, [VP, PTR(Camera), PTR(Tile), VP, VP, VP]),
     "p3d_trace_path_device": (DEFAULT, [VP, U32, U32, VP, VP, I32, U32, U32, C.c_uint64, VP, U32, VP, VP, VP]),
     "p3d_camera_sample_rays_device": (DEFAULT, [VP, PTR(Camera), PTR(Tile), PTR(Config), U32, VP, VP, VP, VP]),
+    "p3d_occlusion_device": (DEFAULT, [VP, U32, U32, VP, VP, VP, PTR(OcclusionParams), VP, VP, VP]),
+    "p3d_occlusion_rays_device": (DEFAULT, [VP, U32, VP, VP, PTR(OcclusionParams), VP, VP, VP]),
+    "p3d_occlusion_rays": (DEFAULT, [U32, VP, VP, PTR(OcclusionParams), VP, VP]),
     "p3d_debug_scene_limits": (DEFAULT, [VP, VP]),
     "p3d_debug_frame_plan": (DEFAULT, [VP, PTR(Config), PTR(Tile), U32, U32, U32, PTR(DebugPlan)]),
     "p3d_debug_frame_plan_size": (U32, None),
     "p3d_debug_staged_f4": (DEFAULT, [VP, VP, VP, PTR(U32)]),
 }
 # EXPORTS: what include/p3d.h itself declares, the entry points of the recorded surface (tests/python_api_surface.json holds the
-# list to what it was).  EXPORTS_ADDED: those declared since, in include/p3d_radiance.h, which p3d.h includes; detected by their symbols
-EXPORTS_ADDED = ["p3d_trace_radiance_device", "p3d_camera_rays_device", "p3d_trace_path_device", "p3d_camera_sample_rays_device"]
+# list to what it was).  EXPORTS_ADDED: those declared since, in include/p3d_radiance.h and p3d_occlusion.h, which p3d.h includes;
+# detected by their symbols
+EXPORTS_ADDED = ["p3d_trace_radiance_device", "p3d_camera_rays_device", "p3d_trace_path_device", "p3d_camera_sample_rays_device",
+                 "p3d_occlusion_device", "p3d_occlusion_rays_device", "p3d_occlusion_rays"]
 EXPORTS = [name for name in PROTOTYPES if not name.startswith("p3d_debug_") and name not in EXPORTS_ADDED]
 
 

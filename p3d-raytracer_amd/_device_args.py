@@ -74,3 +74,6 @@ PATH_ACCUMULATE = 2      # P3D_PATH_ACCUMULATE
 PATH_MAX_DEPTH = 1024    # of a path-traced frame
 _PATH_OUTPUTS = {"rgb": ("float32", 3), "hit_id": ("int32", None)}
 _CAMERA_SAMPLE_RAYS_OUTPUTS = {"origin": ("float32", 3), "direction": ("float32", 3), "rng": ("int64", 2)}
+OCCLUSION_ACCUMULATE = 1  # P3D_OCCLUSION_ACCUMULATE
+_OCCLUSION_OUTPUTS = {"unoccluded": ("int32", None), "bent": ("float32", 3)}  # (the uint32 counts as int32 tensors)
+_OCCLUSION_RAYS_OUTPUTS = {"origin": ("float32", 3), "direction": ("float32", 3)}

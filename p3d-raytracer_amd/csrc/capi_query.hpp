@@ -1,12 +1,13 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
 // p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device,
-// p3d_object_*, p3d_skybox_color)
+// p3d_occlusion_device, p3d_occlusion_rays_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
 #include "capi_update.hpp"  // device_buffer_usable
 #include "hit_list_query.hpp"
 #include "nearest_query.hpp"
+#include "occlusion_query.hpp"
 #include "path_query.hpp"
 #include "radiance_query.hpp"
 #include "ray_query.hpp"
@@ -60,9 +61,9 @@ struct QueryBuffer {
 // (`what` names the batch's elements), and one launch on the caller's stream; launch(q, st) enqueues the kernel, q.lds being
 // the stack window and `list_lds` bytes behind it; `chain`: see bind_query_stack.  No wait anywhere but in a hipFree of a spill
 // area that has to grow.
-template <size_t N, class Launch>
-int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& pre, const char* what, const QueryBuffer (&bufs)[N],
-                  size_t list_lds, void* hip_stream, Launch&& launch, bool chain = false) {
+// The refusals of the buffers of a device-buffer call: alignment, then where each lies and how far it reaches
+template <size_t N>
+int check_query_buffers(p3d_scene* s, const std::string& pre, const QueryBuffer (&bufs)[N]) {
   for (const auto& b : bufs)
     if (b.aligned4 && ((uintptr_t)b.p & 3u)) return fail(P3D_ERR_INVALID, pre + "the float and int32 buffers must be 4-byte aligned");
   for (const auto& b : bufs)
@@ -71,6 +72,13 @@ int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& p
   for (const auto& b : bufs)
     if (b.p)
       if (int rc = device_buffer_usable(s, b.p, b.bytes, pre + b.name)) return rc;
+  return P3D_OK;
+}
+
+template <size_t N, class Launch>
+int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& pre, const char* what, const QueryBuffer (&bufs)[N],
+                  size_t list_lds, void* hip_stream, Launch&& launch, bool chain = false) {
+  if (int rc = check_query_buffers(s, pre, bufs)) return rc;
   QueryLaunch q;
   if (int rc = bind_query_stack(s, accel, n, pre, what, q, chain)) return rc;
   q.lds += list_lds;
@@ -171,6 +179,21 @@ int check_camera_rays_tile(p3d_scene* s, const p3d_tile* tile, float* d_origin, 
   if (int rc = device_buffer_usable(s, d_origin, vec, pre + "d_origin")) return rc;
   if (int rc = device_buffer_usable(s, d_direction, vec, pre + "d_direction")) return rc;
   return P3D_OK;
+}
+
+// The lanes of a team (p3d_occlusion_params.team) as the TEAM template argument of a launch: f is called with a
+// std::integral_constant of 1, 2, 4, ... 64
+template <class F>
+void with_team(uint32_t team, F&& f) {
+  switch (team) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
 }
 
 }  // namespace
@@ -275,6 +298,63 @@ int p3d_camera_sample_rays_device(p3d_scene* s, const p3d_camera* camera, const 
   C.sample_disk = cfg->sample_disk; C.sample_mode = cfg->sample_mode; C.sample = sample; C.seed = cfg->seed;
   C.origin = d_origin; C.direction = d_direction; C.rng = (RngWords*)d_rng;
   hipLaunchKernelGGL(camera_sample_rays_kernel, dim3((uint32_t)((call.pixels + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, C);
+  P3D_HIP(hipGetLastError());
+  return P3D_OK;
+}
+
+// The free samples of the hemisphere above every point, one kernel on the caller's stream (occlusion_query.hpp)
+int p3d_occlusion_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_normal, const float* d_max_dist,
+                         const p3d_occlusion_params* params, uint32_t* d_unoccluded, float* d_bent, void* hip_stream) {
+  const std::string pre = "p3d_occlusion_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "no segment query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (const char* why = occlusion_params_refusal(params)) return fail(P3D_ERR_INVALID, pre + why);
+  if (n == 0) return P3D_OK;
+  if (!d_point || !d_normal || !d_unoccluded) return fail(P3D_ERR_INVALID, pre + "null argument");
+  uint32_t team = params->team;
+  if (team == 0)
+    for (team = 1; team < std::min<uint32_t>(params->samples, kBlock); team *= 2) {}  // the smallest power of two >= min(samples, 64)
+  const uint64_t lanes = (uint64_t)n * team;
+  if (lanes > 0xffffffc0ull)  // (whole waves are launched)
+    return fail(P3D_ERR_CAPACITY, pre + "n x team lanes do not fit 32 bits (split the batch, or lower team)");
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const QueryBuffer bufs[] = {{d_point, vec, "d_point"}, {d_normal, vec, "d_normal"}, {d_max_dist, one, "d_max_dist"},
+                              {d_unoccluded, one, "d_unoccluded"}, {d_bent, vec, "d_bent"}};
+  // (a stack per LANE: the spill area is sized by the lanes launched; every sample starts on a cleared stack: one traversal's worst case)
+  return enqueue_query(s, accel, (uint32_t)lanes, pre, "lanes", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    OcclusionParams P{};
+    P.sc = s->dev; P.n = n; P.point = d_point; P.normal = d_normal; P.max_dist = d_max_dist; P.seed = params->seed;
+    P.samples = params->samples; P.sample_begin = params->sample_begin; P.point_offset = params->point_offset;
+    P.accumulate = (params->flags & P3D_OCCLUSION_ACCUMULATE) ? 1u : 0u; P.bias = params->bias;
+    P.unoccluded = d_unoccluded; P.bent = d_bent; P.stack = q.stack;
+    with_flags([&](auto BVH) {
+      with_team(team, [&](auto TEAM) {
+        hipLaunchKernelGGL((occlusion_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE, decltype(TEAM)::value>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+      });
+    }, accel == P3D_ACCEL_BVH);
+  });
+}
+
+// One launch on the caller's stream, no wait, nothing of the scene's scratch
+int p3d_occlusion_rays_device(p3d_scene* s, uint32_t n, const float* d_point, const float* d_normal, const p3d_occlusion_params* params,
+                              float* d_origin, float* d_direction, void* hip_stream) {
+  const std::string pre = "p3d_occlusion_rays_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (const char* why = occlusion_params_refusal(params)) return fail(P3D_ERR_INVALID, pre + why);
+  if (n == 0) return P3D_OK;
+  if (!d_point || !d_normal || !d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
+  const uint64_t rows = (uint64_t)n * params->samples;
+  if (rows > 0xffffffffull) return fail(P3D_ERR_CAPACITY, pre + "n x samples rows do not fit 32 bits (split the batch)");
+  const size_t vec = (size_t)n * 3 * sizeof(float), out = (size_t)rows * 3 * sizeof(float);
+  const QueryBuffer bufs[] = {{d_point, vec, "d_point"}, {d_normal, vec, "d_normal"}, {d_origin, out, "d_origin"}, {d_direction, out, "d_direction"}};
+  if (int rc = check_query_buffers(s, pre, bufs)) return rc;
+  OcclusionRaysParams R{};
+  R.n = n; R.point = d_point; R.normal = d_normal; R.seed = params->seed; R.samples = params->samples;
+  R.sample_begin = params->sample_begin; R.point_offset = params->point_offset; R.bias = params->bias;
+  R.origin = d_origin; R.direction = d_direction;
+  hipLaunchKernelGGL(occlusion_rays_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, R);
   P3D_HIP(hipGetLastError());
   return P3D_OK;
 }

@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "p3d.h"
+#include "../host/sampling_rule.hpp"  // Rng, det_sincos, kPIf: one spelling for the host and the device
 
 namespace p3d {
 
@@ -973,34 +974,7 @@ __device__ __forceinline__ F3 miss_color(const DevScene& sc, bool skybox, F3 raw
 
 __device__ __forceinline__ F3 offset_intersection(F3 inter, F3 normal) { return inter + normal * .0001f; }  // main.cpp:82-84
 
-// ---------------------------------------------------------------------------
-// RNG: one PCG-XSH-RR 64/32 stream per (pixel, sample); same definition as the oracle's.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-struct Rng {
-  uint64_t state, inc;
-  __device__ __forceinline__ void seed_stream(uint64_t seed, uint32_t pixel, uint32_t sample) {
-    const uint64_t k = mix64(seed ^ mix64(((uint64_t)pixel << 32) | (uint64_t)sample));
-    inc = (mix64(k) << 1) | 1ull;
-    state = k * 6364136223846793005ull + inc;
-  }
-  __device__ __forceinline__ uint32_t next31() {
-    const uint64_t old = state;
-    state = old * 6364136223846793005ull + inc;
-    const uint32_t xs = (uint32_t)(((old >> 18) ^ old) >> 27);
-    const uint32_t rot = (uint32_t)(old >> 59);
-    return ((xs >> rot) | (xs << ((0u - rot) & 31u))) >> 1;
-  }
-  // maths.h:67-70 with RAND_MAX = 2^31-1 ((float)RAND_MAX == 2^31); can return exactly 1.0f
-  __device__ __forceinline__ float rand_float() { return (float)next31() / 2147483648.0f; }
-  // main.cpp:75-77
-  __device__ __forceinline__ double erand48() { return (double)next31() / 2147483647.0; }
-};
+// RNG: Rng, one PCG-XSH-RR 64/32 stream per (pixel, sample), is host/sampling_rule.hpp's (the host draws from it too)
 
 // camera.h:65-82
 __device__ __forceinline__ void primary_ray(const DevCamera& c, float px, float py, F3& o, F3& d) {

@@ -15,7 +15,7 @@
 // sin/cos: the reference calls libm (cosf/sinf main.cpp:400, cos/sin main.cpp:436).  libm
 // differs between platforms by an ulp, which flips rare hit decisions and would make CPU
 // and GPU paths diverge visibly at 256 spp.  Both this kernel and the oracle therefore use
-// the same explicit double-precision routine (det_sincos) built from + - * floor only.
+// the same explicit double-precision routine (det_sincos, host/sampling_rule.hpp) built from + - * floor only.
 #pragma once
 
 #include "kernels.hpp"
@@ -27,33 +27,6 @@
 #endif
 
 namespace p3d {
-
-__device__ __forceinline__ void det_sincos(double x, double& s_out, double& c_out) {
-  const double two_over_pi = 6.36619772367581382433e-01;
-  const double pio2_hi = 1.57079632673412561417e+00, pio2_lo = 6.07710050650619224932e-11;
-  const double kd = floor(x * two_over_pi + 0.5);
-  const double r = (x - kd * pio2_hi) - kd * pio2_lo;
-  const double z = r * r;
-  const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03,
-               S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
-               S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-  const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03,
-               C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
-               C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-  const double sp = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
-  const double s = r + (z * r) * (S1 + z * sp);
-  const double cp = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
-  const double c = 1.0 - (0.5 * z - z * cp);
-  const long long k = (long long)kd;
-  switch (k & 3) {
-    case 0: s_out = s; c_out = c; break;
-    case 1: s_out = c; c_out = -s; break;
-    case 2: s_out = -s; c_out = -c; break;
-    default: s_out = -c; c_out = s; break;
-  }
-}
-
-constexpr float kPIf = 3.141592653589793238462f;  // camera.h:13
 
 // pending dielectric branch (main.cpp:512-513): 3 float4 per entry, 2 entries per lane, in the
 // global scratch the Whitted kernel uses for its level records (rarely touched: only the first

@@ -1,11 +1,14 @@
 """What the *_device queries of a DeviceScene share: their inputs and outputs resolved to addresses, and the one call; and the
 queries added since the class's surface was recorded (tests/python_api_surface.json holds DeviceScene to its members of then):
-trace_radiance_device, camera_rays_device, trace_path_device and camera_sample_rays_device, functions of a DeviceScene."""
+trace_radiance_device, camera_rays_device, trace_path_device, camera_sample_rays_device, occlusion_device and
+occlusion_rays_device, functions of a DeviceScene, and occlusion_rays, which needs neither a scene nor a device."""
 import ctypes as C
+import math
 
-from ._abi import P3DError, _check, _stream
-from ._device_args import (PATH_ACCUMULATE, PATH_MAX_DEPTH, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, _CAMERA_RAYS_OUTPUTS,
-                           _CAMERA_SAMPLE_RAYS_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS, _device_blocks, _device_rows, _device_vector)
+from ._abi import OcclusionParams, P3DError, _check, _stream, lib
+from ._device_args import (OCCLUSION_ACCUMULATE, PATH_ACCUMULATE, PATH_MAX_DEPTH, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, _CAMERA_RAYS_OUTPUTS,
+                           _CAMERA_SAMPLE_RAYS_OUTPUTS, _OCCLUSION_OUTPUTS, _OCCLUSION_RAYS_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS,
+                           _device_blocks, _device_rows, _device_vector)
 
 
 def _device_rays(scene, who, origin, direction, t_max):
@@ -178,3 +181,79 @@ def camera_sample_rays_device(scene, cfg, sample, camera=None, tile=None, want=(
                                                   int(sample) & 0xffffffff, C.c_void_p(res["origin"][1]), C.c_void_p(res["direction"][1]),
                                                   C.c_void_p(res["rng"][1]) if "rng" in res else None, _stream(stream)))
     return {name: v[0] for name, v in res.items()}
+
+
+def _occlusion_params(who, samples, sample_begin, seed, point_offset, bias, flags=0, team=0):
+    """The OcclusionParams of a call, or P3DError for what the library would refuse of them"""
+    samples, sample_begin, point_offset, flags, team, bias = int(samples), int(sample_begin), int(point_offset), int(flags), int(team), float(bias)
+    if samples < 1:
+        raise P3DError(-1, "%s: samples must be at least 1, got %d" % (who, samples))
+    if sample_begin < 0 or sample_begin + samples > 1 << 32:
+        raise P3DError(-1, "%s: sample_begin + samples must stay within 0 .. 2^32, got %d + %d" % (who, sample_begin, samples))
+    if not 0 <= point_offset < 1 << 32:
+        raise P3DError(-1, "%s: point_offset must be 0 .. 2^32 - 1, got %d" % (who, point_offset))
+    if flags & ~OCCLUSION_ACCUMULATE:
+        raise P3DError(-1, "%s: unknown flag in %#x (OCCLUSION_ACCUMULATE is %d)" % (who, flags, OCCLUSION_ACCUMULATE))
+    if not math.isfinite(bias):
+        raise P3DError(-1, "%s: bias must be finite, got %r" % (who, bias))
+    if team < 0 or team > 64 or team & (team - 1):
+        raise P3DError(-1, "%s: team must be 0 (the library chooses) or a power of two <= 64, got %d" % (who, team))
+    return OcclusionParams(int(seed) & 0xffffffffffffffff, samples, sample_begin, point_offset, flags, bias, team)
+
+
+def _occlusion_points(scene, who, points, normals, max_dist):
+    """(address of points, of normals, of max_dist or None, n) of an occlusion query, or P3DError"""
+    d_p, d_m, n = _device_points(scene, who, points, max_dist)
+    d_n, n_n = _device_rows(normals, who + ": normals", 3, ("float32",), scene.device)
+    if n_n != n:
+        raise P3DError(-1, "%s: %d points, %d normals" % (who, n, n_n))
+    return d_p, d_n, d_m, n
+
+
+def occlusion_device(scene, accel, points, normals, samples, max_dist=None, sample_begin=0, seed=0, point_offset=0, bias=1e-4, flags=0,
+                     team=0, want=("unoccluded",), stream=0, out=None):
+    """p3d_occlusion_device: how open the n surface points held in device memory are in the DeviceScene `scene` - for each, the
+    number of the `samples` cosine-weighted rays over the hemisphere around its normal (float32 (n, 3), used as given: bring unit
+    normals) that meet nothing within max_dist (float32 (n,); None: no limit), enqueued on `stream` without a wait ->
+    {"unoccluded": int32 (n,), and, if in `want`, "bent": float32 (n, 3), the unnormalised sum of the free directions}.
+    unoccluded / samples is the ambient-occlusion term.  Sample s of point i draws from the stream of (point_offset + i, s) with
+    `seed`: a later call with the next sample_begin and flags=OCCLUSION_ACCUMULATE (needs `out`) continues the estimate, a split
+    batch with point_offset gives the rows of the whole.  team: lanes per point, 0 (the library chooses) or a power of two <= 64;
+    the counts do not depend on it.  ACCEL_NONE and ACCEL_BVH; points, `out`, `stream` and the refusals as
+    DeviceScene.nearest_device.  The rays themselves: occlusion_rays_device, occlusion_rays."""
+    who = "occlusion_device"
+    names = ["unoccluded"] + [w for w in ("bent",) if w in want]
+    unknown = [w for w in want if w not in _OCCLUSION_OUTPUTS]
+    if unknown:
+        raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
+    params = _occlusion_params(who, samples, sample_begin, seed, point_offset, bias, flags, team)
+    if (params.flags & OCCLUSION_ACCUMULATE) and (out is None or any(name not in out for name in names)):
+        raise P3DError(-1, "%s: OCCLUSION_ACCUMULATE adds to the tensors of `out`, which are not given" % who)
+    return _device_query(scene, who, accel, lambda: _occlusion_points(scene, who, points, normals, max_dist), _OCCLUSION_OUTPUTS, names, want,
+                         ("unoccluded", "bent"), stream, out, points, rows_of="points", options=(C.byref(params),))
+
+
+def occlusion_rays_device(scene, points, normals, samples, sample_begin=0, seed=0, point_offset=0, bias=1e-4, stream=0, out=None):
+    """p3d_occlusion_rays_device: the rays occlusion_device casts, written out -> {"origin", "direction"}: float32 (n * samples, 3),
+    row i * samples + j = sample sample_begin + j of point i; what DeviceScene.trace_any_device takes.  `out`, `stream` as there."""
+    who = "occlusion_rays_device"
+    params = _occlusion_params(who, samples, sample_begin, seed, point_offset, bias)
+    d_p, d_n, _, n = _occlusion_points(scene, who, points, normals, None)
+    res = _device_outputs(scene, who, ("origin", "direction"), n * params.samples, out, points, _OCCLUSION_RAYS_OUTPUTS, "rays")
+    _check(scene._L.p3d_occlusion_rays_device(scene._h, n, C.c_void_p(d_p), C.c_void_p(d_n), C.byref(params), C.c_void_p(res["origin"][1]),
+                                              C.c_void_p(res["direction"][1]), _stream(stream)))
+    return {name: v[0] for name, v in res.items()}
+
+
+def occlusion_rays(points, normals, samples, sample_begin=0, seed=0, point_offset=0, bias=1e-4):
+    """p3d_occlusion_rays: the same rays from host arrays, bit for bit, with no scene and no device: (n, 3) points and normals ->
+    (origin, direction), float32 (n * samples, 3) numpy arrays"""
+    import numpy as np
+    who = "occlusion_rays"
+    params = _occlusion_params(who, samples, sample_begin, seed, point_offset, bias)
+    p, w = np.ascontiguousarray(points, np.float32), np.ascontiguousarray(normals, np.float32)
+    if p.ndim != 2 or p.shape[1] != 3 or w.shape != p.shape:
+        raise P3DError(-1, "%s: points %r and normals %r, needed: (n, 3) both" % (who, p.shape, w.shape))
+    origin, direction = np.empty((len(p) * params.samples, 3), np.float32), np.empty((len(p) * params.samples, 3), np.float32)
+    _check(lib().p3d_occlusion_rays(len(p), p.ctypes.data, w.ctypes.data, C.byref(params), origin.ctypes.data, direction.ctypes.data))
+    return origin, direction

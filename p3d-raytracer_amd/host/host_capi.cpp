@@ -9,6 +9,7 @@
 
 #include "accel_build.hpp"
 #include "nearest_rule.hpp"
+#include "occlusion_rule.hpp"
 #include "p3d.h"
 #include "p3d_error.hpp"
 #include "scene_model.hpp"
@@ -334,6 +335,27 @@ int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const f
       if (dist) dist[row] = j >= 0 ? sqrtf(list.d2(e)) : FLT_MAX;
       if (closest)
         for (int c = 0; c < 3; ++c) closest[3 * row + c] = q[c];
+    }
+  }
+  return P3D_OK;
+}
+
+// The statement of the rays of p3d_occlusion_device: occlusion_rule.hpp for every (point, sample), row i * samples + j
+int p3d_occlusion_rays(uint32_t n, const float* point, const float* normal, const p3d_occlusion_params* params, float* origin,
+                       float* direction) {
+  const std::string pre = "p3d_occlusion_rays: ";
+  if (const char* why = p3d::occlusion_params_refusal(params)) return p3d::fail(P3D_ERR_INVALID, pre + why);
+  if (n == 0) return P3D_OK;
+  if (!point || !normal || !origin || !direction) return p3d::fail(P3D_ERR_INVALID, pre + "null argument");
+  if (static_cast<uint64_t>(n) * params->samples > 0xffffffffull)
+    return p3d::fail(P3D_ERR_CAPACITY, pre + "n x samples rows do not fit 32 bits (split the batch)");
+  for (uint32_t i = 0; i < n; ++i) {
+    p3d::OcclusionFrame f;
+    p3d::occlusion_frame(point + 3 * static_cast<size_t>(i), normal + 3 * static_cast<size_t>(i), params->bias, f);
+    for (uint32_t j = 0; j < params->samples; ++j) {
+      const size_t row = static_cast<size_t>(i) * params->samples + j;
+      p3d::occlusion_direction(f, params->seed, params->point_offset + i, params->sample_begin + j, direction + 3 * row);
+      for (int k = 0; k < 3; ++k) origin[3 * row + k] = f.origin[k];
     }
   }
   return P3D_OK;
