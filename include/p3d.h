@@ -1119,6 +1119,13 @@ int p3d_trace_hits_device(p3d_scene* scene, uint32_t accel, uint32_t n, uint32_t
  */
 #include "p3d_occlusion.h"
 /*
+ * WHAT A SCENE IS LIT BY AND MADE OF - the lights and materials of a live scene, set from host memory
+ * (p3d_scene_set_materials, p3d_scene_set_lights), read back (p3d_scene_materials, p3d_scene_lights) or set from device memory
+ * on the caller's stream (p3d_scene_set_shading_device), and the same on a host scene - is declared in p3d_shading.h, which
+ * this header includes likewise.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ */
+#include "p3d_shading.h"
+/*
  * NEAREST-SURFACE queries: which object's surface is nearest to a point, how far away it is, and where on it - the contact
  * and proximity query of a particle or cloth step, and a distance field around a deforming mesh.  Detected by the symbols
  * (P3D_ABI_VERSION is unchanged).

@@ -32,3 +32,5 @@ from .geometry import _xform_arrays, deformed, deformed_spheres, transformed, tr
 from .host_scene import HostScene
 from .multigpu import _GATHER_MODE, assemble_frame, assemble_frame8, gather_frame, packed_bytes, stripe_rows, stripe_tile
 from .passes import Accumulator, AdaptiveAccumulator, Denoiser, Temporal
+from .shading import (LIGHT_FLOATS, MATERIAL_FLOATS, host_set_lights, host_set_materials, scene_lights, scene_materials, set_lights, set_materials,
+                      set_shading_device)

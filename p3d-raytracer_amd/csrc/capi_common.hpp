@@ -19,6 +19,7 @@
 #include "lbvh.hpp"
 #include "grid_build.hpp"
 #include "update_kernels.hpp"
+#include "shading_update.hpp"
 #include "p3d.h"
 #include "p3d_debug.h"
 #include "wavefront.hpp"
@@ -104,6 +105,7 @@ struct p3d_scene {
   uint32_t* d_cell_start = nullptr;
   uint32_t* d_cell_items = nullptr;
   uint32_t* d_emitters = nullptr;
+  uint32_t emitters_cap = 0;             // words allocated there: p3d_scene_set_materials may grow the list
   uint32_t* d_sky[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool has_sky = false;
   DevScene dev{};
@@ -132,7 +134,7 @@ struct p3d_scene {
   // p3d_scene_update_prims (scenes of p3d_scene_create_device_bvh only)
   bool device_bvh = false;
   uint64_t geom_gen = 0;               // bumped by every update; checked like cam_gen
-  std::vector<uint32_t> obj_tm;        // type | material << 8 of every object: what an update may not change
+  std::vector<uint32_t> obj_tm;        // type | material << 8 of every object (of every scene): what an update may not change
   std::vector<float4> create_boxes;    // the object boxes the tree was built from, until the first update moves them to the device
   lbvh::Workspace lbvh_ws;             // allocated by the first update: object boxes and the topology of the tree in d_blob
   bool lbvh_topology = false;          // lbvh_ws.sorted / children / parent describe the tree in d_blob
@@ -155,6 +157,10 @@ struct p3d_scene {
   uint32_t rig_ranges = 0, rig_xforms = 0, rig_posed = 0;  // what p3d_scene_rig answers
   Scratch pose_skipped;                // {objects with an unusable transform, objects with an unusable box} since the last check_status();
                                        // made by p3d_scene_set_rig, added to by upd::pose_rig together with upd::kStatusPoseSkipped in d_status
+  // p3d_scene_set_shading_device (every scene)
+  Scratch shading_skipped;             // {materials that would flip their emissive predicate, ... their transmissive-and-reflective one}
+                                       // since the last check_status(); made by the first call, added to by shade::set_shading
+                                       // together with shade::kStatusShadingSkipped in d_status
   // p3d_scene_build_grid (the same scenes): d_cell_start / d_cell_items above are then the device-built grid
   bool uploaded_grid = false;          // the descriptor carried the host's grid: it cannot follow updates and is never rebuilt
   uint64_t cell_start_cap = 0, cell_items_cap = 0;  // words allocated; they grow when a build needs more and are kept otherwise
@@ -244,9 +250,10 @@ auto with_accel(uint32_t accel, F&& f) {
 // Device-detected errors (sample hand-out loop hit its trip bound, a leftover outgrew its slot, the hand-off found no
 // fixed point): read and clear the status word.  Call only where the stream has been synchronised.
 // render_call: the check behind a render call with `stats` - the objects p3d_scene_refit_device or p3d_scene_pose_device
-// skipped are not the frame's fault: their bits stay pending for p3d_scene_status.
+// skipped, and the materials p3d_scene_set_shading_device skipped, are not the frame's fault: their bits stay pending for
+// p3d_scene_status.
 int check_status(p3d_scene* s, bool render_call = false) {
-  constexpr uint32_t kSkipped = upd::kStatusRefitSkipped | upd::kStatusPoseSkipped;
+  constexpr uint32_t kSkipped = upd::kStatusRefitSkipped | upd::kStatusPoseSkipped | shade::kStatusShadingSkipped;
   uint32_t h = 0;
   P3D_HIP(hipMemcpy(&h, s->d_status, sizeof(h), hipMemcpyDeviceToHost));
   if (render_call) {
@@ -263,6 +270,8 @@ int check_status(p3d_scene* s, bool render_call = false) {
   static_assert((upd::kStatusRefitSkipped & (kHoErrLeftoverCap | kHoErrNoFixedPoint | kHoErrTrips | kHoErrList | kHoErrHalo)) == 0 &&
                     (upd::kStatusPoseSkipped & (upd::kStatusRefitSkipped | kHoErrLeftoverCap | kHoErrNoFixedPoint | kHoErrTrips | kHoErrList | kHoErrHalo)) == 0,
                 "one word, distinct bits");
+  static_assert((shade::kStatusShadingSkipped & (upd::kStatusPoseSkipped | upd::kStatusRefitSkipped | kHoErrLeftoverCap | kHoErrNoFixedPoint | kHoErrTrips | kHoErrList | kHoErrHalo)) == 0,
+                "one word, distinct bits");
   std::string skipped;  // p3d_scene_refit_device, p3d_scene_pose_device: objects their kernels did not write
   if ((h & upd::kStatusRefitSkipped) && s->d_refit_skipped) {
     uint32_t bad[2] = {0, 0};
@@ -278,6 +287,14 @@ int check_status(p3d_scene* s, bool render_call = false) {
     skipped += " p3d_scene_pose_device: " + std::to_string(bad[0]) +
                " object(s) with an unusable transform (a non-finite entry, a sphere_scale that is not finite and > 0, or a box under a matrix that is not positive-diagonal), " +
                std::to_string(bad[1]) + " object(s) with a non-finite or inverted box: they keep their geometry; the others are updated;";
+  }
+  if ((h & shade::kStatusShadingSkipped) && s->shading_skipped.p) {
+    uint32_t bad[2] = {0, 0};
+    P3D_HIP(hipMemcpy(bad, s->shading_skipped.p, sizeof(bad), hipMemcpyDeviceToHost));
+    P3D_HIP(hipMemset(s->shading_skipped.p, 0, sizeof(bad)));
+    skipped += " p3d_scene_set_shading_device: " + std::to_string(bad[0]) + " material(s) that would change whether they emit, " + std::to_string(bad[1]) +
+               " material(s) that would change whether they are transmissive and reflective: they keep their records (p3d_scene_set_materials"
+               " makes such a change); the others are updated;";
   }
   if (!skipped.empty() && !(h & ~kSkipped)) return fail(P3D_ERR_INVALID, "device-detected error:" + skipped);
   std::string what = skipped;

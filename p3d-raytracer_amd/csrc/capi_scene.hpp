@@ -56,8 +56,6 @@ int build_device_bvh(p3d_scene* s, const p3d_scene_desc* d) {
   s->bvh_max_depth = built.max_depth;
   s->device_bvh_ms = built.build_ms;
   s->create_boxes = std::move(boxes);
-  s->obj_tm.resize(d->n_prims);
-  for (uint32_t i = 0; i < d->n_prims; ++i) s->obj_tm[i] = d->prims[i].type | (d->prims[i].material << 8);
   return P3D_OK;
 }
 
@@ -106,7 +104,10 @@ int create_impl(const p3d_scene_desc* d_in, int device, bool device_bvh, p3d_sce
   if (!L.emitters.empty()) {
     P3D_HIP(hipMalloc((void**)&s->d_emitters, L.emitters.size() * 4));
     P3D_HIP(hipMemcpy(s->d_emitters, L.emitters.data(), L.emitters.size() * 4, hipMemcpyHostToDevice));
+    s->emitters_cap = (uint32_t)L.emitters.size();
   }
+  s->obj_tm.resize(d->n_prims);
+  for (uint32_t i = 0; i < d->n_prims; ++i) s->obj_tm[i] = d->prims[i].type | (d->prims[i].material << 8);
   DevScene& v = s->dev;
   v.nodes = s->d_blob + s->off_nodes;
   v.bgeom = s->d_blob + s->off_bgeom;

@@ -9,6 +9,8 @@
 #include "capi_frame.hpp"         // tile schedules, the enqueue steps, p3d_render_tile*
 #include "capi_grid.hpp"          // the device-built uniform grid: build, rebuild, export
 #include "capi_update.hpp"        // camera and geometry updates, BVH export
+#include "shading_update.hpp"     // set_shading (the kernel of the stream form), the rules of the derived facts
+#include "capi_shading.hpp"       // the lights and materials of a live scene: set, read back
 #include "capi_accum.hpp"         // p3d_accum
 #include "capi_adaptive.hpp"      // p3d_adaptive
 #include "capi_denoise.hpp"       // feature buffers, a-trous filter, variance

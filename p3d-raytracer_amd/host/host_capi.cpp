@@ -176,6 +176,48 @@ int p3d_host_scene_set_geometry(p3d_host_scene* hs, uint32_t n, const uint32_t* 
   return P3D_OK;
 }
 
+// The records of materials [first, first + n) replaced in place: the objects keep their Material pointers, so a host BVH and
+// grid already built stay valid; the next p3d_host_scene_desc flattens anew
+int p3d_host_scene_set_materials(p3d_host_scene* hs, uint32_t first, uint32_t n, const p3d_material* materials) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_materials: null scene");
+  const auto& all = hs->scene.allMaterials();
+  if (static_cast<uint64_t>(first) + n > all.size())
+    return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_materials: the range ends behind the scene's " + std::to_string(all.size()) + " materials");
+  if (n && !materials) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_materials: null array with n > 0");
+  if (n == 0) return P3D_OK;
+  using namespace p3d;
+  for (uint32_t i = 0; i < n; ++i) {
+    const p3d_material& f = materials[i];
+    Material& m = *all[first + i];
+    m.SetDiffColor(Color(f.diff_color[0], f.diff_color[1], f.diff_color[2]));
+    m.SetSpecColor(Color(f.spec_color[0], f.spec_color[1], f.spec_color[2]));
+    m.SetEmission(Color(f.emission[0], f.emission[1], f.emission[2]));
+    m.SetDiffuse(f.diffuse); m.SetSpecular(f.specular); m.SetShine(f.shine);
+    m.SetTransmittance(f.transmittance); m.SetRefrIndex(f.refr_index);
+    m.SetReflection(f.reflection);
+  }
+  hs->flat_valid = false;
+  return P3D_OK;
+}
+
+// The same for lights [first, first + n) of the list as it is now (the replicated one after p3d_host_scene_replicate_lights)
+int p3d_host_scene_set_lights(p3d_host_scene* hs, uint32_t first, uint32_t n, const p3d_light* lights) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_lights: null scene");
+  const uint64_t count = static_cast<uint64_t>(hs->scene.getNumLights());
+  if (static_cast<uint64_t>(first) + n > count)
+    return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_lights: the range ends behind the scene's " + std::to_string(count) + " lights");
+  if (n && !lights) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_set_lights: null array with n > 0");
+  if (n == 0) return P3D_OK;
+  using namespace p3d;
+  for (uint32_t i = 0; i < n; ++i) {
+    Light* l = hs->scene.getLight(first + i);
+    l->position = Vector(lights[i].position[0], lights[i].position[1], lights[i].position[2]);
+    l->color = Color(lights[i].color[0], lights[i].color[1], lights[i].color[2]);
+  }
+  hs->flat_valid = false;
+  return P3D_OK;
+}
+
 // main.cpp:725-745: SPP x SPP copies of every light on a LIGHT_SIDE square, colour / SPP^2
 int p3d_host_scene_replicate_lights(p3d_host_scene* hs, uint32_t spp_sqrt, float light_side) {
   if (!hs || spp_sqrt == 0) return p3d::fail(P3D_ERR_INVALID, "replicate_lights: bad argument");
