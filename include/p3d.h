@@ -1309,4 +1309,10 @@ int p3d_host_scene_skybox_face(p3d_host_scene* hs, int face, const uint8_t** img
 #ifdef __cplusplus
 }
 #endif
+/*
+ * WHEN A MOVING BALL FIRST TOUCHES THE SCENE - the sphere sweep of balls held in device memory, p3d_sweep_sphere_device, and its
+ * statement on the CPU, p3d_host_scene_sweep_sphere - is declared in p3d_sweep.h, which this header includes here, behind the
+ * host scene's type.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ */
+#include "p3d_sweep.h"
 #endif /* P3D_H */

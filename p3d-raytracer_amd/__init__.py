@@ -22,11 +22,12 @@ from ._abi import (ACCEL_BVH, ACCEL_GRID, ACCEL_NONE, CHAIN_AUTO, CHAIN_MEGAKERN
                    SkyboxDesc, SkyboxFace, Stats, TemporalParams, Tile, Xform, XformRange, _check, _Handle, _lib, _ptr, _stream, build,
                    device_count, lib)
 from ._device_args import (NEAREST_K_MAX, OCCLUSION_ACCUMULATE, PATH_ACCUMULATE, PATH_MAX_DEPTH, RADIANCE_MAX_DEPTH, RADIANCE_SKYBOX, TRACE_HITS_K_MAX,
-                           _CAMERA_RAYS_OUTPUTS, _CAMERA_SAMPLE_RAYS_OUTPUTS, _NEAREST_OUTPUTS, _OCCLUSION_OUTPUTS, _OCCLUSION_RAYS_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS, _TRACE_OUTPUTS,
+                           _CAMERA_RAYS_OUTPUTS, _CAMERA_SAMPLE_RAYS_OUTPUTS, _NEAREST_OUTPUTS, _OCCLUSION_OUTPUTS, _OCCLUSION_RAYS_OUTPUTS, _PATH_OUTPUTS, _RADIANCE_OUTPUTS, _SWEEP_OUTPUTS, _TRACE_OUTPUTS,
                            _device_blocks, _device_rows, _device_vector, _nearest_k_outputs, _trace_hits_outputs)
 from .config import _f3, default_config, denoise_params, look_at, pathtrace_config, temporal_params, whitted_config
 from .device_queries import (camera_rays_device, camera_sample_rays_device, occlusion_device, occlusion_rays, occlusion_rays_device,
                              trace_path_device, trace_radiance_device)
+from .sweep import host_sweep_sphere, sweep_sphere_device
 from .device_scene import SKYBOX_FACE_FILES, DeviceScene, load_skybox_dir
 from .geometry import _xform_arrays, deformed, deformed_spheres, transformed, tree_cost
 from .host_scene import HostScene

@@ -77,3 +77,4 @@ _CAMERA_SAMPLE_RAYS_OUTPUTS = {"origin": ("float32", 3), "direction": ("float32"
 OCCLUSION_ACCUMULATE = 1  # P3D_OCCLUSION_ACCUMULATE
 _OCCLUSION_OUTPUTS = {"unoccluded": ("int32", None), "bent": ("float32", 3)}  # (the uint32 counts as int32 tensors)
 _OCCLUSION_RAYS_OUTPUTS = {"origin": ("float32", 3), "direction": ("float32", 3)}
+_SWEEP_OUTPUTS = {"object": ("int32", None), "t": ("float32", None), "centre": ("float32", 3), "contact": ("float32", 3), "normal": ("float32", 3)}

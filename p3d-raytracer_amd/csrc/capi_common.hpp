@@ -118,6 +118,7 @@ struct p3d_scene {
   std::vector<int64_t> ho_chain_key;     // what the row_chain flags and halo pixels on the device were worked out for
   bool has_spheres = false;              // (halo_find_kernel: only a sphere test re-normalises a ray)
   bool has_planes = false;               // (p3d_nearest_device: the tree cannot find a plane, Q12; an update never changes a kind)
+  int64_t first_box = -1;                // (p3d_sweep_sphere_device: a box is not swept) the first box among obj_tm, or -1
   uint32_t* d_halo_verdict = nullptr;    // kHoErrHalo if the memoised halo search could not start some row exactly
   float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};  // box of BVH node 0 (bins of the per-level ray queue)
   bool zero_weight_reflections = false;  // some material is transmissive AND reflective (main.cpp:282,290-300)

@@ -1,6 +1,6 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
 // p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device,
-// p3d_occlusion_device, p3d_occlusion_rays_device, p3d_object_*, p3d_skybox_color)
+// p3d_occlusion_device, p3d_occlusion_rays_device, p3d_sweep_sphere_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
@@ -11,6 +11,7 @@
 #include "path_query.hpp"
 #include "radiance_query.hpp"
 #include "ray_query.hpp"
+#include "sweep_query.hpp"
 
 namespace {
 
@@ -451,6 +452,35 @@ int p3d_nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_
 int p3d_nearest_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_point, const float* d_max_dist, int32_t* d_count,
                          int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
   return nearest_device(s, accel, n, k, true, d_point, d_max_dist, d_count, d_object, d_dist, d_closest, d_normal, hip_stream);
+}
+
+// The first contact of n moving balls, one kernel on the caller's stream (sweep_query.hpp)
+int p3d_sweep_sphere_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_radius,
+                            const float* d_t_max, int32_t* d_object, float* d_t, float* d_centre, float* d_contact, float* d_normal,
+                            void* hip_stream) {
+  const std::string pre = "p3d_sweep_sphere_device: ";
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no sphere sweep through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (s->first_box >= 0)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(s->first_box) + " is a box: a ball against a box (a rounded box, and its inside) is not swept");
+  if (accel == P3D_ACCEL_BVH && s->has_planes)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
+  if (n == 0) return P3D_OK;
+  if (!d_origin || !d_direction || !d_radius || !d_object) return fail(P3D_ERR_INVALID, pre + "null argument");
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const QueryBuffer bufs[] = {
+      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_radius, one, "d_radius"}, {d_t_max, one, "d_t_max"},
+      {d_object, one, "d_object"}, {d_t, one, "d_t"}, {d_centre, vec, "d_centre"}, {d_contact, vec, "d_contact"}, {d_normal, vec, "d_normal"}};
+  // (the best contact stays in registers: nothing behind the stack window)
+  return enqueue_query(s, accel, n, pre, "balls", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    SweepParams P{};
+    P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.radius = d_radius; P.t_max = d_t_max;
+    P.object = d_object; P.t = d_t; P.centre = d_centre; P.contact = d_contact; P.normal = d_normal; P.stack = q.stack;
+    with_flags([&](auto BVH) {
+      hipLaunchKernelGGL((sweep_sphere_device_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+    }, accel == P3D_ACCEL_BVH);
+  });
 }
 
 enum class ObjectQuery { Intercepts = 0, Normal = 1, SkyboxColour = 2 };  // the values are object_query_kernel's WHAT

@@ -145,6 +145,8 @@ int create_impl(const p3d_scene_desc* d_in, int device, bool device_bvh, p3d_sce
   P3D_HIP(hipMemset(s->d_halo_verdict, 0, sizeof(uint32_t)));
   for (uint32_t i = 0; i < d->n_prims; ++i) s->has_spheres = s->has_spheres || d->prims[i].type == P3D_PRIM_SPHERE;
   for (uint32_t i = 0; i < d->n_prims; ++i) s->has_planes = s->has_planes || d->prims[i].type == P3D_PRIM_PLANE;
+  for (uint32_t i = d->n_prims; i-- > 0;)
+    if ((s->obj_tm[i] & 0xffu) == P3D_PRIM_BOX) s->first_box = i;
   for (uint32_t i = 0; i < d->n_materials; ++i)
     if (d->materials[i].transmittance != 0 && d->materials[i].reflection > 0) s->zero_weight_reflections = true;
   P3D_HIP(hipEventCreate(&s->ev0));

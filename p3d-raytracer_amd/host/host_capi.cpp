@@ -13,6 +13,7 @@
 #include "p3d.h"
 #include "p3d_error.hpp"
 #include "scene_model.hpp"
+#include "sweep_rule.hpp"
 
 struct p3d_host_scene {
   p3d::Scene scene;
@@ -377,6 +378,54 @@ int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const f
       if (dist) dist[row] = j >= 0 ? sqrtf(list.d2(e)) : FLT_MAX;
       if (closest)
         for (int c = 0; c < 3; ++c) closest[3 * row + c] = q[c];
+    }
+  }
+  return P3D_OK;
+}
+
+// The statement of the sphere sweep: sweep_rule.hpp on every object, the smallest (T, object index) within the limit wins.
+// contact is not kept during the search: nearest_point is run once more at c(T) on the object found
+int p3d_host_scene_sweep_sphere(const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction, const float* radius,
+                                const float* t_max, int32_t* object, float* t, float* centre, float* contact) {
+  const std::string pre = "p3d_host_scene_sweep_sphere: ";
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
+  using namespace p3d;
+  const int n_objs = hs->scene.getNumObjects();
+  std::vector<float> v(9 * static_cast<size_t>(n_objs));
+  std::vector<uint32_t> kind(n_objs);
+  for (int j = 0; j < n_objs; ++j) {
+    float normal[3];
+    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
+    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
+    if (kind[j] == P3D_PRIM_BOX)
+      return p3d::fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(j) + " is a box: a ball against a box (a rounded box, and its inside) is not swept");
+  }
+  if (n && (!origin || !direction || !radius || !object)) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
+  for (uint32_t i = 0; i < n; ++i) {
+    const size_t row = 3 * static_cast<size_t>(i);
+    SweepRay s;
+    sweep_ray(origin + row, direction + row, radius[i], t_max != nullptr, t_max ? t_max[i] : 0.0f, s);
+    float best = s.limit;
+    int32_t best_object = kSweepNoObject;
+    if (s.ok) {
+      for (int j = 0; j < n_objs; ++j) {
+        float T;
+        if (sweep_contact(kind[j], &v[9 * static_cast<size_t>(j)], s, T) && sweep_wins(T, j, best, best_object)) {
+          best = T; best_object = j;
+        }
+      }
+    }
+    const bool found = best_object != kSweepNoObject;
+    float c[3] = {0.0f, 0.0f, 0.0f}, q[3] = {0.0f, 0.0f, 0.0f};
+    if (found) {
+      sweep_centre(s, best, c);
+      nearest_point(kind[best_object], &v[9 * static_cast<size_t>(best_object)], c, q);
+    }
+    object[i] = found ? best_object : -1;
+    if (t) t[i] = found ? best : FLT_MAX;
+    for (int k = 0; k < 3; ++k) {
+      if (centre) centre[row + k] = c[k];
+      if (contact) contact[row + k] = q[k];
     }
   }
   return P3D_OK;
