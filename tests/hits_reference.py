@@ -116,19 +116,6 @@ def check_against_model(objects, o, d, t_max, k, got, what, table=None):
 
 # ---- scenes -----------------------------------------------------------------------------------------------------------------------
 
-HEAD = """bclr 0 0 0
-v
-from 0 0 20
-at 0 0 0
-up 0 1 0
-angle 40
-hither 0.01
-resolution 32 32
-aperture 0
-focal 1
-l 0 10 10 1 1 1
-f 0.8 0.8 0.8 0.9 1 1 1 0.3 20 0 1 0 0 0
-"""
 N_SLATS = 40
 SLAT_GAP = 0.25
 
@@ -141,7 +128,7 @@ def write_slats(path):
     """N_SLATS large triangles stacked SLAT_GAP apart along z, from z = 0 up: a ray along z crosses them all, in file order"""
     tris = [[(-10, -10, SLAT_GAP * i), (10, -10, SLAT_GAP * i), (0, 10, SLAT_GAP * i)] for i in range(N_SLATS)]
     with open(str(path), "w") as f:
-        f.write(HEAD + _triangles(tris))
+        f.write(ref.HEAD + _triangles(tris))
     return str(path)
 
 
@@ -178,7 +165,7 @@ def write_cube(path):
     """A closed mesh: the cube [-1, 1]^3 as twelve triangles (and nothing else)"""
     tris = [t for q in _CUBE_QUADS for t in ([q[0], q[1], q[2]], [q[0], q[2], q[3]])]
     with open(str(path), "w") as f:
-        f.write(HEAD + _triangles(tris))
+        f.write(ref.HEAD + _triangles(tris))
     return str(path)
 
 

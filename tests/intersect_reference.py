@@ -485,7 +485,8 @@ def check_occluded(objects, o, d, got, what):
 # (scene.cpp:149-186, c > 0), a tangent ray hits (discriminant < 0 is the miss), beta = 0 and gamma = 0 are hits, t and
 # |N.d| against 1e-4 at the neighbouring floats, an origin on a box's face, and the tie order and the sign of zero of the box normal.
 
-EDGES = """bclr 0 0 0
+# The camera, light and material in front of every small scene the tests write: the one definition
+HEAD = """bclr 0 0 0
 v
 from 0 0 20
 at 0 0 0
@@ -497,7 +498,9 @@ aperture 0
 focal 1
 l 0 10 10 1 1 1
 f 0.8 0.8 0.8 0.9 1 1 1 0.3 20 0 1 0 0 0
-p 3
+"""
+
+EDGES = HEAD + """p 3
 0 0 0
 2 0 0
 0 2 0

@@ -1,38 +1,36 @@
-"""What the ray-query tests share (closest hit, segment any-hit, hit lists): the batch sizes, and a World that holds one scene
-with its model objects, its device scenes and shuffled rays on the device and the host.
+"""What the ray-query tests share (closest hit, segment any-hit, hit lists): the batch sizes, and device_query_contract's World
+with the scene's model objects, the oracle's scene and shuffled rays on the device and the host.
 
 A helper module: test modules import helper and reference modules only, never one another ("Layout of tests/")."""
 import numpy as np
 
+import device_query_contract as dq
+from device_query_contract import BATCHES  # noqa: F401 (the one definition; the ray-query modules take it from here)
 import intersect_reference as ref
-import p3d_amd as p3d
 import segment_reference as seg
-from frame_checks import gpu
 from oracle import binding as ob
 
-BATCHES = [1, 63, 64, 65, 129, 4099]  # kBlock is 64: a lone lane, a full wave, one lane over, a ragged last block of many
 CLOSEST_ALL = ("hit_id", "t", "hit_point", "normal")
 INF = np.float32(np.inf)
 N_MODEL = 2000   # rays of the comparisons with the oracle's per-object test (the CPU suite's set)
 N_MESH = 515     # rays on the triangle mesh: eight blocks and three lanes
 
 
-class World:
-    """One scene: host scene, model objects, the device scene(s), max(BATCHES) shuffled rays on the device and the host"""
+class World(dq.World):
+    """The shared World (host scene, device scenes by tree, each with its grid) with the model objects, the oracle's scene and
+    max(BATCHES) shuffled rays on the device and the host"""
 
     def __init__(self, path, trees, seed=8, n=max(BATCHES), oracle=True):
-        self.hs = p3d.HostScene(path)
+        super().__init__(path, trees, grid=True)
         self.objs = ref.load_objects(path)
         self.sc = ob.Scene(path) if oracle else None
-        self.devs = {}
-        if "host" in trees:
-            self.devs["host"] = p3d.DeviceScene(self.hs, bvh=True, grid=True)
-        if "device" in trees:
-            self.devs["device"] = p3d.DeviceScene(self.hs, bvh="device", grid="device")
         o, d = ref.scene_rays(self.objs, seed, n)
         order = np.random.default_rng(seed + 100).permutation(len(o))  # every prefix holds aimed and random rays
-        self.o, self.d = np.ascontiguousarray(o[order]), np.ascontiguousarray(d[order])
-        self.d_o, self.d_d = gpu(self.o), gpu(self.d)
+        self.set_rays(o[order], d[order])
+
+    def set_rays(self, o, d):
+        self.attach(d_origin=np.ascontiguousarray(o, np.float32), d_direction=np.ascontiguousarray(d, np.float32))
+        self.o, self.d, self.d_o, self.d_d = self.host["d_origin"], self.host["d_direction"], self.dev["d_origin"], self.dev["d_direction"]
         self._tests = self._table = None
 
     @property

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+import device_query_contract as dq
+from device_query_contract import BIG, CAPACITY, INVALID, UNSUPPORTED
 from frame_checks import assert_bits, gpu
 import intersect_reference as ref
 from occlusion_checks import BEGIN, OFFSET, SEED, bent_bound, bent_from, choose_points, counts_from, drawn_limits, surface_points
@@ -165,19 +167,7 @@ def test_progressive_samples_and_split_batches(name, cases):
 
 # ---- 6. a case a person can check ---------------------------------------------------------------------------------------------------
 
-HEAD = """bclr 0 0 0
-v
-from 0 6 20
-at 0 0 0
-up 0 1 0
-angle 40
-hither 0.01
-resolution 32 32
-aperture 0
-focal 1
-l 0 10 10 1 1 1
-f 0.8 0.8 0.8 0.9 1 1 1 0.3 20 0 1 0 0 0
-"""
+HEAD = ref.HEAD.replace("from 0 0 20", "from 0 6 20")
 FLOOR = "box -5 -1 -5 5 0 5\n"
 LID = "box -3 -0.5 2 3 3 2.5\nbox -3 -0.5 -2.5 3 3 -2\nbox 2 -0.5 -3 2.5 3 3\nbox -2.5 -0.5 -3 -2 3 3\nbox -3 2 -3 3 2.5 3\n"  # four walls 2 away and a ceiling at 2
 
@@ -239,37 +229,28 @@ def test_refusals_write_nothing(cases):
     c = cases["mixed, uploaded tree"]
     dev, n = c.dev, 33
     p, nrm = c.d_p[:n], c.d_n[:n]
-    count = torch.full((n,), 77, dtype=torch.int32, device="cuda")
-    bent = torch.full((n, 3), 123.0, device="cuda")
+    query = dq.occlusion(4, seed=1)
+    out = dq.check_buffer_refusals(query, dev, {"d_point": p, "d_normal": nrm, "d_max_dist": c.d_limits[:n]}, n)
     rows = torch.full((n * 4, 3), 123.0, device="cuda")
-    out = {"unoccluded": count, "bent": bent}
     host = np.zeros((n, 3), np.float32)
-    big = 0x00ffff00  # rows no buffer here holds
-    q = lambda accel=p3d.ACCEL_BVH, points=p, **kw: p3d.occlusion_device(dev, accel, points, nrm, 4, want=("unoccluded", "bent"), out=out, **kw)
-    for what, code, word, call in [
-        ("the grid", -3, "grid", lambda: q(accel=p3d.ACCEL_GRID)),
-        ("an unknown accel", -1, "accel", lambda: q(accel=7)),
-        ("host points", -1, "host memory", lambda: q(points=(host.ctypes.data, n))),
-        ("misaligned points", -1, "aligned", lambda: q(points=(p.data_ptr() + 2, n))),
-        ("a misaligned limit", -1, "aligned", lambda: q(max_dist=(c.d_limits.data_ptr() + 1, n))),
-        ("rows too short", -1, "ends behind its allocation",
-         lambda: p3d.occlusion_rays_device(dev, (p.data_ptr(), big), (nrm.data_ptr(), big), 4, out={"origin": (rows.data_ptr(), 4 * big), "direction": (rows.data_ptr(), 4 * big)})),
-        ("host rows", -1, "host memory", lambda: p3d.occlusion_rays_device(dev, p, nrm, 4, out={"origin": (host.ctypes.data, 4 * n), "direction": rows})),
-    ]:
-        with pytest.raises(p3d.P3DError) as e:
-            call()
-        assert e.value.code == code and word in str(e.value), "%s: %s" % (what, e.value)
+    dq.assert_refused([
+        ("the grid", UNSUPPORTED, "grid", lambda: query.call(dev, p3d.ACCEL_GRID, {"d_point": p, "d_normal": nrm}, query.optional, 0, out)),
+        # the ray writer, which does not traverse: its own two
+        ("rows too short", INVALID, "ends behind its allocation",
+         lambda: p3d.occlusion_rays_device(dev, (p.data_ptr(), BIG), (nrm.data_ptr(), BIG), 4, out={"origin": (rows.data_ptr(), 4 * BIG), "direction": (rows.data_ptr(), 4 * BIG)})),
+        ("host rows", INVALID, "host memory", lambda: p3d.occlusion_rays_device(dev, p, nrm, 4, out={"origin": (host.ctypes.data, 4 * n), "direction": rows})),
+    ])
     L = p3d.lib()
-    par = lambda **kw: p3d.OcclusionParams(**dict(dict(seed=1, samples=4, sample_begin=0, point_offset=0, flags=0, bias=1e-4, team=0), **kw))
-    raw = lambda q, cnt=count.data_ptr(): L.p3d_occlusion_device(dev._h, p3d.ACCEL_BVH, n, p.data_ptr(), nrm.data_ptr(), None, C.byref(q), cnt, bent.data_ptr(), None)
-    for what, word, refused in [("team = 3", "team", lambda: raw(par(team=3))), ("samples = 0", "samples", lambda: raw(par(samples=0))),
-                                ("a flag bit", "unknown flag", lambda: raw(par(flags=2))), ("a NaN bias", "bias", lambda: raw(par(bias=float("nan")))),
-                                ("a null count", "null argument", lambda: raw(par(), cnt=None)), ("a misaligned count", "aligned", lambda: raw(par(), cnt=count.data_ptr() + 2))]:
-        assert refused() == -1, what
+    good = {"d_point": p, "d_normal": nrm, "d_unoccluded": out["unoccluded"], "d_bent": out["bent"]}
+    for what, word, other, bufs in [("team = 3", "team", dq.occlusion(4, team=3), good), ("samples = 0", "samples", dq.occlusion(0), good),
+                                    ("a flag bit", "unknown flag", dq.occlusion(4, flags=2), good), ("a NaN bias", "bias", dq.occlusion(4, bias=float("nan")), good),
+                                    ("a misaligned count", "aligned", query, dict(good, d_unoccluded=out["unoccluded"].data_ptr() + 2))]:
+        assert other.raw(dev, p3d.ACCEL_BVH, n, **bufs) == INVALID, what
         assert word in L.p3d_last_error().decode(), "%s: %s" % (what, L.p3d_last_error())
-    assert L.p3d_occlusion_device(dev._h, p3d.ACCEL_BVH, 0x10000000, p.data_ptr(), nrm.data_ptr(), None, C.byref(par(team=64)), count.data_ptr(), None, None) == -4
-    assert L.p3d_occlusion_rays_device(dev._h, 0x10000, p.data_ptr(), nrm.data_ptr(), C.byref(par(samples=0x10000)), rows.data_ptr(), rows.data_ptr(), None) == -4
-    assert L.p3d_occlusion_device(dev._h, p3d.ACCEL_BVH, 0, None, None, None, C.byref(par()), None, None, None) == 0  # n = 0
-    torch.cuda.synchronize()
-    assert bool((count == 77).all()) and bool((bent == 123.0).all()) and bool((rows == 123.0).all()), "a refused call wrote"
-    assert raw(par()) == 0 and dev.status() == 0 and not bool((count == 77).any())
+    del good["d_bent"]
+    assert dq.occlusion(4, team=64).raw(dev, p3d.ACCEL_BVH, 0x10000000, **good) == CAPACITY
+    wide = p3d.OcclusionParams(seed=1, samples=0x10000, sample_begin=0, point_offset=0, flags=0, bias=1e-4, team=0)
+    assert L.p3d_occlusion_rays_device(dev._h, 0x10000, p.data_ptr(), nrm.data_ptr(), C.byref(wide), rows.data_ptr(), rows.data_ptr(), None) == CAPACITY
+    dq.check_empty_batch(query, dev)
+    dq.assert_untouched(dict(out, rows=rows))
+    assert query.raw(dev, p3d.ACCEL_BVH, n, **good) == 0 and dev.status() == 0 and not bool((out["unoccluded"] == 77).any())

@@ -8,12 +8,12 @@ segment_reference.py calls well-conditioned, under the 5 % cap of intersect_refe
 
 The library's debug hooks (csrc/p3d_debug.h) expose no scratch sizes, so "a second call of the same n allocates nothing" is
 not tested here."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+import device_query_contract as dq
+from device_query_contract import ANY, CLOSEST, FLT_MAX, UNSUPPORTED
 from frame_checks import ACCELS, gpu, same_bits_or_nan
 import intersect_reference as ref
 from oracle import binding as ob
@@ -22,8 +22,6 @@ from ray_query_checks import BATCHES, CLOSEST_ALL, INF, N_MESH, N_MODEL, World, 
 import segment_reference as seg
 
 pytestmark = pytest.mark.gpu
-
-FLT_MAX = np.finfo(np.float32).max
 
 
 @pytest.fixture(scope="module")
@@ -76,10 +74,7 @@ def test_device_forms_equal_the_host_forms(n, worlds, mesh):
             assert occ.dtype == np.uint8 and (occ == dev.trace_any(accel, o, d)).all(), what + ": occluded"
             if n_here >= 63 and not any(m["kind"] == ref.PLANE for m in w.objs):
                 assert 0 < (hit >= 0).sum() < n_here and 0 < occ.sum() < n_here, what + ": hits and misses in one batch"
-            # the optional outputs may be left out, and outputs may be the caller's
-            mine = {"hit_id": torch.full((n_here,), 77, dtype=torch.int32, device="cuda")}
-            back = dev.trace_closest_device(accel, d_o, d_d, want=(), out=mine)
-            assert list(back) == ["hit_id"] and back["hit_id"] is mine["hit_id"] and (mine["hit_id"].cpu().numpy() == hit).all(), what
+            dq.check_callers_outputs(CLOSEST, dev, accel, {"d_origin": d_o, "d_direction": d_d}, {"hit_id": hit}, what)
 
 
 # ---- closest hit with a limit -------------------------------------------------------------------------------------------------
@@ -216,25 +211,10 @@ def test_segment_any_hit_through_a_deep_device_tree(mesh):
 
 # ---- what it is for ---------------------------------------------------------------------------------------------------------------
 
-HEAD = """bclr 0 0 0
-v
-from 0 0 20
-at 0 0 0
-up 0 1 0
-angle 40
-hither 0.01
-resolution 32 32
-aperture 0
-focal 1
-l 0 10 10 1 1 1
-f 0.8 0.8 0.8 0.9 1 1 1 0.3 20 0 1 0 0 0
-"""
-
-
 def test_an_occluder_behind_the_target_does_not_shadow_it(tmp_path):
     """A at the origin looks at B = (0, 0, -5); a sphere stands behind B.  The feeler, which has no limit, calls A shadowed."""
     path = tmp_path / "behind.p3f"
-    path.write_text(HEAD + "s 0 0 -10 1\ns 50 0 0 1\ns -50 3 0 1\n")
+    path.write_text(ref.HEAD + "s 0 0 -10 1\ns 50 0 0 1\ns -50 3 0 1\n")
     dev = p3d.DeviceScene(p3d.HostScene(str(path)), bvh=True, grid=True)
     a, b = np.zeros((1, 3), np.float32), np.array([[0, 0, -5]], np.float32)
     d = ref.normalize32(b - a)
@@ -251,7 +231,7 @@ def test_a_query_on_a_side_stream_and_after_an_update(tmp_path):
     then update_triangles moves the occluder away and the same query reports free."""
     tris = np.array([[[-1, -1, -5], [1, -1, -5], [0, 1, -5]], [[9, 9, -5], [10, 9, -5], [9, 10, -5]], [[-9, 9, -4], [-10, 9, -4], [-9, 10, -4]]], np.float32)
     path = tmp_path / "wall.p3f"
-    path.write_text(HEAD + "".join("p 3\n" + "".join("%g %g %g\n" % tuple(v) for v in t) for t in tris))
+    path.write_text(ref.HEAD + "".join("p 3\n" + "".join("%g %g %g\n" % tuple(v) for v in t) for t in tris))
     dev = p3d.DeviceScene(p3d.HostScene(str(path)), bvh="device")
     n = 4099
     base = gpu(np.random.default_rng(5).uniform(-0.2, 0.2, (n, 3)).astype(np.float32))
@@ -283,51 +263,12 @@ def test_a_query_on_a_side_stream_and_after_an_update(tmp_path):
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------------
 
-def test_refusals_enqueue_nothing(worlds, mesh):
-    w = worlds["mixed"]
+def test_refusals_enqueue_nothing(worlds):
+    w, n = worlds["mixed"], 129
     dev = w.devs["host"]
-    lib = p3d.lib()
-    # Host memory must be refused BEFORE any launch.  It goes in first with a ray count no call can serve: were the pointer check
-    # to let it through, the direction buffer would end behind its allocation, and over the mesh's deep tree the count does not
-    # fit the spill area's offsets either: no kernel would ever be given a host address.
-    deep, too_many = mesh.devs["device"], 0xffffff00
-    guard = np.zeros((4, 3), np.float32)
-    assert lib.p3d_trace_any_device(deep._h, p3d.ACCEL_BVH, too_many, C.c_void_p(guard.ctypes.data), C.c_void_p(mesh.d_d.data_ptr()), None,
-                                    C.c_void_p(mesh.d_d.data_ptr()), None) == -1
-    assert b"d_origin is host memory" in lib.p3d_last_error(), lib.p3d_last_error()
-    n = 129
-    o, d = w.d_o[:n], w.d_d[:n]
-    t_max = torch.full((n,), 3.0, dtype=torch.float32, device="cuda")
-    outs = dict(hit_id=torch.full((n,), 77, dtype=torch.int32, device="cuda"), t=torch.full((n,), 123.0, device="cuda"),
-                hit_point=torch.full((n, 3), 123.0, device="cuda"), normal=torch.full((n, 3), 123.0, device="cuda"),
-                occluded=torch.full((n,), 9, dtype=torch.uint8, device="cuda"))
-    host = np.zeros((n, 3), np.float32)
-    closest_out = {k: outs[k] for k in CLOSEST_ALL}
-    any_out = {"occluded": outs["occluded"]}
-
-    def raw_closest(hit_id, origin=None):
-        return lib.p3d_trace_closest_device(dev._h, p3d.ACCEL_BVH, n, C.c_void_p(origin or o.data_ptr()), C.c_void_p(d.data_ptr()), None,
-                                            C.c_void_p(hit_id), C.c_void_p(outs["t"].data_ptr()), C.c_void_p(outs["hit_point"].data_ptr()),
-                                            C.c_void_p(outs["normal"].data_ptr()), None)
-
-    cases = [
-        ("the grid with a limit", -3, "grid", lambda: dev.trace_any_device(p3d.ACCEL_GRID, o, d, t_max=t_max, out=any_out)),
-        ("a misaligned origin", -1, "aligned", lambda: dev.trace_closest_device(p3d.ACCEL_BVH, (o.data_ptr() + 2, n), d, want=CLOSEST_ALL, out=closest_out)),
-        ("a misaligned limit", -1, "aligned", lambda: dev.trace_any_device(p3d.ACCEL_BVH, o, d, t_max=(t_max.data_ptr() + 1, n), out=any_out)),
-        ("a host origin", -1, "host memory", lambda: dev.trace_closest_device(p3d.ACCEL_BVH, (host.ctypes.data, n), d, want=CLOSEST_ALL, out=closest_out)),
-        ("a host direction", -1, "host memory", lambda: dev.trace_any_device(p3d.ACCEL_NONE, o, (host.ctypes.data, n), out=any_out)),
-        ("an unknown accel", -1, "accel", lambda: dev.trace_any_device(7, o, d, out=any_out)),
-    ]
-    for what, code, word, call in cases:
-        with pytest.raises(p3d.P3DError) as e:
-            call()
-        assert e.value.code == code and word in str(e.value), "%s: %s" % (what, e.value)
-    assert raw_closest(None) == -1 and b"null argument" in lib.p3d_last_error()  # null d_hit_id
-    assert lib.p3d_trace_any_device(dev._h, p3d.ACCEL_BVH, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), None, None, None) == -1
-    # an empty batch is fine, whatever the pointers
-    assert lib.p3d_trace_any_device(dev._h, p3d.ACCEL_BVH, 0, None, None, None, None, None) == 0
-    assert lib.p3d_trace_closest_device(dev._h, p3d.ACCEL_NONE, 0, None, None, None, None, None, None, None, None) == 0
-    torch.cuda.synchronize()
-    assert bool((outs["hit_id"] == 77).all()) and bool((outs["occluded"] == 9).all())
-    assert all(bool((outs[k] == 123.0).all()) for k in ("t", "hit_point", "normal"))
-    assert dev.status() == 0
+    inputs = dict(CLOSEST.inputs_of(w, n), d_t_max=torch.full((n,), 3.0, dtype=torch.float32, device="cuda"))
+    outs = [dq.check_buffer_refusals(query, dev, inputs, n) for query in (CLOSEST, ANY)]
+    dq.assert_refused([("the grid with a limit", UNSUPPORTED, "grid", lambda: ANY.call(dev, p3d.ACCEL_GRID, inputs, (), 0, outs[1]))])
+    for query, out in zip((CLOSEST, ANY), outs):
+        dq.check_empty_batch(query, dev)
+        dq.assert_untouched(out)

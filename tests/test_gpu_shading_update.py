@@ -20,6 +20,7 @@ import torch
 
 import p3d_amd as p3d
 from conftest import scene_path
+from device_query_contract import INVALID
 from frame_checks import CORNELL, assert_same_frames, check_whitted, frames, frames_differ, gpu, same_bits_or_nan
 from live_scene_checks import camera_rays, configs, last_error, legacy, produced, trace_outputs
 from oracle import binding as ob
@@ -28,7 +29,6 @@ from shading_update_checks import (COL, DIFF, EMIT, IOR, KD, KS, REFL, RES, SHIN
 
 pytestmark = pytest.mark.gpu
 
-INVALID = -1
 BUILDS = {
     "balls_low": lambda hs: p3d.DeviceScene(hs, bvh=True, grid=True),  # the host's tree and grid: no geometry update accepts it
     "tri5k": lambda hs: p3d.DeviceScene(hs, bvh="device"),

@@ -22,6 +22,7 @@ import torch
 
 import p3d_amd as p3d
 from conftest import scene_path
+from device_query_contract import INVALID, UNSUPPORTED
 from device_geometry_helpers import deformed_mesh
 from scene_update_helpers import BOX, PLANE, SPHERE, TRIANGLE, random_moves
 from frame_checks import CORNELL, PLANES, RENDER_COUNTERS, assert_same_frames, assert_same_tree, frames, frames_differ, gpu, load
@@ -31,7 +32,6 @@ from live_scene_checks import (HEAD, IDENTITY, LEAF, RES, SCENES, SEED, TRACE_OU
 
 pytestmark = pytest.mark.gpu
 
-INVALID, UNSUPPORTED = -1, -3
 MOVABLE = (SPHERE, TRIANGLE)
 
 

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import p3d_amd as p3d
+from device_query_contract import CAPACITY, INVALID, UNSUPPORTED
 from device_geometry_helpers import deformed_mesh, diagonal, moved_spheres
 from scene_update_helpers import SPHERE, TRIANGLE
 from frame_checks import CORNELL, RENDER_COUNTERS, assert_same_frames, assert_same_tree, frames, frames_differ, gpu, load
@@ -25,7 +26,6 @@ from variant_scenes import scene_path
 
 pytestmark = pytest.mark.gpu
 
-INVALID, UNSUPPORTED, CAPACITY = -1, -3, -4
 
 
 @pytest.fixture

@@ -5,16 +5,18 @@ every ray, count, total, object and t in bits.  The BVH traversal is held to tha
 model calls well-conditioned (hits_reference.all_hits_margin, under the 5 % cap of intersect_reference.py): every output in
 bits, with and without total (the two cull bounds), with and without limits, on uploaded and device-built trees and through
 the spill path of a deep tree.  The slats fill a list of sixteen; the closed cube gives the parity of the crossings."""
+import copy
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import device_query_contract as dq
+from device_query_contract import FLT_MAX, INVALID, UNSUPPORTED
 from frame_checks import as_bytes, gpu
 import hits_reference as hr
 import intersect_reference as ref
-from live_scene_checks import plan
 import p3d_amd as p3d
 from ray_query_checks import BATCHES, CLOSEST_ALL, N_MESH, N_MODEL, World, limit_sets
 from scene_update_helpers import BOX, SPHERE, TRIANGLE
@@ -25,9 +27,7 @@ pytestmark = pytest.mark.gpu
 KS = (1, 2, 5, 16)
 ROWS = ("count", "object", "t", "hit_point", "normal")
 ALL = ROWS + ("total",)
-FLT_MAX = hr.FLT_MAX
 INF = np.float32(np.inf)
-INVALID, UNSUPPORTED = -1, -3
 
 
 class RayWorld(World):
@@ -35,8 +35,7 @@ class RayWorld(World):
 
     def __init__(self, path, trees, o, d, oracle=True):
         super().__init__(path, trees, n=8, oracle=oracle)
-        self.o, self.d = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
-        self.d_o, self.d_d = gpu(self.o), gpu(self.d)
+        self.set_rays(o, d)
 
 
 @pytest.fixture(scope="module")
@@ -314,67 +313,28 @@ def model_objects(a):
     return out
 
 
-def assert_sees_the_moved_scene(hs, o, d, d_o, d_d, k, t_max, on_stream, before, what):
-    """on_stream: {accel: answers taken behind the update}.  The brute force is a fresh scene's, on every ray; the tree's is on
-    the rays the model of the moved geometry calls well-conditioned"""
-    fresh = p3d.DeviceScene(hs, bvh=False)
-    again = ask(fresh, p3d.ACCEL_NONE, d_o, d_d, k, t_max)
-    for key in ALL:
-        assert as_bytes(on_stream[p3d.ACCEL_NONE][key]) == as_bytes(again[key]), "%s, against a fresh scene: %s" % (what, key)
-    assert as_bytes(again["t"]) != as_bytes(before["t"]), what + ": the update moved nothing the rays can see"
+def tree_is_brute_where_well_conditioned(got, brute, hs, w, n, limited, what):
+    """device_query_contract's assert_tree: the tree's answers behind an update are the fresh scene's brute force on the rays the
+    model of the moved geometry calls well-conditioned (the brute force itself is held to that scene on every ray, in every bit)"""
     objs = model_objects(hs.arrays())
-    ok, left = ref.well_conditioned(hr.all_hits_margin(objs, o, d, t_max, ref._all(objs, o, d)), what)
-    assert_bvh_is_brute(on_stream[p3d.ACCEL_BVH], again, ok, what)
-    assert fresh.status() == 0
+    o, d = w.o[:n], w.d[:n]
+    ok, left = ref.well_conditioned(hr.all_hits_margin(objs, o, d, w.host["d_t_max"][:n] if limited else None, ref._all(objs, o, d)), what)
+    assert_bvh_is_brute(got, brute, ok, what)
 
 
-def test_behind_a_refit_on_the_same_stream(worlds, tmp_path):
-    s = worlds["slats"]
-    hs = p3d.HostScene(hr.write_slats(tmp_path / "slats.p3f"))
-    a = hs.arrays()
-    dev = p3d.DeviceScene(hs, bvh="device")
-    n, k = 4099, 4
-    soup = (a["prim_v"].reshape(-1, 3) + np.float32([0.3, -0.2, 0.11])).astype(np.float32)
-    base, d_soup = gpu(a["prim_v"].reshape(-1, 3)), gpu(soup)
-    t_max = hr.slat_limits(s.table(n), 25)
-    d_t = gpu(t_max)
-    before = ask(dev, p3d.ACCEL_NONE, s.d_o[:n], s.d_d[:n], k, d_t)
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        wave = base
-        for _ in range(50):  # some work in front, so that the positions are still being produced when the calls begin
-            wave = torch.sin(wave * 1.5 + 0.25)
-        moved = (d_soup + 0.0 * wave).contiguous()
-        dev.refit_triangles(0, moved, stream=side)
-        res = {accel: dev.trace_hits_device(accel, s.d_o[:n], s.d_d[:n], k, t_max=d_t, want=ALL, stream=side) for accel in (p3d.ACCEL_BVH, p3d.ACCEL_NONE)}
-    side.synchronize()
-    got = {accel: {key: v.cpu().numpy() for key, v in r.items()} for accel, r in res.items()}
-    hs.set_geometry(*p3d.deformed(a["prim_v"], 0, soup))
-    assert_sees_the_moved_scene(hs, s.o[:n], s.d[:n], s.d_o[:n], s.d_d[:n], k, t_max, got, before, "slats behind a refit")
-    assert dev.status() == 0
+FOUR_HITS = dq.trace_hits(4, assert_tree=tree_is_brute_where_well_conditioned)
+
+
+def test_behind_a_refit_on_the_same_stream(worlds):
+    n = 4099
+    s = copy.copy(worlds["slats"])  # (the limits are this test's: the module's world stays as it is)
+    s.host, s.dev = dict(s.host), dict(s.dev)
+    s.attach(d_t_max=hr.slat_limits(s.table(n), 25))
+    dq.check_behind_a_refit(FOUR_HITS, s, n, soup=lambda a: (a["prim_v"].reshape(-1, 3) + np.float32([0.3, -0.2, 0.11])).astype(np.float32), what="slats behind a refit")
 
 
 def test_behind_a_pose_on_the_same_stream(worlds):
-    w = worlds["mixed"]
-    hs = p3d.HostScene(w.hs.path)
-    a = hs.arrays()
-    dev = p3d.DeviceScene(hs, bvh="device")
-    ranges, xforms, scale = plan(a, 93)  # spheres and triangles under a rigid move, boxes under a positive-diagonal one
-    dev.set_rig(ranges, 2)
-    n, k = 4099, 4
-    before = ask(dev, p3d.ACCEL_NONE, w.d_o[:n], w.d_d[:n], k)
-    side = torch.cuda.Stream()
-    d_x, d_s = gpu(xforms), gpu(scale)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        dev.pose_device(d_x, d_s, stream=side)
-        res = {accel: dev.trace_hits_device(accel, w.d_o[:n], w.d_d[:n], k, want=ALL, stream=side) for accel in (p3d.ACCEL_BVH, p3d.ACCEL_NONE)}
-    side.synchronize()
-    got = {accel: {key: v.cpu().numpy() for key, v in r.items()} for accel, r in res.items()}
-    hs.set_geometry(*p3d.transformed(a["prim_type"], a["prim_v"], ranges, xforms, scale))
-    assert_sees_the_moved_scene(hs, w.o[:n], w.d[:n], w.d_o[:n], w.d_d[:n], k, None, got, before, "mixed behind a pose")
-    assert dev.status() == 0
+    dq.check_behind_a_pose(FOUR_HITS, worlds["mixed"], 4099, limits=(False,), what="mixed behind a pose")
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------------------
@@ -399,54 +359,24 @@ def test_refusals_enqueue_nothing(worlds):
     lib = p3d.lib()
     n, k = 129, 2
     d_o, d_d = w.d_o[:n], w.d_d[:n]
-    d_t = torch.full((n,), 3.0, dtype=torch.float32, device="cuda")
-    i32 = lambda *shape: torch.full(shape, 77, dtype=torch.int32, device="cuda")
-    f32 = lambda *shape: torch.full(shape, 123.0, device="cuda")
-    outs = dict(count=i32(n), total=i32(n), object=i32(n, k), t=f32(n, k), hit_point=f32(n, k, 3), normal=f32(n, k, 3))
+    # what every device query refuses: host memory first, every input misaligned, in host memory and too short, the required
+    # outputs too short, an unknown accel, a missing tree, the null pointers
+    outs = dq.check_buffer_refusals(dq.trace_hits(k), dev, {"d_origin": d_o, "d_direction": d_d, "d_t_max": torch.full((n,), 3.0, device="cuda")}, n)
     ptr = lambda name: C.c_void_p(outs[name].data_ptr())
     host = np.zeros((n, k * 3), np.float32)
-    big = 0x00ffff00  # rays no buffer of this call's outputs holds
-    # Host memory must be refused BEFORE any launch.  It goes in first with a count no output buffer here can serve: were the
-    # pointer check to let it through, the count buffer would end behind its allocation: no kernel would ever be given a host address.
-    assert lib.p3d_trace_hits_device(dev._h, p3d.ACCEL_BVH, big, k, C.c_void_p(host.ctypes.data), C.c_void_p(d_d.data_ptr()), None, ptr("count"), None,
-                                     ptr("object"), None, None, None, None) == INVALID
-    assert b"d_origin is host memory" in lib.p3d_last_error(), lib.p3d_last_error()
+    big = dq.BIG
     huge = torch.empty((big, 3), device="cuda")  # (never read: every call it is given to is refused)
     raws = {name: (v.data_ptr(), n) for name, v in outs.items()}
     q = lambda accel, o=d_o, d=d_d, kk=k, **kw: dev.trace_hits_device(accel, o, d, kk, want=kw.pop("want", ALL), out=kw.pop("out", outs), **kw)
-    short = lambda **over: dict({name: (v.data_ptr(), big) for name, v in outs.items()}, **over)
-    hr_, hd_ = (huge.data_ptr(), big), (huge.data_ptr(), big)
-    cases = [
-        ("the grid", UNSUPPORTED, "grid", lambda: q(p3d.ACCEL_GRID)),
-        ("an unknown accel", INVALID, "accel", lambda: q(7)),
-        ("k = 17", INVALID, "k must be", lambda: q(p3d.ACCEL_NONE, kk=17, out=raws)),
-        ("a misaligned origin", INVALID, "aligned", lambda: q(p3d.ACCEL_BVH, o=(d_o.data_ptr() + 2, n))),
-        ("a misaligned limit", INVALID, "aligned", lambda: q(p3d.ACCEL_NONE, t_max=(d_t.data_ptr() + 1, n))),
-        ("a misaligned total", INVALID, "aligned", lambda: q(p3d.ACCEL_BVH, out=dict(outs, total=(outs["total"].data_ptr() + 2, n)))),
-        ("a host origin", INVALID, "d_origin is host memory", lambda: q(p3d.ACCEL_BVH, o=(host.ctypes.data, n))),
-        ("a host direction", INVALID, "d_direction is host memory", lambda: q(p3d.ACCEL_NONE, d=(host.ctypes.data, n))),
-        ("a host limit", INVALID, "d_t_max is host memory", lambda: q(p3d.ACCEL_NONE, t_max=(host.ctypes.data, n))),
-        ("a host count", INVALID, "d_count is host memory", lambda: q(p3d.ACCEL_NONE, out=dict(outs, count=(host.ctypes.data, n)))),
-        ("a host total", INVALID, "d_total is host memory", lambda: q(p3d.ACCEL_BVH, out=dict(outs, total=(host.ctypes.data, n)))),
-        ("a host total, k = 0", INVALID, "d_total is host memory", lambda: q(p3d.ACCEL_BVH, kk=0, want=("total",), out={"total": (host.ctypes.data, n)})),
-        ("a host object", INVALID, "d_object is host memory", lambda: q(p3d.ACCEL_BVH, out=dict(outs, object=(host.ctypes.data, n)))),
-        ("a host t", INVALID, "d_t is host memory", lambda: q(p3d.ACCEL_BVH, out=dict(outs, t=(host.ctypes.data, n)))),
-        ("a host hit_point", INVALID, "d_hit_point is host memory", lambda: q(p3d.ACCEL_NONE, out=dict(outs, hit_point=(host.ctypes.data, n)))),
-        ("a host normal", INVALID, "d_normal is host memory", lambda: q(p3d.ACCEL_BVH, out=dict(outs, normal=(host.ctypes.data, n)))),
-        # too short: torch hands out pieces of larger allocations, so "behind the allocation" needs a count beyond any of them
-        ("an origin too short", INVALID, "d_origin ends behind its allocation", lambda: q(p3d.ACCEL_BVH, o=(d_o.data_ptr(), big), d=hd_, out=short())),
-        ("a limit too short", INVALID, "d_t_max ends behind its allocation", lambda: q(p3d.ACCEL_NONE, o=hr_, d=hd_, t_max=(d_t.data_ptr(), big), out=short())),
-        ("a count too short", INVALID, "d_count ends behind its allocation", lambda: q(p3d.ACCEL_NONE, o=hr_, d=hd_, out=short())),
-        ("a total too short", INVALID, "d_total ends behind its allocation", lambda: q(p3d.ACCEL_NONE, o=hr_, d=hd_, kk=0, want=("total",), out=short())),
-    ]
-    for what, code, word, call in cases:
-        try:
-            call()
-            raised = None
-        except p3d.P3DError as e:
-            raised = e
-        assert raised is not None, what + ": accepted"
-        assert raised.code == code and word in str(raised), "%s: %s" % (what, raised)
+    far = (huge.data_ptr(), big)
+    dq.assert_refused(
+        [("the grid", UNSUPPORTED, "grid", lambda: q(p3d.ACCEL_GRID)),
+         ("k = 17", INVALID, "k must be", lambda: q(p3d.ACCEL_NONE, kk=17, out=raws)),
+         ("a misaligned total", INVALID, "aligned", lambda: q(p3d.ACCEL_BVH, out=dict(outs, total=(outs["total"].data_ptr() + 2, n)))),
+         ("a host total, k = 0", INVALID, "d_total is host memory", lambda: q(p3d.ACCEL_BVH, kk=0, want=("total",), out={"total": (host.ctypes.data, n)})),
+         ("a total too short", INVALID, "d_total ends behind its allocation",
+          lambda: q(p3d.ACCEL_NONE, o=far, d=far, kk=0, want=("total",), out={name: (v.data_ptr(), big) for name, v in outs.items()}))] +
+        [("a host " + name, INVALID, "d_%s is host memory" % name, lambda name=name: q(p3d.ACCEL_BVH, out=dict(outs, **{name: (host.ctypes.data, n)}))) for name in outs])
     # a buffer short by one element: an allocation of its own, straight from the runtime, which therefore knows where it ends
     # (torch hands out pieces of larger segments).  Every call is refused: none may be accepted with a buffer shorter than the
     # kernel would write, so the extent the runtime reports is asserted before the library sees the pointer

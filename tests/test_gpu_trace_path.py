@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, scene_path
+import device_query_contract as dq
+from device_query_contract import INVALID, UNSUPPORTED
 from frame_checks import ACCELS, assert_bits, f32_bits, tile_of
 from oracle import binding as ob
 import p3d_amd as p3d
@@ -389,47 +391,32 @@ def test_refusals_enqueue_nothing(scenes):
     dev = scenes("path_mirror")
     rays = pixel_rays(dev, SUB_TILE)
     n = rays["origin"].shape[0]
-    rgb = torch.full((n, 3), -7.0, device="cuda")
-    hit = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    query, inputs = dq.trace_path(4), {"d_origin": rays["origin"], "d_direction": rays["direction"]}
+    out = dq.check_buffer_refusals(query, dev, inputs, n)
     rng = torch.full((n + 1, 2), 9, dtype=torch.int64, device="cuda")
-    out = {"rgb": rgb, "hit_id": hit}
     host = np.zeros((n, 3), np.float32)
-    big = 0x00ffff00  # rays no buffer here holds: 200 MB of them
-    q = lambda accel=p3d.ACCEL_BVH, origin=rays["origin"], d=dev, **kw: p3d.trace_path_device(d, accel, origin, rays["direction"], 4, out=out, **kw)
     empty = empty_scene_with_a_grid()
     no_grid = p3d.DeviceScene(p3d.HostScene(scene_path("path_mirror.p3f")), bvh=True)
-    for what, code, word, call in [
-        ("a misaligned rng", -1, "8-byte aligned", lambda: q(rng=(rng.data_ptr() + 4, n))),
-        ("a host origin", -1, "host memory", lambda: q(origin=(host.ctypes.data, n))),
-        ("a host rng", -1, "host memory", lambda: q(rng=(host.ctypes.data, n))),
-        # too short: torch hands out pieces of larger allocations, so "behind the allocation" needs a count beyond any of them
-        ("buffers too short", -1, "d_origin ends behind its allocation",
-         lambda: p3d.trace_path_device(dev, p3d.ACCEL_BVH, (rays["origin"].data_ptr(), big), (rays["direction"].data_ptr(), big), 4,
-                                       out={"rgb": (rgb.data_ptr(), big), "hit_id": (hit.data_ptr(), big)})),
-        ("the skybox without a cubemap", -1, "cubemap", lambda: q(flags=p3d.RADIANCE_SKYBOX)),
-        ("a grid over an empty scene", -3, "empty scene", lambda: q(accel=p3d.ACCEL_GRID, d=empty)),
-        ("the object loop over no grid", -1, "without a grid", lambda: q(accel=p3d.ACCEL_GRID, d=no_grid)),
-        ("an unknown accel", -1, "accel", lambda: q(accel=7)),
-    ]:
-        with pytest.raises(p3d.P3DError) as e:
-            call()
-        assert e.value.code == code and word in str(e.value), "%s: %s" % (what, e.value)
+    q = lambda accel=p3d.ACCEL_BVH, d=dev, other=query, **more: other.call(d, accel, dict(inputs, **more), query.optional, 0, out)
+    dq.assert_refused([
+        # d_rng is checked behind the outputs: the contract's count cannot guard it, so it is refused here with n good rows
+        ("a misaligned rng", INVALID, "8-byte aligned", lambda: q(d_rng=(rng.data_ptr() + 4, n))),
+        ("a host rng", INVALID, "host memory", lambda: q(d_rng=(host.ctypes.data, n))),
+        ("the skybox without a cubemap", INVALID, "cubemap", lambda: q(other=dq.trace_path(4, flags=p3d.RADIANCE_SKYBOX))),
+        ("a grid over an empty scene", UNSUPPORTED, "empty scene", lambda: q(accel=p3d.ACCEL_GRID, d=empty)),
+        ("the object loop over no grid", INVALID, "without a grid", lambda: q(accel=p3d.ACCEL_GRID, d=no_grid)),
+    ])
     L = p3d.lib()
-    o, d, c = rays["origin"].data_ptr(), rays["direction"].data_ptr(), rgb.data_ptr()
-    raw = lambda depth=4, begin=0, samples=1, flags=0, c=c: L.p3d_trace_path_device(dev._h, p3d.ACCEL_BVH, n, o, d, depth, begin, samples, 0, None, flags, c, None, None)
-    for what, word, refused in [
-        ("max_depth 1025", "max_depth", lambda: raw(depth=1025)),
-        ("max_depth -1", "max_depth", lambda: raw(depth=-1)),
-        ("samples = 0", "samples", lambda: raw(samples=0)),
-        ("samples past 2^32", "2^32", lambda: raw(begin=0xffffffff, samples=2)),
-        ("a flag bit", "unknown flag", lambda: raw(flags=4)),
-        ("a null rgb", "null argument", lambda: raw(c=None)),
-        ("a misaligned rgb", "aligned", lambda: raw(c=c + 2)),
+    good = dict(inputs, d_rgb=out["rgb"])
+    for what, word, other, bufs in [
+        ("max_depth 1025", "max_depth", dq.trace_path(1025), good), ("max_depth -1", "max_depth", dq.trace_path(-1), good),
+        ("samples = 0", "samples", dq.trace_path(4, samples=0), good), ("samples past 2^32", "2^32", dq.trace_path(4, samples=2, sample_begin=0xffffffff), good),
+        ("a flag bit", "unknown flag", dq.trace_path(4, flags=4), good), ("a misaligned rgb", "aligned", query, dict(good, d_rgb=out["rgb"].data_ptr() + 2)),
     ]:
-        assert refused() == -1, what
+        assert other.raw(dev, p3d.ACCEL_BVH, n, **bufs) == INVALID, what
         assert word in L.p3d_last_error().decode(), "%s: %s" % (what, L.p3d_last_error())
-    assert L.p3d_trace_path_device(dev._h, p3d.ACCEL_BVH, 0, None, None, 4, 0, 1, 0, None, 0, None, None, None) == 0  # n = 0
-    torch.cuda.synchronize()
-    assert bool((rgb == -7.0).all()) and bool((hit == -7).all()) and bool((rng == 9).all()), "a refused call wrote"
-    assert raw(begin=0xffffffff, samples=1) == 0  # the last sample number there is
+    dq.check_empty_batch(query, dev)
+    dq.assert_untouched(out)
+    assert bool((rng == 9).all()), "a refused call wrote"
+    assert dq.trace_path(4, sample_begin=0xffffffff).raw(dev, p3d.ACCEL_BVH, n, **good) == 0  # the last sample number there is
     assert dev.status() == 0 and empty.status() == 0

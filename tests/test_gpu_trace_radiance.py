@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, scene_path
+import device_query_contract as dq
+from device_query_contract import INVALID
 from frame_checks import ACCELS, assert_bits, f32_bits, tile_of
 from oracle import binding as ob
 import p3d_amd as p3d
@@ -293,15 +295,9 @@ def test_outputs(files):
     dev = p3d.DeviceScene(p3d.HostScene(files["glassbox"]), bvh=True)
     rays = p3d.camera_rays_device(dev)
     n = rays["origin"].shape[0]
+    query, inputs = dq.trace_radiance(4), {"d_origin": rays["origin"], "d_direction": rays["direction"]}
     both = p3d.trace_radiance_device(dev, p3d.ACCEL_BVH, rays["origin"], rays["direction"], 4)
-    alone = p3d.trace_radiance_device(dev, p3d.ACCEL_BVH, rays["origin"], rays["direction"], 4, want=())
-    assert sorted(alone) == ["rgb"] and sorted(both) == ["hit_id", "rgb"]
-    assert_bits(alone["rgb"].cpu().numpy(), both["rgb"].cpu().numpy(), "rgb without hit_id")
-    out = {"rgb": torch.full((n, 3), -7.0, device="cuda"), "hit_id": torch.full((n,), -7, dtype=torch.int32, device="cuda")}
-    back = p3d.trace_radiance_device(dev, p3d.ACCEL_BVH, rays["origin"], rays["direction"], 4, out=out)
-    assert back["rgb"] is out["rgb"] and back["hit_id"] is out["hit_id"]
-    assert_bits(out["rgb"].cpu().numpy(), both["rgb"].cpu().numpy(), "out['rgb']")
-    assert_bits(out["hit_id"].cpu().numpy(), both["hit_id"].cpu().numpy(), "out['hit_id']")
+    dq.check_callers_outputs(query, dev, p3d.ACCEL_BVH, inputs, {name: t.cpu().numpy() for name, t in both.items()}, "glassbox", optional=("hit_id",))
     # raw (address, rows) pairs; a prefix leaves the rows behind it alone
     rows = torch.full((n, 3), -7.0, device="cuda")
     p3d.trace_radiance_device(dev, p3d.ACCEL_BVH, (rays["origin"].data_ptr(), 100), (rays["direction"].data_ptr(), 100), 4, want=(),
@@ -311,18 +307,15 @@ def test_outputs(files):
     keep = {"origin": torch.empty((n, 3), device="cuda"), "direction": torch.empty((n, 3), device="cuda")}
     assert p3d.camera_rays_device(dev, out=keep)["direction"] is keep["direction"]
     assert_bits(keep["direction"].cpu().numpy(), rays["direction"].cpu().numpy(), "camera rays into out=")
-    # the library's own refusals
+    # what every device query refuses, and the library's own refusals
+    outs = dq.check_buffer_refusals(query, dev, inputs, n)
     L = p3d.lib()
-    o, d, c = rays["origin"].data_ptr(), rays["direction"].data_ptr(), both["rgb"].data_ptr()
-    for what, word, call in [
-        ("max_depth 17", "max_depth", lambda: L.p3d_trace_radiance_device(dev._h, p3d.ACCEL_BVH, n, o, d, 17, 0, c, None, None)),
-        ("max_depth -1", "max_depth", lambda: L.p3d_trace_radiance_device(dev._h, p3d.ACCEL_BVH, n, o, d, -1, 0, c, None, None)),
-        ("a flag bit", "unknown flag", lambda: L.p3d_trace_radiance_device(dev._h, p3d.ACCEL_BVH, n, o, d, 4, 2, c, None, None)),
-        ("no grid", "grid", lambda: L.p3d_trace_radiance_device(dev._h, p3d.ACCEL_GRID, n, o, d, 4, 0, c, None, None)),
-        ("a null rgb", "null argument", lambda: L.p3d_trace_radiance_device(dev._h, p3d.ACCEL_BVH, n, o, d, 4, 0, None, None, None)),
-        ("a misaligned rgb", "aligned", lambda: L.p3d_trace_radiance_device(dev._h, p3d.ACCEL_BVH, n, o, d, 4, 0, c + 2, None, None)),
-    ]:
-        assert call() == -1, what
+    good = dict(inputs, d_rgb=outs["rgb"])
+    for what, word, other, accel in [("max_depth 17", "max_depth", dq.trace_radiance(17), p3d.ACCEL_BVH), ("max_depth -1", "max_depth", dq.trace_radiance(-1), p3d.ACCEL_BVH),
+                                     ("a flag bit", "unknown flag", dq.trace_radiance(4, flags=2), p3d.ACCEL_BVH), ("no grid", "grid", query, p3d.ACCEL_GRID)]:
+        assert other.raw(dev, accel, n, **good) == INVALID, what
         assert word in L.p3d_last_error().decode(), "%s: %s" % (what, L.p3d_last_error())
-    assert L.p3d_trace_radiance_device(dev._h, p3d.ACCEL_BVH, 0, None, None, 4, 0, None, None, None) == 0  # n = 0
+    assert query.raw(dev, p3d.ACCEL_BVH, n, **dict(good, d_rgb=outs["rgb"].data_ptr() + 2)) == INVALID and b"aligned" in L.p3d_last_error()
+    dq.check_empty_batch(query, dev)
+    dq.assert_untouched(outs)
     assert dev.status() == 0

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from frame_checks import as_bytes
+from device_query_contract import INVALID
 import intersect_reference as ref
 import nearest_k_reference as nk
 import nearest_reference as near
@@ -14,7 +15,6 @@ SCENES = ("mixed", "mixed_planes", "planes", "axis_aligned", "tri5k")
 SEED = {name: 400 + k for k, name in enumerate(SCENES)}  # test_nearest_reference.py's
 KS = nk.KS
 FLT_MAX = near.FLT_MAX
-INVALID = -1
 
 
 @pytest.fixture(scope="module")
@@ -86,22 +86,9 @@ def test_a_smaller_k_is_a_prefix(name, worlds):
             nk.check_rows(pts, k, small, "%s, k = %d" % (name, k))
 
 
-HEAD = """bclr 0 0 0
-v
-from 0 0 20
-at 0 0 0
-up 0 1 0
-angle 40
-hither 0.01
-resolution 32 32
-aperture 0
-focal 1
-l 0 10 10 1 1 1
-f 0.8 0.8 0.8 0.9 1 1 1 0.3 20 0 1 0 0 0
-"""
 # the EXACT scene of test_nearest_reference.py (small dyadic numbers: every operation of the rule is exact on them), and behind
 # it one triangle three times
-EXACT = HEAD + """s 4 0 0 1
+EXACT = ref.HEAD + """s 4 0 0 1
 p 3
 0 0 0
 2 0 0
@@ -165,7 +152,7 @@ def test_exact_cases(tmp_path):
 
 def test_edge_inputs(tmp_path):
     path = tmp_path / "empty.p3f"
-    path.write_text(HEAD)
+    path.write_text(ref.HEAD)
     hs = p3d.HostScene(str(path))
     count, obj, dist, closest = hs.nearest_k(np.zeros((3, 3), np.float32), 4)  # an empty scene
     assert count.tolist() == [0] * 3 and (obj == -1).all() and obj.shape == (3, 4) and (dist == FLT_MAX).all() and not closest.any()

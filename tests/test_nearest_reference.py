@@ -50,21 +50,8 @@ def test_limits(name, worlds):
     assert all(a.tobytes() == b.tobytes() for a, b in zip(everything, free))
 
 
-HEAD = """bclr 0 0 0
-v
-from 0 0 20
-at 0 0 0
-up 0 1 0
-angle 40
-hither 0.01
-resolution 32 32
-aperture 0
-focal 1
-l 0 10 10 1 1 1
-f 0.8 0.8 0.8 0.9 1 1 1 0.3 20 0 1 0 0 0
-"""
 # small dyadic numbers: every operation of the rule is exact on them
-EXACT = HEAD + """s 4 0 0 1
+EXACT = ref.HEAD + """s 4 0 0 1
 p 3
 0 0 0
 2 0 0
@@ -132,7 +119,7 @@ def test_exact_cases(tmp_path):
 
 def test_an_empty_batch_and_an_empty_scene(tmp_path):
     path = tmp_path / "empty.p3f"
-    path.write_text(HEAD)
+    path.write_text(ref.HEAD)
     hs = p3d.HostScene(str(path))
     obj, dist, closest = hs.nearest(np.zeros((3, 3), np.float32))
     assert obj.tolist() == [-1] * 3 and (dist == FLT_MAX).all() and not closest.any()

@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 from api_checks import header_code, scene_without_a_library
+from device_query_contract import FLT_MAX, INVALID, UNSUPPORTED
+from intersect_reference import HEAD
 import p3d_amd as p3d
 import sweep_reference as sw
 
-FLT_MAX = sw.FLT_MAX
-INVALID, UNSUPPORTED = -1, -3
 
 
 def test_the_header_declares_them():
@@ -46,21 +46,6 @@ def test_the_library_exports_them_and_python_wraps_them_as_functions():
     assert b"p3d_sweep_sphere_device" in lib.p3d_last_error() and b"null scene" in lib.p3d_last_error()
     assert lib.p3d_host_scene_sweep_sphere(None, 0, *([None] * 8)) == INVALID
     assert b"p3d_host_scene_sweep_sphere" in lib.p3d_last_error() and b"null scene" in lib.p3d_last_error()
-
-
-HEAD = """bclr 0 0 0
-v
-from 0 0 20
-at 0 0 0
-up 0 1 0
-angle 40
-hither 0.01
-resolution 32 32
-aperture 0
-focal 1
-l 0 10 10 1 1 1
-f 0.8 0.8 0.8 0.9 1 1 1 0.3 20 0 1 0 0 0
-"""
 
 
 def scene(tmp_path, name, body):
