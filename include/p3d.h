@@ -1315,4 +1315,10 @@ int p3d_host_scene_skybox_face(p3d_host_scene* hs, int face, const uint8_t** img
  * host scene's type.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
  */
 #include "p3d_sweep.h"
+/*
+ * QUERIES THAT LEAVE OBJECTS OUT, PER QUERY - p3d_nearest_k_filtered_device and p3d_sweep_sphere_filtered_device, for a cloth
+ * vertex, a particle or a body that is itself part of the scene, and their statements on the CPU - are declared in p3d_filter.h,
+ * which this header includes here.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ */
+#include "p3d_filter.h"
 #endif /* P3D_H */

@@ -28,6 +28,8 @@ from .config import _f3, default_config, denoise_params, look_at, pathtrace_conf
 from .device_queries import (camera_rays_device, camera_sample_rays_device, occlusion_device, occlusion_rays, occlusion_rays_device,
                              trace_path_device, trace_radiance_device)
 from .sweep import host_sweep_sphere, sweep_sphere_device
+from .filtered import (FILTER_SKIP_MAX, host_nearest_k_filtered, host_sweep_sphere_filtered, nearest_k_filtered_device,
+                       sweep_sphere_filtered_device)
 from .device_scene import SKYBOX_FACE_FILES, DeviceScene, load_skybox_dir
 from .geometry import _xform_arrays, deformed, deformed_spheres, transformed, tree_cost
 from .host_scene import HostScene

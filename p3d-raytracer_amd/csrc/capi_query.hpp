@@ -1,6 +1,7 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
 // p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device,
-// p3d_occlusion_device, p3d_occlusion_rays_device, p3d_sweep_sphere_device, p3d_object_*, p3d_skybox_color)
+// p3d_occlusion_device, p3d_occlusion_rays_device, p3d_sweep_sphere_device, p3d_nearest_k_filtered_device,
+// p3d_sweep_sphere_filtered_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
@@ -113,22 +114,47 @@ int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin
   });
 }
 
-// p3d_nearest_device (k_form false: k = 1, no d_count) and p3d_nearest_k_device.  One set of checks for both; the outputs hold
-// k rows per point
+// The skip buffers of a *_filtered_device call (include/p3d_filter.h).  The unfiltered entry points pass none: a null
+// FilterArgs*, the same checks and launches as before
+struct FilterArgs {
+  const int32_t* d_skip;  // n x n_skip, or null
+  uint32_t n_skip;
+  const int32_t* d_skip_range;  // n x 2, or null
+  bool absent() const { return n_skip == 0 && !d_skip_range; }  // the call is the unfiltered call: its kernel is launched
+};
+// What a filtered call refuses of its filter whatever n is, and with n > 0
+int check_filter(const FilterArgs& fa, const std::string& pre) {
+  if (fa.n_skip > P3D_FILTER_SKIP_MAX) return fail(P3D_ERR_INVALID, pre + "n_skip must be 0 .. P3D_FILTER_SKIP_MAX (8)");
+  return P3D_OK;
+}
+int check_filter_buffers(const FilterArgs& fa, const std::string& pre) {
+  if (fa.n_skip > 0 && !fa.d_skip) return fail(P3D_ERR_INVALID, pre + "null argument (d_skip is needed with n_skip > 0)");
+  return P3D_OK;
+}
+FilterParams filter_params(const FilterArgs& fa) { return FilterParams{fa.n_skip ? fa.d_skip : nullptr, fa.d_skip_range, fa.n_skip}; }
+
+// p3d_nearest_device (k_form false: k = 1, no d_count), p3d_nearest_k_device and, with `filter`, p3d_nearest_k_filtered_device.
+// One set of checks for all; the outputs hold k rows per point
 int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_form, const float* d_point, const float* d_max_dist,
-                   int32_t* d_count, int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
-  const std::string pre = k_form ? "p3d_nearest_k_device: " : "p3d_nearest_device: ";
+                   int32_t* d_count, int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream,
+                   const FilterArgs* filter = nullptr) {
+  const std::string pre = filter ? "p3d_nearest_k_filtered_device: " : k_form ? "p3d_nearest_k_device: " : "p3d_nearest_device: ";
+  const FilterArgs fa = filter ? *filter : FilterArgs{nullptr, 0, nullptr};
   if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
   if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no nearest-surface query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
   if (int rc = check_accel(s, accel)) return rc;
   if (accel == P3D_ACCEL_BVH && s->has_planes)
     return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
   if (k == 0 || k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
+  if (int rc = check_filter(fa, pre)) return rc;
   if (n == 0) return P3D_OK;
   if (!d_point || !d_object || (k_form && !d_count)) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (int rc = check_filter_buffers(fa, pre)) return rc;
   const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
+  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
   const QueryBuffer bufs[] = {
-      {d_point, vec, "d_point"}, {d_max_dist, one, "d_max_dist"}, {d_count, one, "d_count"}, {d_object, one * k, "d_object"},
+      {d_point, vec, "d_point"}, {d_max_dist, one, "d_max_dist"}, {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"},
+      {d_count, one, "d_count"}, {d_object, one * k, "d_object"},
       {d_dist, one * k, "d_dist"}, {d_closest, vec * k, "d_closest"}, {d_normal, vec * k, "d_normal"}};
   // (the lists of this call's k behind the stack window)
   return enqueue_query(s, accel, n, pre, "points", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
@@ -136,7 +162,9 @@ int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_
     P.sc = s->dev; P.n = n; P.k = k; P.point = d_point; P.max_dist = d_max_dist;
     P.count = d_count; P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal; P.stack = q.stack;
     with_flags([&](auto BVH) {
-      hipLaunchKernelGGL((nearest_k_device_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
+      if (fa.absent()) hipLaunchKernelGGL((nearest_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+      else hipLaunchKernelGGL((nearest_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, NearestKFilteredParams{P, F});
     }, accel == P3D_ACCEL_BVH);
   });
 }
@@ -454,11 +482,20 @@ int p3d_nearest_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, c
   return nearest_device(s, accel, n, k, true, d_point, d_max_dist, d_count, d_object, d_dist, d_closest, d_normal, hip_stream);
 }
 
-// The first contact of n moving balls, one kernel on the caller's stream (sweep_query.hpp)
-int p3d_sweep_sphere_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_radius,
-                            const float* d_t_max, int32_t* d_object, float* d_t, float* d_centre, float* d_contact, float* d_normal,
-                            void* hip_stream) {
-  const std::string pre = "p3d_sweep_sphere_device: ";
+int p3d_nearest_k_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_point, const float* d_max_dist,
+                                  const int32_t* d_skip, uint32_t n_skip, const int32_t* d_skip_range, int32_t* d_count, int32_t* d_object,
+                                  float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
+  const FilterArgs fa{d_skip, n_skip, d_skip_range};
+  return nearest_device(s, accel, n, k, true, d_point, d_max_dist, d_count, d_object, d_dist, d_closest, d_normal, hip_stream, &fa);
+}
+
+// The first contact of n moving balls, one kernel on the caller's stream (sweep_query.hpp); with `filter`,
+// p3d_sweep_sphere_filtered_device
+static int sweep_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_radius,
+                        const float* d_t_max, int32_t* d_object, float* d_t, float* d_centre, float* d_contact, float* d_normal,
+                        void* hip_stream, const FilterArgs* filter) {
+  const std::string pre = filter ? "p3d_sweep_sphere_filtered_device: " : "p3d_sweep_sphere_device: ";
+  const FilterArgs fa = filter ? *filter : FilterArgs{nullptr, 0, nullptr};
   if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
   if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no sphere sweep through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
   if (int rc = check_accel(s, accel)) return rc;
@@ -466,21 +503,38 @@ int p3d_sweep_sphere_device(p3d_scene* s, uint32_t accel, uint32_t n, const floa
     return fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(s->first_box) + " is a box: a ball against a box (a rounded box, and its inside) is not swept");
   if (accel == P3D_ACCEL_BVH && s->has_planes)
     return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
+  if (int rc = check_filter(fa, pre)) return rc;
   if (n == 0) return P3D_OK;
   if (!d_origin || !d_direction || !d_radius || !d_object) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (int rc = check_filter_buffers(fa, pre)) return rc;
   const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
   const QueryBuffer bufs[] = {
       {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_radius, one, "d_radius"}, {d_t_max, one, "d_t_max"},
-      {d_object, one, "d_object"}, {d_t, one, "d_t"}, {d_centre, vec, "d_centre"}, {d_contact, vec, "d_contact"}, {d_normal, vec, "d_normal"}};
+      {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"}, {d_object, one, "d_object"}, {d_t, one, "d_t"}, {d_centre, vec, "d_centre"}, {d_contact, vec, "d_contact"}, {d_normal, vec, "d_normal"}};
   // (the best contact stays in registers: nothing behind the stack window)
   return enqueue_query(s, accel, n, pre, "balls", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
     SweepParams P{};
     P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.radius = d_radius; P.t_max = d_t_max;
     P.object = d_object; P.t = d_t; P.centre = d_centre; P.contact = d_contact; P.normal = d_normal; P.stack = q.stack;
     with_flags([&](auto BVH) {
-      hipLaunchKernelGGL((sweep_sphere_device_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
+      if (fa.absent()) hipLaunchKernelGGL((sweep_sphere_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+      else hipLaunchKernelGGL((sweep_sphere_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, SweepFilteredParams{P, F});
     }, accel == P3D_ACCEL_BVH);
   });
+}
+int p3d_sweep_sphere_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_radius,
+                            const float* d_t_max, int32_t* d_object, float* d_t, float* d_centre, float* d_contact, float* d_normal,
+                            void* hip_stream) {
+  return sweep_device(s, accel, n, d_origin, d_direction, d_radius, d_t_max, d_object, d_t, d_centre, d_contact, d_normal, hip_stream, nullptr);
+}
+int p3d_sweep_sphere_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction,
+                                     const float* d_radius, const float* d_t_max, const int32_t* d_skip, uint32_t n_skip,
+                                     const int32_t* d_skip_range, int32_t* d_object, float* d_t, float* d_centre, float* d_contact,
+                                     float* d_normal, void* hip_stream) {
+  const FilterArgs fa{d_skip, n_skip, d_skip_range};
+  return sweep_device(s, accel, n, d_origin, d_direction, d_radius, d_t_max, d_object, d_t, d_centre, d_contact, d_normal, hip_stream, &fa);
 }
 
 enum class ObjectQuery { Intercepts = 0, Normal = 1, SkyboxColour = 2 };  // the values are object_query_kernel's WHAT

@@ -48,7 +48,13 @@ __device__ __forceinline__ float nearest_node_d2(const NodeRec& n, const float p
   return nearest_box_d2(p, lo, hi);
 }
 
-__device__ __forceinline__ void nearest_k_offer(const Geom& g, uint32_t slot, const float p[3], NearestKSearch& s) {
+// An object the lane's filter names is not offered: the rule is not evaluated for it (filter_rule.hpp).  NoFilter: the test is
+// not compiled at all (if constexpr: a test that folds to false still left other instructions in the sweep's kernels)
+template <class Filter>
+__device__ __forceinline__ void nearest_k_offer(const Geom& g, uint32_t slot, const float p[3], NearestKSearch& s, const Filter& f) {
+  if constexpr (Filter::kFilters) {
+    if (filter_skips(f, (int32_t)geom_object(g))) return;
+  }
   const float v[9] = {g.a.x, g.a.y, g.a.z, g.a.w, g.b.x, g.b.y, g.b.z, g.b.w, g.c.x};
   float q[3];
   const float d2 = nearest_point(geom_type(g), v, p, q);
@@ -57,8 +63,9 @@ __device__ __forceinline__ void nearest_k_offer(const Geom& g, uint32_t slot, co
 }
 
 // P3D_ACCEL_NONE: every object, planes included - the loop of p3d_host_scene_nearest_k
-__device__ void brute_nearest_k(const DevScene& sc, const float p[3], NearestKSearch& s) {
-  for (uint32_t i = 0; i < sc.n_objs; ++i) nearest_k_offer(load_geom(sc.ogeom, i), i, p, s);
+template <class Filter>
+__device__ void brute_nearest_k(const DevScene& sc, const float p[3], NearestKSearch& s, const Filter& f) {
+  for (uint32_t i = 0; i < sc.n_objs; ++i) nearest_k_offer(load_geom(sc.ogeom, i), i, p, s, f);
 }
 
 // P3D_ACCEL_BVH: bvh_culled_walk (queries.hpp), not a ray traversal: a box is keyed, ordered and stacked by its d2 from the
@@ -69,10 +76,14 @@ __device__ void brute_nearest_k(const DevScene& sc, const float p[3], NearestKSe
 //     fill the list;
 //   - a popped entry meets the cull again: the radius has shrunk since it was pushed;
 //   - a leaf offers each of its objects to the list; (d2, object) is a total order and every object sits in one leaf, so the
-//     order of the visits does not show in the list.
+//     order of the visits does not show in the list;
+//   - a filter changes what a leaf offers and nothing else: the boxes, the cull and its slack are those of the whole scene.  A
+//     skipped object tightens no bound, so a filtered search is as wide as the unfiltered search of the scene without it.
+template <class Filter>
 struct NearestKWalk {
   const float* p;
   NearestKSearch& s;
+  const Filter& f;
   __device__ __forceinline__ bool key(const NodeRec& n, float& order, float& stacked) const {
     order = stacked = nearest_node_d2(n, p);
     return !nearest_culls(order, s.gate.d2);
@@ -80,13 +91,14 @@ struct NearestKWalk {
   __device__ __forceinline__ bool culled(float d2) const { return nearest_culls(d2, s.gate.d2); }
   __device__ __forceinline__ bool left_first(float l_d2, float r_d2) const { return !(r_d2 < l_d2); }
   __device__ __forceinline__ bool leaf(const DevScene& sc, uint32_t first, uint32_t end) {
-    for (uint32_t g = first; g < end; ++g) nearest_k_offer(load_geom(sc.bgeom, g), g, p, s);
+    for (uint32_t g = first; g < end; ++g) nearest_k_offer(load_geom(sc.bgeom, g), g, p, s, f);
     return false;
   }
 };
-__device__ void bvh_nearest_k(const DevScene& sc, Stack& st, const float p[3], NearestKSearch& s) {
+template <class Filter>
+__device__ void bvh_nearest_k(const DevScene& sc, Stack& st, const float p[3], NearestKSearch& s, const Filter& f) {
   Counters<false> ct;
-  NearestKWalk walk{p, s};
+  NearestKWalk<Filter> walk{p, s, f};
   bvh_culled_walk(sc, st, walk, ct);
 }
 
@@ -102,6 +114,11 @@ struct NearestKParams {
   float* normal;
   QueryStack stack;
 };
+// p3d_nearest_k_filtered_device: the same, and where the lanes' filters are
+struct NearestKFilteredParams {
+  NearestKParams q;
+  FilterParams f;
+};
 
 // One point per lane on an empty stack; the dynamic LDS holds the stack window and, behind it, the lists of
 // the call's k (not of P3D_NEAREST_K_MAX: LDS per workgroup decides how many waves a CU holds).  Row i k + j, j < count: the
@@ -114,45 +131,21 @@ struct NearestKParams {
 // (the lists are already there) or to give the outputs the layout (k, n).
 // A lane reads its point with three dword loads 12 bytes apart from its neighbours' (ray_query_kernel: whole 128-byte lines
 // either way, in front of dozens of dependent node fetches).  UNMEASURED, like the staged form.
+// Two kernels of one name, told apart by their parameters: the one p3d_nearest_device and p3d_nearest_k_device launch, which
+// knows no filters, and the one of p3d_nearest_k_filtered_device.  A filter costs registers (ten words, and the compares in
+// every leaf), which is why the unfiltered calls do not go through the filtered kernel with an empty filter (DESIGN.md
+// "Filtered queries" has the compiler's numbers).  The list in LDS next to the candidate lists, read in the leaf, is the
+// alternative: not tried, UNMEASURED.
 template <int ACCEL>
 __global__ void __launch_bounds__(kBlock) nearest_k_device_kernel(const NearestKParams P) {
-  extern __shared__ float4 smem[];
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  Stack st;
-  query_stack_bind(st, smem, P.stack, i);
-  NearestKSearch s;
-  s.list.base = query_list_base(smem, P.stack);
-  s.count = 0; s.k = P.k;
-  if (i >= P.n) return;
-  const float p[3] = {P.point[3 * i], P.point[3 * i + 1], P.point[3 * i + 2]};
-  const bool open = nearest_k_open(P.max_dist != nullptr, P.max_dist ? P.max_dist[i] : 0.0f, s.gate);
-  if (open && P.sc.n_objs > 0) {
-    if (ACCEL == P3D_ACCEL_BVH) bvh_nearest_k(P.sc, st, p, s);
-    else brute_nearest_k(P.sc, p, s);
-  }
-  if (P.count) P.count[i] = (int32_t)s.count;
-  const float4* geom = ACCEL == P3D_ACCEL_BVH ? P.sc.bgeom : P.sc.ogeom;
-  for (uint32_t e = 0; e < P.k; ++e) {
-    const size_t row = (size_t)i * P.k + e;
-    const bool found = e < s.count;
-    int32_t object = -1;
-    float dist = FLT_MAX;
-    F3 q = f3(0, 0, 0), nrm = f3(0, 0, 0);
-    if (found) {
-      const Geom g = load_geom(geom, s.list.slot(e));
-      const float v[9] = {g.a.x, g.a.y, g.a.z, g.a.w, g.b.x, g.b.y, g.b.z, g.b.w, g.c.x};
-      float c[3];
-      nearest_point(geom_type(g), v, p, c);
-      object = s.list.object(e);
-      dist = sqrtf(s.list.d2(e));
-      q = f3(c[0], c[1], c[2]);
-      if (P.normal) nrm = get_normal(g, P.sc.normals, q);
-    }
-    P.object[row] = object;
-    if (P.dist) P.dist[row] = dist;
-    if (P.closest) store_f3(P.closest, row, q);
-    if (P.normal) store_f3(P.normal, row, nrm);
-  }
+  const NoFilterSource filters{};
+#include "nearest_k_body.inc"
+}
+template <int ACCEL>
+__global__ void __launch_bounds__(kBlock) nearest_k_device_kernel(const NearestKFilteredParams PF) {
+  const NearestKParams& P = PF.q;
+  const FilterParams& filters = PF.f;
+#include "nearest_k_body.inc"
 }
 
 }  // namespace p3d

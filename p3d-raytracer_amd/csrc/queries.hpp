@@ -1,9 +1,11 @@
 // queries.hpp — batched per-object queries against a scene, for the unit-level parity of the host classes
 // (object_query_kernel), and what the traversing query kernels share: QueryStack, the stack their parameters embed,
-// bvh_culled_walk, the one stack traversal with a cull, and the output helpers store_f3 and query_list_base.
+// bvh_culled_walk, the one stack traversal with a cull, the output helpers store_f3 and query_list_base, and the two sources
+// of a lane's filter, FilterParams and NoFilterSource.
 #pragma once
 
 #include "device_core.hpp"
+#include "filter_rule.hpp"
 
 namespace p3d {
 
@@ -62,6 +64,20 @@ template <class Index>
 __device__ __forceinline__ void store_f3(float* base, Index row, F3 v) {
   base[3 * row] = v.x; base[3 * row + 1] = v.y; base[3 * row + 2] = v.z;
 }
+
+// Where a query kernel's lanes get their filters from (host/filter_rule.hpp): the template argument that tells a filtered
+// instantiation from the unfiltered one.  FilterParams: the skip buffers of a *_filtered_device call, row i read once, before
+// the walk, into ten registers.  NoFilterSource: nothing is read and filter_skips is a constant false, so the instantiation is
+// instruction for instruction the kernel that knows no filters.
+struct FilterParams {
+  const int32_t* skip;   // n x n_skip, or null
+  const int32_t* range;  // n x 2, or null
+  uint32_t n_skip;
+  __device__ __forceinline__ QueryFilter load(uint32_t i, uint32_t n_objs) const { return filter_load(skip, n_skip, range, i, n_objs); }
+};
+struct NoFilterSource {
+  __device__ __forceinline__ NoFilter load(uint32_t, uint32_t) const { return NoFilter{}; }
+};
 
 // The stack traversal over sc.nodes / sc.bgeom of the queries that cull (DESIGN.md "One culled walk"): the segment any-hit
 // (ray_query.hpp), the hit list (hit_list_query.hpp) and the k nearest surfaces (nearest_query.hpp).  The walk owns the state

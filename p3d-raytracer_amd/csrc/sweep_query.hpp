@@ -19,7 +19,13 @@ struct SweepBest {
   uint32_t slot;
 };
 
-__device__ __forceinline__ void sweep_offer(const Geom& g, uint32_t slot, const SweepRay& s, SweepBest& best) {
+// An object the lane's filter names is not offered: the rule is not evaluated for it (filter_rule.hpp).  NoFilter: the test is
+// not compiled at all (if constexpr: a test that folds to false still left other instructions in these kernels)
+template <class Filter>
+__device__ __forceinline__ void sweep_offer(const Geom& g, uint32_t slot, const SweepRay& s, SweepBest& best, const Filter& f) {
+  if constexpr (Filter::kFilters) {
+    if (filter_skips(f, (int32_t)geom_object(g))) return;
+  }
   const float v[9] = {g.a.x, g.a.y, g.a.z, g.a.w, g.b.x, g.b.y, g.b.z, g.b.w, g.c.x};
   const int32_t object = (int32_t)geom_object(g);
   float t;
@@ -29,8 +35,9 @@ __device__ __forceinline__ void sweep_offer(const Geom& g, uint32_t slot, const 
 }
 
 // P3D_ACCEL_NONE: every object, planes included - the loop of p3d_host_scene_sweep_sphere
-__device__ void brute_sweep(const DevScene& sc, const SweepRay& s, SweepBest& best) {
-  for (uint32_t i = 0; i < sc.n_objs; ++i) sweep_offer(load_geom(sc.ogeom, i), i, s, best);
+template <class Filter>
+__device__ void brute_sweep(const DevScene& sc, const SweepRay& s, SweepBest& best, const Filter& f) {
+  for (uint32_t i = 0; i < sc.n_objs; ++i) sweep_offer(load_geom(sc.ogeom, i), i, s, best, f);
 }
 
 // P3D_ACCEL_BVH: bvh_culled_walk (queries.hpp).  A box is keyed, ordered and stacked by the parameter at which the ray
@@ -41,11 +48,14 @@ __device__ void brute_sweep(const DevScene& sc, const SweepRay& s, SweepBest& be
 //     found, its T from then on.  An entry beyond the best T and one beyond t_max are this one comparison;
 //   - a popped entry meets the cull again: the bound has shrunk since it was pushed;
 //   - a leaf offers each of its objects and never ends the lane: (T, object) is a total order and every object sits in one
-//     leaf, so the order of the visits does not show in the answer.
+//     leaf, so the order of the visits does not show in the answer;
+//   - a filter changes what a leaf offers and nothing else: a skipped object is no contact and shrinks no bound.
+template <class Filter>
 struct SweepWalk {
   const SweepRay& s;
   const SweepSlabs& slabs;
   SweepBest& best;
+  const Filter& f;
   __device__ __forceinline__ bool key(const NodeRec& n, float& order, float& stacked) const {
     const float lo[3] = {n.lo.x, n.lo.y, n.lo.z}, hi[3] = {n.hi.x, n.hi.y, n.hi.z};
     float entry;
@@ -56,15 +66,16 @@ struct SweepWalk {
   __device__ __forceinline__ bool culled(float entry) const { return sweep_culls(entry, best.t); }
   __device__ __forceinline__ bool left_first(float l, float r) const { return !(r < l); }
   __device__ __forceinline__ bool leaf(const DevScene& sc, uint32_t first, uint32_t end) {
-    for (uint32_t g = first; g < end; ++g) sweep_offer(load_geom(sc.bgeom, g), g, s, best);
+    for (uint32_t g = first; g < end; ++g) sweep_offer(load_geom(sc.bgeom, g), g, s, best, f);
     return false;
   }
 };
-__device__ void bvh_sweep(const DevScene& sc, Stack& st, const SweepRay& s, SweepBest& best) {
+template <class Filter>
+__device__ void bvh_sweep(const DevScene& sc, Stack& st, const SweepRay& s, SweepBest& best, const Filter& f) {
   Counters<false> ct;
   SweepSlabs slabs;
   sweep_slabs(s, slabs);
-  SweepWalk walk{s, slabs, best};
+  SweepWalk<Filter> walk{s, slabs, best, f};
   bvh_culled_walk(sc, st, walk, ct);
 }
 
@@ -82,6 +93,11 @@ struct SweepParams {
   float* normal;
   QueryStack stack;
 };
+// p3d_sweep_sphere_filtered_device: the same, and where the lanes' filters are
+struct SweepFilteredParams {
+  SweepParams q;
+  FilterParams f;
+};
 
 // One ball per lane on an empty stack; the dynamic LDS holds the stack window only.  Found: the object, T, c(T), the closest
 // point of the object at c(T) (nearest_point once more at the kept slot: evaluated as written in both translation units, so
@@ -91,44 +107,19 @@ struct SweepParams {
 // primitive tests (collect leaf slots, test them in a second phase) was not tried: UNMEASURED.
 // A lane reads its ray with dword loads 12 bytes apart from its neighbours' (ray_query_kernel: whole 128-byte lines either
 // way, in front of dozens of dependent node fetches).  UNMEASURED, like the staged form.
+// Two kernels of one name, told apart by their parameters: the one p3d_sweep_sphere_device launches, which knows no filters,
+// and the one of p3d_sweep_sphere_filtered_device, which holds ten more words per lane through the walk (DESIGN.md "Filtered
+// queries" has what that costs in registers).  The list in LDS, read in the leaf, is the alternative: not tried, UNMEASURED.
 template <int ACCEL>
 __global__ void __launch_bounds__(kBlock) sweep_sphere_device_kernel(const SweepParams P) {
-  extern __shared__ float4 smem[];
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  Stack st;
-  query_stack_bind(st, smem, P.stack, i);
-  if (i >= P.n) return;
-  const size_t row = i;  // (3 * row in 64 bits)
-  const float o[3] = {P.origin[3 * row], P.origin[3 * row + 1], P.origin[3 * row + 2]};
-  const float d[3] = {P.direction[3 * row], P.direction[3 * row + 1], P.direction[3 * row + 2]};
-  SweepRay s;
-  sweep_ray(o, d, P.radius[i], P.t_max != nullptr, P.t_max ? P.t_max[i] : 0.0f, s);
-  SweepBest best{s.limit, kSweepNoObject, 0u};
-  if (s.ok && P.sc.n_objs > 0) {
-    if (ACCEL == P3D_ACCEL_BVH) bvh_sweep(P.sc, st, s, best);
-    else brute_sweep(P.sc, s, best);
-  }
-  const bool found = best.object != kSweepNoObject;
-  int32_t object = -1;
-  float t = FLT_MAX;
-  F3 c = f3(0, 0, 0), q = f3(0, 0, 0), nrm = f3(0, 0, 0);
-  if (found) {
-    const Geom g = load_geom(ACCEL == P3D_ACCEL_BVH ? P.sc.bgeom : P.sc.ogeom, best.slot);
-    const float v[9] = {g.a.x, g.a.y, g.a.z, g.a.w, g.b.x, g.b.y, g.b.z, g.b.w, g.c.x};
-    float cc[3], qq[3];
-    sweep_centre(s, best.t, cc);
-    nearest_point(geom_type(g), v, cc, qq);
-    object = best.object;
-    t = best.t;
-    c = f3(cc[0], cc[1], cc[2]);
-    q = f3(qq[0], qq[1], qq[2]);
-    if (P.normal) nrm = get_normal(g, P.sc.normals, q);
-  }
-  P.object[i] = object;
-  if (P.t) P.t[i] = t;
-  if (P.centre) store_f3(P.centre, row, c);
-  if (P.contact) store_f3(P.contact, row, q);
-  if (P.normal) store_f3(P.normal, row, nrm);
+  const NoFilterSource filters{};
+#include "sweep_body.inc"
+}
+template <int ACCEL>
+__global__ void __launch_bounds__(kBlock) sweep_sphere_device_kernel(const SweepFilteredParams PF) {
+  const SweepParams& P = PF.q;
+  const FilterParams& filters = PF.f;
+#include "sweep_body.inc"
 }
 
 }  // namespace p3d

@@ -63,7 +63,8 @@ def _device_query(scene, who, accel, inputs, table, names, want, order, stream, 
     """What the *_device queries share.  In this order: a name in `want` that `known` (default: `table`) does not hold is
     refused; inputs() gives the input addresses and, last, n; `refusal`, the caller's own (about k), is raised if there is
     one; the outputs `names` are resolved against `table`; and L.p3d_<who> is called with (scene, accel, n, [k,] inputs,
-    `options` (plain numbers), the outputs in the C order `order` - null where not in names -, stream) -> {name: tensor}"""
+    `options` (plain numbers), the outputs in the C order `order` - null where not in names -, stream) -> {name: tensor}.
+    An input that is a ctypes value already (a count that stands between two buffers in the C order) is passed as it is"""
     unknown = [w for w in want if w not in (table if known is None else known)]
     if unknown:
         raise P3DError(-1, "%s: unknown output %r" % (who, unknown[0]))
@@ -71,7 +72,7 @@ def _device_query(scene, who, accel, inputs, table, names, want, order, stream, 
     if refusal:
         raise P3DError(-1, "%s: %s" % (who, refusal))
     res = _device_outputs(scene, who, names, n, out, like, table, rows_of)
-    args = ([] if k is None else [k & 0xffffffff]) + [C.c_void_p(a) for a in addresses] + list(options)
+    args = ([] if k is None else [k & 0xffffffff]) + [a if isinstance(a, C._SimpleCData) else C.c_void_p(a) for a in addresses] + list(options)
     args += [C.c_void_p(res[name][1]) if name in res else None for name in order]
     _check(getattr(scene._L, "p3d_" + who)(scene._h, int(accel), n, *args, _stream(stream)))
     return {name: v[0] for name, v in res.items()}

@@ -1,0 +1,146 @@
+"""Queries that leave objects out, per query (include/p3d_filter.h): nearest_k_filtered_device and sweep_sphere_filtered_device,
+functions of a DeviceScene over device tensors, and host_nearest_k_filtered and host_sweep_sphere_filtered, the brute force on
+the CPU over a HostScene.  For a cloth vertex, a particle or a body that is itself part of the scene.  Functions and not
+members: tests/python_api_surface.json holds both classes to the members they had.
+
+A filter is a skip list, `skip`: int32 (n, s) with s <= FILTER_SKIP_MAX object indices per query (an entry < 0 or >= the
+object count names nothing: pad with -1), and a skip range, `skip_range`: int32 (n, 2) rows (first, count).  Either may be
+None.  The answers are those of the unfiltered query over the scene without the named objects; with both None they are the
+unfiltered query's, bit for bit."""
+import ctypes as C
+
+import numpy as np
+
+from ._abi import P3DError, _check
+from ._device_args import NEAREST_K_MAX, _device_rows, _nearest_k_outputs
+from .device_queries import _device_points, _device_query
+from .sweep import _sweep
+
+FILTER_SKIP_MAX = 8  # P3D_FILTER_SKIP_MAX
+
+
+def _device_filter(scene, who, skip, n_skip, skip_range, n, rows_of):
+    """(address of skip or None, n_skip as the C argument, address of skip_range or None) of a device query of n rows.  A
+    tensor brings its own width; a raw (address, rows) pair needs `n_skip`"""
+    d_s, width = None, 0
+    if skip is not None:
+        if hasattr(skip, "shape") and hasattr(skip, "dim"):
+            if skip.dim() != 2:
+                raise P3DError(-1, "%s: skip: shape %r, needed: (n, s) with s <= %d" % (who, tuple(skip.shape), FILTER_SKIP_MAX))
+            width = int(skip.shape[1])
+            if n_skip is not None and int(n_skip) != width:
+                raise P3DError(-1, "%s: skip has %d columns, n_skip says %d" % (who, width, int(n_skip)))
+        elif n_skip is None:
+            raise P3DError(-1, "%s: skip as a raw (address, rows) pair needs n_skip" % who)
+        else:
+            width = int(n_skip)
+        if width < 0:
+            raise P3DError(-1, "%s: n_skip must be 0 .. %d, got %d" % (who, FILTER_SKIP_MAX, width))
+        if width > 0:  # (no columns: no list)
+            d_s, rows = _device_rows(skip, who + ": skip", width, ("int32",), scene.device)
+            if rows != n:
+                raise P3DError(-1, "%s: %d %s, %d skip rows" % (who, n, rows_of, rows))
+    d_r = None
+    if skip_range is not None:
+        d_r, rows = _device_rows(skip_range, who + ": skip_range", 2, ("int32",), scene.device)
+        if rows != n:
+            raise P3DError(-1, "%s: %d %s, %d skip ranges" % (who, n, rows_of, rows))
+    return d_s, C.c_uint32(width & 0xffffffff), d_r
+
+
+def nearest_k_filtered_device(scene, accel, points, k, max_dist=None, skip=None, skip_range=None, want=("count", "object", "dist"), stream=0,
+                              out=None, n_skip=None):
+    """p3d_nearest_k_filtered_device: DeviceScene.nearest_k_device for the scene without the objects each point names (the
+    module's docstring has the filter; k = 1 is nearest_device's answer).  skip: a contiguous int32 (n, s) CUDA/HIP tensor on the
+    scene's device, or a raw (address, rows) pair with n_skip = s; skip_range: int32 (n, 2) likewise.  Outputs, `want`, `out`,
+    `stream` and the refusals as nearest_k_device; the answers are host_nearest_k_filtered's, bit for bit."""
+    who = "nearest_k_filtered_device"
+    k = int(k)
+    names = ["count", "object"] + [w for w in ("dist", "closest", "normal") if w in want]
+    refusal = None
+    if out is None and not 1 <= k <= NEAREST_K_MAX:  # (with the caller's outputs the library says it)
+        refusal = "k must be 1 .. %d, got %d" % (NEAREST_K_MAX, k)
+
+    def inputs():
+        d_p, d_m, n = _device_points(scene, who, points, max_dist)
+        return (d_p, d_m) + _device_filter(scene, who, skip, n_skip, skip_range, n, "points") + (n,)
+
+    return _device_query(scene, who, accel, inputs, _nearest_k_outputs(max(k, 0)), names, want, ("count", "object", "dist", "closest", "normal"),
+                         stream, out, points, "points", k=k, refusal=refusal)
+
+
+def sweep_sphere_filtered_device(scene, accel, origin, direction, radius, t_max=None, skip=None, skip_range=None, want=("t",), out=None, stream=0,
+                                 n_skip=None):
+    """p3d_sweep_sphere_filtered_device: sweep.sweep_sphere_device for the scene without the objects each ball names (a particle
+    that is a sphere of the scene skips itself).  skip, skip_range, n_skip as nearest_k_filtered_device; everything else, the
+    refusals included, as sweep_sphere_device; the answers are host_sweep_sphere_filtered's, bit for bit."""
+    who = "sweep_sphere_filtered_device"
+    return _sweep(scene, who, accel, origin, direction, radius, t_max, want, out, stream,
+                  more=lambda n: _device_filter(scene, who, skip, n_skip, skip_range, n, "balls"))
+
+
+def _host_filter(who, skip, skip_range, n, rows_of):
+    """(skip array or None, n_skip, skip_range array or None) of a host query of n rows; the arrays are held by the caller"""
+    s, width = None, 0
+    if skip is not None:
+        s = np.ascontiguousarray(skip, np.int32)
+        if s.ndim != 2 or len(s) != n:
+            raise P3DError(-1, "%s: skip %r, needed: (%d, s) for %d %s" % (who, s.shape, n, n, rows_of))
+        width = s.shape[1]
+    r = None
+    if skip_range is not None:
+        r = np.ascontiguousarray(skip_range, np.int32)
+        if r.shape != (n, 2):
+            raise P3DError(-1, "%s: skip_range %r, needed: (%d, 2)" % (who, r.shape, n))
+    return s, width, r
+
+
+def _address(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def host_nearest_k_filtered(host_scene, points, k, max_dist=None, skip=None, skip_range=None):
+    """p3d_host_scene_nearest_k_filtered: HostScene.nearest_k for the scene without the objects each point names, by brute force
+    on the CPU -> (count int32 (n,), object int32 (n, k), dist float32 (n, k), closest float32 (n, k, 3)).  skip: int32 (n, s),
+    s <= FILTER_SKIP_MAX; skip_range: int32 (n, 2); either may be None."""
+    who = "host_nearest_k_filtered"
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n, k = len(p), int(k)
+    m = None
+    if max_dist is not None:
+        m = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
+        if len(m) != n:
+            raise P3DError(-1, "%s: %d points, %d limits" % (who, n, len(m)))
+    s, width, r = _host_filter(who, skip, skip_range, n, "points")
+    rows = max(k, 0)
+    count, obj = np.zeros(n, np.int32), np.zeros((n, rows), np.int32)
+    dist, closest = np.zeros((n, rows), np.float32), np.zeros((n, rows, 3), np.float32)
+    _check(host_scene._L.p3d_host_scene_nearest_k_filtered(host_scene._h, n, k & 0xffffffff, p.ctypes.data, m.ctypes.data if m is not None else None,
+                                                           _address(s), width, _address(r), count.ctypes.data, obj.ctypes.data,
+                                                           dist.ctypes.data, closest.ctypes.data))
+    return count, obj, dist, closest
+
+
+def host_sweep_sphere_filtered(host_scene, origin, direction, radius, t_max=None, skip=None, skip_range=None):
+    """p3d_host_scene_sweep_sphere_filtered: sweep.host_sweep_sphere for the scene without the objects each ball names ->
+    (object int32 (n,), t float32 (n,), centre float32 (n, 3), contact float32 (n, 3))."""
+    who = "host_sweep_sphere_filtered"
+    o, d = np.ascontiguousarray(origin, np.float32), np.ascontiguousarray(direction, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise P3DError(-1, "%s: origins %r and directions %r, needed: (n, 3) both" % (who, o.shape, d.shape))
+    n = len(o)
+    rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)) if np.ndim(radius) == 0 else radius, np.float32).reshape(-1)
+    if len(rad) != n:
+        raise P3DError(-1, "%s: %d origins, %d radii" % (who, n, len(rad)))
+    m = None
+    if t_max is not None:
+        m = np.ascontiguousarray(t_max, np.float32).reshape(-1)
+        if len(m) != n:
+            raise P3DError(-1, "%s: %d origins, %d limits" % (who, n, len(m)))
+    s, width, r = _host_filter(who, skip, skip_range, n, "balls")
+    obj, t = np.zeros(n, np.int32), np.zeros(n, np.float32)
+    centre, contact = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    _check(host_scene._L.p3d_host_scene_sweep_sphere_filtered(host_scene._h, n, o.ctypes.data, d.ctypes.data, rad.ctypes.data,
+                                                              m.ctypes.data if m is not None else None, _address(s), width, _address(r),
+                                                              obj.ctypes.data, t.ctypes.data, centre.ctypes.data, contact.ctypes.data))
+    return obj, t, centre, contact

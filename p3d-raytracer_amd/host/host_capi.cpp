@@ -10,6 +10,7 @@
 #include "accel_build.hpp"
 #include "nearest_rule.hpp"
 #include "occlusion_rule.hpp"
+#include "filter_rule.hpp"
 #include "p3d.h"
 #include "p3d_error.hpp"
 #include "scene_model.hpp"
@@ -340,13 +341,36 @@ int p3d_host_scene_nearest(p3d_host_scene* hs, uint32_t n, const float* points, 
   return P3D_OK;
 }
 
-// The statement of the k-nearest query: nearest_rule.hpp on every object, the k smallest (d2, object index) under the limit
-// in that order.  q is not kept in the list: the rule is run once more on each listed object, which gives the same bits
-int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist, int32_t* count,
-                             int32_t* object, float* dist, float* closest) {
-  if (!hs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest_k: null scene");
-  if (k == 0 || k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest_k: k must be 1 .. P3D_NEAREST_K_MAX (16)");
-  if (n && (!points || !count || !object)) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest_k: null array with n > 0");
+}  // extern "C"
+
+namespace {
+
+// Where a host form's queries get their filters from (filter_rule.hpp): the skip arrays of a *_filtered call, or nothing
+struct HostFilters {
+  const int32_t* skip;
+  uint32_t n_skip;
+  const int32_t* skip_range;
+  p3d::QueryFilter load(uint32_t i, uint32_t n_objs) const { return p3d::filter_load(n_skip ? skip : nullptr, n_skip, skip_range, i, n_objs); }
+};
+struct NoHostFilters {
+  p3d::NoFilter load(uint32_t, uint32_t) const { return p3d::NoFilter{}; }
+};
+// What the filtered host forms refuse of their filter
+int check_host_filter(const HostFilters& f, uint32_t n, const std::string& pre) {
+  if (f.n_skip > P3D_FILTER_SKIP_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "n_skip must be 0 .. P3D_FILTER_SKIP_MAX (8)");
+  if (n && f.n_skip > 0 && !f.skip) return p3d::fail(P3D_ERR_INVALID, pre + "null skip with n > 0 and n_skip > 0");
+  return P3D_OK;
+}
+
+// The statement of the k-nearest query: nearest_rule.hpp on every object the query's filter does not name, the k smallest
+// (d2, object index) under the limit in that order.  q is not kept in the list: the rule is run once more on each listed
+// object, which gives the same bits
+template <class Filters>
+int host_nearest_k(const std::string& pre, p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist,
+                   const Filters& filters, int32_t* count, int32_t* object, float* dist, float* closest) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
+  if (k == 0 || k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
+  if (n && (!points || !count || !object)) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
   using namespace p3d;
   const int n_objs = hs->scene.getNumObjects();
   std::vector<float> v(9 * static_cast<size_t>(n_objs));
@@ -361,8 +385,10 @@ int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const f
     HostNearestList list;
     NearestKGate gate;
     uint32_t found = 0;
+    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
     if (nearest_k_open(max_dist != nullptr, max_dist ? max_dist[i] : 0.0f, gate)) {
       for (int j = 0; j < n_objs; ++j) {
+        if (filter_skips(filter, j)) continue;
         float q[3];
         const float d2 = nearest_point(kind[j], &v[9 * static_cast<size_t>(j)], p, q);
         if (nearest_k_admits(d2, j, gate)) nearest_k_insert(list, found, k, gate, d2, j, static_cast<uint32_t>(j));
@@ -383,11 +409,12 @@ int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const f
   return P3D_OK;
 }
 
-// The statement of the sphere sweep: sweep_rule.hpp on every object, the smallest (T, object index) within the limit wins.
-// contact is not kept during the search: nearest_point is run once more at c(T) on the object found
-int p3d_host_scene_sweep_sphere(const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction, const float* radius,
-                                const float* t_max, int32_t* object, float* t, float* centre, float* contact) {
-  const std::string pre = "p3d_host_scene_sweep_sphere: ";
+// The statement of the sphere sweep: sweep_rule.hpp on every object the query's filter does not name, the smallest (T, object
+// index) within the limit wins.  contact is not kept during the search: nearest_point is run once more at c(T) on the object found
+template <class Filters>
+int host_sweep_sphere(const std::string& pre, const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction,
+                      const float* radius, const float* t_max, const Filters& filters, int32_t* object, float* t, float* centre,
+                      float* contact) {
   if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
   using namespace p3d;
   const int n_objs = hs->scene.getNumObjects();
@@ -407,8 +434,10 @@ int p3d_host_scene_sweep_sphere(const p3d_host_scene* hs, uint32_t n, const floa
     sweep_ray(origin + row, direction + row, radius[i], t_max != nullptr, t_max ? t_max[i] : 0.0f, s);
     float best = s.limit;
     int32_t best_object = kSweepNoObject;
+    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
     if (s.ok) {
       for (int j = 0; j < n_objs; ++j) {
+        if (filter_skips(filter, j)) continue;
         float T;
         if (sweep_contact(kind[j], &v[9 * static_cast<size_t>(j)], s, T) && sweep_wins(T, j, best, best_object)) {
           best = T; best_object = j;
@@ -429,6 +458,35 @@ int p3d_host_scene_sweep_sphere(const p3d_host_scene* hs, uint32_t n, const floa
     }
   }
   return P3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist, int32_t* count,
+                             int32_t* object, float* dist, float* closest) {
+  return host_nearest_k("p3d_host_scene_nearest_k: ", hs, n, k, points, max_dist, NoHostFilters{}, count, object, dist, closest);
+}
+int p3d_host_scene_nearest_k_filtered(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist,
+                                      const int32_t* skip, uint32_t n_skip, const int32_t* skip_range, int32_t* count, int32_t* object,
+                                      float* dist, float* closest) {
+  const std::string pre = "p3d_host_scene_nearest_k_filtered: ";
+  const HostFilters filters{skip, n_skip, skip_range};
+  if (int rc = check_host_filter(filters, n, pre)) return rc;
+  return host_nearest_k(pre, hs, n, k, points, max_dist, filters, count, object, dist, closest);
+}
+int p3d_host_scene_sweep_sphere(const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction, const float* radius,
+                                const float* t_max, int32_t* object, float* t, float* centre, float* contact) {
+  return host_sweep_sphere("p3d_host_scene_sweep_sphere: ", hs, n, origin, direction, radius, t_max, NoHostFilters{}, object, t, centre, contact);
+}
+int p3d_host_scene_sweep_sphere_filtered(const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction,
+                                         const float* radius, const float* t_max, const int32_t* skip, uint32_t n_skip,
+                                         const int32_t* skip_range, int32_t* object, float* t, float* centre, float* contact) {
+  const std::string pre = "p3d_host_scene_sweep_sphere_filtered: ";
+  const HostFilters filters{skip, n_skip, skip_range};
+  if (int rc = check_host_filter(filters, n, pre)) return rc;
+  return host_sweep_sphere(pre, hs, n, origin, direction, radius, t_max, filters, object, t, centre, contact);
 }
 
 // The statement of the rays of p3d_occlusion_device: occlusion_rule.hpp for every (point, sample), row i * samples + j

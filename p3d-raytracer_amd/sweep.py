@@ -46,7 +46,12 @@ def sweep_sphere_device(scene, accel, origin, direction, radius, t_max=None, wan
     ACCEL_NONE and ACCEL_BVH; ACCEL_GRID, a scene that holds a box, and ACCEL_BVH over a scene that holds a plane are refused
     with P3D_ERR_UNSUPPORTED - by this function already where the scene came from a HostScene.  Rays, `out`, `stream` and the
     other refusals as DeviceScene.trace_closest_device."""
-    who = "sweep_sphere_device"
+    return _sweep(scene, "sweep_sphere_device", accel, origin, direction, radius, t_max, want, out, stream)
+
+
+def _sweep(scene, who, accel, origin, direction, radius, t_max, want, out, stream, more=None):
+    """sweep_sphere_device, and what filtered.sweep_sphere_filtered_device shares with it: more(n) -> the inputs that follow
+    t_max in the C order of p3d_<who>"""
     names = ["object"] + [w for w in ("t", "centre", "contact", "normal") if w in want]
     refusal = None
     if int(accel) == ACCEL_GRID:
@@ -74,7 +79,7 @@ def sweep_sphere_device(scene, accel, origin, direction, radius, t_max=None, wan
         d_r, n_r = _device_vector(r, who + ": radius", ("float32",), scene.device)
         if n_r != n:
             raise P3DError(-1, "%s: %d origins, %d radii" % (who, n, n_r))
-        return d_o, d_d, d_r, d_tm, n
+        return (d_o, d_d, d_r, d_tm) + (tuple(more(n)) if more else ()) + (n,)
 
     # `filled` outlives the call: _device_query resolves the inputs first, allocates the outputs next and enqueues the kernel
     # last, so a tensor owned by balls() would be back with torch's allocator - and handed out again as an output of the same
