@@ -1321,4 +1321,10 @@ int p3d_host_scene_skybox_face(p3d_host_scene* hs, int face, const uint8_t** img
  * which this header includes here.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
  */
 #include "p3d_filter.h"
+/*
+ * NEAREST SURFACES TO A SEGMENT - capsule overlap and edge proximity: the k objects nearest to any point of each segment held in
+ * device memory, p3d_nearest_segment_k_device, with the filters of p3d_filter.h, and its statement on the CPU - are declared in
+ * p3d_segment.h, which this header includes here.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ */
+#include "p3d_segment.h"
 #endif /* P3D_H */

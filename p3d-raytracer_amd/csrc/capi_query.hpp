@@ -1,13 +1,14 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
 // p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device,
 // p3d_occlusion_device, p3d_occlusion_rays_device, p3d_sweep_sphere_device, p3d_nearest_k_filtered_device,
-// p3d_sweep_sphere_filtered_device, p3d_object_*, p3d_skybox_color)
+// p3d_sweep_sphere_filtered_device, p3d_nearest_segment_k_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
 #include "capi_update.hpp"  // device_buffer_usable
 #include "hit_list_query.hpp"
 #include "nearest_query.hpp"
+#include "nearest_segment_query.hpp"
 #include "occlusion_query.hpp"
 #include "path_query.hpp"
 #include "radiance_query.hpp"
@@ -535,6 +536,45 @@ int p3d_sweep_sphere_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, c
                                      float* d_normal, void* hip_stream) {
   const FilterArgs fa{d_skip, n_skip, d_skip_range};
   return sweep_device(s, accel, n, d_origin, d_direction, d_radius, d_t_max, d_object, d_t, d_centre, d_contact, d_normal, hip_stream, &fa);
+}
+
+// The k nearest surfaces to n segments, one kernel on the caller's stream (nearest_segment_query.hpp).  The checks are
+// p3d_nearest_k_filtered_device's, and the sweep's refusal of a box
+int p3d_nearest_segment_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_a, const float* d_b, const float* d_max_dist,
+                                 const int32_t* d_skip, uint32_t n_skip, const int32_t* d_skip_range, int32_t* d_count, int32_t* d_object,
+                                 float* d_dist, float* d_param, float* d_on_segment, float* d_closest, float* d_normal, void* hip_stream) {
+  const std::string pre = "p3d_nearest_segment_k_device: ";
+  const FilterArgs fa{d_skip, n_skip, d_skip_range};
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no nearest-surface query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (s->first_box >= 0)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(s->first_box) + " is a box: a segment against a box's faces is not part of this query");
+  if (accel == P3D_ACCEL_BVH && s->has_planes)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
+  if (k == 0 || k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
+  if (int rc = check_filter(fa, pre)) return rc;
+  if (n == 0) return P3D_OK;
+  if (!d_a || !d_b || !d_count || !d_object) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (int rc = check_filter_buffers(fa, pre)) return rc;
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
+  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
+  const QueryBuffer bufs[] = {
+      {d_a, vec, "d_a"}, {d_b, vec, "d_b"}, {d_max_dist, one, "d_max_dist"}, {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"},
+      {d_count, one, "d_count"}, {d_object, one * k, "d_object"}, {d_dist, one * k, "d_dist"}, {d_param, one * k, "d_param"},
+      {d_on_segment, vec * k, "d_on_segment"}, {d_closest, vec * k, "d_closest"}, {d_normal, vec * k, "d_normal"}};
+  // (the lists of this call's k behind the stack window)
+  return enqueue_query(s, accel, n, pre, "segments", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    NearestSegmentParams P{};
+    P.sc = s->dev; P.n = n; P.k = k; P.a = d_a; P.b = d_b; P.max_dist = d_max_dist;
+    P.count = d_count; P.object = d_object; P.dist = d_dist; P.param = d_param; P.on_segment = d_on_segment; P.closest = d_closest;
+    P.normal = d_normal; P.stack = q.stack;
+    with_flags([&](auto BVH) {
+      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
+      if (fa.absent()) hipLaunchKernelGGL((nearest_segment_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+      else hipLaunchKernelGGL((nearest_segment_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, NearestSegmentFilteredParams{P, F});
+    }, accel == P3D_ACCEL_BVH);
+  });
 }
 
 enum class ObjectQuery { Intercepts = 0, Normal = 1, SkyboxColour = 2 };  // the values are object_query_kernel's WHAT

@@ -9,6 +9,7 @@
 
 #include "accel_build.hpp"
 #include "nearest_rule.hpp"
+#include "nearest_segment_rule.hpp"
 #include "occlusion_rule.hpp"
 #include "filter_rule.hpp"
 #include "p3d.h"
@@ -460,9 +461,81 @@ int host_sweep_sphere(const std::string& pre, const p3d_host_scene* hs, uint32_t
   return P3D_OK;
 }
 
+// The statement of the nearest-surfaces-to-a-segment query: nearest_segment_rule.hpp on every object the segment's filter does
+// not name, in object order; the k smallest (d2, object index) under the limit in that order.  s, x and q are not kept in the
+// list: the rule is run once more on each listed object, which gives the same bits
+template <class Filters>
+int host_nearest_segment_k(const std::string& pre, p3d_host_scene* hs, uint32_t n, uint32_t k, const float* a, const float* b,
+                           const float* max_dist, const Filters& filters, int32_t* count, int32_t* object, float* dist, float* param,
+                           float* on_segment, float* closest) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
+  using namespace p3d;
+  const int n_objs = hs->scene.getNumObjects();
+  std::vector<float> v(9 * static_cast<size_t>(n_objs));
+  std::vector<uint32_t> kind(n_objs);
+  for (int j = 0; j < n_objs; ++j) {
+    float normal[3];
+    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
+    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
+    if (kind[j] == P3D_PRIM_BOX)
+      return p3d::fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(j) + " is a box: a segment against a box's faces is not part of this query");
+  }
+  if (k == 0 || k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
+  if (n && (!a || !b || !count || !object)) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* pa = a + 3 * static_cast<size_t>(i);
+    const float* pb = b + 3 * static_cast<size_t>(i);
+    HostNearestList list;
+    NearestKGate gate;
+    uint32_t found = 0;
+    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
+    if (nearest_k_open(max_dist != nullptr, max_dist ? max_dist[i] : 0.0f, gate)) {
+      for (int j = 0; j < n_objs; ++j) {
+        if (filter_skips(filter, j)) continue;
+        float s, x[3], q[3];
+        const float d2 = segment_nearest(kind[j], &v[9 * static_cast<size_t>(j)], pa, pb, s, x, q);
+        if (nearest_k_admits(d2, j, gate)) nearest_k_insert(list, found, k, gate, d2, j, static_cast<uint32_t>(j));
+      }
+    }
+    count[i] = static_cast<int32_t>(found);
+    for (uint32_t e = 0; e < k; ++e) {
+      const size_t row = static_cast<size_t>(i) * k + e;
+      float s = FLT_MAX, x[3] = {0.0f, 0.0f, 0.0f}, q[3] = {0.0f, 0.0f, 0.0f};
+      const int32_t j = e < found ? list.object(e) : -1;
+      if (j >= 0) segment_nearest(kind[j], &v[9 * static_cast<size_t>(j)], pa, pb, s, x, q);
+      object[row] = j;
+      if (dist) dist[row] = j >= 0 ? sqrtf(list.d2(e)) : FLT_MAX;
+      if (param) param[row] = s;
+      for (int c = 0; c < 3; ++c) {
+        if (on_segment) on_segment[3 * row + c] = x[c];
+        if (closest) closest[3 * row + c] = q[c];
+      }
+    }
+  }
+  return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int p3d_host_scene_nearest_segment_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* a, const float* b, const float* max_dist,
+                                     const int32_t* skip, uint32_t n_skip, const int32_t* skip_range, int32_t* count, int32_t* object,
+                                     float* dist, float* param, float* on_segment, float* closest) {
+  const std::string pre = "p3d_host_scene_nearest_segment_k: ";
+  const HostFilters filters{skip, n_skip, skip_range};
+  if (int rc = check_host_filter(filters, n, pre)) return rc;
+  if (n_skip == 0 && !skip_range)
+    return host_nearest_segment_k(pre, hs, n, k, a, b, max_dist, NoHostFilters{}, count, object, dist, param, on_segment, closest);
+  return host_nearest_segment_k(pre, hs, n, k, a, b, max_dist, filters, count, object, dist, param, on_segment, closest);
+}
+
+// The key of a BVH node under the segment query, for the tests (host only)
+int p3d_debug_segment_box_d2(uint32_t n, const float* a, const float* b, const float* lo, const float* hi, float* out) {
+  if (n && (!a || !b || !lo || !hi || !out)) return p3d::fail(P3D_ERR_INVALID, "p3d_debug_segment_box_d2: null array with n > 0");
+  for (size_t i = 0; i < n; ++i) out[i] = p3d::segment_box_d2(a + 3 * i, b + 3 * i, lo + 3 * i, hi + 3 * i);
+  return P3D_OK;
+}
 
 int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist, int32_t* count,
                              int32_t* object, float* dist, float* closest) {
