@@ -1327,4 +1327,10 @@ int p3d_host_scene_skybox_face(p3d_host_scene* hs, int face, const uint8_t** img
  * p3d_segment.h, which this header includes here.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
  */
 #include "p3d_segment.h"
+/*
+ * WHAT IS IN THIS REGION - overlap queries: the objects that touch each axis-aligned box held in device memory, their number
+ * and the lowest k of them, p3d_overlap_box_device, with the filters of p3d_filter.h, and its statement on the CPU - are
+ * declared in p3d_overlap.h, which this header includes here.  Detected by the symbols (P3D_ABI_VERSION is unchanged).
+ */
+#include "p3d_overlap.h"
 #endif /* P3D_H */

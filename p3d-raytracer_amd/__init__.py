@@ -31,6 +31,7 @@ from .sweep import host_sweep_sphere, sweep_sphere_device
 from .filtered import (FILTER_SKIP_MAX, host_nearest_k_filtered, host_sweep_sphere_filtered, nearest_k_filtered_device,
                        sweep_sphere_filtered_device)
 from .segment_queries import _nearest_segment_k_outputs, host_nearest_segment_k, nearest_segment_k_device, segment_box_d2
+from .overlap import OVERLAP_SOLID, _overlap_outputs, host_overlap_box, overlap_box_device
 from .device_scene import SKYBOX_FACE_FILES, DeviceScene, load_skybox_dir
 from .geometry import _xform_arrays, deformed, deformed_spheres, transformed, tree_cost
 from .host_scene import HostScene

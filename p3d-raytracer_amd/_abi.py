@@ -276,6 +276,8 @@ PROTOTYPES = {
     "p3d_host_scene_sweep_sphere_filtered": (DEFAULT, [VP, U32, VP, VP, VP, VP, VP, U32, VP] + [VP] * 4),
     "p3d_nearest_segment_k_device": (DEFAULT, [VP, U32, U32, U32, VP, VP, VP, VP, U32, VP] + [VP] * 8),
     "p3d_host_scene_nearest_segment_k": (DEFAULT, [VP, U32, U32, VP, VP, VP, VP, U32, VP] + [VP] * 6),
+    "p3d_overlap_box_device": (DEFAULT, [VP, U32, U32, U32, VP, VP, VP, U32, VP, U32, VP, VP, VP]),
+    "p3d_host_scene_overlap_box": (DEFAULT, [VP, U32, U32, VP, VP, VP, U32, VP, U32, VP, VP]),
     "p3d_debug_segment_box_d2": (DEFAULT, [U32] + [VP] * 5),
     "p3d_debug_scene_limits": (DEFAULT, [VP, VP]),
     "p3d_debug_frame_plan": (DEFAULT, [VP, PTR(Config), PTR(Tile), U32, U32, U32, PTR(DebugPlan)]),
@@ -284,7 +286,7 @@ PROTOTYPES = {
 }
 # EXPORTS: what include/p3d.h itself declares, the entry points of the recorded surface (tests/python_api_surface.json holds the
 # list to what it was).  EXPORTS_ADDED: those declared since, in include/p3d_radiance.h, p3d_occlusion.h and p3d_shading.h, which
-# p3d.h includes, and in p3d_sweep.h, p3d_filter.h and p3d_segment.h likewise; detected by their symbols
+# p3d.h includes, and in p3d_sweep.h, p3d_filter.h, p3d_segment.h and p3d_overlap.h likewise; detected by their symbols
 EXPORTS_ADDED = ["p3d_trace_radiance_device", "p3d_camera_rays_device", "p3d_trace_path_device", "p3d_camera_sample_rays_device",
                  "p3d_occlusion_device", "p3d_occlusion_rays_device", "p3d_occlusion_rays",
                  "p3d_scene_set_materials", "p3d_scene_set_lights", "p3d_scene_materials", "p3d_scene_lights",
@@ -292,7 +294,8 @@ EXPORTS_ADDED = ["p3d_trace_radiance_device", "p3d_camera_rays_device", "p3d_tra
                  "p3d_sweep_sphere_device", "p3d_host_scene_sweep_sphere",
                  "p3d_nearest_k_filtered_device", "p3d_sweep_sphere_filtered_device", "p3d_host_scene_nearest_k_filtered",
                  "p3d_host_scene_sweep_sphere_filtered",
-                 "p3d_nearest_segment_k_device", "p3d_host_scene_nearest_segment_k"]
+                 "p3d_nearest_segment_k_device", "p3d_host_scene_nearest_segment_k",
+                 "p3d_overlap_box_device", "p3d_host_scene_overlap_box"]
 EXPORTS = [name for name in PROTOTYPES if not name.startswith("p3d_debug_") and name not in EXPORTS_ADDED]
 
 

@@ -1,7 +1,7 @@
 // capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
 // p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device,
 // p3d_occlusion_device, p3d_occlusion_rays_device, p3d_sweep_sphere_device, p3d_nearest_k_filtered_device,
-// p3d_sweep_sphere_filtered_device, p3d_nearest_segment_k_device, p3d_object_*, p3d_skybox_color)
+// p3d_sweep_sphere_filtered_device, p3d_nearest_segment_k_device, p3d_overlap_box_device, p3d_object_*, p3d_skybox_color)
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
@@ -10,6 +10,7 @@
 #include "nearest_query.hpp"
 #include "nearest_segment_query.hpp"
 #include "occlusion_query.hpp"
+#include "overlap_query.hpp"
 #include "path_query.hpp"
 #include "radiance_query.hpp"
 #include "ray_query.hpp"
@@ -573,6 +574,41 @@ int p3d_nearest_segment_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint3
       constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
       if (fa.absent()) hipLaunchKernelGGL((nearest_segment_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
       else hipLaunchKernelGGL((nearest_segment_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, NearestSegmentFilteredParams{P, F});
+    }, accel == P3D_ACCEL_BVH);
+  });
+}
+
+// The objects that touch n boxes, one kernel on the caller's stream (overlap_query.hpp).  The checks are
+// p3d_nearest_segment_k_device's, with p3d_trace_hits_device's k == 0: the count alone, no list behind the stack window
+int p3d_overlap_box_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_lo, const float* d_hi, const int32_t* d_skip,
+                           uint32_t n_skip, const int32_t* d_skip_range, uint32_t flags, int32_t* d_total, int32_t* d_object, void* hip_stream) {
+  const std::string pre = "p3d_overlap_box_device: ";
+  const FilterArgs fa{d_skip, n_skip, d_skip_range};
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no overlap query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (accel == P3D_ACCEL_BVH && s->has_planes)
+    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
+  if (k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_NEAREST_K_MAX (16)");
+  if (flags & ~P3D_OVERLAP_SOLID) return fail(P3D_ERR_INVALID, pre + "unknown flag (P3D_OVERLAP_SOLID is the only one)");
+  if (int rc = check_filter(fa, pre)) return rc;
+  if (n == 0) return P3D_OK;
+  if (k == 0) d_object = nullptr;
+  if (!d_lo || !d_hi || !d_total) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (k > 0 && !d_object) return fail(P3D_ERR_INVALID, pre + "null argument (d_object is needed with k >= 1)");
+  if (int rc = check_filter_buffers(fa, pre)) return rc;
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 4 < 2^40)
+  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
+  const QueryBuffer bufs[] = {{d_lo, vec, "d_lo"}, {d_hi, vec, "d_hi"}, {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"},
+                              {d_total, one, "d_total"}, {d_object, one * k, "d_object"}};
+  // (the lists of this call's k behind the stack window; none for k = 0)
+  return enqueue_query(s, accel, n, pre, "boxes", bufs, overlap_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    OverlapParams P{};
+    P.sc = s->dev; P.n = n; P.k = k; P.flags = flags; P.lo = d_lo; P.hi = d_hi; P.total = d_total; P.object = d_object; P.stack = q.stack;
+    with_flags([&](auto BVH) {
+      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
+      if (fa.absent()) hipLaunchKernelGGL((overlap_box_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
+      else hipLaunchKernelGGL((overlap_box_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, OverlapFilteredParams{P, F});
     }, accel == P3D_ACCEL_BVH);
   });
 }

@@ -19,5 +19,6 @@
 #include "hit_list_query.hpp"     // trace_hits_kernel, bvh_segment_hits (the hits in order along a ray)
 #include "radiance_query.hpp"     // radiance_query_kernel (the Whitted chain for rays in device memory), camera_rays_kernel
 #include "path_query.hpp"         // path_query_kernel (the path tracer for rays in device memory), camera_sample_rays_kernel
+#include "overlap_query.hpp"      // overlap_box_device_kernel, bvh_overlap_box (the objects that touch a box)
 #include "capi_query.hpp"         // p3d_trace_*, p3d_object_*, p3d_skybox_color
 #include "capi_debug.hpp"         // test hooks, instrumented builds

@@ -11,6 +11,7 @@
 #include "nearest_rule.hpp"
 #include "nearest_segment_rule.hpp"
 #include "occlusion_rule.hpp"
+#include "overlap_rule.hpp"
 #include "filter_rule.hpp"
 #include "p3d.h"
 #include "p3d_error.hpp"
@@ -515,9 +516,56 @@ int host_nearest_segment_k(const std::string& pre, p3d_host_scene* hs, uint32_t 
   return P3D_OK;
 }
 
+// The statement of the overlap query: overlap_rule.hpp on every object the box's filter does not name, in object order; all
+// of them counted, the first k listed (object order is index order: the k lowest, ascending)
+template <class Filters>
+int host_overlap_box(const std::string& pre, p3d_host_scene* hs, uint32_t n, uint32_t k, const float* lo, const float* hi,
+                     const Filters& filters, uint32_t flags, int32_t* total, int32_t* object) {
+  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
+  if (k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_NEAREST_K_MAX (16)");
+  if (flags & ~P3D_OVERLAP_SOLID) return p3d::fail(P3D_ERR_INVALID, pre + "unknown flag (P3D_OVERLAP_SOLID is the only one)");
+  if (n && (!lo || !hi || !total || (k > 0 && !object))) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
+  using namespace p3d;
+  const int n_objs = hs->scene.getNumObjects();
+  std::vector<float> v(9 * static_cast<size_t>(n_objs));
+  std::vector<uint32_t> kind(n_objs);
+  for (int j = 0; j < n_objs; ++j) {
+    float normal[3];
+    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
+    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* qlo = lo + 3 * static_cast<size_t>(i);
+    const float* qhi = hi + 3 * static_cast<size_t>(i);
+    int32_t* row = k ? object + static_cast<size_t>(i) * k : nullptr;
+    uint32_t found = 0;
+    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
+    if (overlap_query_open(qlo, qhi)) {
+      for (int j = 0; j < n_objs; ++j) {
+        if (filter_skips(filter, j)) continue;
+        if (!overlap_box(kind[j], &v[9 * static_cast<size_t>(j)], qlo, qhi, flags)) continue;
+        if (found < k) row[found] = j;
+        ++found;
+      }
+    }
+    total[i] = static_cast<int32_t>(found);
+    for (uint32_t e = found; e < k; ++e) row[e] = -1;
+  }
+  return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int p3d_host_scene_overlap_box(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* lo, const float* hi, const int32_t* skip,
+                               uint32_t n_skip, const int32_t* skip_range, uint32_t flags, int32_t* total, int32_t* object) {
+  const std::string pre = "p3d_host_scene_overlap_box: ";
+  const HostFilters filters{skip, n_skip, skip_range};
+  if (int rc = check_host_filter(filters, n, pre)) return rc;
+  if (n_skip == 0 && !skip_range) return host_overlap_box(pre, hs, n, k, lo, hi, NoHostFilters{}, flags, total, object);
+  return host_overlap_box(pre, hs, n, k, lo, hi, filters, flags, total, object);
+}
 
 int p3d_host_scene_nearest_segment_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* a, const float* b, const float* max_dist,
                                      const int32_t* skip, uint32_t n_skip, const int32_t* skip_range, int32_t* count, int32_t* object,
