@@ -1,20 +1,18 @@
-// capi_query.hpp — batched single-ray, nearest-surface and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_nearest_device,
-// p3d_nearest_k_device, p3d_trace_radiance_device, p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device,
-// p3d_occlusion_device, p3d_occlusion_rays_device, p3d_sweep_sphere_device, p3d_nearest_k_filtered_device,
-// p3d_sweep_sphere_filtered_device, p3d_nearest_segment_k_device, p3d_overlap_box_device, p3d_object_*, p3d_skybox_color)
+// capi_query.hpp — batched ray and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_trace_radiance_device,
+// p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device, p3d_occlusion_device, p3d_occlusion_rays_device,
+// p3d_object_*, p3d_skybox_color), and what every query over device buffers goes through: open_object_query, check_query_buffers,
+// bind_query_stack, enqueue_query.  The proximity queries (nearest, sweep, segment, overlap) are capi_proximity.hpp's
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
 #include "capi_update.hpp"  // device_buffer_usable
 #include "hit_list_query.hpp"
-#include "nearest_query.hpp"
-#include "nearest_segment_query.hpp"
+#include "nearest_query.hpp"  // nearest_k_lds_bytes
 #include "occlusion_query.hpp"
-#include "overlap_query.hpp"
 #include "path_query.hpp"
+#include "query_refusals.hpp"
 #include "radiance_query.hpp"
 #include "ray_query.hpp"
-#include "sweep_query.hpp"
 
 namespace {
 
@@ -93,6 +91,19 @@ int enqueue_query(p3d_scene* s, uint32_t accel, uint32_t n, const std::string& p
   return P3D_OK;
 }
 
+// The opening refusals of a per-object query over device buffers, in the one order all of them have: a null scene, the grid
+// ("no <noun> through the grid"), check_accel, a box in the scene (no_box: the query's sentence of query_refusals.hpp; null:
+// boxes are taken) and, asked for, a plane under P3D_ACCEL_BVH.  Each entry point's own checks follow
+int open_object_query(const p3d_scene* s, uint32_t accel, const std::string& pre, const char* noun, const char* no_box = nullptr,
+                      bool no_plane_under_tree = false) {
+  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
+  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no " + noun + " through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
+  if (int rc = check_accel(s, accel)) return rc;
+  if (no_box && s->first_box >= 0) return fail(P3D_ERR_UNSUPPORTED, pre + refuse_box((int)s->first_box, no_box));
+  if (no_plane_under_tree && accel == P3D_ACCEL_BVH && s->has_planes) return fail(P3D_ERR_UNSUPPORTED, pre + kRefusePlaneUnderTree);
+  return P3D_OK;
+}
+
 // p3d_trace_closest_device / p3d_trace_any_device
 int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
                  int32_t* d_hit_id, float* d_t, float* d_hit_point, float* d_normal, uint8_t* d_occluded, void* hip_stream, bool any) {
@@ -113,61 +124,6 @@ int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin
     P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
     P.hit_id = d_hit_id; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.occluded = d_occluded; P.stack = q.stack;
     launch_ray_query<true>(accel, any, q, st, P);
-  });
-}
-
-// The skip buffers of a *_filtered_device call (include/p3d_filter.h).  The unfiltered entry points pass none: a null
-// FilterArgs*, the same checks and launches as before
-struct FilterArgs {
-  const int32_t* d_skip;  // n x n_skip, or null
-  uint32_t n_skip;
-  const int32_t* d_skip_range;  // n x 2, or null
-  bool absent() const { return n_skip == 0 && !d_skip_range; }  // the call is the unfiltered call: its kernel is launched
-};
-// What a filtered call refuses of its filter whatever n is, and with n > 0
-int check_filter(const FilterArgs& fa, const std::string& pre) {
-  if (fa.n_skip > P3D_FILTER_SKIP_MAX) return fail(P3D_ERR_INVALID, pre + "n_skip must be 0 .. P3D_FILTER_SKIP_MAX (8)");
-  return P3D_OK;
-}
-int check_filter_buffers(const FilterArgs& fa, const std::string& pre) {
-  if (fa.n_skip > 0 && !fa.d_skip) return fail(P3D_ERR_INVALID, pre + "null argument (d_skip is needed with n_skip > 0)");
-  return P3D_OK;
-}
-FilterParams filter_params(const FilterArgs& fa) { return FilterParams{fa.n_skip ? fa.d_skip : nullptr, fa.d_skip_range, fa.n_skip}; }
-
-// p3d_nearest_device (k_form false: k = 1, no d_count), p3d_nearest_k_device and, with `filter`, p3d_nearest_k_filtered_device.
-// One set of checks for all; the outputs hold k rows per point
-int nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, bool k_form, const float* d_point, const float* d_max_dist,
-                   int32_t* d_count, int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream,
-                   const FilterArgs* filter = nullptr) {
-  const std::string pre = filter ? "p3d_nearest_k_filtered_device: " : k_form ? "p3d_nearest_k_device: " : "p3d_nearest_device: ";
-  const FilterArgs fa = filter ? *filter : FilterArgs{nullptr, 0, nullptr};
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no nearest-surface query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
-  if (int rc = check_accel(s, accel)) return rc;
-  if (accel == P3D_ACCEL_BVH && s->has_planes)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
-  if (k == 0 || k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
-  if (int rc = check_filter(fa, pre)) return rc;
-  if (n == 0) return P3D_OK;
-  if (!d_point || !d_object || (k_form && !d_count)) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (int rc = check_filter_buffers(fa, pre)) return rc;
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
-  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
-  const QueryBuffer bufs[] = {
-      {d_point, vec, "d_point"}, {d_max_dist, one, "d_max_dist"}, {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"},
-      {d_count, one, "d_count"}, {d_object, one * k, "d_object"},
-      {d_dist, one * k, "d_dist"}, {d_closest, vec * k, "d_closest"}, {d_normal, vec * k, "d_normal"}};
-  // (the lists of this call's k behind the stack window)
-  return enqueue_query(s, accel, n, pre, "points", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
-    NearestKParams P{};
-    P.sc = s->dev; P.n = n; P.k = k; P.point = d_point; P.max_dist = d_max_dist;
-    P.count = d_count; P.object = d_object; P.dist = d_dist; P.closest = d_closest; P.normal = d_normal; P.stack = q.stack;
-    with_flags([&](auto BVH) {
-      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
-      if (fa.absent()) hipLaunchKernelGGL((nearest_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-      else hipLaunchKernelGGL((nearest_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, NearestKFilteredParams{P, F});
-    }, accel == P3D_ACCEL_BVH);
   });
 }
 
@@ -337,10 +293,7 @@ int p3d_camera_sample_rays_device(p3d_scene* s, const p3d_camera* camera, const 
 int p3d_occlusion_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_normal, const float* d_max_dist,
                          const p3d_occlusion_params* params, uint32_t* d_unoccluded, float* d_bent, void* hip_stream) {
   const std::string pre = "p3d_occlusion_device: ";
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (accel == P3D_ACCEL_GRID)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "no segment query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
-  if (int rc = check_accel(s, accel)) return rc;
+  if (int rc = open_object_query(s, accel, pre, "segment query")) return rc;
   if (const char* why = occlusion_params_refusal(params)) return fail(P3D_ERR_INVALID, pre + why);
   if (n == 0) return P3D_OK;
   if (!d_point || !d_normal || !d_unoccluded) return fail(P3D_ERR_INVALID, pre + "null argument");
@@ -450,9 +403,7 @@ int p3d_trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, 
                           const float* d_t_max, int32_t* d_count, int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point,
                           float* d_normal, void* hip_stream) {
   const std::string pre = "p3d_trace_hits_device: ";
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no hit list through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
-  if (int rc = check_accel(s, accel)) return rc;
+  if (int rc = open_object_query(s, accel, pre, "hit list")) return rc;
   if (k > P3D_TRACE_HITS_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_TRACE_HITS_K_MAX (16)");
   if (n == 0) return P3D_OK;
   if (k == 0) d_count = d_object = nullptr, d_t = d_hit_point = d_normal = nullptr;
@@ -471,144 +422,6 @@ int p3d_trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, 
     P.count = d_count; P.total = d_total; P.object = d_object; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.stack = q.stack;
     with_flags([&](auto BVH) {
       hipLaunchKernelGGL((trace_hits_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-    }, accel == P3D_ACCEL_BVH);
-  });
-}
-
-int p3d_nearest_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_max_dist, int32_t* d_object,
-                       float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
-  return nearest_device(s, accel, n, 1, false, d_point, d_max_dist, nullptr, d_object, d_dist, d_closest, d_normal, hip_stream);
-}
-int p3d_nearest_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_point, const float* d_max_dist, int32_t* d_count,
-                         int32_t* d_object, float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
-  return nearest_device(s, accel, n, k, true, d_point, d_max_dist, d_count, d_object, d_dist, d_closest, d_normal, hip_stream);
-}
-
-int p3d_nearest_k_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_point, const float* d_max_dist,
-                                  const int32_t* d_skip, uint32_t n_skip, const int32_t* d_skip_range, int32_t* d_count, int32_t* d_object,
-                                  float* d_dist, float* d_closest, float* d_normal, void* hip_stream) {
-  const FilterArgs fa{d_skip, n_skip, d_skip_range};
-  return nearest_device(s, accel, n, k, true, d_point, d_max_dist, d_count, d_object, d_dist, d_closest, d_normal, hip_stream, &fa);
-}
-
-// The first contact of n moving balls, one kernel on the caller's stream (sweep_query.hpp); with `filter`,
-// p3d_sweep_sphere_filtered_device
-static int sweep_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_radius,
-                        const float* d_t_max, int32_t* d_object, float* d_t, float* d_centre, float* d_contact, float* d_normal,
-                        void* hip_stream, const FilterArgs* filter) {
-  const std::string pre = filter ? "p3d_sweep_sphere_filtered_device: " : "p3d_sweep_sphere_device: ";
-  const FilterArgs fa = filter ? *filter : FilterArgs{nullptr, 0, nullptr};
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no sphere sweep through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
-  if (int rc = check_accel(s, accel)) return rc;
-  if (s->first_box >= 0)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(s->first_box) + " is a box: a ball against a box (a rounded box, and its inside) is not swept");
-  if (accel == P3D_ACCEL_BVH && s->has_planes)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
-  if (int rc = check_filter(fa, pre)) return rc;
-  if (n == 0) return P3D_OK;
-  if (!d_origin || !d_direction || !d_radius || !d_object) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (int rc = check_filter_buffers(fa, pre)) return rc;
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
-  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
-  const QueryBuffer bufs[] = {
-      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_radius, one, "d_radius"}, {d_t_max, one, "d_t_max"},
-      {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"}, {d_object, one, "d_object"}, {d_t, one, "d_t"}, {d_centre, vec, "d_centre"}, {d_contact, vec, "d_contact"}, {d_normal, vec, "d_normal"}};
-  // (the best contact stays in registers: nothing behind the stack window)
-  return enqueue_query(s, accel, n, pre, "balls", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
-    SweepParams P{};
-    P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.radius = d_radius; P.t_max = d_t_max;
-    P.object = d_object; P.t = d_t; P.centre = d_centre; P.contact = d_contact; P.normal = d_normal; P.stack = q.stack;
-    with_flags([&](auto BVH) {
-      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
-      if (fa.absent()) hipLaunchKernelGGL((sweep_sphere_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-      else hipLaunchKernelGGL((sweep_sphere_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, SweepFilteredParams{P, F});
-    }, accel == P3D_ACCEL_BVH);
-  });
-}
-int p3d_sweep_sphere_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_radius,
-                            const float* d_t_max, int32_t* d_object, float* d_t, float* d_centre, float* d_contact, float* d_normal,
-                            void* hip_stream) {
-  return sweep_device(s, accel, n, d_origin, d_direction, d_radius, d_t_max, d_object, d_t, d_centre, d_contact, d_normal, hip_stream, nullptr);
-}
-int p3d_sweep_sphere_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction,
-                                     const float* d_radius, const float* d_t_max, const int32_t* d_skip, uint32_t n_skip,
-                                     const int32_t* d_skip_range, int32_t* d_object, float* d_t, float* d_centre, float* d_contact,
-                                     float* d_normal, void* hip_stream) {
-  const FilterArgs fa{d_skip, n_skip, d_skip_range};
-  return sweep_device(s, accel, n, d_origin, d_direction, d_radius, d_t_max, d_object, d_t, d_centre, d_contact, d_normal, hip_stream, &fa);
-}
-
-// The k nearest surfaces to n segments, one kernel on the caller's stream (nearest_segment_query.hpp).  The checks are
-// p3d_nearest_k_filtered_device's, and the sweep's refusal of a box
-int p3d_nearest_segment_k_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_a, const float* d_b, const float* d_max_dist,
-                                 const int32_t* d_skip, uint32_t n_skip, const int32_t* d_skip_range, int32_t* d_count, int32_t* d_object,
-                                 float* d_dist, float* d_param, float* d_on_segment, float* d_closest, float* d_normal, void* hip_stream) {
-  const std::string pre = "p3d_nearest_segment_k_device: ";
-  const FilterArgs fa{d_skip, n_skip, d_skip_range};
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no nearest-surface query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
-  if (int rc = check_accel(s, accel)) return rc;
-  if (s->first_box >= 0)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(s->first_box) + " is a box: a segment against a box's faces is not part of this query");
-  if (accel == P3D_ACCEL_BVH && s->has_planes)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
-  if (k == 0 || k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
-  if (int rc = check_filter(fa, pre)) return rc;
-  if (n == 0) return P3D_OK;
-  if (!d_a || !d_b || !d_count || !d_object) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (int rc = check_filter_buffers(fa, pre)) return rc;
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
-  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
-  const QueryBuffer bufs[] = {
-      {d_a, vec, "d_a"}, {d_b, vec, "d_b"}, {d_max_dist, one, "d_max_dist"}, {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"},
-      {d_count, one, "d_count"}, {d_object, one * k, "d_object"}, {d_dist, one * k, "d_dist"}, {d_param, one * k, "d_param"},
-      {d_on_segment, vec * k, "d_on_segment"}, {d_closest, vec * k, "d_closest"}, {d_normal, vec * k, "d_normal"}};
-  // (the lists of this call's k behind the stack window)
-  return enqueue_query(s, accel, n, pre, "segments", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
-    NearestSegmentParams P{};
-    P.sc = s->dev; P.n = n; P.k = k; P.a = d_a; P.b = d_b; P.max_dist = d_max_dist;
-    P.count = d_count; P.object = d_object; P.dist = d_dist; P.param = d_param; P.on_segment = d_on_segment; P.closest = d_closest;
-    P.normal = d_normal; P.stack = q.stack;
-    with_flags([&](auto BVH) {
-      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
-      if (fa.absent()) hipLaunchKernelGGL((nearest_segment_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-      else hipLaunchKernelGGL((nearest_segment_k_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, NearestSegmentFilteredParams{P, F});
-    }, accel == P3D_ACCEL_BVH);
-  });
-}
-
-// The objects that touch n boxes, one kernel on the caller's stream (overlap_query.hpp).  The checks are
-// p3d_nearest_segment_k_device's, with p3d_trace_hits_device's k == 0: the count alone, no list behind the stack window
-int p3d_overlap_box_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_lo, const float* d_hi, const int32_t* d_skip,
-                           uint32_t n_skip, const int32_t* d_skip_range, uint32_t flags, int32_t* d_total, int32_t* d_object, void* hip_stream) {
-  const std::string pre = "p3d_overlap_box_device: ";
-  const FilterArgs fa{d_skip, n_skip, d_skip_range};
-  if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
-  if (accel == P3D_ACCEL_GRID) return fail(P3D_ERR_UNSUPPORTED, pre + "no overlap query through the grid (use P3D_ACCEL_BVH or P3D_ACCEL_NONE)");
-  if (int rc = check_accel(s, accel)) return rc;
-  if (accel == P3D_ACCEL_BVH && s->has_planes)
-    return fail(P3D_ERR_UNSUPPORTED, pre + "the scene holds a plane, whose box in the BVH is the [-1,1]^3 default: the tree cannot find it (use P3D_ACCEL_NONE)");
-  if (k > P3D_NEAREST_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_NEAREST_K_MAX (16)");
-  if (flags & ~P3D_OVERLAP_SOLID) return fail(P3D_ERR_INVALID, pre + "unknown flag (P3D_OVERLAP_SOLID is the only one)");
-  if (int rc = check_filter(fa, pre)) return rc;
-  if (n == 0) return P3D_OK;
-  if (k == 0) d_object = nullptr;
-  if (!d_lo || !d_hi || !d_total) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (k > 0 && !d_object) return fail(P3D_ERR_INVALID, pre + "null argument (d_object is needed with k >= 1)");
-  if (int rc = check_filter_buffers(fa, pre)) return rc;
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 4 < 2^40)
-  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
-  const QueryBuffer bufs[] = {{d_lo, vec, "d_lo"}, {d_hi, vec, "d_hi"}, {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"},
-                              {d_total, one, "d_total"}, {d_object, one * k, "d_object"}};
-  // (the lists of this call's k behind the stack window; none for k = 0)
-  return enqueue_query(s, accel, n, pre, "boxes", bufs, overlap_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
-    OverlapParams P{};
-    P.sc = s->dev; P.n = n; P.k = k; P.flags = flags; P.lo = d_lo; P.hi = d_hi; P.total = d_total; P.object = d_object; P.stack = q.stack;
-    with_flags([&](auto BVH) {
-      constexpr int ACCEL = BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE;
-      if (fa.absent()) hipLaunchKernelGGL((overlap_box_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-      else hipLaunchKernelGGL((overlap_box_device_kernel<ACCEL>), dim3(q.blocks), dim3(kBlock), q.lds, st, OverlapFilteredParams{P, F});
     }, accel == P3D_ACCEL_BVH);
   });
 }

@@ -21,4 +21,5 @@
 #include "path_query.hpp"         // path_query_kernel (the path tracer for rays in device memory), camera_sample_rays_kernel
 #include "overlap_query.hpp"      // overlap_box_device_kernel, bvh_overlap_box (the objects that touch a box)
 #include "capi_query.hpp"         // p3d_trace_*, p3d_object_*, p3d_skybox_color
+#include "capi_proximity.hpp"     // p3d_nearest_*, p3d_sweep_sphere_*, p3d_nearest_segment_k_device, p3d_overlap_box_device
 #include "capi_debug.hpp"         // test hooks, instrumented builds

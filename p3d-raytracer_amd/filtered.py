@@ -9,12 +9,11 @@ None.  The answers are those of the unfiltered query over the scene without the 
 unfiltered query's, bit for bit."""
 import ctypes as C
 
-import numpy as np
-
-from ._abi import P3DError, _check
+from ._abi import P3DError
 from ._device_args import NEAREST_K_MAX, _device_rows, _nearest_k_outputs
 from .device_queries import _device_points, _device_query
-from .sweep import _sweep
+from ._host_args import _host_nearest_k
+from .sweep import _host_sweep, _sweep
 
 FILTER_SKIP_MAX = 8  # P3D_FILTER_SKIP_MAX
 
@@ -79,68 +78,14 @@ def sweep_sphere_filtered_device(scene, accel, origin, direction, radius, t_max=
                   more=lambda n: _device_filter(scene, who, skip, n_skip, skip_range, n, "balls"))
 
 
-def _host_filter(who, skip, skip_range, n, rows_of):
-    """(skip array or None, n_skip, skip_range array or None) of a host query of n rows; the arrays are held by the caller"""
-    s, width = None, 0
-    if skip is not None:
-        s = np.ascontiguousarray(skip, np.int32)
-        if s.ndim != 2 or len(s) != n:
-            raise P3DError(-1, "%s: skip %r, needed: (%d, s) for %d %s" % (who, s.shape, n, n, rows_of))
-        width = s.shape[1]
-    r = None
-    if skip_range is not None:
-        r = np.ascontiguousarray(skip_range, np.int32)
-        if r.shape != (n, 2):
-            raise P3DError(-1, "%s: skip_range %r, needed: (%d, 2)" % (who, r.shape, n))
-    return s, width, r
-
-
-def _address(a):
-    return a.ctypes.data if a is not None and a.size else None
-
-
 def host_nearest_k_filtered(host_scene, points, k, max_dist=None, skip=None, skip_range=None):
     """p3d_host_scene_nearest_k_filtered: HostScene.nearest_k for the scene without the objects each point names, by brute force
     on the CPU -> (count int32 (n,), object int32 (n, k), dist float32 (n, k), closest float32 (n, k, 3)).  skip: int32 (n, s),
     s <= FILTER_SKIP_MAX; skip_range: int32 (n, 2); either may be None."""
-    who = "host_nearest_k_filtered"
-    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-    n, k = len(p), int(k)
-    m = None
-    if max_dist is not None:
-        m = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
-        if len(m) != n:
-            raise P3DError(-1, "%s: %d points, %d limits" % (who, n, len(m)))
-    s, width, r = _host_filter(who, skip, skip_range, n, "points")
-    rows = max(k, 0)
-    count, obj = np.zeros(n, np.int32), np.zeros((n, rows), np.int32)
-    dist, closest = np.zeros((n, rows), np.float32), np.zeros((n, rows, 3), np.float32)
-    _check(host_scene._L.p3d_host_scene_nearest_k_filtered(host_scene._h, n, k & 0xffffffff, p.ctypes.data, m.ctypes.data if m is not None else None,
-                                                           _address(s), width, _address(r), count.ctypes.data, obj.ctypes.data,
-                                                           dist.ctypes.data, closest.ctypes.data))
-    return count, obj, dist, closest
+    return _host_nearest_k(host_scene, "host_nearest_k_filtered", points, k, max_dist, filters=(skip, skip_range))
 
 
 def host_sweep_sphere_filtered(host_scene, origin, direction, radius, t_max=None, skip=None, skip_range=None):
     """p3d_host_scene_sweep_sphere_filtered: sweep.host_sweep_sphere for the scene without the objects each ball names ->
     (object int32 (n,), t float32 (n,), centre float32 (n, 3), contact float32 (n, 3))."""
-    who = "host_sweep_sphere_filtered"
-    o, d = np.ascontiguousarray(origin, np.float32), np.ascontiguousarray(direction, np.float32)
-    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
-        raise P3DError(-1, "%s: origins %r and directions %r, needed: (n, 3) both" % (who, o.shape, d.shape))
-    n = len(o)
-    rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)) if np.ndim(radius) == 0 else radius, np.float32).reshape(-1)
-    if len(rad) != n:
-        raise P3DError(-1, "%s: %d origins, %d radii" % (who, n, len(rad)))
-    m = None
-    if t_max is not None:
-        m = np.ascontiguousarray(t_max, np.float32).reshape(-1)
-        if len(m) != n:
-            raise P3DError(-1, "%s: %d origins, %d limits" % (who, n, len(m)))
-    s, width, r = _host_filter(who, skip, skip_range, n, "balls")
-    obj, t = np.zeros(n, np.int32), np.zeros(n, np.float32)
-    centre, contact = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
-    _check(host_scene._L.p3d_host_scene_sweep_sphere_filtered(host_scene._h, n, o.ctypes.data, d.ctypes.data, rad.ctypes.data,
-                                                              m.ctypes.data if m is not None else None, _address(s), width, _address(r),
-                                                              obj.ctypes.data, t.ctypes.data, centre.ctypes.data, contact.ctypes.data))
-    return obj, t, centre, contact
+    return _host_sweep(host_scene, "host_sweep_sphere_filtered", origin, direction, radius, t_max, filters=(skip, skip_range))

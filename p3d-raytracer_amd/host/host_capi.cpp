@@ -1,33 +1,10 @@
 // host_capi.cpp — the p3d_host_* half of include/p3d.h: .p3f -> Scene -> accel builds ->
-// flat p3d_scene_desc.  Pure host code (no HIP).
-#include <cfloat>
-#include <cmath>
+// flat p3d_scene_desc.  Pure host code (no HIP).  The queries on a host scene are host_queries.cpp's.
 #include <cstring>
-#include <memory>
 #include <string>
-#include <vector>
 
-#include "accel_build.hpp"
-#include "nearest_rule.hpp"
-#include "nearest_segment_rule.hpp"
-#include "occlusion_rule.hpp"
-#include "overlap_rule.hpp"
-#include "filter_rule.hpp"
-#include "p3d.h"
+#include "host_scene.hpp"
 #include "p3d_error.hpp"
-#include "scene_model.hpp"
-#include "sweep_rule.hpp"
-
-struct p3d_host_scene {
-  p3d::Scene scene;
-  std::unique_ptr<p3d::BVH> bvh;
-  std::unique_ptr<p3d::Grid> grid;
-  std::vector<p3d_prim> prims;
-  std::vector<p3d_material> materials;
-  std::vector<p3d_light> lights;
-  p3d_scene_desc desc{};
-  bool flat_valid = false;
-};
 
 namespace {
 
@@ -107,16 +84,6 @@ std::vector<p3d::Object*> object_list(const p3d::Scene& S) {
   for (int i = 0; i < S.getNumObjects(); ++i) v.push_back(S.getObject(i));
   return v;
 }
-
-// the candidate list of nearest_rule.hpp as the host keeps it: k entries in an array
-struct HostNearestList {
-  struct Entry { float d2; int32_t object; };
-  Entry e_[P3D_NEAREST_K_MAX];
-  float d2(uint32_t e) const { return e_[e].d2; }
-  int32_t object(uint32_t e) const { return e_[e].object; }
-  void move(uint32_t to, uint32_t from) { e_[to] = e_[from]; }
-  void set(uint32_t e, float d2, int32_t object, uint32_t) { e_[e] = Entry{d2, object}; }
-};
 
 }  // namespace
 
@@ -304,331 +271,6 @@ int p3d_host_scene_skybox_face(p3d_host_scene* hs, int face, const uint8_t** img
   if (!hs || !img) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_skybox_face: null argument");
   *img = hs->scene.SkyboxFace(face, res_x, res_y);
   return *img ? P3D_OK : p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_skybox_face: no cubemap loaded, or face not in 0..5");
-}
-
-// The statement of the nearest-surface query: nearest_rule.hpp on every object, the smallest (d2, object index) wins
-int p3d_host_scene_nearest(p3d_host_scene* hs, uint32_t n, const float* points, const float* max_dist, int32_t* object, float* dist,
-                           float* closest) {
-  if (!hs) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest: null scene");
-  if (n && (!points || !object)) return p3d::fail(P3D_ERR_INVALID, "p3d_host_scene_nearest: null array with n > 0");
-  using namespace p3d;
-  const int n_objs = hs->scene.getNumObjects();
-  std::vector<float> v(9 * static_cast<size_t>(n_objs));
-  std::vector<uint32_t> kind(n_objs);
-  for (int j = 0; j < n_objs; ++j) {
-    float normal[3];
-    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
-    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
-  }
-  for (uint32_t i = 0; i < n; ++i) {
-    const float* p = points + 3 * static_cast<size_t>(i);
-    float best, best_q[3] = {0.0f, 0.0f, 0.0f};
-    int32_t best_object = -1;
-    if (nearest_radius(max_dist != nullptr, max_dist ? max_dist[i] : 0.0f, best)) {
-      for (int j = 0; j < n_objs; ++j) {
-        float q[3];
-        const float d2 = nearest_point(kind[j], &v[9 * static_cast<size_t>(j)], p, q);
-        if (nearest_wins(d2, j, best, best_object)) {
-          best = d2; best_object = j;
-          best_q[0] = q[0]; best_q[1] = q[1]; best_q[2] = q[2];
-        }
-      }
-    }
-    const bool found = best_object >= 0;
-    object[i] = best_object;
-    if (dist) dist[i] = found ? sqrtf(best) : FLT_MAX;
-    if (closest)
-      for (int k = 0; k < 3; ++k) closest[3 * static_cast<size_t>(i) + k] = found ? best_q[k] : 0.0f;
-  }
-  return P3D_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Where a host form's queries get their filters from (filter_rule.hpp): the skip arrays of a *_filtered call, or nothing
-struct HostFilters {
-  const int32_t* skip;
-  uint32_t n_skip;
-  const int32_t* skip_range;
-  p3d::QueryFilter load(uint32_t i, uint32_t n_objs) const { return p3d::filter_load(n_skip ? skip : nullptr, n_skip, skip_range, i, n_objs); }
-};
-struct NoHostFilters {
-  p3d::NoFilter load(uint32_t, uint32_t) const { return p3d::NoFilter{}; }
-};
-// What the filtered host forms refuse of their filter
-int check_host_filter(const HostFilters& f, uint32_t n, const std::string& pre) {
-  if (f.n_skip > P3D_FILTER_SKIP_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "n_skip must be 0 .. P3D_FILTER_SKIP_MAX (8)");
-  if (n && f.n_skip > 0 && !f.skip) return p3d::fail(P3D_ERR_INVALID, pre + "null skip with n > 0 and n_skip > 0");
-  return P3D_OK;
-}
-
-// The statement of the k-nearest query: nearest_rule.hpp on every object the query's filter does not name, the k smallest
-// (d2, object index) under the limit in that order.  q is not kept in the list: the rule is run once more on each listed
-// object, which gives the same bits
-template <class Filters>
-int host_nearest_k(const std::string& pre, p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist,
-                   const Filters& filters, int32_t* count, int32_t* object, float* dist, float* closest) {
-  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
-  if (k == 0 || k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
-  if (n && (!points || !count || !object)) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
-  using namespace p3d;
-  const int n_objs = hs->scene.getNumObjects();
-  std::vector<float> v(9 * static_cast<size_t>(n_objs));
-  std::vector<uint32_t> kind(n_objs);
-  for (int j = 0; j < n_objs; ++j) {
-    float normal[3];
-    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
-    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
-  }
-  for (uint32_t i = 0; i < n; ++i) {
-    const float* p = points + 3 * static_cast<size_t>(i);
-    HostNearestList list;
-    NearestKGate gate;
-    uint32_t found = 0;
-    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
-    if (nearest_k_open(max_dist != nullptr, max_dist ? max_dist[i] : 0.0f, gate)) {
-      for (int j = 0; j < n_objs; ++j) {
-        if (filter_skips(filter, j)) continue;
-        float q[3];
-        const float d2 = nearest_point(kind[j], &v[9 * static_cast<size_t>(j)], p, q);
-        if (nearest_k_admits(d2, j, gate)) nearest_k_insert(list, found, k, gate, d2, j, static_cast<uint32_t>(j));
-      }
-    }
-    count[i] = static_cast<int32_t>(found);
-    for (uint32_t e = 0; e < k; ++e) {
-      const size_t row = static_cast<size_t>(i) * k + e;
-      float q[3] = {0.0f, 0.0f, 0.0f};
-      const int32_t j = e < found ? list.object(e) : -1;
-      if (j >= 0) nearest_point(kind[j], &v[9 * static_cast<size_t>(j)], p, q);
-      object[row] = j;
-      if (dist) dist[row] = j >= 0 ? sqrtf(list.d2(e)) : FLT_MAX;
-      if (closest)
-        for (int c = 0; c < 3; ++c) closest[3 * row + c] = q[c];
-    }
-  }
-  return P3D_OK;
-}
-
-// The statement of the sphere sweep: sweep_rule.hpp on every object the query's filter does not name, the smallest (T, object
-// index) within the limit wins.  contact is not kept during the search: nearest_point is run once more at c(T) on the object found
-template <class Filters>
-int host_sweep_sphere(const std::string& pre, const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction,
-                      const float* radius, const float* t_max, const Filters& filters, int32_t* object, float* t, float* centre,
-                      float* contact) {
-  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
-  using namespace p3d;
-  const int n_objs = hs->scene.getNumObjects();
-  std::vector<float> v(9 * static_cast<size_t>(n_objs));
-  std::vector<uint32_t> kind(n_objs);
-  for (int j = 0; j < n_objs; ++j) {
-    float normal[3];
-    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
-    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
-    if (kind[j] == P3D_PRIM_BOX)
-      return p3d::fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(j) + " is a box: a ball against a box (a rounded box, and its inside) is not swept");
-  }
-  if (n && (!origin || !direction || !radius || !object)) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
-  for (uint32_t i = 0; i < n; ++i) {
-    const size_t row = 3 * static_cast<size_t>(i);
-    SweepRay s;
-    sweep_ray(origin + row, direction + row, radius[i], t_max != nullptr, t_max ? t_max[i] : 0.0f, s);
-    float best = s.limit;
-    int32_t best_object = kSweepNoObject;
-    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
-    if (s.ok) {
-      for (int j = 0; j < n_objs; ++j) {
-        if (filter_skips(filter, j)) continue;
-        float T;
-        if (sweep_contact(kind[j], &v[9 * static_cast<size_t>(j)], s, T) && sweep_wins(T, j, best, best_object)) {
-          best = T; best_object = j;
-        }
-      }
-    }
-    const bool found = best_object != kSweepNoObject;
-    float c[3] = {0.0f, 0.0f, 0.0f}, q[3] = {0.0f, 0.0f, 0.0f};
-    if (found) {
-      sweep_centre(s, best, c);
-      nearest_point(kind[best_object], &v[9 * static_cast<size_t>(best_object)], c, q);
-    }
-    object[i] = found ? best_object : -1;
-    if (t) t[i] = found ? best : FLT_MAX;
-    for (int k = 0; k < 3; ++k) {
-      if (centre) centre[row + k] = c[k];
-      if (contact) contact[row + k] = q[k];
-    }
-  }
-  return P3D_OK;
-}
-
-// The statement of the nearest-surfaces-to-a-segment query: nearest_segment_rule.hpp on every object the segment's filter does
-// not name, in object order; the k smallest (d2, object index) under the limit in that order.  s, x and q are not kept in the
-// list: the rule is run once more on each listed object, which gives the same bits
-template <class Filters>
-int host_nearest_segment_k(const std::string& pre, p3d_host_scene* hs, uint32_t n, uint32_t k, const float* a, const float* b,
-                           const float* max_dist, const Filters& filters, int32_t* count, int32_t* object, float* dist, float* param,
-                           float* on_segment, float* closest) {
-  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
-  using namespace p3d;
-  const int n_objs = hs->scene.getNumObjects();
-  std::vector<float> v(9 * static_cast<size_t>(n_objs));
-  std::vector<uint32_t> kind(n_objs);
-  for (int j = 0; j < n_objs; ++j) {
-    float normal[3];
-    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
-    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
-    if (kind[j] == P3D_PRIM_BOX)
-      return p3d::fail(P3D_ERR_UNSUPPORTED, pre + "object " + std::to_string(j) + " is a box: a segment against a box's faces is not part of this query");
-  }
-  if (k == 0 || k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "k must be 1 .. P3D_NEAREST_K_MAX (16)");
-  if (n && (!a || !b || !count || !object)) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
-  for (uint32_t i = 0; i < n; ++i) {
-    const float* pa = a + 3 * static_cast<size_t>(i);
-    const float* pb = b + 3 * static_cast<size_t>(i);
-    HostNearestList list;
-    NearestKGate gate;
-    uint32_t found = 0;
-    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
-    if (nearest_k_open(max_dist != nullptr, max_dist ? max_dist[i] : 0.0f, gate)) {
-      for (int j = 0; j < n_objs; ++j) {
-        if (filter_skips(filter, j)) continue;
-        float s, x[3], q[3];
-        const float d2 = segment_nearest(kind[j], &v[9 * static_cast<size_t>(j)], pa, pb, s, x, q);
-        if (nearest_k_admits(d2, j, gate)) nearest_k_insert(list, found, k, gate, d2, j, static_cast<uint32_t>(j));
-      }
-    }
-    count[i] = static_cast<int32_t>(found);
-    for (uint32_t e = 0; e < k; ++e) {
-      const size_t row = static_cast<size_t>(i) * k + e;
-      float s = FLT_MAX, x[3] = {0.0f, 0.0f, 0.0f}, q[3] = {0.0f, 0.0f, 0.0f};
-      const int32_t j = e < found ? list.object(e) : -1;
-      if (j >= 0) segment_nearest(kind[j], &v[9 * static_cast<size_t>(j)], pa, pb, s, x, q);
-      object[row] = j;
-      if (dist) dist[row] = j >= 0 ? sqrtf(list.d2(e)) : FLT_MAX;
-      if (param) param[row] = s;
-      for (int c = 0; c < 3; ++c) {
-        if (on_segment) on_segment[3 * row + c] = x[c];
-        if (closest) closest[3 * row + c] = q[c];
-      }
-    }
-  }
-  return P3D_OK;
-}
-
-// The statement of the overlap query: overlap_rule.hpp on every object the box's filter does not name, in object order; all
-// of them counted, the first k listed (object order is index order: the k lowest, ascending)
-template <class Filters>
-int host_overlap_box(const std::string& pre, p3d_host_scene* hs, uint32_t n, uint32_t k, const float* lo, const float* hi,
-                     const Filters& filters, uint32_t flags, int32_t* total, int32_t* object) {
-  if (!hs) return p3d::fail(P3D_ERR_INVALID, pre + "null scene");
-  if (k > P3D_NEAREST_K_MAX) return p3d::fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_NEAREST_K_MAX (16)");
-  if (flags & ~P3D_OVERLAP_SOLID) return p3d::fail(P3D_ERR_INVALID, pre + "unknown flag (P3D_OVERLAP_SOLID is the only one)");
-  if (n && (!lo || !hi || !total || (k > 0 && !object))) return p3d::fail(P3D_ERR_INVALID, pre + "null array with n > 0");
-  using namespace p3d;
-  const int n_objs = hs->scene.getNumObjects();
-  std::vector<float> v(9 * static_cast<size_t>(n_objs));
-  std::vector<uint32_t> kind(n_objs);
-  for (int j = 0; j < n_objs; ++j) {
-    float normal[3];
-    hs->scene.getObject(j)->pack(&v[9 * static_cast<size_t>(j)], normal);
-    kind[j] = static_cast<uint32_t>(hs->scene.getObject(j)->kind());
-  }
-  for (uint32_t i = 0; i < n; ++i) {
-    const float* qlo = lo + 3 * static_cast<size_t>(i);
-    const float* qhi = hi + 3 * static_cast<size_t>(i);
-    int32_t* row = k ? object + static_cast<size_t>(i) * k : nullptr;
-    uint32_t found = 0;
-    const auto filter = filters.load(i, static_cast<uint32_t>(n_objs));
-    if (overlap_query_open(qlo, qhi)) {
-      for (int j = 0; j < n_objs; ++j) {
-        if (filter_skips(filter, j)) continue;
-        if (!overlap_box(kind[j], &v[9 * static_cast<size_t>(j)], qlo, qhi, flags)) continue;
-        if (found < k) row[found] = j;
-        ++found;
-      }
-    }
-    total[i] = static_cast<int32_t>(found);
-    for (uint32_t e = found; e < k; ++e) row[e] = -1;
-  }
-  return P3D_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int p3d_host_scene_overlap_box(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* lo, const float* hi, const int32_t* skip,
-                               uint32_t n_skip, const int32_t* skip_range, uint32_t flags, int32_t* total, int32_t* object) {
-  const std::string pre = "p3d_host_scene_overlap_box: ";
-  const HostFilters filters{skip, n_skip, skip_range};
-  if (int rc = check_host_filter(filters, n, pre)) return rc;
-  if (n_skip == 0 && !skip_range) return host_overlap_box(pre, hs, n, k, lo, hi, NoHostFilters{}, flags, total, object);
-  return host_overlap_box(pre, hs, n, k, lo, hi, filters, flags, total, object);
-}
-
-int p3d_host_scene_nearest_segment_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* a, const float* b, const float* max_dist,
-                                     const int32_t* skip, uint32_t n_skip, const int32_t* skip_range, int32_t* count, int32_t* object,
-                                     float* dist, float* param, float* on_segment, float* closest) {
-  const std::string pre = "p3d_host_scene_nearest_segment_k: ";
-  const HostFilters filters{skip, n_skip, skip_range};
-  if (int rc = check_host_filter(filters, n, pre)) return rc;
-  if (n_skip == 0 && !skip_range)
-    return host_nearest_segment_k(pre, hs, n, k, a, b, max_dist, NoHostFilters{}, count, object, dist, param, on_segment, closest);
-  return host_nearest_segment_k(pre, hs, n, k, a, b, max_dist, filters, count, object, dist, param, on_segment, closest);
-}
-
-// The key of a BVH node under the segment query, for the tests (host only)
-int p3d_debug_segment_box_d2(uint32_t n, const float* a, const float* b, const float* lo, const float* hi, float* out) {
-  if (n && (!a || !b || !lo || !hi || !out)) return p3d::fail(P3D_ERR_INVALID, "p3d_debug_segment_box_d2: null array with n > 0");
-  for (size_t i = 0; i < n; ++i) out[i] = p3d::segment_box_d2(a + 3 * i, b + 3 * i, lo + 3 * i, hi + 3 * i);
-  return P3D_OK;
-}
-
-int p3d_host_scene_nearest_k(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist, int32_t* count,
-                             int32_t* object, float* dist, float* closest) {
-  return host_nearest_k("p3d_host_scene_nearest_k: ", hs, n, k, points, max_dist, NoHostFilters{}, count, object, dist, closest);
-}
-int p3d_host_scene_nearest_k_filtered(p3d_host_scene* hs, uint32_t n, uint32_t k, const float* points, const float* max_dist,
-                                      const int32_t* skip, uint32_t n_skip, const int32_t* skip_range, int32_t* count, int32_t* object,
-                                      float* dist, float* closest) {
-  const std::string pre = "p3d_host_scene_nearest_k_filtered: ";
-  const HostFilters filters{skip, n_skip, skip_range};
-  if (int rc = check_host_filter(filters, n, pre)) return rc;
-  return host_nearest_k(pre, hs, n, k, points, max_dist, filters, count, object, dist, closest);
-}
-int p3d_host_scene_sweep_sphere(const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction, const float* radius,
-                                const float* t_max, int32_t* object, float* t, float* centre, float* contact) {
-  return host_sweep_sphere("p3d_host_scene_sweep_sphere: ", hs, n, origin, direction, radius, t_max, NoHostFilters{}, object, t, centre, contact);
-}
-int p3d_host_scene_sweep_sphere_filtered(const p3d_host_scene* hs, uint32_t n, const float* origin, const float* direction,
-                                         const float* radius, const float* t_max, const int32_t* skip, uint32_t n_skip,
-                                         const int32_t* skip_range, int32_t* object, float* t, float* centre, float* contact) {
-  const std::string pre = "p3d_host_scene_sweep_sphere_filtered: ";
-  const HostFilters filters{skip, n_skip, skip_range};
-  if (int rc = check_host_filter(filters, n, pre)) return rc;
-  return host_sweep_sphere(pre, hs, n, origin, direction, radius, t_max, filters, object, t, centre, contact);
-}
-
-// The statement of the rays of p3d_occlusion_device: occlusion_rule.hpp for every (point, sample), row i * samples + j
-int p3d_occlusion_rays(uint32_t n, const float* point, const float* normal, const p3d_occlusion_params* params, float* origin,
-                       float* direction) {
-  const std::string pre = "p3d_occlusion_rays: ";
-  if (const char* why = p3d::occlusion_params_refusal(params)) return p3d::fail(P3D_ERR_INVALID, pre + why);
-  if (n == 0) return P3D_OK;
-  if (!point || !normal || !origin || !direction) return p3d::fail(P3D_ERR_INVALID, pre + "null argument");
-  if (static_cast<uint64_t>(n) * params->samples > 0xffffffffull)
-    return p3d::fail(P3D_ERR_CAPACITY, pre + "n x samples rows do not fit 32 bits (split the batch)");
-  for (uint32_t i = 0; i < n; ++i) {
-    p3d::OcclusionFrame f;
-    p3d::occlusion_frame(point + 3 * static_cast<size_t>(i), normal + 3 * static_cast<size_t>(i), params->bias, f);
-    for (uint32_t j = 0; j < params->samples; ++j) {
-      const size_t row = static_cast<size_t>(i) * params->samples + j;
-      p3d::occlusion_direction(f, params->seed, params->point_offset + i, params->sample_begin + j, direction + 3 * row);
-      for (int k = 0; k < 3; ++k) origin[3 * row + k] = f.origin[k];
-    }
-  }
-  return P3D_OK;
 }
 
 int p3d_host_scene_bind_device(p3d_host_scene* hs, p3d_scene* scene) {

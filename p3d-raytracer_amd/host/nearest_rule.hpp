@@ -1,5 +1,5 @@
 // nearest_rule.hpp — the arithmetic of a nearest-surface query, in ONE place for its users: p3d_host_scene_nearest and
-// p3d_host_scene_nearest_k (host_capi.cpp), which state the semantics by brute force, and nearest_k_device_kernel
+// p3d_host_scene_nearest_k (host_queries.cpp), which state the semantics by brute force, and nearest_k_device_kernel
 // (csrc/nearest_query.hpp), whose answers must be the host forms' bits.  For a point p and an object's nine geometry floats (what p3d_prim.v holds for its
 // kind) nearest_point gives the closest point q on the object's SURFACE and d2 = |p - q|^2, taken from q as stored.  Also
 // here: the squared distance from p to a BVH node's box, and the two comparisons of a search - which candidate wins, and

@@ -1,5 +1,5 @@
 // nearest_segment_rule.hpp — the arithmetic of a nearest-surface query for a SEGMENT (an edge of a cloth mesh, the axis of a
-// capsule, a piece of rope), in ONE place for its users: p3d_host_scene_nearest_segment_k (host_capi.cpp), which states the
+// capsule, a piece of rope), in ONE place for its users: p3d_host_scene_nearest_segment_k (host_queries.cpp), which states the
 // semantics by brute force, and nearest_segment_k_device_kernel (csrc/nearest_segment_query.hpp), whose answers must be the host
 // form's bits.  For a segment a b and an object's nine geometry floats (what p3d_prim.v holds for its kind) segment_nearest
 // gives the parameter s in [0, 1] of the point of the segment nearest to the object's SURFACE (nearest_rule.hpp: a sphere's

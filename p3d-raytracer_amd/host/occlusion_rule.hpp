@@ -1,5 +1,5 @@
 // occlusion_rule.hpp — the rays of a hemisphere-occlusion query, in ONE place for their users: p3d_occlusion_rays
-// (host_capi.cpp), which states them on host arrays, and occlusion_kernel and occlusion_rays_kernel
+// (host_queries.cpp), which states them on host arrays, and occlusion_kernel and occlusion_rays_kernel
 // (csrc/occlusion_query.hpp), whose rays must be the host form's bits.  Sample s of point i draws from the stream
 // seed_stream(seed, point_offset + i, s) and is the cosine-weighted direction of the path tracer's diffuse bounce
 // (main.cpp:391-405), spelled as csrc/pt_bounce.inc:49-57 spells it: the same operations in the same order.

@@ -1,5 +1,5 @@
 // overlap_rule.hpp — does an object touch an axis-aligned box?  In ONE place for its users: p3d_host_scene_overlap_box
-// (host_capi.cpp), which states the semantics by brute force, and overlap_box_device_kernel (csrc/overlap_query.hpp), whose
+// (host_queries.cpp), which states the semantics by brute force, and overlap_box_device_kernel (csrc/overlap_query.hpp), whose
 // answers must be the host form's bits.  For a query box lo .. hi (closed) and an object's nine geometry floats (what
 // p3d_prim.v holds for its kind) overlap_box says whether the box overlaps the object's SURFACE - the closed triangle, a
 // sphere's shell, a box's faces, the plane: the surface p3d_nearest_device measures to - or, with P3D_OVERLAP_SOLID, the solid

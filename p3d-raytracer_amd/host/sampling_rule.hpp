@@ -1,6 +1,6 @@
 // sampling_rule.hpp — what a sampler draws with, in ONE place for its users on both sides of the boundary: the PCG stream of a
 // (pixel or point, sample) pair and the sine and cosine of an angle.  The device kernels (csrc/device_core.hpp, pt_kernel.hpp,
-// occlusion_query.hpp) and the host writer of the occlusion rays (host_capi.cpp, through occlusion_rule.hpp) must give the
+// occlusion_query.hpp) and the host writer of the occlusion rays (host_queries.cpp, through occlusion_rule.hpp) must give the
 // same bits, so neither side spells these out for itself.  Integers, and double arithmetic built from + - * floor only; both
 // translation units are compiled without contraction (-ffp-contract=off).
 #pragma once

@@ -1,5 +1,5 @@
 // sweep_rule.hpp — the arithmetic of a sphere sweep (continuous collision detection of a moving ball), in ONE place for its
-// users: p3d_host_scene_sweep_sphere (host_capi.cpp), which states the semantics by brute force, and sweep_sphere_device_kernel
+// users: p3d_host_scene_sweep_sphere (host_queries.cpp), which states the semantics by brute force, and sweep_sphere_device_kernel
 // (csrc/sweep_query.hpp), whose answers must be the host form's bits.  A ball of radius r moves with its centre on
 // c(t) = o + t d (d as given: t is in units of d).  For an object's nine geometry floats (what p3d_prim.v holds for its kind)
 // sweep_contact gives T = min { t >= 0 : dist(c(t)) <= r }, dist being the distance to the object's SURFACE as

@@ -5,6 +5,8 @@ import os
 import numpy as np
 
 from ._abi import LOAD_LEGACY_F11, SceneDesc, _check, _Handle, lib
+from ._device_args import _NEAREST_OUTPUTS
+from ._host_args import _host_nearest_k, _host_query, _per_row, _points
 
 
 class HostScene(_Handle):
@@ -40,36 +42,16 @@ class HostScene(_Handle):
         """p3d_host_scene_nearest: for every point the object whose surface is nearest, by brute force on the CPU ->
         (object int32 (n,), dist float32 (n,), closest float32 (n, 3)); -1, FLT_MAX and zeros where nothing lies within
         max_dist (float32 (n,), or None: no limit)."""
-        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        n = len(p)
-        m = None
-        if max_dist is not None:
-            m = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
-            if len(m) != n:
-                raise ValueError("nearest: %d points, %d limits" % (n, len(m)))
-        obj, dist, closest = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
-        _check(self._L.p3d_host_scene_nearest(self._h, n, p.ctypes.data, m.ctypes.data if m is not None else None, obj.ctypes.data,
-                                              dist.ctypes.data, closest.ctypes.data))
-        return obj, dist, closest
+        p = _points(points)
+        m = _per_row("nearest", max_dist, len(p), "points", "limits", error=ValueError)
+        return _host_query(self, "nearest", len(p), (p, m), _NEAREST_OUTPUTS, ("object", "dist", "closest"))
 
     def nearest_k(self, points, k, max_dist=None):
         """p3d_host_scene_nearest_k: for every point the (at most) k objects whose surfaces are nearest, nearer than max_dist
         (float32 (n,), or None: no limit), ordered by (distance, object index), by brute force on the CPU -> (count int32 (n,),
         object int32 (n, k), dist float32 (n, k), closest float32 (n, k, 3)); rows from count on hold -1, FLT_MAX and zeros.
         count == k: there may be more.  1 <= k <= NEAREST_K_MAX."""
-        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        n, k = len(p), int(k)
-        m = None
-        if max_dist is not None:
-            m = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
-            if len(m) != n:
-                raise ValueError("nearest_k: %d points, %d limits" % (n, len(m)))
-        rows = max(k, 0)
-        count, obj = np.zeros(n, np.int32), np.zeros((n, rows), np.int32)
-        dist, closest = np.zeros((n, rows), np.float32), np.zeros((n, rows, 3), np.float32)
-        _check(self._L.p3d_host_scene_nearest_k(self._h, n, k & 0xffffffff, p.ctypes.data, m.ctypes.data if m is not None else None,
-                                                count.ctypes.data, obj.ctypes.data, dist.ctypes.data, closest.ctypes.data))
-        return count, obj, dist, closest
+        return _host_nearest_k(self, "nearest_k", points, k, max_dist, error=ValueError)
 
     def has_skybox(self):
         """A cubemap is loaded: the folder of the scene's `env` line was found, or load_skybox was called (p3d_host_scene_has_skybox)."""

@@ -6,13 +6,12 @@ Box i is the closed box lo[i] .. hi[i].  The answers are the number of objects t
 object indices among them, ascending; k = 0 is the count alone.  "Overlaps" means the surface nearest_device measures to - the
 closed triangle, a sphere's shell, a box's faces, the plane; with solid=True spheres and boxes count as solids.  Touching
 counts; a box with lo > hi on some axis, or with a NaN, finds nothing.  Filters (`skip`, `skip_range`) are filtered.py's."""
-import numpy as np
-
-from ._abi import ACCEL_BVH, ACCEL_GRID, P3DError, _check
+from ._abi import P3DError
 from ._device_args import NEAREST_K_MAX, _device_rows
 from .device_queries import _device_query
-from .filtered import _address, _device_filter, _host_filter
-from .sweep import UNSUPPORTED, _kinds
+from ._host_args import _host_filter, _host_query, _row_pair
+from .filtered import _device_filter
+from .sweep import _refuse_by_host_scene
 
 OVERLAP_SOLID = 1  # P3D_OVERLAP_SOLID
 _ORDER = ("total", "object")
@@ -36,13 +35,8 @@ def overlap_box_device(scene, accel, lo, hi, k, skip=None, skip_range=None, soli
     `out`, `stream` and the other refusals as nearest_k_filtered_device; the answers are host_overlap_box's, bit for bit."""
     who = "overlap_box_device"
     k = int(k)
+    _refuse_by_host_scene(scene, who, accel, "no overlap query through the grid (use ACCEL_BVH or ACCEL_NONE)", None)
     refusal = None
-    if int(accel) == ACCEL_GRID:
-        refusal = "no overlap query through the grid (use ACCEL_BVH or ACCEL_NONE)"
-    elif getattr(scene, "host", None) is not None and int(accel) == ACCEL_BVH and _kinds(scene.host)[1]:
-        refusal = "the scene holds a plane, which the tree cannot find (use ACCEL_NONE)"
-    if refusal:
-        raise P3DError(UNSUPPORTED, "%s: %s" % (who, refusal))
     if out is None and not 0 <= k <= NEAREST_K_MAX:  # (with the caller's outputs the library says it)
         refusal = "k must be 0 .. %d, got %d" % (NEAREST_K_MAX, k)
 
@@ -63,12 +57,7 @@ def host_overlap_box(host_scene, lo, hi, k, skip=None, skip_range=None, solid=Fa
     order -> (total int32 (n,), object int32 (n, k)).  skip: int32 (n, s), s <= FILTER_SKIP_MAX; skip_range: int32 (n, 2); either
     may be None."""
     who = "host_overlap_box"
-    plo, phi = np.ascontiguousarray(lo, np.float32), np.ascontiguousarray(hi, np.float32)
-    if plo.ndim != 2 or plo.shape[1] != 3 or phi.shape != plo.shape:
-        raise P3DError(-1, "%s: lo %r and hi %r, needed: (n, 3) both" % (who, plo.shape, phi.shape))
+    plo, phi = _row_pair(who, "lo", lo, "hi", hi)
     n, k = len(plo), int(k)
-    s, width, r = _host_filter(who, skip, skip_range, n, "boxes")
-    total, obj = np.zeros(n, np.int32), np.zeros((n, min(max(k, 0), NEAREST_K_MAX)), np.int32)
-    _check(host_scene._L.p3d_host_scene_overlap_box(host_scene._h, n, k & 0xffffffff, _address(plo), _address(phi), _address(s), width, _address(r),
-                                                    OVERLAP_SOLID if solid else 0, _address(total), _address(obj)))
-    return total, obj
+    args = (k & 0xffffffff, plo, phi) + _host_filter(who, skip, skip_range, n, "boxes") + (OVERLAP_SOLID if solid else 0,)
+    return _host_query(host_scene, "overlap_box", n, args, {"total": ("int32", None), "object": ("int32", min(max(k, 0), NEAREST_K_MAX))}, _ORDER)

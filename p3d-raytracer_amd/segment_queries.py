@@ -9,11 +9,12 @@ x = a + (b - a) s, that point, and the object's nearest point; a segment that cr
 Filters (`skip`, `skip_range`) are filtered.py's."""
 import numpy as np
 
-from ._abi import ACCEL_BVH, ACCEL_GRID, P3DError, _check, lib
+from ._abi import P3DError, _check, lib
 from ._device_args import NEAREST_K_MAX, _device_rows, _device_vector
 from .device_queries import _device_query
-from .filtered import _address, _device_filter, _host_filter
-from .sweep import UNSUPPORTED, _kinds
+from ._host_args import _host_filter, _host_query, _per_row, _row_pair
+from .filtered import _device_filter
+from .sweep import _refuse_by_host_scene
 
 _ORDER = ("count", "object", "dist", "param", "on_segment", "closest", "normal")
 
@@ -37,17 +38,9 @@ def nearest_segment_k_device(scene, accel, a, b, k, max_dist=None, skip=None, sk
     who = "nearest_segment_k_device"
     k = int(k)
     names = ["count", "object"] + [w for w in _ORDER[2:] if w in want]
+    _refuse_by_host_scene(scene, who, accel, "no nearest-surface query through the grid (use ACCEL_BVH or ACCEL_NONE)",
+                          "the scene holds a box: a segment against a box's faces is not part of this query")
     refusal = None
-    if int(accel) == ACCEL_GRID:
-        refusal = "no nearest-surface query through the grid (use ACCEL_BVH or ACCEL_NONE)"
-    elif getattr(scene, "host", None) is not None:
-        box, plane = _kinds(scene.host)
-        if box:
-            refusal = "the scene holds a box: a segment against a box's faces is not part of this query"
-        elif plane and int(accel) == ACCEL_BVH:
-            refusal = "the scene holds a plane, which the tree cannot find (use ACCEL_NONE)"
-    if refusal:
-        raise P3DError(UNSUPPORTED, "%s: %s" % (who, refusal))
     if out is None and not 1 <= k <= NEAREST_K_MAX:  # (with the caller's outputs the library says it)
         refusal = "k must be 1 .. %d, got %d" % (NEAREST_K_MAX, k)
 
@@ -69,25 +62,10 @@ def host_nearest_segment_k(host_scene, a, b, k, max_dist=None, skip=None, skip_r
     (n, k, 3), closest float32 (n, k, 3)).  skip: int32 (n, s), s <= FILTER_SKIP_MAX; skip_range: int32 (n, 2); either may be
     None.  A scene that holds a box is refused (P3D_ERR_UNSUPPORTED)."""
     who = "host_nearest_segment_k"
-    pa, pb = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    if pa.ndim != 2 or pa.shape[1] != 3 or pb.shape != pa.shape:
-        raise P3DError(-1, "%s: a %r and b %r, needed: (n, 3) both" % (who, pa.shape, pb.shape))
+    pa, pb = _row_pair(who, "a", a, "b", b)
     n, k = len(pa), int(k)
-    m = None
-    if max_dist is not None:
-        m = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
-        if len(m) != n:
-            raise P3DError(-1, "%s: %d segments, %d limits" % (who, n, len(m)))
-    s, width, r = _host_filter(who, skip, skip_range, n, "segments")
-    rows = max(k, 0)
-    count, obj = np.zeros(n, np.int32), np.zeros((n, rows), np.int32)
-    dist, param = np.zeros((n, rows), np.float32), np.zeros((n, rows), np.float32)
-    on_segment, closest = np.zeros((n, rows, 3), np.float32), np.zeros((n, rows, 3), np.float32)
-    _check(host_scene._L.p3d_host_scene_nearest_segment_k(host_scene._h, n, k & 0xffffffff, pa.ctypes.data, pb.ctypes.data,
-                                                          m.ctypes.data if m is not None else None, _address(s), width, _address(r),
-                                                          count.ctypes.data, obj.ctypes.data, dist.ctypes.data, param.ctypes.data,
-                                                          on_segment.ctypes.data, closest.ctypes.data))
-    return count, obj, dist, param, on_segment, closest
+    args = (k & 0xffffffff, pa, pb, _per_row(who, max_dist, n, "segments", "limits")) + _host_filter(who, skip, skip_range, n, "segments")
+    return _host_query(host_scene, "nearest_segment_k", n, args, _nearest_segment_k_outputs(max(k, 0)), _ORDER[:-1])
 
 
 def segment_box_d2(a, b, lo, hi):

@@ -6,8 +6,9 @@ import weakref
 
 import numpy as np
 
-from ._abi import ACCEL_BVH, ACCEL_GRID, P3DError, Prim, _check
+from ._abi import ACCEL_BVH, ACCEL_GRID, P3DError, Prim
 from ._device_args import _SWEEP_OUTPUTS, _device_vector
+from ._host_args import _host_filter, _host_query, _per_row, _row_pair
 from .device_queries import _device_query, _device_rays
 
 UNSUPPORTED = -3  # P3D_ERR_UNSUPPORTED
@@ -26,6 +27,23 @@ def _kinds(host_scene):
         types = np.ctypeslib.as_array(C.cast(d.prims, C.POINTER(C.c_uint32)), shape=(d.n_prims, words))[:, at] if d.n_prims else np.zeros(0, np.uint32)
         known = _KINDS[host_scene] = (bool((types == PRIM_BOX).any()), bool((types == PRIM_PLANE).any()))
     return known
+
+
+def _refuse_by_host_scene(scene, who, accel, grid, box):
+    """What a per-object device query refuses before the library is called: the grid (`grid`: the query's sentence) and,
+    where the DeviceScene came from a HostScene, a scene that holds a box (`box`: the query's sentence; None: boxes are
+    taken) and a plane under ACCEL_BVH"""
+    refusal = None
+    if int(accel) == ACCEL_GRID:
+        refusal = grid
+    elif getattr(scene, "host", None) is not None:
+        holds_box, holds_plane = _kinds(scene.host)
+        if box and holds_box:
+            refusal = box
+        elif holds_plane and int(accel) == ACCEL_BVH:
+            refusal = "the scene holds a plane, which the tree cannot find (use ACCEL_NONE)"
+    if refusal:
+        raise P3DError(UNSUPPORTED, "%s: %s" % (who, refusal))
 
 
 def _torch_stream(stream, device):
@@ -53,17 +71,8 @@ def _sweep(scene, who, accel, origin, direction, radius, t_max, want, out, strea
     """sweep_sphere_device, and what filtered.sweep_sphere_filtered_device shares with it: more(n) -> the inputs that follow
     t_max in the C order of p3d_<who>"""
     names = ["object"] + [w for w in ("t", "centre", "contact", "normal") if w in want]
-    refusal = None
-    if int(accel) == ACCEL_GRID:
-        refusal = "no sphere sweep through the grid (use ACCEL_BVH or ACCEL_NONE)"
-    elif getattr(scene, "host", None) is not None:
-        box, plane = _kinds(scene.host)
-        if box:
-            refusal = "the scene holds a box: a ball against a box (a rounded box, and its inside) is not swept"
-        elif plane and int(accel) == ACCEL_BVH:
-            refusal = "the scene holds a plane, which the tree cannot find (use ACCEL_NONE)"
-    if refusal:
-        raise P3DError(UNSUPPORTED, "%s: %s" % (who, refusal))
+    _refuse_by_host_scene(scene, who, accel, "no sphere sweep through the grid (use ACCEL_BVH or ACCEL_NONE)",
+                          "the scene holds a box: a ball against a box (a rounded box, and its inside) is not swept")
 
     filled = []  # one number for all radii: the tensor made of it, held HERE until the library call has returned
 
@@ -96,22 +105,14 @@ def host_sweep_sphere(host_scene, origin, direction, radius, t_max=None):
     (n, 3) origins and directions, a radius per ball or one number, t_max (n,) or None -> (object int32 (n,), t float32 (n,),
     centre float32 (n, 3), contact float32 (n, 3)); -1, FLT_MAX and zeros where nothing is met.  A scene that holds a box is
     refused (P3D_ERR_UNSUPPORTED)."""
-    who = "host_sweep_sphere"
-    o, d = np.ascontiguousarray(origin, np.float32), np.ascontiguousarray(direction, np.float32)
-    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
-        raise P3DError(-1, "%s: origins %r and directions %r, needed: (n, 3) both" % (who, o.shape, d.shape))
+    return _host_sweep(host_scene, "host_sweep_sphere", origin, direction, radius, t_max)
+
+
+def _host_sweep(host_scene, who, origin, direction, radius, t_max, filters=None):
+    """host_sweep_sphere and, with filters = (skip, skip_range), filtered.host_sweep_sphere_filtered"""
+    o, d = _row_pair(who, "origins", origin, "directions", direction)
     n = len(o)
-    r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)) if np.ndim(radius) == 0 else radius, np.float32).reshape(-1)
-    if len(r) != n:
-        raise P3DError(-1, "%s: %d origins, %d radii" % (who, n, len(r)))
-    m = None
-    if t_max is not None:
-        m = np.ascontiguousarray(t_max, np.float32).reshape(-1)
-        if len(m) != n:
-            raise P3DError(-1, "%s: %d origins, %d limits" % (who, n, len(m)))
-    obj, t = np.zeros(n, np.int32), np.zeros(n, np.float32)
-    centre, contact = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
-    _check(host_scene._L.p3d_host_scene_sweep_sphere(host_scene._h, n, o.ctypes.data, d.ctypes.data, r.ctypes.data,
-                                                     m.ctypes.data if m is not None else None, obj.ctypes.data, t.ctypes.data,
-                                                     centre.ctypes.data, contact.ctypes.data))
-    return obj, t, centre, contact
+    args, form = (o, d, _per_row(who, radius, n, "origins", "radii", one_for_all=True), _per_row(who, t_max, n, "origins", "limits")), "sweep_sphere"
+    if filters is not None:
+        args, form = args + _host_filter(who, filters[0], filters[1], n, "balls"), "sweep_sphere_filtered"
+    return _host_query(host_scene, form, n, args, _SWEEP_OUTPUTS, ("object", "t", "centre", "contact"))
