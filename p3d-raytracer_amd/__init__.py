@@ -29,7 +29,7 @@ from .device_queries import (camera_rays_device, camera_sample_rays_device, occl
                              trace_path_device, trace_radiance_device)
 from .sweep import host_sweep_sphere, sweep_sphere_device
 from .filtered import (FILTER_SKIP_MAX, host_nearest_k_filtered, host_sweep_sphere_filtered, nearest_k_filtered_device,
-                       sweep_sphere_filtered_device)
+                       occlusion_filtered_device, sweep_sphere_filtered_device, trace_any_filtered_device, trace_hits_filtered_device)
 from .segment_queries import _nearest_segment_k_outputs, host_nearest_segment_k, nearest_segment_k_device, segment_box_d2
 from .overlap import OVERLAP_SOLID, _overlap_outputs, host_overlap_box, overlap_box_device
 from .device_scene import SKYBOX_FACE_FILES, DeviceScene, load_skybox_dir

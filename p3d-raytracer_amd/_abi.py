@@ -274,6 +274,9 @@ PROTOTYPES = {
     "p3d_sweep_sphere_filtered_device": (DEFAULT, [VP, U32, U32, VP, VP, VP, VP, VP, U32, VP] + [VP] * 6),
     "p3d_host_scene_nearest_k_filtered": (DEFAULT, [VP, U32, U32, VP, VP, VP, U32, VP] + [VP] * 4),
     "p3d_host_scene_sweep_sphere_filtered": (DEFAULT, [VP, U32, VP, VP, VP, VP, VP, U32, VP] + [VP] * 4),
+    "p3d_trace_any_filtered_device": (DEFAULT, [VP, U32, U32, VP, VP, VP, VP, U32, VP, VP, VP]),
+    "p3d_trace_hits_filtered_device": (DEFAULT, [VP, U32, U32, U32, VP, VP, VP, VP, U32, VP] + [VP] * 7),
+    "p3d_occlusion_filtered_device": (DEFAULT, [VP, U32, U32, VP, VP, VP, PTR(OcclusionParams), VP, U32, VP, VP, VP, VP]),
     "p3d_nearest_segment_k_device": (DEFAULT, [VP, U32, U32, U32, VP, VP, VP, VP, U32, VP] + [VP] * 8),
     "p3d_host_scene_nearest_segment_k": (DEFAULT, [VP, U32, U32, VP, VP, VP, VP, U32, VP] + [VP] * 6),
     "p3d_overlap_box_device": (DEFAULT, [VP, U32, U32, U32, VP, VP, VP, U32, VP, U32, VP, VP, VP]),
@@ -294,6 +297,7 @@ EXPORTS_ADDED = ["p3d_trace_radiance_device", "p3d_camera_rays_device", "p3d_tra
                  "p3d_sweep_sphere_device", "p3d_host_scene_sweep_sphere",
                  "p3d_nearest_k_filtered_device", "p3d_sweep_sphere_filtered_device", "p3d_host_scene_nearest_k_filtered",
                  "p3d_host_scene_sweep_sphere_filtered",
+                 "p3d_trace_any_filtered_device", "p3d_trace_hits_filtered_device", "p3d_occlusion_filtered_device",
                  "p3d_nearest_segment_k_device", "p3d_host_scene_nearest_segment_k",
                  "p3d_overlap_box_device", "p3d_host_scene_overlap_box"]
 EXPORTS = [name for name in PROTOTYPES if not name.startswith("p3d_debug_") and name not in EXPORTS_ADDED]

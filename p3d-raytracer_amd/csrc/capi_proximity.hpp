@@ -3,7 +3,7 @@
 // p3d_nearest_segment_k_device, p3d_overlap_box_device).  Every one opens with open_object_query, keeps its own k / flag /
 // filter / null-argument checks behind it, goes through enqueue_query (capi_query.hpp) and launches with launch_filterable.
 #pragma once
-#include "capi_query.hpp"  // open_object_query, QueryBuffer, enqueue_query
+#include "capi_query.hpp"  // open_object_query, QueryBuffer, enqueue_query, FilterArgs, check_filter, launch_filterable
 #include "nearest_query.hpp"
 #include "nearest_segment_query.hpp"
 #include "overlap_query.hpp"
@@ -11,37 +11,6 @@
 #include "sweep_query.hpp"
 
 namespace {
-
-// The skip buffers of a *_filtered_device call (include/p3d_filter.h).  The unfiltered entry points pass none: a null
-// FilterArgs*, the same checks and launches as before
-struct FilterArgs {
-  const int32_t* d_skip;  // n x n_skip, or null
-  uint32_t n_skip;
-  const int32_t* d_skip_range;  // n x 2, or null
-  bool absent() const { return n_skip == 0 && !d_skip_range; }  // the call is the unfiltered call: its kernel is launched
-};
-// What a filtered call refuses of its filter whatever n is, and with n > 0
-int check_filter(const FilterArgs& fa, const std::string& pre) {
-  if (fa.n_skip > P3D_FILTER_SKIP_MAX) return fail(P3D_ERR_INVALID, pre + kRefuseSkipCount);
-  return P3D_OK;
-}
-int check_filter_buffers(const FilterArgs& fa, const std::string& pre) {
-  if (fa.n_skip > 0 && !fa.d_skip) return fail(P3D_ERR_INVALID, pre + "null argument (d_skip is needed with n_skip > 0)");
-  return P3D_OK;
-}
-FilterParams filter_params(const FilterArgs& fa) { return FilterParams{fa.n_skip ? fa.d_skip : nullptr, fa.d_skip_range, fa.n_skip}; }
-
-// One kernel family under P3D_ACCEL_NONE or P3D_ACCEL_BVH, without or with a filter: launch(A, params) is called with the
-// accel as a std::integral_constant and with the bare P (no filter given: the unfiltered kernel) or Filtered{P, F}; it names
-// the kernel template and launches kernel<decltype(A)::value> with `params`
-template <class Filtered, class P, class Launch>
-void launch_filterable(uint32_t accel, const FilterArgs& fa, const P& params, Launch&& launch) {
-  with_flags([&](auto BVH) {
-    constexpr std::integral_constant<int, BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE> A{};
-    if (fa.absent()) launch(A, params);
-    else launch(A, Filtered{params, filter_params(fa)});
-  }, accel == P3D_ACCEL_BVH);
-}
 
 // p3d_nearest_device (k_form false: k = 1, no d_count), p3d_nearest_k_device and, with `filter`, p3d_nearest_k_filtered_device.
 // One set of checks for all; the outputs hold k rows per point

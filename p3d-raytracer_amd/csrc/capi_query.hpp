@@ -1,7 +1,9 @@
 // capi_query.hpp — batched ray and per-object queries (p3d_trace_*, p3d_trace_hits_device, p3d_trace_radiance_device,
 // p3d_camera_rays_device, p3d_trace_path_device, p3d_camera_sample_rays_device, p3d_occlusion_device, p3d_occlusion_rays_device,
-// p3d_object_*, p3d_skybox_color), and what every query over device buffers goes through: open_object_query, check_query_buffers,
-// bind_query_stack, enqueue_query.  The proximity queries (nearest, sweep, segment, overlap) are capi_proximity.hpp's
+// p3d_object_*, p3d_skybox_color, and the filtered forms of the segment family: p3d_trace_any_filtered_device,
+// p3d_trace_hits_filtered_device, p3d_occlusion_filtered_device), and what every query over device buffers goes through:
+// open_object_query, check_query_buffers, bind_query_stack, enqueue_query, and for a filter FilterArgs, check_filter,
+// launch_filterable.  The proximity queries (nearest, sweep, segment, overlap) are capi_proximity.hpp's
 #pragma once
 #include "capi_dispatch.hpp"  // with_flags
 #include "capi_frame_plan.hpp"  // stack_bound
@@ -104,26 +106,70 @@ int open_object_query(const p3d_scene* s, uint32_t accel, const std::string& pre
   return P3D_OK;
 }
 
-// p3d_trace_closest_device / p3d_trace_any_device
+// The skip buffers of a *_filtered_device call (include/p3d_filter.h).  The unfiltered entry points pass none: a null
+// FilterArgs*, the same checks and launches as before
+struct FilterArgs {
+  const int32_t* d_skip;  // n x n_skip, or null
+  uint32_t n_skip;
+  const int32_t* d_skip_range;  // n x 2, or null
+  bool absent() const { return n_skip == 0 && !d_skip_range; }  // the call is the unfiltered call: its kernel is launched
+};
+// What a filtered call refuses of its filter whatever n is, and with n > 0
+int check_filter(const FilterArgs& fa, const std::string& pre) {
+  if (fa.n_skip > P3D_FILTER_SKIP_MAX) return fail(P3D_ERR_INVALID, pre + kRefuseSkipCount);
+  return P3D_OK;
+}
+int check_filter_buffers(const FilterArgs& fa, const std::string& pre) {
+  if (fa.n_skip > 0 && !fa.d_skip) return fail(P3D_ERR_INVALID, pre + "null argument (d_skip is needed with n_skip > 0)");
+  return P3D_OK;
+}
+FilterParams filter_params(const FilterArgs& fa) { return FilterParams{fa.n_skip ? fa.d_skip : nullptr, fa.d_skip_range, fa.n_skip}; }
+
+// One kernel family under P3D_ACCEL_NONE or P3D_ACCEL_BVH, without or with a filter: launch(A, params) is called with the
+// accel as a std::integral_constant and with the bare P (no filter given: the unfiltered kernel) or Filtered{P, F}; it names
+// the kernel template and launches kernel<decltype(A)::value> with `params`
+template <class Filtered, class P, class Launch>
+void launch_filterable(uint32_t accel, const FilterArgs& fa, const P& params, Launch&& launch) {
+  with_flags([&](auto BVH) {
+    constexpr std::integral_constant<int, BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE> A{};
+    if (fa.absent()) launch(A, params);
+    else launch(A, Filtered{params, filter_params(fa)});
+  }, accel == P3D_ACCEL_BVH);
+}
+
+// p3d_trace_closest_device / p3d_trace_any_device and, with `filter`, p3d_trace_any_filtered_device: the segment query alone
+// (the grid and a call without d_t_max are refused), launched with launch_filterable like the other filtered queries
 int trace_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
-                 int32_t* d_hit_id, float* d_t, float* d_hit_point, float* d_normal, uint8_t* d_occluded, void* hip_stream, bool any) {
-  const std::string pre = any ? "p3d_trace_any_device: " : "p3d_trace_closest_device: ";
+                 int32_t* d_hit_id, float* d_t, float* d_hit_point, float* d_normal, uint8_t* d_occluded, void* hip_stream, bool any,
+                 const FilterArgs* filter = nullptr) {
+  const std::string pre = filter ? "p3d_trace_any_filtered_device: " : any ? "p3d_trace_any_device: " : "p3d_trace_closest_device: ";
+  const FilterArgs fa = filter ? *filter : FilterArgs{nullptr, 0, nullptr};
   if (!s) return fail(P3D_ERR_INVALID, pre + "null scene");
   if (int rc = check_accel(s, accel)) return rc;
   if (accel == P3D_ACCEL_GRID && s->dev.n_objs == 0) return fail(P3D_ERR_UNSUPPORTED, "grid over an empty scene");
-  if (any && d_t_max && accel == P3D_ACCEL_GRID)
+  if (any && (d_t_max || filter) && accel == P3D_ACCEL_GRID)
     return fail(P3D_ERR_UNSUPPORTED, pre + "no segment query through the grid (P3D_ACCEL_NONE gives the answer the grid's feeler would: it runs the brute-force loop as well)");
+  if (int rc = check_filter(fa, pre)) return rc;
   if (n == 0) return P3D_OK;
   if (!d_origin || !d_direction || (any ? !d_occluded : !d_hit_id)) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (filter && !d_t_max)
+    return fail(P3D_ERR_INVALID, pre + "null argument (d_t_max is needed: pass +inf for a half-line; the feeler without a limit has no filtered form)");
+  if (int rc = check_filter_buffers(fa, pre)) return rc;
   const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
   const QueryBuffer bufs[] = {
-      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"}, {d_hit_id, one, "d_hit_id"},
+      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"},
+      {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"}, {d_hit_id, one, "d_hit_id"},
       {d_t, one, "d_t"}, {d_hit_point, vec, "d_hit_point"}, {d_normal, vec, "d_normal"}, {d_occluded, (size_t)n, "d_occluded", false}};
   return enqueue_query(s, accel, n, pre, "rays", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
     RayQueryParams P{};
     P.sc = s->dev; P.n = n; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
     P.hit_id = d_hit_id; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.occluded = d_occluded; P.stack = q.stack;
-    launch_ray_query<true>(accel, any, q, st, P);
+    if (!filter) return launch_ray_query<true>(accel, any, q, st, P);
+    // (the segment any-hit under P3D_ACCEL_NONE or P3D_ACCEL_BVH: an absent filter launches the instantiation launch_ray_query would)
+    launch_filterable<RayQueryFilteredParams>(accel, fa, P, [&](auto A, const auto& params) {
+      hipLaunchKernelGGL((ray_query_kernel<decltype(A)::value, true, true>), dim3(q.blocks), dim3(kBlock), q.lds, st, params);
+    });
   });
 }
 
@@ -181,6 +227,78 @@ void with_team(uint32_t team, F&& f) {
     case 32: return f(std::integral_constant<int, 32>{});
     default: return f(std::integral_constant<int, 64>{});
   }
+}
+
+// The free samples of the hemisphere above every point, one kernel on the caller's stream (occlusion_query.hpp);
+// with `filter`, p3d_occlusion_filtered_device: one filter row per point
+int occlusion_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_normal, const float* d_max_dist,
+                     const p3d_occlusion_params* params, uint32_t* d_unoccluded, float* d_bent, void* hip_stream, const FilterArgs* filter) {
+  const std::string pre = filter ? "p3d_occlusion_filtered_device: " : "p3d_occlusion_device: ";
+  const FilterArgs fa = filter ? *filter : FilterArgs{nullptr, 0, nullptr};
+  if (int rc = open_object_query(s, accel, pre, "segment query")) return rc;
+  if (const char* why = occlusion_params_refusal(params)) return fail(P3D_ERR_INVALID, pre + why);
+  if (int rc = check_filter(fa, pre)) return rc;
+  if (n == 0) return P3D_OK;
+  if (!d_point || !d_normal || !d_unoccluded) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (int rc = check_filter_buffers(fa, pre)) return rc;
+  uint32_t team = params->team;
+  if (team == 0)
+    for (team = 1; team < std::min<uint32_t>(params->samples, kBlock); team *= 2) {}  // the smallest power of two >= min(samples, 64)
+  const uint64_t lanes = (uint64_t)n * team;
+  if (lanes > 0xffffffc0ull)  // (whole waves are launched)
+    return fail(P3D_ERR_CAPACITY, pre + "n x team lanes do not fit 32 bits (split the batch, or lower team)");
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
+  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
+  const QueryBuffer bufs[] = {{d_point, vec, "d_point"}, {d_normal, vec, "d_normal"}, {d_max_dist, one, "d_max_dist"},
+                              {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"},
+                              {d_unoccluded, one, "d_unoccluded"}, {d_bent, vec, "d_bent"}};
+  // (a stack per LANE: the spill area is sized by the lanes launched; every sample starts on a cleared stack: one traversal's worst case)
+  return enqueue_query(s, accel, (uint32_t)lanes, pre, "lanes", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    OcclusionParams P{};
+    P.sc = s->dev; P.n = n; P.point = d_point; P.normal = d_normal; P.max_dist = d_max_dist; P.seed = params->seed;
+    P.samples = params->samples; P.sample_begin = params->sample_begin; P.point_offset = params->point_offset;
+    P.accumulate = (params->flags & P3D_OCCLUSION_ACCUMULATE) ? 1u : 0u; P.bias = params->bias;
+    P.unoccluded = d_unoccluded; P.bent = d_bent; P.stack = q.stack;
+    launch_filterable<OcclusionFilteredParams>(accel, fa, P, [&](auto A, const auto& launch_params) {
+      with_team(team, [&](auto TEAM) {
+        hipLaunchKernelGGL((occlusion_kernel<decltype(A)::value, decltype(TEAM)::value>), dim3(q.blocks), dim3(kBlock), q.lds, st, launch_params);
+      });
+    });
+  });
+}
+
+// k == 0 is the pure count: d_total is required and the row outputs are not looked at.  With `filter`,
+// p3d_trace_hits_filtered_device
+int trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_origin, const float* d_direction,
+                      const float* d_t_max, int32_t* d_count, int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point,
+                      float* d_normal, void* hip_stream, const FilterArgs* filter) {
+  const std::string pre = filter ? "p3d_trace_hits_filtered_device: " : "p3d_trace_hits_device: ";
+  const FilterArgs fa = filter ? *filter : FilterArgs{nullptr, 0, nullptr};
+  if (int rc = open_object_query(s, accel, pre, "hit list")) return rc;
+  if (k > P3D_TRACE_HITS_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_TRACE_HITS_K_MAX (16)");
+  if (int rc = check_filter(fa, pre)) return rc;
+  if (n == 0) return P3D_OK;
+  if (k == 0) d_count = d_object = nullptr, d_t = d_hit_point = d_normal = nullptr;
+  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
+  if (k == 0 && !d_total) return fail(P3D_ERR_INVALID, pre + "null argument (k = 0 is the count alone: d_total is needed)");
+  if (k > 0 && (!d_count || !d_object)) return fail(P3D_ERR_INVALID, pre + "null argument (d_count and d_object are needed with k >= 1)");
+  if (int rc = check_filter_buffers(fa, pre)) return rc;
+  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
+  const FilterParams F = filter_params(fa);  // (null without a filter: a null buffer is not looked at)
+  const QueryBuffer bufs[] = {
+      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"},
+      {F.skip, one * fa.n_skip, "d_skip"}, {F.range, one * 2, "d_skip_range"}, {d_count, one, "d_count"},
+      {d_total, one, "d_total"}, {d_object, one * k, "d_object"}, {d_t, one * k, "d_t"}, {d_hit_point, vec * k, "d_hit_point"},
+      {d_normal, vec * k, "d_normal"}};
+  // (the lists of this call's k behind the stack window; none for k = 0)
+  return enqueue_query(s, accel, n, pre, "rays", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
+    TraceHitsParams P{};
+    P.sc = s->dev; P.n = n; P.k = k; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
+    P.count = d_count; P.total = d_total; P.object = d_object; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.stack = q.stack;
+    launch_filterable<TraceHitsFilteredParams>(accel, fa, P, [&](auto A, const auto& params) {
+      hipLaunchKernelGGL((trace_hits_kernel<decltype(A)::value>), dim3(q.blocks), dim3(kBlock), q.lds, st, params);
+    });
+  });
 }
 
 }  // namespace
@@ -289,36 +407,15 @@ int p3d_camera_sample_rays_device(p3d_scene* s, const p3d_camera* camera, const 
   return P3D_OK;
 }
 
-// The free samples of the hemisphere above every point, one kernel on the caller's stream (occlusion_query.hpp)
 int p3d_occlusion_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_normal, const float* d_max_dist,
                          const p3d_occlusion_params* params, uint32_t* d_unoccluded, float* d_bent, void* hip_stream) {
-  const std::string pre = "p3d_occlusion_device: ";
-  if (int rc = open_object_query(s, accel, pre, "segment query")) return rc;
-  if (const char* why = occlusion_params_refusal(params)) return fail(P3D_ERR_INVALID, pre + why);
-  if (n == 0) return P3D_OK;
-  if (!d_point || !d_normal || !d_unoccluded) return fail(P3D_ERR_INVALID, pre + "null argument");
-  uint32_t team = params->team;
-  if (team == 0)
-    for (team = 1; team < std::min<uint32_t>(params->samples, kBlock); team *= 2) {}  // the smallest power of two >= min(samples, 64)
-  const uint64_t lanes = (uint64_t)n * team;
-  if (lanes > 0xffffffc0ull)  // (whole waves are launched)
-    return fail(P3D_ERR_CAPACITY, pre + "n x team lanes do not fit 32 bits (split the batch, or lower team)");
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);
-  const QueryBuffer bufs[] = {{d_point, vec, "d_point"}, {d_normal, vec, "d_normal"}, {d_max_dist, one, "d_max_dist"},
-                              {d_unoccluded, one, "d_unoccluded"}, {d_bent, vec, "d_bent"}};
-  // (a stack per LANE: the spill area is sized by the lanes launched; every sample starts on a cleared stack: one traversal's worst case)
-  return enqueue_query(s, accel, (uint32_t)lanes, pre, "lanes", bufs, 0, hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
-    OcclusionParams P{};
-    P.sc = s->dev; P.n = n; P.point = d_point; P.normal = d_normal; P.max_dist = d_max_dist; P.seed = params->seed;
-    P.samples = params->samples; P.sample_begin = params->sample_begin; P.point_offset = params->point_offset;
-    P.accumulate = (params->flags & P3D_OCCLUSION_ACCUMULATE) ? 1u : 0u; P.bias = params->bias;
-    P.unoccluded = d_unoccluded; P.bent = d_bent; P.stack = q.stack;
-    with_flags([&](auto BVH) {
-      with_team(team, [&](auto TEAM) {
-        hipLaunchKernelGGL((occlusion_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE, decltype(TEAM)::value>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-      });
-    }, accel == P3D_ACCEL_BVH);
-  });
+  return occlusion_device(s, accel, n, d_point, d_normal, d_max_dist, params, d_unoccluded, d_bent, hip_stream, nullptr);
+}
+int p3d_occlusion_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_point, const float* d_normal, const float* d_max_dist,
+                                  const p3d_occlusion_params* params, const int32_t* d_skip, uint32_t n_skip, const int32_t* d_skip_range,
+                                  uint32_t* d_unoccluded, float* d_bent, void* hip_stream) {
+  const FilterArgs fa{d_skip, n_skip, d_skip_range};
+  return occlusion_device(s, accel, n, d_point, d_normal, d_max_dist, params, d_unoccluded, d_bent, hip_stream, &fa);
 }
 
 // One launch on the caller's stream, no wait, nothing of the scene's scratch
@@ -398,32 +495,22 @@ int p3d_trace_any_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* 
   return trace_device(s, accel, n, d_origin, d_direction, d_t_max, nullptr, nullptr, nullptr, nullptr, d_occluded, hip_stream, true);
 }
 
-// k == 0 is the pure count: d_total is required and the row outputs are not looked at
+int p3d_trace_any_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, const float* d_origin, const float* d_direction, const float* d_t_max,
+                                  const int32_t* d_skip, uint32_t n_skip, const int32_t* d_skip_range, uint8_t* d_occluded, void* hip_stream) {
+  const FilterArgs fa{d_skip, n_skip, d_skip_range};
+  return trace_device(s, accel, n, d_origin, d_direction, d_t_max, nullptr, nullptr, nullptr, nullptr, d_occluded, hip_stream, true, &fa);
+}
+
 int p3d_trace_hits_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_origin, const float* d_direction,
                           const float* d_t_max, int32_t* d_count, int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point,
                           float* d_normal, void* hip_stream) {
-  const std::string pre = "p3d_trace_hits_device: ";
-  if (int rc = open_object_query(s, accel, pre, "hit list")) return rc;
-  if (k > P3D_TRACE_HITS_K_MAX) return fail(P3D_ERR_INVALID, pre + "k must be 0 .. P3D_TRACE_HITS_K_MAX (16)");
-  if (n == 0) return P3D_OK;
-  if (k == 0) d_count = d_object = nullptr, d_t = d_hit_point = d_normal = nullptr;
-  if (!d_origin || !d_direction) return fail(P3D_ERR_INVALID, pre + "null argument");
-  if (k == 0 && !d_total) return fail(P3D_ERR_INVALID, pre + "null argument (k = 0 is the count alone: d_total is needed)");
-  if (k > 0 && (!d_count || !d_object)) return fail(P3D_ERR_INVALID, pre + "null argument (d_count and d_object are needed with k >= 1)");
-  const size_t vec = (size_t)n * 3 * sizeof(float), one = (size_t)n * sizeof(float);  // (64 bits: n k 12 < 2^40)
-  const QueryBuffer bufs[] = {
-      {d_origin, vec, "d_origin"}, {d_direction, vec, "d_direction"}, {d_t_max, one, "d_t_max"}, {d_count, one, "d_count"},
-      {d_total, one, "d_total"}, {d_object, one * k, "d_object"}, {d_t, one * k, "d_t"}, {d_hit_point, vec * k, "d_hit_point"},
-      {d_normal, vec * k, "d_normal"}};
-  // (the lists of this call's k behind the stack window; none for k = 0)
-  return enqueue_query(s, accel, n, pre, "rays", bufs, nearest_k_lds_bytes(k), hip_stream, [&](const QueryLaunch& q, hipStream_t st) {
-    TraceHitsParams P{};
-    P.sc = s->dev; P.n = n; P.k = k; P.origin = d_origin; P.direction = d_direction; P.t_max = d_t_max;
-    P.count = d_count; P.total = d_total; P.object = d_object; P.t = d_t; P.hit_point = d_hit_point; P.normal = d_normal; P.stack = q.stack;
-    with_flags([&](auto BVH) {
-      hipLaunchKernelGGL((trace_hits_kernel<BVH ? P3D_ACCEL_BVH : P3D_ACCEL_NONE>), dim3(q.blocks), dim3(kBlock), q.lds, st, P);
-    }, accel == P3D_ACCEL_BVH);
-  });
+  return trace_hits_device(s, accel, n, k, d_origin, d_direction, d_t_max, d_count, d_total, d_object, d_t, d_hit_point, d_normal, hip_stream, nullptr);
+}
+int p3d_trace_hits_filtered_device(p3d_scene* s, uint32_t accel, uint32_t n, uint32_t k, const float* d_origin, const float* d_direction,
+                                   const float* d_t_max, const int32_t* d_skip, uint32_t n_skip, const int32_t* d_skip_range, int32_t* d_count,
+                                   int32_t* d_total, int32_t* d_object, float* d_t, float* d_hit_point, float* d_normal, void* hip_stream) {
+  const FilterArgs fa{d_skip, n_skip, d_skip_range};
+  return trace_hits_device(s, accel, n, k, d_origin, d_direction, d_t_max, d_count, d_total, d_object, d_t, d_hit_point, d_normal, hip_stream, &fa);
 }
 
 enum class ObjectQuery { Intercepts = 0, Normal = 1, SkyboxColour = 2 };  // the values are object_query_kernel's WHAT

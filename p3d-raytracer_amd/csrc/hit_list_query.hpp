@@ -36,9 +36,14 @@ __device__ __forceinline__ bool hit_list_open(const float* t_max, uint32_t i, Hi
 }
 
 // segment_test, keeping its t: a hit in front of the limit is counted and offered to the list.  While the list is not full
-// the gate is (limit, -1) and admission is t < limit once more; a NaN t passes neither comparison
-template <class CT>
-__device__ __forceinline__ void hit_list_offer(const Geom& g, uint32_t slot, const RayS& ray, HitListSearch& s, CT& ct) {
+// the gate is (limit, -1) and admission is t < limit once more; a NaN t passes neither comparison.
+// An object the lane's filter names is not offered: it is not tested, not counted in total, not listed, and so tightens no
+// bound (host/filter_rule.hpp).  NoFilter: the test is not compiled at all (nearest_k_offer has the reason)
+template <class Filter, class CT>
+__device__ __forceinline__ void hit_list_offer(const Geom& g, uint32_t slot, const RayS& ray, HitListSearch& s, const Filter& f, CT& ct) {
+  if constexpr (Filter::kFilters) {
+    if (filter_skips(f, (int32_t)geom_object(g))) return;
+  }
   RayS r = ray;
   float t;
   if (intercepts(g, r, t, ct) && t < s.limit) {
@@ -49,9 +54,9 @@ __device__ __forceinline__ void hit_list_offer(const Geom& g, uint32_t slot, con
 }
 
 // P3D_ACCEL_NONE: every object, planes included
-template <class CT>
-__device__ void brute_segment_hits(const DevScene& sc, const RayS& ray, HitListSearch& s, CT& ct) {
-  for (uint32_t i = 0; i < sc.n_objs; ++i) hit_list_offer(load_geom(sc.ogeom, i), i, ray, s, ct);
+template <class Filter, class CT>
+__device__ void brute_segment_hits(const DevScene& sc, const RayS& ray, HitListSearch& s, const Filter& f, CT& ct) {
+  for (uint32_t i = 0; i < sc.n_objs; ++i) hit_list_offer(load_geom(sc.ogeom, i), i, ray, s, f, ct);
 }
 
 // P3D_ACCEL_BVH: bvh_culled_walk (queries.hpp) with bvh_segment_any's key of a box, never stopped by a hit.  What differs:
@@ -59,11 +64,14 @@ __device__ void brute_segment_hits(const DevScene& sc, const RayS& ray, HitListS
 //     order of the visits does not show in the answer;
 //   - the cull is taken against s.bound(), not a constant.  The bound only shrinks when total is not wanted and the list is full;
 //   - so the float of a stack entry is the child's t0, and a popped entry meets the cull again.
-template <class CT>
+// The boxes are the whole scene's: a filter takes objects out of the leaves, never nodes out of the walk, and the bound of a
+// filtered search shrinks no sooner than the unfiltered one's.
+template <class Filter, class CT>
 struct SegmentHitsWalk {
   const RayS& ray;
   HitListSearch& s;
   bool fin;  // slab_fast_path of the ray
+  const Filter& f;
   CT& ct;
   __device__ __forceinline__ bool key(const NodeRec& n, float& order, float& stacked) const {
     return segment_box(n, ray, fin, s.bound(), order, stacked);
@@ -71,13 +79,13 @@ struct SegmentHitsWalk {
   __device__ __forceinline__ bool culled(float t0) const { return t0 > s.bound(); }
   __device__ __forceinline__ bool left_first(float l_t, float r_t) const { return l_t < r_t; }
   __device__ __forceinline__ bool leaf(const DevScene& sc, uint32_t first, uint32_t end) {
-    for (uint32_t g = first; g < end; ++g) hit_list_offer(load_geom(sc.bgeom, g), g, ray, s, ct);
+    for (uint32_t g = first; g < end; ++g) hit_list_offer(load_geom(sc.bgeom, g), g, ray, s, f, ct);
     return false;
   }
 };
-template <class CT>
-__device__ void bvh_segment_hits(const DevScene& sc, Stack& st, const RayS& ray, HitListSearch& s, CT& ct) {
-  SegmentHitsWalk<CT> walk{ray, s, slab_fast_path<true>(sc, ray), ct};
+template <class Filter, class CT>
+__device__ void bvh_segment_hits(const DevScene& sc, Stack& st, const RayS& ray, HitListSearch& s, const Filter& f, CT& ct) {
+  SegmentHitsWalk<Filter, CT> walk{ray, s, slab_fast_path<true>(sc, ray), f, ct};
   bvh_culled_walk(sc, st, walk, ct);
 }
 
@@ -102,50 +110,23 @@ struct TraceHitsParams {
 // Rows j >= count: -1, FLT_MAX, zeros.
 // k is a runtime argument, a lane writes its k rows itself, and the rays are read with dword loads: the three choices of
 // nearest_k_device_kernel, UNMEASURED here as there (k as a template parameter; row stores through LDS; staged rays).
+// Two kernels of one name, told apart by their parameters, for the reason nearest_k_device_kernel has two: the one launched
+// without filters holds no filter code.  The filtered one (p3d_trace_hits_filtered_device) reads row i of the skip buffers once,
+// before the walk, into ten registers.
+struct TraceHitsFilteredParams {
+  TraceHitsParams q;
+  FilterParams f;
+};
 template <int ACCEL>
 __global__ void __launch_bounds__(kBlock) trace_hits_kernel(const TraceHitsParams P) {
-  extern __shared__ float4 smem[];
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  Stack st;
-  query_stack_bind(st, smem, P.stack, i);
-  HitListSearch s;
-  s.list.base = query_list_base(smem, P.stack);
-  s.k = P.k; s.want_total = P.total != nullptr;
-  if (i >= P.n) return;
-  Counters<false> ct;
-  RayS ray;
-  ray_set(ray, f3(P.origin[3 * i], P.origin[3 * i + 1], P.origin[3 * i + 2]),
-          f3(P.direction[3 * i], P.direction[3 * i + 1], P.direction[3 * i + 2]));
-  if (hit_list_open(P.t_max, i, s) && P.sc.n_objs > 0) {
-    if (ACCEL == P3D_ACCEL_BVH) bvh_segment_hits(P.sc, st, ray, s, ct);
-    else brute_segment_hits(P.sc, ray, s, ct);
-  }
-  if (P.total) P.total[i] = (int32_t)s.total;
-  if (P.k == 0) return;
-  P.count[i] = (int32_t)s.count;
-  const float4* geom = ACCEL == P3D_ACCEL_BVH ? P.sc.bgeom : P.sc.ogeom;
-  for (uint32_t e = 0; e < P.k; ++e) {
-    const size_t row = (size_t)i * P.k + e;
-    int32_t object = -1;
-    float t = FLT_MAX;
-    F3 hp = f3(0, 0, 0), nrm = f3(0, 0, 0);
-    if (e < s.count) {
-      object = s.list.object(e);
-      t = s.list.d2(e);
-      if (P.hit_point || P.normal) {
-        const Geom g = load_geom(geom, s.list.slot(e));
-        RayS r = ray;
-        float again;
-        intercepts(g, r, again, ct);  // (for the ray it leaves behind: a sphere has normalised it, Q8)
-        hp = r.o + r.d * t;
-        if (P.normal) nrm = get_normal(g, P.sc.normals, hp);
-      }
-    }
-    P.object[row] = object;
-    if (P.t) P.t[row] = t;
-    if (P.hit_point) store_f3(P.hit_point, row, hp);
-    if (P.normal) store_f3(P.normal, row, nrm);
-  }
+  const NoFilterSource filters{};
+#include "trace_hits_body.inc"
+}
+template <int ACCEL>
+__global__ void __launch_bounds__(kBlock) trace_hits_kernel(const TraceHitsFilteredParams PF) {
+  const TraceHitsParams& P = PF.q;
+  const FilterParams& filters = PF.f;
+#include "trace_hits_body.inc"
 }
 
 }  // namespace p3d

@@ -1,10 +1,11 @@
 // ray_query.hpp — the batched ray queries, from host arrays (p3d_trace_closest, p3d_trace_any) and over device buffers
 // (p3d_trace_closest_device, p3d_trace_any_device): ray_query_kernel, one body for both, and bvh_segment_any, the any-hit
 // with a distance limit.  The unlimited paths call device_core.hpp's closest_hit / any_hit (bvh.cpp:198-340,
-// grid.cpp:71-208, main.cpp:116-124,208-216), the segment query is a policy of the culled walk.
+// grid.cpp:71-208, main.cpp:116-124,208-216), the segment query is a policy of the culled walk.  The segment query takes a
+// lane's filter (p3d_trace_any_filtered_device); closest_hit and any_hit know none.
 #pragma once
 
-#include "queries.hpp"  // QueryStack, bvh_culled_walk, store_f3
+#include "queries.hpp"  // QueryStack, bvh_culled_walk, store_f3, FilterParams, NoFilterSource
 
 namespace p3d {
 
@@ -12,19 +13,24 @@ namespace p3d {
 //   occluded = some object j has intercepts(object j, a fresh copy of the ray, t) true and t < t_max.
 // Every primitive is tested on a copy of the caller's ray, so a sphere test's re-normalisation (Q8) never reaches a later
 // test and the answer does not depend on the order of the visits.  A NaN t (A10) and a NaN t_max keep nothing.
-template <class CT>
-__device__ __forceinline__ bool segment_test(const Geom& g, const RayS& ray, float t_max, CT& ct) {
+// An object the lane's filter names is not tested at all (host/filter_rule.hpp): the answer is a set over objects, so it is the
+// answer over the scene without them.  NoFilter: the test is not compiled (nearest_k_offer has the reason).
+template <class Filter, class CT>
+__device__ __forceinline__ bool segment_test(const Geom& g, const RayS& ray, float t_max, const Filter& f, CT& ct) {
+  if constexpr (Filter::kFilters) {
+    if (filter_skips(f, (int32_t)geom_object(g))) return false;
+  }
   RayS r = ray;
   float t;
   return intercepts(g, r, t, ct) && t < t_max;
 }
 
 // P3D_ACCEL_NONE: every object
-template <class CT>
-__device__ bool brute_segment_any(const DevScene& sc, const RayS& ray, float t_max, CT& ct) {
+template <class Filter, class CT>
+__device__ bool brute_segment_any(const DevScene& sc, const RayS& ray, float t_max, const Filter& f, CT& ct) {
   for (uint32_t i = 0; i < sc.n_objs; ++i) {
     const Geom g = load_geom(sc.ogeom, i);
-    if (segment_test(g, ray, t_max, ct)) return true;
+    if (segment_test(g, ray, t_max, f, ct)) return true;
   }
   return false;
 }
@@ -42,11 +48,13 @@ __device__ __forceinline__ bool segment_box(const NodeRec& n, const RayS& ray, b
 //   - a primitive counts only with t < t_max, and the first one that does ends the lane;
 //   - a dead end pops the next entry: no restart from the bottom-most entry (Q1), so nothing the ray can reach is skipped.
 //     t_max never moves, so a popped entry is not tested again; the float that travels with it is the child's t.
-template <class CT>
+// The boxes are the whole scene's: a filter takes objects out of the leaves, never nodes out of the walk.
+template <class Filter, class CT>
 struct SegmentAnyWalk {
   const RayS& ray;
   float t_max;
   bool fin;  // slab_fast_path of the ray
+  const Filter& f;
   CT& ct;
   __device__ __forceinline__ bool key(const NodeRec& n, float& order, float& stacked) const {
     float t0;
@@ -60,16 +68,16 @@ struct SegmentAnyWalk {
     bool occluded = false, more = s < end;
     while (more) {
       const Geom g = load_geom(sc.bgeom, s);
-      occluded = segment_test(g, ray, t_max, ct);
+      occluded = segment_test(g, ray, t_max, f, ct);
       ++s;
       more = !occluded && s < end;
     }
     return occluded;
   }
 };
-template <class CT>
-__device__ bool bvh_segment_any(const DevScene& sc, Stack& st, const RayS& ray, float t_max, CT& ct) {
-  SegmentAnyWalk<CT> walk{ray, t_max, slab_fast_path<true>(sc, ray), ct};
+template <class Filter, class CT>
+__device__ bool bvh_segment_any(const DevScene& sc, Stack& st, const RayS& ray, float t_max, const Filter& f, CT& ct) {
+  SegmentAnyWalk<Filter, CT> walk{ray, t_max, slab_fast_path<true>(sc, ray), f, ct};
   return bvh_culled_walk(sc, st, walk, ct);
 }
 
@@ -96,36 +104,23 @@ struct RayQueryParams {
 // A lane reads its ray with six dword loads 12 bytes apart from its neighbours': a wave's 768 bytes per array are six whole
 // 128-byte lines either way, fetched once per ray in front of a traversal of dozens of dependent node fetches, so the rays
 // are not staged through LDS with wide loads.  UNMEASURED, like the staged form.
+// Two kernels of one name, told apart by their parameters, for the reason nearest_k_device_kernel has two: the ones launched
+// without filters hold no filter code.  The filtered one is launched as <accel, ANY = true, EXTRAS = true> with a t_max alone
+// (p3d_trace_any_filtered_device): row i of the skip buffers is read once, before the walk, into ten registers.
+struct RayQueryFilteredParams {
+  RayQueryParams q;
+  FilterParams f;
+};
 template <int ACCEL, bool ANY, bool EXTRAS>
 __global__ void __launch_bounds__(kBlock) ray_query_kernel(const RayQueryParams P) {
-  extern __shared__ float4 smem[];
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  Stack st;
-  query_stack_bind(st, smem, P.stack, i);
-  if (i >= P.n) return;
-  Counters<false> ct;
-  RayS ray;
-  ray_set(ray, f3(P.origin[3 * i], P.origin[3 * i + 1], P.origin[3 * i + 2]),
-          f3(P.direction[3 * i], P.direction[3 * i + 1], P.direction[3 * i + 2]));
-  const float* t_max = EXTRAS ? P.t_max : nullptr;
-  if (ANY) {
-    bool occluded;
-    if (!t_max) occluded = any_hit<ACCEL, true, true>(P.sc, st, ray, ct);
-    else if (ACCEL == P3D_ACCEL_BVH) occluded = bvh_segment_any(P.sc, st, ray, t_max[i], ct);
-    else occluded = brute_segment_any(P.sc, ray, t_max[i], ct);
-    P.occluded[i] = occluded ? 1 : 0;
-  } else {
-    F3 hp = f3(0, 0, 0);
-    Geom g;
-    float t = FLT_MAX;
-    int obj = closest_hit<ACCEL, true, true>(P.sc, st, ray, hp, g, ct, nullptr, &t);
-    if (t_max && obj >= 0 && !(t < t_max[i])) obj = -1;
-    P.hit_id[i] = obj;
-    if (P.t) P.t[i] = obj < 0 ? FLT_MAX : t;
-    if (obj < 0) hp = f3(0, 0, 0);
-    if (P.hit_point) store_f3(P.hit_point, i, hp);
-    if (EXTRAS && P.normal) store_f3(P.normal, i, obj < 0 ? f3(0, 0, 0) : get_normal(g, P.sc.normals, hp));
-  }
+  const NoFilterSource filters{};
+#include "ray_query_body.inc"
+}
+template <int ACCEL, bool ANY, bool EXTRAS>
+__global__ void __launch_bounds__(kBlock) ray_query_kernel(const RayQueryFilteredParams PF) {
+  const RayQueryParams& P = PF.q;
+  const FilterParams& filters = PF.f;
+#include "ray_query_body.inc"
 }
 
 }  // namespace p3d

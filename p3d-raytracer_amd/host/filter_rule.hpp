@@ -1,7 +1,10 @@
 // filter_rule.hpp — which objects a filtered query leaves out, in ONE place for its users: p3d_host_scene_nearest_k_filtered and
 // p3d_host_scene_sweep_sphere_filtered (host_queries.cpp), which state the semantics by brute force, and the filtered instantiations
 // of nearest_k_device_kernel and sweep_sphere_device_kernel (csrc/nearest_query.hpp, csrc/sweep_query.hpp), whose answers must be
-// the host forms' bits.  A filtered query is the unfiltered query over the scene without the objects its filter names: a skipped
+// the host forms' bits; the segment and overlap queries (csrc/nearest_segment_query.hpp, csrc/overlap_query.hpp); and the filtered
+// instantiations of the segment family of the ray queries, which have no host form: ray_query_kernel's any-hit with a limit,
+// trace_hits_kernel and occlusion_kernel (csrc/ray_query.hpp, csrc/hit_list_query.hpp, csrc/occlusion_query.hpp), where the test
+// stands in front of the ray-object test.  A filtered query is the unfiltered query over the scene without the objects its filter names: a skipped
 // object is never offered, so it is not listed, is not the contact and tightens no bound.  No arithmetic of a query is here, only
 // integer comparisons; a filter that names nothing leaves every bit of the unfiltered answer.
 #pragma once
